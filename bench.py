@@ -21,12 +21,17 @@ kernels + sync, gpu.cu:1266-1291).  ms_per_step = that wall clock / K.  With N >
 barrier, and every rank then runs [100 ms re-settle][warm-up][K timed] uninterrupted; value uses the MAX over ranks.
 
 Every rank (round 4): pins itself to the CPUs next to its GPU BEFORE its first HIP call (shard.pin_to_gpu_cpus), filters its
-share of ONE seeded frame set (frames dealt f mod N), hashes 16 of its output frames -- rank 0 filters two frames of every
-other rank on ITS GPU again and compares (`cross_rank.frames_equal_1gpu`) -- and runs the PCIe-inclusive legs between common
-barriers: the reference-shaped host call on one pageable frame, the sequence operator from page-locked and from pageable
+share of ONE seeded frame set (frames dealt f mod N), and with --full hashes 16 of its output frames -- rank 0 filters two frames
+of every other rank on ITS GPU again and compares (`cross_rank.frames_equal_1gpu`) -- and runs the PCIe-inclusive legs between
+common barriers: the reference-shaped host call on one pageable frame, the sequence operator from page-locked and from pageable
 planes (`e2e_host_frame`, `per_rank[*].e2e_*`; never `value`).
 
-After the headline measurement, rank 0 of a one-GPU run adds (each with its own bit-exactness spot check):
+A plain run does only what the headline figure needs: set up, settle and warm up, time the --steps launches, write the
+outputs when --dump-outputs DIR is given (dump_outputs), print the JSON line.  Everything else moves behind --full: the copy-floor
+and live-PMC child processes, the clock / power telemetry, the bit-exactness spot checks of the timed launches and the
+cross-rank check, the PCIe-inclusive legs, and what follows here.
+
+After the headline measurement, rank 0 of a one-GPU --full run adds (each with its own bit-exactness spot check):
   extra_configs   the same kernel at 64 frames per launch (a decoder-sized batch), BASELINE config 4 as whole
                   4:2:0 frames (Y + U + V), deblocking + SAO in one kernel against the two launches it replaces
                   (SURVEY 8f rank 4), BASELINE configs 1 and 3 on the reference's bundled inputs (config3 also at 64 x 4K with a
@@ -312,6 +317,35 @@ def settled_run(ctx, planes_list, qp, steps, variant, args, warmup=3):
     """One uninterrupted [settle by time][warm-up][timed] stream on ctx; (kernel ms of the timed launches, replay info)."""
     return ctx.replay(planes_list, qp, steps, warmup=warmup, settle_min_ms=args.settle_min_ms, settle_max_ms=args.settle_max_ms,
                       variant=variant)
+
+
+DUMP_FRAME_BYTES = 32 << 20   # frame 0 is written in full when it takes at most this much as float32
+DUMP_SAMPLES = 1 << 22        # samples of the whole batch (16 MiB as float32)
+
+
+def dump_outputs(batch, outdir, seed=0):
+    """--dump-outputs: what the last timed launch left in the destination frames -- what a caller of the device entry point
+    receives -- as float32 .npy files (exact for 8..16-bit samples), 48 MiB at most:
+      filtered_frame0.npy  frame 0, shape (H, W), when it fits in DUMP_FRAME_BYTES;
+      filtered_sample.npy  the samples of the whole (F, H, W) output at sorted flat positions drawn by a generator seeded with
+                           `seed` alone (all of them when there are at most DUMP_SAMPLES), so two runs with the same arguments
+                           read the same positions."""
+    os.makedirs(outdir, exist_ok=True)
+    F, h, w = batch.n, batch.h, batch.w
+    if h * w * 4 <= DUMP_FRAME_BYTES:
+        np.save(os.path.join(outdir, "filtered_frame0.npy"), batch.download_frame(0).astype(np.float32))
+    total = F * h * w
+    if total <= DUMP_SAMPLES:
+        pos = np.arange(total)
+    else:
+        pos = np.unique(np.random.default_rng(seed).integers(0, total, DUMP_SAMPLES))
+    sample = np.empty(pos.size, np.float32)
+    cuts = np.searchsorted(pos, np.arange(F + 1) * (h * w))
+    for f in range(F):
+        a, b = cuts[f], cuts[f + 1]
+        if a < b:
+            sample[a:b] = batch.download_frame(f).ravel()[pos[a:b] - f * h * w]
+    np.save(os.path.join(outdir, "filtered_sample.npy"), sample)
 
 
 def extra_configs(ctx, args, frames, batch, variant):
@@ -858,11 +892,11 @@ def main():
                     help="load libhevcdbk_diag.so and set these knobs (csrc/hevcdbk_diag.h): A/B runs only, never a result")
     ap.add_argument("--traffic", choices=["live", "file", "none"], default="file",
                     help="roofline.traffic: file = newest matching profiles/*_hbm_traffic.json (collected with tools/hbm_traffic.py); "
-                         "live = the same four rocprofv3 --pmc passes run now as child processes, before this process touches the "
-                         "GPU (about 20 s of GPU time; falls back to file)")
+                         "live (with --full) = the same four rocprofv3 --pmc passes run now as child processes, before this process "
+                         "touches the GPU (about 20 s of GPU time; falls back to file)")
     ap.add_argument("--copy-floor", choices=["auto", "off"], default="auto",
-                    help="auto: a child process measures the copy variant of the kernel (libhevcdbk_diag.so) on the same workload "
-                         "before this process touches the GPU -> roofline.copy_floor_ms")
+                    help="auto (with --full): a child process measures the copy variant of the kernel (libhevcdbk_diag.so) on the same "
+                         "workload before this process touches the GPU -> roofline.copy_floor_ms")
     ap.add_argument("--oversubscribe", action="store_true",
                     help="allow more ranks than HIP devices (ranks then share devices: rehearsal only, not a scaling figure)")
     ap.add_argument("--rank-timeout", type=float, default=540.0, help="seconds the self-spawned ranks of --gpus N may run")
@@ -874,6 +908,14 @@ def main():
     ap.add_argument("--no-e2e", action="store_true")
     ap.add_argument("--no-extra", action="store_true", help="skip extra_configs and the reference table line")
     ap.add_argument("--no-config5", action="store_true", help="skip the 8K 10-bit extra config (3.2 GB of host frames)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: the copy floor and live PMC passes (child "
+                         "processes), clock / power telemetry, bit-exactness spot checks of the timed launches, the cross-rank check, "
+                         "the PCIe-inclusive legs, extra_configs, the CPU baseline and the reference table (the --no-* options and "
+                         "--traffic / --copy-floor select among these)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed launch produced (rank 0's filtered frames) as float32 "
+                         ".npy files under DIR: frame 0 in full and a fixed seeded sample of the whole batch (dump_outputs)")
     args = ap.parse_args()
     args.settle_min_ms = min(args.settle_min_ms, args.settle_max_ms)   # --settle-max-ms 0 = no settling at all
 
@@ -925,9 +967,9 @@ def main():
     # child processes first: this process has not touched the GPU yet
     traffic, floor = None, None
     if world == 1 and default_kernel:
-        if args.copy_floor == "auto":
+        if args.full and args.copy_floor == "auto":
             floor = copy_floor(args)
-        if args.traffic == "live":
+        if args.full and args.traffic == "live":
             traffic = live_traffic(w, h, F, bd)
         if traffic is None and args.traffic in ("live", "file"):
             traffic = measured_traffic(w, h, F, bd)
@@ -961,7 +1003,7 @@ def main():
     # everything on the host side BEFORE the first launch: the sampler thread reads this rank's card (PCI id from the
     # context that is already open) every 10 ms from here to the end of the timed window
     sampler = None
-    if not args.no_telemetry and pci:
+    if args.full and not args.no_telemetry and pci:
         try:
             sys.path.insert(0, os.path.join(ROOT, "tools"))
             from clock_power_trace import Sampler
@@ -999,18 +1041,24 @@ def main():
     my_elapsed = elapsed
     elapsed = shard.max_over_ranks(dist, elapsed)  # MAX over ranks (gloo; control plane only)
 
-    # parity spot check on what the timed launches wrote (not timed)
-    from oracle import oracle
-    bit_exact = True
-    for f in sorted({0, F // 2, F - 1}):
-        want = frames[f] if args.variant == "copy" else oracle.filter_plane(frames[f], args.qp, bit_depth=bd, threads=8)
-        bit_exact &= bool(np.array_equal(batch.download_frame(f), want))
+    # what the last timed launch wrote, before anything else touches the device memory (extra_configs reuses the pool)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(batch, args.dump_outputs)
+
+    # parity spot check on what the timed launches wrote (not timed); None = not checked (a run without --full)
+    bit_exact = None
+    if args.full:
+        from oracle import oracle
+        bit_exact = True
+        for f in sorted({0, F // 2, F - 1}):
+            want = frames[f] if args.variant == "copy" else oracle.filter_plane(frames[f], args.qp, bit_depth=bd, threads=8)
+            bit_exact &= bool(np.array_equal(batch.download_frame(f), want))
 
     # N-GPU output == 1-GPU output on a sample: every rank hashes 16 of its filtered frames; rank 0 filters two frames of every
     # other rank's sample on ITS GPU again and compares (shard.frames_equal_across_ranks)
     import hashlib
     cross = None
-    if args.variant != "copy":
+    if args.full and args.variant != "copy":
         local_hashes = {gidx[f]: hashlib.sha256(batch.download_frame(f).tobytes()).hexdigest() for f in range(0, F, max(1, F // 16))}
 
         def refilter(g):
@@ -1026,7 +1074,7 @@ def main():
     # PCIe-inclusive legs, every rank at once between two barriers (never `value`): the reference-shaped host call on ONE pageable
     # frame, and the streaming operator on page-locked frames
     e2e = None
-    if not args.no_e2e and args.variant != "copy" and args.diag is None:
+    if args.full and not args.no_e2e and args.variant != "copy" and args.diag is None:
         e2e = e2e_legs(ctx, args, frames, barrier)
 
     ms_per_step = elapsed * 1e3 / args.steps
@@ -1082,7 +1130,7 @@ def main():
         out["e2e_host_frame"]["all_ranks_sequence_frames_per_s"] = shard.aggregate_rate(ranks, "e2e_sequence_frames", "e2e_sequence_s")
         out["e2e_host_frame"]["all_ranks_host_frames_per_s"] = (world / max(r["e2e_host_frame_s"] for r in ranks))
         out["e2e_host_frame"]["all_ranks_sequence_pcie_GBps"] = (out["e2e_host_frame"]["all_ranks_sequence_frames_per_s"] * 2 * w * h * sb / 1e9)
-    if rank == 0 and world == 1 and args.variant != "copy" and args.diag is None:
+    if args.full and rank == 0 and world == 1 and args.variant != "copy" and args.diag is None:
         if not args.no_extra:
             out["extra_configs"] = extra_configs(ctx, args, frames, batch, variant)
         if not args.no_cpu_baseline:
@@ -1101,7 +1149,7 @@ def main():
         raise SystemExit("bench: frames filtered by other ranks differ from rank 0's GPU: %s" % cross["mismatches"])
     if not all(r.get("e2e_bit_exact", True) for r in ranks):
         raise SystemExit("bench: a PCIe-inclusive leg differs from the oracle")
-    if not bit_exact or not extras_ok or not all(r.get("bit_exact_vs_oracle", True) for r in ranks):
+    if bit_exact is False or not extras_ok or any(r.get("bit_exact_vs_oracle") is False for r in ranks):
         raise SystemExit("bench: HIP output differs from the oracle")
 
 

@@ -14,7 +14,10 @@ What it writes (all data, no reference source):
                                  default pattern and LCG-seeded luma bS in {0,1,2}
                                  (oracle.lcg_bs: s = s*1664525+1013904223, (s>>16)%3, vert then hor),
   * synth_*.json entries      -- sha256 of reference outputs on seeded synthetic 4:2:0 frames
-                                 (gpu_video_codec_amd.synth.blocky_yuv420), small and 4K.
+                                 (gpu_video_codec_amd.synth.blocky_yuv420), small and 4K,
+  * ref_fresh.json            -- sha256 of reference outputs on the hard seeded inputs of fresh_cases()
+                                 and the reference constructor's return codes on the files of ERROR_CASES
+                                 (tests/test_oracle.py checks the restatement against both).
 """
 import hashlib
 import json
@@ -43,6 +46,48 @@ SYNTH_QPS = [27, 32, 45]
 
 def sha(b):
     return hashlib.sha256(b).hexdigest()
+
+
+def fresh_cases():
+    """Seeded 4:2:0 frames with hard content (noise patches, saturated areas) at sizes and QPs no other fixture covers:
+    yields (w, h, qp, bs_seed, yuv bytes, vert bS, hor bS); bS None = the reference's default pattern."""
+    import numpy as np
+    rng = np.random.default_rng(11)
+    for (w, h) in [(16, 16), (32, 16), (16, 48), (64, 64), (176, 144), (400, 240)]:
+        for qp in (20, 27, 33, 40, 51):
+            y, u, v = synth.blocky_yuv420(w, h, seed=int(rng.integers(1, 1 << 30)))
+            y = y.copy()
+            y[: h // 4, : w // 4] = rng.integers(0, 256, (h // 4, w // 4), dtype=np.uint8)
+            y[h // 2:, w // 2:] = 255
+            y[h // 2:, : w // 8] = 0
+            buf = oracle.join_yuv420(y, u, v)
+            for seed in (None, 9):
+                vb = hb = None
+                if seed is not None:
+                    vb, hb = oracle.lcg_bs(w, h, seed)
+                yield w, h, qp, seed, buf, vb, hb
+
+
+# constructor error cases (cpu.h:43-48): name -> (file size in bytes, width, height)
+ERROR_CASES = {"short_file": (100, 352, 288), "dimensions_not_multiple_of_8": (3 * 20 * 20 // 2, 20, 20)}
+
+
+def record_fresh():
+    import ctypes as C
+    import tempfile
+    cases = [{"width": w, "height": h, "qp": qp, "bs_seed": seed, "input_sha256": sha(buf),
+              "sha256": sha(oracle.ref_filter_yuv420(buf, w, h, qp, vb, hb, threads=1))}
+             for (w, h, qp, seed, buf, vb, hb) in fresh_cases()]
+    errors = {}
+    with tempfile.TemporaryDirectory() as d:
+        for name, (size, w, h) in ERROR_CASES.items():
+            p = os.path.join(d, name + ".yuv")
+            with open(p, "wb") as fh:
+                fh.write(b"\0" * size)
+            errors[name] = oracle.ref().ref_frame_create(C.byref(C.c_void_p()), p.encode(), w, h, 30)
+    with open(os.path.join(HERE, "ref_fresh.json"), "w") as fh:
+        json.dump({"cases": cases, "constructor_errors": errors}, fh, indent=1)
+    print("wrote", os.path.join(HERE, "ref_fresh.json"))
 
 
 def main():
@@ -79,6 +124,7 @@ def main():
     with open(os.path.join(HERE, "manifest.json"), "w") as fh:
         json.dump(man, fh, indent=1)
     print("wrote", os.path.join(HERE, "manifest.json"))
+    record_fresh()
 
 
 if __name__ == "__main__":

@@ -21,12 +21,12 @@ run_stats() { # name, then the python script and its arguments
     echo "== $name"; cat "$OUT/kernel_stats_$name.csv"
 }
 
-# (1) the driver's exact command, NOT under the profiler: the headline record of the round
-( cd "$R" && python3 bench.py --gpus 1 --steps 20 --warmup 5 > "$OUT/bench_driver_cmd.json" 2> "$OUT/bench_driver_cmd.err" ) || true
+# (1) the driver's command with --full, NOT under the profiler: the headline record of the round and every figure around it
+( cd "$R" && python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > "$OUT/bench_driver_cmd.json" 2> "$OUT/bench_driver_cmd.err" ) || true
 # (2) the same bench under rocprofv3 --kernel-trace --stats with 200 timed steps (no copy-floor child, no PMC children: they
 #     must not nest inside another rocprofv3)
-run_stats bench_default_1gpu "$R/bench.py" --steps 200 --warmup 5 --traffic file --copy-floor off
-run_stats bench_8k10_1gpu "$R/bench.py" --traffic none --no-extra --copy-floor off --width 7680 --height 4320 --bit-depth 10 --frames 32
+run_stats bench_default_1gpu "$R/bench.py" --full --steps 200 --warmup 5 --traffic file --copy-floor off
+run_stats bench_8k10_1gpu "$R/bench.py" --full --traffic none --no-extra --copy-floor off --width 7680 --height 4320 --bit-depth 10 --frames 32
 run_stats bench_h265 "$R/tools/bench_h265.py"
 # what a decoder's operands cost: bS 0 / 1 / 2 mixed per segment, and a QP per 16x16 quantization group
 python3 "$R/tools/bench_h265.py" --only packed --bs mixed > "$OUT/bench_h265_decoder_operands.json" 2>/dev/null || true
@@ -44,7 +44,7 @@ rows.sort(key=lambda r: int(r["Start_Timestamp"]))
 d = [(int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) * 1e-6 for r in rows]
 lo, hi = settle + warm, settle + warm + steps
 win = sorted(d[lo:hi])
-res = {"source": "rocprofv3 --kernel-trace of `python3 bench.py --steps 200 --warmup 5 --traffic file --copy-floor off`: the luma kernel's dispatches in "
+res = {"source": "rocprofv3 --kernel-trace of `python3 bench.py --full --steps 200 --warmup 5 --traffic file --copy-floor off`: the luma kernel's dispatches in "
                  "launch order are [settle by time][warm-up][timed], then the extra configs' launches of the same kernel",
        "settle_launches": settle, "warmup": warm, "steps": steps, "dispatches_of_the_luma_kernel": len(d),
        "avg_first_32_ms": sum(d[:32]) / 32, "avg_last_32_settle_ms": sum(d[settle - 32:settle]) / 32,

@@ -32,7 +32,7 @@ HEVCDBK_HOST_PUSH=0 HEVCDBK_HOST_DIRECT_OUT=0 python3 "$R/tools/host_frame_4k.py
 "$R/tools/ubench/host_stage" > "$OUT/ubench_host_stage.json" 2>/dev/null || true
 "$R/tools/ubench/bar_write" > "$OUT/ubench_bar_write.json" 2>/dev/null || true
 # (2) the N-rank bench on one card (rehearsal of the 8-GPU line: every field filled, not a scaling figure)
-( cd "$R" && python3 bench.py --gpus 2 --oversubscribe --steps 20 --warmup 5 --frames 64 --no-extra --no-cpu-baseline --copy-floor off --traffic none \
+( cd "$R" && python3 bench.py --full --gpus 2 --oversubscribe --steps 20 --warmup 5 --frames 64 --no-extra --no-cpu-baseline --copy-floor off --traffic none \
     > "$OUT/bench_2ranks_one_gpu_oversubscribed.json" 2> "$OUT/bench_2ranks.err" ) || true
 # (3) the QP-map kernels: timings and SQ counters
 for m in 6 4 3; do python3 "$R/tools/bench_qpmap.py" --qp-map $m --bs lcg >> "$OUT/bench_qpmap.json"; done
