@@ -41,7 +41,24 @@ EXPORTS = [
     "hevc_deblock_sao_device_planes", "hevc_deblock_sao_h265_device_planes",
     "hevcdbk_set_host_threads", "hevcdbk_get_host_threads", "hevcdbk_host_register", "hevcdbk_host_unregister",
     "hevcdbk_last_frame_trace", "hevcdbk_device_malloc_probed",
+    "hevcdbk_h265_derive_bs_device_cf", "hevcdbk_h265_filter_device_cf", "hevcdbk_h265_filter_frame_cf",
+    "hevcdbk_sao_filter_device_cf", "hevcdbk_h265_deblock_sao_device_cf", "hevcdbk_h265_deblock_sao_device_planes_cf",
 ]
+
+# chroma_format_idc of the spec-exact mode and SAO (HEVCDBK_CHROMA_*): 4:0:0, 4:2:0, 4:2:2, 4:4:4
+CHROMA_400, CHROMA_420, CHROMA_422, CHROMA_444 = 0, 1, 2, 3
+CHROMA_FORMATS = {"400": CHROMA_400, "420": CHROMA_420, "422": CHROMA_422, "444": CHROMA_444}
+# SubWidthC, SubHeightC (H.265 Table 6-1) of the formats with chroma planes
+CHROMA_SUB = {CHROMA_420: (2, 2), CHROMA_422: (2, 1), CHROMA_444: (1, 1)}
+
+
+def chroma_format_idc(fmt):
+    """'400' / '420' / '422' / '444' (or the idc itself) -> chroma_format_idc"""
+    if isinstance(fmt, int) and fmt in CHROMA_FORMATS.values():
+        return fmt
+    if str(fmt) not in CHROMA_FORMATS:
+        raise ValueError("chroma_format must be one of %s, not %r" % (sorted(CHROMA_FORMATS), fmt))
+    return CHROMA_FORMATS[str(fmt)]
 
 
 class Frame(C.Structure):
@@ -75,6 +92,12 @@ class SaoPlane(C.Structure):
     """hevcdbk_sao_plane: the SAO operands of one plane of a multi-plane deblocking + SAO call (device pointers)"""
     _fields_ = [("params", C.c_void_p), ("params_stride", C.c_uint), ("params_frame_stride", C.c_size_t), ("ctb_log2", C.c_uint),
                 ("keep", C.c_void_p), ("keep_stride", C.c_uint), ("keep_frame_stride", C.c_size_t)]
+
+
+class SaoPlaneCf(C.Structure):
+    """hevcdbk_sao_plane_cf: SaoPlane with CTBs of (1 << ctb_log2_w) x (1 << ctb_log2_h) samples"""
+    _fields_ = [("params", C.c_void_p), ("params_stride", C.c_uint), ("params_frame_stride", C.c_size_t), ("ctb_log2_w", C.c_uint),
+                ("ctb_log2_h", C.c_uint), ("keep", C.c_void_p), ("keep_stride", C.c_uint), ("keep_frame_stride", C.c_size_t)]
 
 
 class Replay(C.Structure):
@@ -215,6 +238,19 @@ def lib():
                                                    C.c_int, C.c_void_p]
         L.hevc_deblock_sao_device_planes.argtypes = [C.c_void_p, C.POINTER(DevicePlanes), C.c_uint, C.c_uint, C.POINTER(Tables),
                                                      C.POINTER(SaoPlane), C.c_int, C.c_void_p]
+        L.hevcdbk_h265_derive_bs_device_cf.argtypes = [C.c_void_p, C.POINTER(H265Units), C.c_uint, C.c_uint, C.c_int, C.c_void_p,
+                                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.hevcdbk_h265_filter_device_cf.argtypes = [C.c_void_p, C.POINTER(DevicePlanes), C.c_int, C.c_int, C.c_uint,
+                                                            C.POINTER(H265Params), C.c_int, C.c_void_p]
+        L.hevcdbk_h265_filter_frame_cf.argtypes = [C.c_void_p, C.POINTER(Frame), C.c_int, C.POINTER(H265Units), C.POINTER(Bs),
+                                                     C.POINTER(Qp), C.POINTER(H265Params), C.POINTER(Timing)]
+        L.hevcdbk_sao_filter_device_cf.argtypes = [C.c_void_p, C.POINTER(DevicePlanes), C.c_void_p, C.c_uint, C.c_size_t, C.c_uint,
+                                                C.c_uint, C.c_void_p, C.c_uint, C.c_size_t, C.c_void_p]
+        L.hevcdbk_h265_deblock_sao_device_cf.argtypes = [C.c_void_p, C.POINTER(DevicePlanes), C.c_int, C.c_int, C.c_uint,
+                                                      C.POINTER(H265Params), C.c_void_p, C.c_uint, C.c_size_t, C.c_uint, C.c_uint,
+                                                      C.c_void_p, C.c_uint, C.c_size_t, C.c_int, C.c_void_p]
+        L.hevcdbk_h265_deblock_sao_device_planes_cf.argtypes = [C.c_void_p, C.POINTER(DevicePlanes), C.c_uint, C.c_int, C.c_uint,
+                                                             C.POINTER(H265Params), C.POINTER(SaoPlaneCf), C.c_int, C.c_void_p]
         L.hevc_deblock_sao_h265_device_planes.argtypes = [C.c_void_p, C.POINTER(DevicePlanes), C.c_uint, C.c_uint, C.POINTER(H265Params),
                                                           C.POINTER(SaoPlane), C.c_int, C.c_void_p]
         L.hevcdbk_set_host_threads.argtypes = [C.c_void_p, C.c_uint]

@@ -193,6 +193,18 @@ DBK_HD int seg_qp_from_map(const uint8_t *map, int map_stride, int ctu_log2, int
     return q > 51 ? 51 : q;
 }
 
+/* the same with a scale per axis (chroma formats other than 4:2:0: SubWidthC / SubHeightC, H.265 Table 6-1) */
+DBK_HD int seg_qp_from_map_xy(const uint8_t *map, int map_stride, int ctu_log2, int sx, int sy, int lw, int lh,
+                              int xp, int yp, int xq, int yq)
+{
+    const int lxp = clampi(xp * sx, 0, lw - 1), lyp = clampi(yp * sy, 0, lh - 1);
+    const int lxq = clampi(xq * sx, 0, lw - 1), lyq = clampi(yq * sy, 0, lh - 1);
+    const int qpp = map[(lyp >> ctu_log2) * map_stride + (lxp >> ctu_log2)];
+    const int qpq = map[(lyq >> ctu_log2) * map_stride + (lxq >> ctu_log2)];
+    const int q = (qpp + qpq + 1) >> 1;
+    return q > 51 ? 51 : q;
+}
+
 /*
  * The same QPs with half the look-ups, for the packed kernels: an offset block lies across the corner where four 8x8-aligned
  * blocks meet, a map unit is at least 8x8 luma samples, so the eight positions the four segments ask for fall into FOUR map

@@ -31,6 +31,9 @@ struct hevcdbk_context {
     Growable dev_tmp; /* the deblocked planes between the two launches of hevc_deblock_sao_*_device where the fused kernel does not apply */
     hipEvent_t tmp_ev = nullptr; /* end of the last launch that read dev_tmp: the next user of the scratch plane waits for it */
     bool tmp_used = false;
+    Growable dev_sao; /* SAO parameters of 4:2:2 chroma planes rewritten for square CTBs (dbk_launch_sao_rows_x2) */
+    hipEvent_t sao_ev = nullptr; /* end of the last launch that read dev_sao */
+    bool sao_used = false;
     std::vector<hipEvent_t> timed_events;
     /* streaming operator: ring of kSeqSlots frames in flight */
     static constexpr int kSeqSlots = 3;

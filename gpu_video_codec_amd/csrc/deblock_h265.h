@@ -43,6 +43,28 @@ DBK_HD int h265_chroma_qp(int qpi)
     return qpi < 35 ? qpi - 1 : (qpi + 32) >> 1; /* 30..34 -> 29..33; 35..43 -> 33,34,34,35,35,36,36,37,37 */
 }
 
+/*
+ * Chroma formats (chroma_format_idc, 7.4.3.2.2): 0 = 4:0:0 (no chroma planes), 1 = 4:2:0, 2 = 4:2:2, 3 = 4:4:4, with
+ * SubWidthC / SubHeightC of Table 6-1.  The 4:2:0 paths above and below are the CF == 1 case and stay as they are; the other
+ * formats take the _cf templates, whose format is a compile-time operand.
+ */
+template <int CF>
+struct ChromaFmt {
+    static_assert(CF >= 1 && CF <= 3, "chroma planes exist for chroma_format_idc 1..3");
+    static constexpr int sx = CF == 3 ? 1 : 2; /* SubWidthC */
+    static constexpr int sy = CF == 1 ? 2 : 1; /* SubHeightC */
+};
+/* QpC of a chroma edge, 8.7.2.5.5: "If ChromaArrayType is equal to 1, QpC is determined as specified in Table 8-10 based on
+ * the index qPi; otherwise QpC = Min(qPi, 51)", with qPi = ((QpQ + QpP + 1) >> 1) + cQpPicOffset.  cQpPicOffset is
+ * pps_cb_qp_offset / pps_cr_qp_offset alone: the clause's note says it does not include slice_cb_qp_offset or CuQpOffsetC,
+ * so neither enters the deblocking of any format. */
+template <int CF>
+DBK_HD int h265_chroma_qp_cf(int qpi)
+{
+    if constexpr (CF == 1) return h265_chroma_qp(qpi);
+    else return qpi < 51 ? qpi : 51;
+}
+
 struct H265Prm {
     int tc_off;      /* slice_tc_offset_div2 << 1 */
     int beta_off;    /* slice_beta_offset_div2 << 1 */
@@ -150,6 +172,29 @@ DBK_HD void h265_chroma_segment(int (&v)[8][8], int entry, int qpl, const H265Pr
     h265_chroma_line<S, 3>(v, tc, entry, p.max_v);
 }
 
+/* the same for any chroma format: only QpC differs (the filter and tC' = tC table << (BitDepthC - 8) do not) */
+template <class S, int CF>
+DBK_HD void h265_chroma_segment_cf(int (&v)[8][8], int entry, int qpl, const H265Prm &p)
+{
+    if ((entry & kH265BsMask) != 2) return;
+    const int qpc = h265_chroma_qp_cf<CF>(qpl + p.c_qp_offset);
+    const int tc = h265_tc(clampi(qpc + 2 + p.tc_off, 0, 53)) << p.shift;
+    h265_chroma_line<S, 0>(v, tc, entry, p.max_v);
+    h265_chroma_line<S, 1>(v, tc, entry, p.max_v);
+    h265_chroma_line<S, 2>(v, tc, entry, p.max_v);
+    h265_chroma_line<S, 3>(v, tc, entry, p.max_v);
+}
+/* the four chroma segments of one offset block of a chroma plane of format CF (the chroma plane's own 8-sample grid: an offset
+ * block of the plane holds one crossing of that grid in every format) */
+template <int CF>
+DBK_HD void filter_block_h265_chroma_cf(int (&v)[8][8], const int (&entry)[4], const int (&qpl)[4], const H265Prm &p)
+{
+    h265_chroma_segment_cf<SegVer1, CF>(v, entry[0], qpl[0], p);
+    h265_chroma_segment_cf<SegVer2, CF>(v, entry[1], qpl[1], p);
+    h265_chroma_segment_cf<SegHor1, CF>(v, entry[2], qpl[2], p);
+    h265_chroma_segment_cf<SegHor2S, CF>(v, entry[3], qpl[3], p);
+}
+
 /* the four segments of one offset block; entry[] / qpl[] in the order ver1, ver2, hor1, hor2 */
 template <bool CHROMA>
 DBK_HD void filter_block_h265(int (&v)[8][8], const int (&entry)[4], const int (&qpl)[4], const H265Prm &p)
@@ -195,6 +240,20 @@ DBK_HD void h265_block_qpl(const uint8_t *map, int map_stride, int unit_log2, in
     qpl[1] = seg_qp_from_map(map, map_stride, unit_log2, sc, lw, lh, x0 + 3, y0 + 4, x0 + 4, y0 + 4);
     qpl[2] = seg_qp_from_map(map, map_stride, unit_log2, sc, lw, lh, x0 + 0, y0 + 3, x0 + 0, y0 + 4);
     qpl[3] = seg_qp_from_map(map, map_stride, unit_log2, sc, lw, lh, x0 + 4, y0 + 3, x0 + 4, y0 + 4);
+}
+/* the same with a scale per axis: QpY of the units covering luma sample (x * SubWidthC, y * SubHeightC) (8.7.2.5.5);
+ * lw / lh = the luma picture size */
+DBK_HD void h265_block_qpl_xy(const uint8_t *map, int map_stride, int unit_log2, int sx, int sy, int lw, int lh, int x0, int y0,
+                              int qp, int (&qpl)[4])
+{
+    if (!map) {
+        qpl[0] = qpl[1] = qpl[2] = qpl[3] = qp;
+        return;
+    }
+    qpl[0] = seg_qp_from_map_xy(map, map_stride, unit_log2, sx, sy, lw, lh, x0 + 3, y0 + 0, x0 + 4, y0 + 0);
+    qpl[1] = seg_qp_from_map_xy(map, map_stride, unit_log2, sx, sy, lw, lh, x0 + 3, y0 + 4, x0 + 4, y0 + 4);
+    qpl[2] = seg_qp_from_map_xy(map, map_stride, unit_log2, sx, sy, lw, lh, x0 + 0, y0 + 3, x0 + 0, y0 + 4);
+    qpl[3] = seg_qp_from_map_xy(map, map_stride, unit_log2, sx, sy, lw, lh, x0 + 4, y0 + 3, x0 + 4, y0 + 4);
 }
 /* the packed kernels' form: four map look-ups instead of eight (block_unit_qps, deblock_core.h); same values */
 DBK_HD void h265_block_qpl4(const uint8_t *map, int map_stride, int unit_log2, int sc, int lw, int lh, int x0, int y0, int (&qpl)[4])

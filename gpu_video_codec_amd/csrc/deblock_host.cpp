@@ -592,6 +592,8 @@ void hevcdbk_destroy(hevcdbk_context *ctx)
     if (ctx->dev_tmp.p) (void)hipFree(ctx->dev_tmp.p);
     if (ctx->dev_push.p) (void)hipFree(ctx->dev_push.p);
     if (ctx->tmp_ev) (void)hipEventDestroy(ctx->tmp_ev);
+    if (ctx->dev_sao.p) (void)hipFree(ctx->dev_sao.p);
+    if (ctx->sao_ev) (void)hipEventDestroy(ctx->sao_ev);
     for (auto &e : ctx->ev) if (e) (void)hipEventDestroy(e);
     for (auto &e : ctx->timed_events) if (e) (void)hipEventDestroy(e);
     for (int k = 0; k < hevcdbk_context::kSeqSlots; k++)

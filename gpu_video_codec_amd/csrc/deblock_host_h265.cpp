@@ -34,7 +34,33 @@ int hevcdbk_h265_derive_bs_device(hevcdbk_context *ctx, const hevcdbk_h265_units
     return hip_ok(ctx, e, "bS derivation launch") ? HEVCDBK_OK : HEVCDBK_ERR_HIP;
 }
 
+int hevcdbk_h265_derive_bs_device_cf(hevcdbk_context *ctx, const hevcdbk_h265_units *u, unsigned width, unsigned height,
+                                     int chroma_format_idc, uint8_t *vert_bs4, uint8_t *hor_bs4, uint8_t *chroma_vert_bs4,
+                                     uint8_t *chroma_hor_bs4, void *hip_stream)
+{
+    const int cf = chroma_format_idc;
+    if (cf == HEVCDBK_CHROMA_420)
+        return hevcdbk_h265_derive_bs_device(ctx, u, width, height, vert_bs4, hor_bs4, chroma_vert_bs4, chroma_hor_bs4, hip_stream);
+    if (!ctx || !u || !u->flags || !u->mv0 || !u->mv1 || !u->ref0 || !u->ref1 || !vert_bs4 || !hor_bs4) return HEVCDBK_ERR_ARG;
+    if (cf < HEVCDBK_CHROMA_400 || cf > HEVCDBK_CHROMA_444) return HEVCDBK_ERR_ARG;
+    if ((chroma_vert_bs4 != nullptr) != (chroma_hor_bs4 != nullptr)) return HEVCDBK_ERR_ARG;
+    if (cf == HEVCDBK_CHROMA_400 && chroma_vert_bs4) return HEVCDBK_ERR_ARG;
+    if (width == 0 || height == 0 || width % 8 != 0 || height % 8 != 0) return HEVCDBK_ERR_DIMENSIONS;
+    if (chroma_vert_bs4 && cf == HEVCDBK_CHROMA_422 && width % 16 != 0) return HEVCDBK_ERR_ARG; /* chroma plane W/2: 8-sample grid */
+    if (int rc = bind(ctx)) return rc;
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->compute;
+    hipError_t e = dbk_launch_h265_bs(u->flags, u->mv0, u->mv1, u->ref0, u->ref1, (int)width, (int)height, vert_bs4, hor_bs4,
+                                      nullptr, nullptr, s);
+    if (e == hipSuccess && chroma_vert_bs4)
+        e = dbk_launch_h265_chroma_bs_cf(vert_bs4, hor_bs4, (int)width, (int)height, cf, chroma_vert_bs4, chroma_hor_bs4, s);
+    return hip_ok(ctx, e, "bS derivation launch") ? HEVCDBK_OK : HEVCDBK_ERR_HIP;
+}
+
 namespace {
+
+/* SubWidthC / SubHeightC of chroma_format_idc 1..3 (H.265 Table 6-1) */
+inline unsigned sub_w(int cf) { return cf == HEVCDBK_CHROMA_444 ? 1u : 2u; }
+inline unsigned sub_h(int cf) { return cf == HEVCDBK_CHROMA_420 ? 2u : 1u; }
 
 int h265_args(const hevcdbk_device_planes *planes, int c_idx, unsigned qp, const hevcdbk_h265_params *prm, DbkH265Args &h)
 {
@@ -56,7 +82,16 @@ int h265_args(const hevcdbk_device_planes *planes, int c_idx, unsigned qp, const
     return HEVCDBK_OK;
 }
 
-int launch_h265(hevcdbk_context *ctx, const DbkH265Args &h0, int sample_bytes, bool chroma, int variant, hipStream_t s)
+/* h265_args with the picture's chroma format: 4:0:0 has no chroma plane */
+int h265_args_cf(const hevcdbk_device_planes *planes, int c_idx, int cf, unsigned qp, const hevcdbk_h265_params *prm, DbkH265Args &h)
+{
+    if (cf < HEVCDBK_CHROMA_400 || cf > HEVCDBK_CHROMA_444) return HEVCDBK_ERR_ARG;
+    if (cf == HEVCDBK_CHROMA_400 && (c_idx != 0 || (planes && planes->is_chroma))) return HEVCDBK_ERR_ARG;
+    return h265_args(planes, c_idx, qp, prm, h);
+}
+
+/* cf = chroma_format_idc of a chroma plane (1 for luma: the format does not enter luma) */
+int launch_h265(hevcdbk_context *ctx, const DbkH265Args &h0, int sample_bytes, bool chroma, int variant, hipStream_t s, int cf = 1)
 {
     const int map = variant & HEVCDBK_MAP_MASK; /* as in dbkh::launch */
     variant &= ~HEVCDBK_MAP_MASK;
@@ -67,8 +102,18 @@ int launch_h265(hevcdbk_context *ctx, const DbkH265Args &h0, int sample_bytes, b
 #endif
     DbkH265Args h = h0;
     h.base.map_override = map == HEVCDBK_MAP_ROWS ? 1 : (map == HEVCDBK_MAP_LINEAR ? 2 : (map == 0x300 ? 3 : (map == 0x400 ? 4 : (map == 0x500 ? 5 : (map == 0x600 ? 6 : 0)))));
-    const bool can_pack = dbk_packed_h265_supports(h, sample_bytes, chroma);
     hipError_t e;
+    if (chroma && cf != HEVCDBK_CHROMA_420) {
+        /* 4:2:2 / 4:4:4 chroma: the packed kernels (one QP: the 4:2:0 kernels with QpC folded into their scalar tc; a QP map: the
+         * format's own instantiations), the 32-bit kernel for every operand kind */
+        const bool pack = dbk_packed_h265_supports(h, sample_bytes, true);
+        if (variant == HEVCDBK_KERNEL_PACKED && !pack) return HEVCDBK_ERR_UNSUPPORTED;
+        if (variant != HEVCDBK_KERNEL_PACKED && variant != HEVCDBK_KERNEL_GENERIC && variant != HEVCDBK_KERNEL_AUTO) return HEVCDBK_ERR_ARG;
+        if (variant != HEVCDBK_KERNEL_GENERIC && pack) e = dbk_launch_packed_h265_cf(h, sample_bytes, true, cf, s);
+        else e = dbk_launch_h265_cf(h, sample_bytes, cf, s);
+        return hip_ok(ctx, e, "kernel launch") ? HEVCDBK_OK : HEVCDBK_ERR_HIP;
+    }
+    const bool can_pack = dbk_packed_h265_supports(h, sample_bytes, chroma);
     if (variant == HEVCDBK_KERNEL_PACKED) {
         if (!can_pack) return HEVCDBK_ERR_UNSUPPORTED;
         e = dbk_launch_packed_h265(h, sample_bytes, chroma, s);
@@ -95,22 +140,44 @@ int hevc_deblocking_filter_h265_device(hevcdbk_context *ctx, const hevcdbk_devic
     return launch_h265(ctx, h, (int)planes->sample_bytes, c_idx != 0, kernel_variant, s);
 }
 
+int hevcdbk_h265_filter_device_cf(hevcdbk_context *ctx, const hevcdbk_device_planes *planes, int c_idx, int chroma_format_idc,
+                                          unsigned qp, const hevcdbk_h265_params *params, int kernel_variant, void *hip_stream)
+{
+    if (!ctx) return HEVCDBK_ERR_ARG;
+    DbkH265Args h;
+    if (int rc = h265_args_cf(planes, c_idx, chroma_format_idc, qp, params, h)) return rc;
+    if (int rc = bind(ctx)) return rc;
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->compute;
+    return launch_h265(ctx, h, (int)planes->sample_bytes, c_idx != 0, kernel_variant, s, c_idx != 0 ? chroma_format_idc : 1);
+}
+
 int hevc_deblocking_filter_h265(hevcdbk_context *ctx, hevcdbk_frame *frame, const hevcdbk_h265_units *units,
                                 const hevcdbk_bs *bs4, const hevcdbk_qp *qp, const hevcdbk_h265_params *params,
                                 hevcdbk_timing *timing)
 {
+    return hevcdbk_h265_filter_frame_cf(ctx, frame, HEVCDBK_CHROMA_420, units, bs4, qp, params, timing);
+}
+
+int hevcdbk_h265_filter_frame_cf(hevcdbk_context *ctx, hevcdbk_frame *frame, int chroma_format_idc, const hevcdbk_h265_units *units,
+                                   const hevcdbk_bs *bs4, const hevcdbk_qp *qp, const hevcdbk_h265_params *params,
+                                   hevcdbk_timing *timing)
+{
+    const int cf = chroma_format_idc;
     if (!ctx || !frame || !qp || !frame->plane[0] || (units != nullptr) == (bs4 != nullptr)) return HEVCDBK_ERR_ARG;
+    if (cf < HEVCDBK_CHROMA_400 || cf > HEVCDBK_CHROMA_444) return HEVCDBK_ERR_ARG;
     if (bad_depth(frame->bit_depth, frame->sample_bytes)) return HEVCDBK_ERR_ARG;
     const unsigned W = frame->width, H = frame->height, sb = frame->sample_bytes;
     if (W == 0 || H == 0 || W % 8 != 0 || H % 8 != 0) return HEVCDBK_ERR_DIMENSIONS;
     const bool chroma = frame->plane[1] && frame->plane[2];
-    if (chroma && ((W / 2) % 8 != 0 || (H / 2) % 8 != 0)) return HEVCDBK_ERR_DIMENSIONS;
+    if (cf == HEVCDBK_CHROMA_400 && (frame->plane[1] || frame->plane[2])) return HEVCDBK_ERR_ARG;
+    const unsigned cw = cf ? W / sub_w(cf) : 0, ch = cf ? H / sub_h(cf) : 0;
+    if (chroma && (cw % 8 != 0 || ch % 8 != 0)) return cf == HEVCDBK_CHROMA_420 ? HEVCDBK_ERR_DIMENSIONS : HEVCDBK_ERR_ARG;
     const int npl = chroma ? 3 : 1;
-    const unsigned pw[3] = {W, W / 2, W / 2}, ph[3] = {H, H / 2, H / 2};
+    const unsigned pw[3] = {W, cw, cw}, ph[3] = {H, ch, ch};
     for (int i = 0; i < npl; i++)
         if (frame->pitch[i] < (size_t)pw[i] * sb) return HEVCDBK_ERR_ARG;
     const size_t nv = hevcdbk_h265_num_vert_bs(W, H), nh = hevcdbk_h265_num_hor_bs(W, H);
-    const size_t ncv = chroma ? hevcdbk_h265_num_vert_bs(W / 2, H / 2) : 0, nch = chroma ? hevcdbk_h265_num_hor_bs(W / 2, H / 2) : 0;
+    const size_t ncv = chroma ? hevcdbk_h265_num_vert_bs(cw, ch) : 0, nch = chroma ? hevcdbk_h265_num_hor_bs(cw, ch) : 0;
     if (bs4) {
         if (!bs4->vert || !bs4->hor) return HEVCDBK_ERR_ARG;
         if (bs4->n_vert != nv || bs4->n_hor != nh) return HEVCDBK_ERR_BS_SIZE;
@@ -173,8 +240,15 @@ int hevc_deblocking_filter_h265(hevcdbk_context *ctx, hevcdbk_frame *frame, cons
     HIP_TRY(ctx, hipEventRecord(ev[1], s));
     uint8_t *dcv = chroma ? dbs + nv + nh : nullptr, *dch = chroma ? dbs + nv + nh + ncv : nullptr;
     hipError_t e;
-    if (units) e = dbk_launch_h265_bs(dun + 16 * U, dun + 8 * U, dun + 12 * U, dun, dun + 4 * U, (int)W, (int)H, dbs, dbs + nv, dcv, dch, s);
-    else e = chroma ? dbk_launch_h265_chroma_bs(dbs, dbs + nv, (int)W, (int)H, dcv, dch, s) : hipSuccess;
+    if (cf == HEVCDBK_CHROMA_420 || !chroma) {
+        if (units) e = dbk_launch_h265_bs(dun + 16 * U, dun + 8 * U, dun + 12 * U, dun, dun + 4 * U, (int)W, (int)H, dbs, dbs + nv, dcv, dch, s);
+        else e = chroma ? dbk_launch_h265_chroma_bs(dbs, dbs + nv, (int)W, (int)H, dcv, dch, s) : hipSuccess;
+    } else {
+        e = units ? dbk_launch_h265_bs(dun + 16 * U, dun + 8 * U, dun + 12 * U, dun, dun + 4 * U, (int)W, (int)H, dbs, dbs + nv, nullptr,
+                                       nullptr, s)
+                  : hipSuccess;
+        if (e == hipSuccess) e = dbk_launch_h265_chroma_bs_cf(dbs, dbs + nv, (int)W, (int)H, cf, dcv, dch, s);
+    }
     if (!hip_ok(ctx, e, "bS derivation launch")) return HEVCDBK_ERR_HIP;
     for (int i = 0; i < npl; i++) {
         hevcdbk_device_planes p;
@@ -189,7 +263,7 @@ int hevc_deblocking_filter_h265(hevcdbk_context *ctx, hevcdbk_frame *frame, cons
         p.qp_map = dmap; p.qp_map_stride = qp->map_stride; p.ctu_log2 = qp->ctu_log2;
         DbkH265Args h;
         if (int rc = h265_args(&p, i, qp->qp, params, h)) return rc;
-        if (int rc = launch_h265(ctx, h, (int)sb, i != 0, HEVCDBK_KERNEL_AUTO, s)) return rc;
+        if (int rc = launch_h265(ctx, h, (int)sb, i != 0, HEVCDBK_KERNEL_AUTO, s, i != 0 ? cf : 1)) return rc;
     }
     HIP_TRY(ctx, hipEventRecord(ev[2], s));
     if (!dpush) HIP_TRY(ctx, hipMemcpyAsync(ring, ctx->dev[0].p, frame_bytes, hipMemcpyDeviceToHost, s));
@@ -240,6 +314,16 @@ int sao_args(const hevcdbk_device_planes *p, const hevcdbk_sao_ctb *params, unsi
     a.ctb_log2 = (int)ctb_log2;
     a.keep = keep; a.keep_stride = (int)keep_stride; a.keep_frame_stride = (long long)keep_frame_stride;
     return HEVCDBK_OK;
+}
+
+/* sao_args for CTBs of (1 << ctb_log2_w) x (1 << ctb_log2_h) samples: square, or twice as tall as wide (4:2:2 chroma) */
+int sao_args_cf(const hevcdbk_device_planes *p, const hevcdbk_sao_ctb *params, unsigned params_stride, size_t params_frame_stride,
+                unsigned ctb_log2_w, unsigned ctb_log2_h, const uint8_t *keep, unsigned keep_stride, size_t keep_frame_stride,
+                DbkSaoArgs &a)
+{
+    if (ctb_log2_h != ctb_log2_w && ctb_log2_h != ctb_log2_w + 1) return HEVCDBK_ERR_ARG;
+    if (ctb_log2_h < 3 || ctb_log2_h > 6) return HEVCDBK_ERR_ARG;
+    return sao_args(p, params, params_stride, params_frame_stride, ctb_log2_w, keep, keep_stride, keep_frame_stride, a);
 }
 
 /* the two-launch form of deblocking + SAO: the deblocked planes go through ctx->dev_tmp (same pitch and frame stride).
@@ -302,7 +386,80 @@ int deblock_sao_plane_h265(hevcdbk_context *ctx, const hevcdbk_device_planes *p,
     return tmp_done(ctx, s);
 }
 
+/* 4:2:2 chroma planes (ctb_log2_h[i] = sa[i].ctb_log2 + 1): their SAO parameters rewritten as those of square CTBs into the
+ * context's scratch (dbk_launch_sao_rows_x2), so that every kernel after this sees square CTBs.  Like dev_tmp, the scratch is
+ * fenced by an event: the next user waits for the last launch that read it (sao_done) */
+int sao_square_params(hevcdbk_context *ctx, DbkSaoArgs *sa, const unsigned *ctb_log2_h, unsigned n, hipStream_t s)
+{
+    size_t entries = 0;
+    for (unsigned i = 0; i < n; i++)
+        if (ctb_log2_h[i] != (unsigned)sa[i].ctb_log2) entries += dbk_sao_rows_x2_entries(sa[i]);
+    if (entries == 0) return HEVCDBK_OK;
+    const size_t bytes = entries * sizeof(DbkSaoCtb);
+    if (!ctx->sao_ev) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->sao_ev, hipEventDisableTiming));
+    if (ctx->sao_used) {
+        if (ctx->dev_sao.cap < bytes) HIP_TRY(ctx, hipEventSynchronize(ctx->sao_ev)); /* about to free it */
+        else HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->sao_ev, 0));
+    }
+    if (int rc = grow_device(ctx, ctx->dev_sao, bytes)) return rc;
+    DbkSaoCtb *dst = (DbkSaoCtb *)ctx->dev_sao.p;
+    for (unsigned i = 0; i < n; i++)
+        if (ctb_log2_h[i] != (unsigned)sa[i].ctb_log2) {
+            const size_t k = dbk_sao_rows_x2_entries(sa[i]);
+            if (!hip_ok(ctx, dbk_launch_sao_rows_x2(sa[i], dst, s), "SAO parameter launch")) return HEVCDBK_ERR_HIP;
+            dst += k;
+        }
+    return HEVCDBK_OK;
+}
+int sao_done(hevcdbk_context *ctx, hipStream_t s)
+{
+    if (!ctx->sao_ev) return HEVCDBK_OK; /* no 4:2:2 plane ever used the scratch */
+    HIP_TRY(ctx, hipEventRecord(ctx->sao_ev, s));
+    ctx->sao_used = true;
+    return HEVCDBK_OK;
+}
+
+/* the fused kernel takes plane p (every chroma format, one QP or a QP map: the conditions of deblock_sao_plane_h265) */
+bool fused_can(const DbkH265Args &h, const DbkSaoArgs &sa, const hevcdbk_device_planes *p, int c_idx)
+{
+    return dbk_packed_h265_supports(h, (int)p->sample_bytes, c_idx != 0) && dbk_deblock_sao_supports(h.base, sa, (int)p->sample_bytes, c_idx != 0);
+}
+
+/* deblock_sao_plane_h265 for a plane of a picture in chroma format cf (luma: cf 1), square CTBs (after sao_square_params) */
+int deblock_sao_plane_h265_cf(hevcdbk_context *ctx, const hevcdbk_device_planes *p, int c_idx, int cf, unsigned qp,
+                              const hevcdbk_h265_params *prm, DbkH265Args &h, DbkSaoArgs &sa, int fused, hipStream_t s)
+{
+    if (cf == HEVCDBK_CHROMA_420 || c_idx == 0) return deblock_sao_plane_h265(ctx, p, c_idx, qp, prm, h, sa, fused, s);
+    const bool can = fused_can(h, sa, p, c_idx);
+    if (fused == HEVCDBK_FUSED_ON && !can) return HEVCDBK_ERR_UNSUPPORTED;
+    if (can && fused != HEVCDBK_FUSED_OFF)
+        return hip_ok(ctx, dbk_launch_deblock_sao_h265_cf(h, sa, (int)p->sample_bytes, true, cf, s), "fused deblocking + SAO launch")
+                   ? HEVCDBK_OK : HEVCDBK_ERR_HIP;
+    hevcdbk_device_planes first, second;
+    if (int rc = tmp_planes(ctx, p, s, first, second)) return rc;
+    if (int rc = h265_args(&first, c_idx, qp, prm, h)) return rc;
+    if (int rc = launch_h265(ctx, h, (int)p->sample_bytes, true, HEVCDBK_KERNEL_AUTO, s, cf)) return rc;
+    sa.src = (const uint8_t *)second.src;
+    if (!hip_ok(ctx, dbk_launch_sao(sa, (int)p->sample_bytes, s), "SAO launch")) return HEVCDBK_ERR_HIP;
+    return tmp_done(ctx, s);
+}
+
 } /* namespace */
+
+int hevcdbk_sao_filter_device_cf(hevcdbk_context *ctx, const hevcdbk_device_planes *p, const hevcdbk_sao_ctb *params,
+                              unsigned params_stride, size_t params_frame_stride, unsigned ctb_log2_w, unsigned ctb_log2_h,
+                              const uint8_t *keep, unsigned keep_stride, size_t keep_frame_stride, void *hip_stream)
+{
+    if (!ctx) return HEVCDBK_ERR_ARG;
+    DbkSaoArgs a;
+    if (int rc = sao_args_cf(p, params, params_stride, params_frame_stride, ctb_log2_w, ctb_log2_h, keep, keep_stride, keep_frame_stride, a))
+        return rc;
+    if (int rc = bind(ctx)) return rc;
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->compute;
+    if (int rc = sao_square_params(ctx, &a, &ctb_log2_h, 1, s)) return rc;
+    if (!hip_ok(ctx, dbk_launch_sao(a, (int)p->sample_bytes, s), "SAO launch")) return HEVCDBK_ERR_HIP;
+    return ctb_log2_h != ctb_log2_w ? sao_done(ctx, s) : HEVCDBK_OK;
+}
 
 int hevc_sao_filter_device(hevcdbk_context *ctx, const hevcdbk_device_planes *p, const hevcdbk_sao_ctb *params,
                            unsigned params_stride, size_t params_frame_stride, unsigned ctb_log2, const uint8_t *keep,
@@ -412,6 +569,89 @@ int hevc_deblock_sao_h265_device_planes(hevcdbk_context *ctx, const hevcdbk_devi
     for (unsigned i = 0; i < n_planes; i++)
         if (int rc = deblock_sao_plane_h265(ctx, &planes[i], (int)i, qp, prm, h[i], sa[i], fused, s)) return rc;
     return HEVCDBK_OK;
+}
+
+/* ---- chroma formats other than 4:2:0 (chroma_format_idc operand) ---------------------------------------------- */
+
+int hevcdbk_h265_deblock_sao_device_cf(hevcdbk_context *ctx, const hevcdbk_device_planes *p, int c_idx, int chroma_format_idc, unsigned qp,
+                                    const hevcdbk_h265_params *prm, const hevcdbk_sao_ctb *params, unsigned params_stride,
+                                    size_t params_frame_stride, unsigned ctb_log2_w, unsigned ctb_log2_h, const uint8_t *keep,
+                                    unsigned keep_stride, size_t keep_frame_stride, int fused, void *hip_stream)
+{
+    if (!ctx || (fused != HEVCDBK_FUSED_AUTO && fused != HEVCDBK_FUSED_OFF && fused != HEVCDBK_FUSED_ON)) return HEVCDBK_ERR_ARG;
+    DbkSaoArgs sa;
+    if (int rc = sao_args_cf(p, params, params_stride, params_frame_stride, ctb_log2_w, ctb_log2_h, keep, keep_stride, keep_frame_stride, sa))
+        return rc;
+    DbkH265Args h;
+    if (int rc = h265_args_cf(p, c_idx, chroma_format_idc, qp, prm, h)) return rc;
+    if (fused == HEVCDBK_FUSED_ON && !fused_can(h, sa, p, c_idx)) return HEVCDBK_ERR_UNSUPPORTED; /* before any launch */
+    if (int rc = bind(ctx)) return rc;
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->compute;
+    if (int rc = sao_square_params(ctx, &sa, &ctb_log2_h, 1, s)) return rc;
+    const int rc = deblock_sao_plane_h265_cf(ctx, p, c_idx, c_idx != 0 ? chroma_format_idc : 1, qp, prm, h, sa, fused, s);
+    if (ctb_log2_h != ctb_log2_w)
+        if (int rc2 = sao_done(ctx, s)) return rc ? rc : rc2; /* the parameter launch is fenced whatever followed it */
+    return rc;
+}
+
+int hevcdbk_h265_deblock_sao_device_planes_cf(hevcdbk_context *ctx, const hevcdbk_device_planes *planes, unsigned n_planes,
+                                           int chroma_format_idc, unsigned qp, const hevcdbk_h265_params *prm,
+                                           const hevcdbk_sao_plane_cf *sao, int fused, void *hip_stream)
+{
+    const int cf = chroma_format_idc;
+    if (!ctx || !planes || !sao || n_planes == 0 || n_planes > 3 || cf < HEVCDBK_CHROMA_400 || cf > HEVCDBK_CHROMA_444 ||
+        (fused != HEVCDBK_FUSED_AUTO && fused != HEVCDBK_FUSED_OFF && fused != HEVCDBK_FUSED_ON))
+        return HEVCDBK_ERR_ARG;
+    if (cf == HEVCDBK_CHROMA_400 && n_planes > 1) return HEVCDBK_ERR_ARG;
+    if (cf == HEVCDBK_CHROMA_420) { /* square CTBs: exactly the 4:2:0 entry, checks included */
+        bool square = true;
+        hevcdbk_sao_plane sq[3];
+        for (unsigned i = 0; i < n_planes; i++) {
+            square = square && sao[i].ctb_log2_w == sao[i].ctb_log2_h;
+            sq[i] = {sao[i].params, sao[i].params_stride, sao[i].params_frame_stride, sao[i].ctb_log2_w, sao[i].keep, sao[i].keep_stride,
+                     sao[i].keep_frame_stride};
+        }
+        if (square) return hevc_deblock_sao_h265_device_planes(ctx, planes, n_planes, qp, prm, sq, fused, hip_stream);
+    }
+    DbkH265Args h[3];
+    DbkSaoArgs sa[3];
+    bool can[3] = {false, false, false}, rect = false;
+    unsigned log2_h[3] = {0, 0, 0};
+    bool one = n_planes >= 2 && fused != HEVCDBK_FUSED_OFF && !planes[0].is_chroma;
+    for (unsigned i = 0; i < n_planes; i++) {
+        if (int rc = sao_args_cf(&planes[i], sao[i].params, sao[i].params_stride, sao[i].params_frame_stride, sao[i].ctb_log2_w,
+                                 sao[i].ctb_log2_h, sao[i].keep, sao[i].keep_stride, sao[i].keep_frame_stride, sa[i]))
+            return rc;
+        if (int rc = h265_args_cf(&planes[i], (int)i, cf, qp, prm, h[i])) return rc; /* c_idx = plane index: 0 Y, 1 Cb, 2 Cr */
+        if (planes[i].n_frames != planes[0].n_frames) return HEVCDBK_ERR_ARG;
+        /* chroma planes in the format's geometry of the luma plane (when planes[0] is the luma plane; 4:2:0 as its own entry) */
+        if (i > 0 && !planes[0].is_chroma && cf != HEVCDBK_CHROMA_420 &&
+            (planes[i].plane_w * sub_w(cf) != planes[0].plane_w || planes[i].plane_h * sub_h(cf) != planes[0].plane_h))
+            return HEVCDBK_ERR_ARG;
+        log2_h[i] = sao[i].ctb_log2_h;
+        rect = rect || sao[i].ctb_log2_h != sao[i].ctb_log2_w;
+        can[i] = fused_can(h[i], sa[i], &planes[i], (int)i);
+        one = one && (i == 0 || planes[i].is_chroma) && planes[i].sample_bytes == planes[0].sample_bytes &&
+              planes[i].bit_depth == planes[0].bit_depth && (h[i].base.qp_map != nullptr) == (h[0].base.qp_map != nullptr) && can[i];
+    }
+    if (!one && fused == HEVCDBK_FUSED_ON)
+        for (unsigned i = 0; i < n_planes; i++)
+            if (!can[i]) return HEVCDBK_ERR_UNSUPPORTED;
+    if (int rc = bind(ctx)) return rc;
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->compute;
+    if (int rc = sao_square_params(ctx, sa, log2_h, n_planes, s)) return rc;
+    int rc = HEVCDBK_OK;
+    if (one) {
+        if (!hip_ok(ctx, dbk_launch_deblock_sao_multi_h265_cf(h, sa, (int)n_planes, (int)planes[0].sample_bytes, cf, s),
+                    "fused deblocking + SAO launch"))
+            rc = HEVCDBK_ERR_HIP;
+    } else {
+        for (unsigned i = 0; i < n_planes && rc == HEVCDBK_OK; i++)
+            rc = deblock_sao_plane_h265_cf(ctx, &planes[i], (int)i, i != 0 ? cf : 1, qp, prm, h[i], sa[i], fused, s);
+    }
+    if (rect)
+        if (int rc2 = sao_done(ctx, s)) return rc ? rc : rc2; /* the parameter launch is fenced whatever followed it */
+    return rc;
 }
 
 } /* extern "C" */

@@ -124,6 +124,14 @@ hipError_t dbk_launch_h265_bs(const void *flags, const void *mv0, const void *mv
                               int h, uint8_t *vert, uint8_t *hor, uint8_t *cvert, uint8_t *chor, hipStream_t stream);
 hipError_t dbk_launch_h265_chroma_bs(const uint8_t *vert, const uint8_t *hor, int w, int h, uint8_t *cvert, uint8_t *chor,
                                      hipStream_t stream);
+/* chroma formats (chroma_format_idc 1 = 4:2:0, 2 = 4:2:2, 3 = 4:4:4; deblock_h265.h ChromaFmt): a chroma plane of format 2 or 3
+ * through the 32-bit kernel (format 1: dbk_launch_h265), and the chroma arrays of a w x h luma picture in that format */
+hipError_t dbk_launch_h265_cf(const DbkH265Args &h, int sample_bytes, int chroma_format, hipStream_t stream);
+hipError_t dbk_launch_h265_chroma_bs_cf(const uint8_t *vert, const uint8_t *hor, int w, int h, int chroma_format, uint8_t *cvert,
+                                        uint8_t *chor, hipStream_t stream);
+/* the packed one-QP kernels for a chroma plane of any format: with one QP the format enters only through QpC (Table 8-10 for
+ * 4:2:0, Min(qPi, 51) otherwise), which the launcher turns into the kernel's scalar tc; the kernels are the 4:2:0 ones */
+hipError_t dbk_launch_packed_h265_cf(const DbkH265Args &h, int sample_bytes, bool chroma, int chroma_format, hipStream_t stream);
 
 /* ---- sample adaptive offset (H.265 clause 8.7.3), sao.hip ---- */
 struct DbkSaoCtb {
@@ -146,6 +154,10 @@ struct DbkSaoArgs {
     long long keep_frame_stride;
 };
 hipError_t dbk_launch_sao(const DbkSaoArgs &a, int sample_bytes, hipStream_t stream);
+/* CTBs of (1 << a.ctb_log2) x (2 << a.ctb_log2) samples (4:2:2 chroma): writes the parameters as those of square CTBs of
+ * (1 << a.ctb_log2) -- every row twice -- into dst (dbk_sao_rows_x2_entries(a) entries, device memory) and points a at them */
+size_t dbk_sao_rows_x2_entries(const DbkSaoArgs &a);
+hipError_t dbk_launch_sao_rows_x2(DbkSaoArgs &a, DbkSaoCtb *dst, hipStream_t stream);
 
 /* ---- deblocking + SAO in one kernel (deblock_sao_fused.inc): 8-bit planes, scalar QP; d.src -> s.dst, d.dst and s.src unused ---- */
 /* tile numbering of the fused kernel (filled by its launchers): a 1-D grid, workgroups renumbered so that each XCD gets a
@@ -165,7 +177,7 @@ struct DbkFusedH265Args {
     DbkSaoArgs s;
     DbkFusedGrid g;
 };
-/* the planes of a 4:2:0 batch in one fused launch: the grid is the planes' grids one after the other */
+/* the planes of a batch in one fused launch (4:2:0; spec-exact mode also 4:4:4 with one QP): the grid is the planes' grids one after the other */
 struct DbkFusedMultiArgs {
     DbkFusedArgs pl[3];
     uint32_t wg_end[3]; /* cumulative grid sizes: blockIdx.x < wg_end[i] belongs to plane <= i */
@@ -182,4 +194,10 @@ hipError_t dbk_launch_deblock_sao_h265(const DbkH265Args &h, const DbkSaoArgs &s
  * and bit depth, one frame count */
 hipError_t dbk_launch_deblock_sao_multi(const DbkArgs *d, const DbkSaoArgs *s, int n, int sample_bytes, hipStream_t stream);
 hipError_t dbk_launch_deblock_sao_multi_h265(const DbkH265Args *h, const DbkSaoArgs *s, int n, int sample_bytes, hipStream_t stream);
+/* the same for the chroma planes of 4:2:2 / 4:4:4 pictures with one QP (QpC by Min(qPi, 51), folded into the scalar tc as above;
+ * square CTBs: 4:2:2 parameters through dbk_launch_sao_rows_x2 first) */
+hipError_t dbk_launch_deblock_sao_h265_cf(const DbkH265Args &h, const DbkSaoArgs &s, int sample_bytes, bool chroma, int chroma_format,
+                                          hipStream_t stream);
+hipError_t dbk_launch_deblock_sao_multi_h265_cf(const DbkH265Args *h, const DbkSaoArgs *s, int n, int sample_bytes, int chroma_format,
+                                                hipStream_t stream);
 

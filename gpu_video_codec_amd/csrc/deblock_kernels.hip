@@ -257,7 +257,7 @@ __device__ __forceinline__ void load_bs_buffer_h265(const DbkArgs &a, int f, int
 /* per-segment tc / beta of a lane's block: the scalar-QP values, or -- QPMAP -- looked up from the per-CTU
  * map exactly as the generic kernel and the oracle do (QP = (QpP + QpQ + 1) >> 1 of the CTUs holding P0 / Q0
  * of the segment's first line) */
-template <bool CHROMA>
+template <bool CHROMA, int CF = 1>
 __device__ __forceinline__ void block_unit_qps_dev(const DbkArgs &a, int f, int by, int bx, int (&u)[4]);
 template <bool QPMAP, bool CHROMA>
 __device__ __forceinline__ dbk::BlockQp block_qp(const DbkArgs &a, int f, int by, int bx)
@@ -287,13 +287,15 @@ __device__ __forceinline__ dbk::BlockQp block_qp(const DbkArgs &a, int f, int by
  * the block's centre) through a buffer resource: 32-bit offsets from ONE 24-bit multiply-add (map rows and strides are far below
  * 2^24: the entry points check the stride) instead of two 32 x 32-bit multiplies -- quarter rate on this hardware -- and four
  * 64-bit address sums.  Same clamping, same values. */
-template <bool CHROMA>
+template <bool CHROMA, int CF>
 __device__ __forceinline__ void block_unit_qps_dev(const DbkArgs &a, int f, int by, int bx, int (&u)[4])
 {
-    const int sc = CHROMA ? 2 : 1, lw = a.plane_w * sc, lh = a.plane_h * sc;
+    /* chroma of a picture of chroma_format_idc CF reads luma (x * SubWidthC, y * SubHeightC); CF 1 (4:2:0): sx = sy = 2 */
+    constexpr int sx = CHROMA ? (CF == 3 ? 1 : 2) : 1, sy = CHROMA ? (CF == 1 ? 2 : 1) : 1;
+    const int lw = a.plane_w * sx, lh = a.plane_h * sy;
     const int x0 = bx * 8 - 4, y0 = by * 8 - 4;
-    const int xl = dbk::clampi((x0 + 3) * sc, 0, lw - 1) >> a.ctu_log2, xr = dbk::clampi((x0 + 4) * sc, 0, lw - 1) >> a.ctu_log2;
-    const int yt = dbk::clampi((y0 + 3) * sc, 0, lh - 1) >> a.ctu_log2, yb = dbk::clampi((y0 + 4) * sc, 0, lh - 1) >> a.ctu_log2;
+    const int xl = dbk::clampi((x0 + 3) * sx, 0, lw - 1) >> a.ctu_log2, xr = dbk::clampi((x0 + 4) * sx, 0, lw - 1) >> a.ctu_log2;
+    const int yt = dbk::clampi((y0 + 3) * sy, 0, lh - 1) >> a.ctu_log2, yb = dbk::clampi((y0 + 4) * sy, 0, lh - 1) >> a.ctu_log2;
     const __amdgpu_buffer_rsrc_t rm = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<uint8_t *>(a.qp_map) + (long long)f * a.map_frame_stride, 0, 0x80000000u, 0x00020000);
     const uint32_t ot = __umul24((uint32_t)yt, (uint32_t)a.map_stride);
@@ -304,11 +306,11 @@ __device__ __forceinline__ void block_unit_qps_dev(const DbkArgs &a, int f, int 
     u[3] = __builtin_amdgcn_raw_buffer_load_b8(rm, ob + (uint32_t)xr, 0, 0);
 }
 /* the spec-exact mode's four segment QPs from them (dbk::h265_block_qpl4) */
-template <bool CHROMA>
+template <bool CHROMA, int CF = 1>
 __device__ __forceinline__ void block_qpl4_dev(const DbkArgs &a, int f, int by, int bx, int (&qpl)[4])
 {
     int q[4];
-    block_unit_qps_dev<CHROMA>(a, f, by, bx, q);
+    block_unit_qps_dev<CHROMA, CF>(a, f, by, bx, q);
     qpl[0] = dbk::seg_qp_avg(q[0], q[1]); /* ver1: above-left | above-right */
     qpl[1] = dbk::seg_qp_avg(q[2], q[3]); /* ver2: below-left | below-right */
     qpl[2] = dbk::seg_qp_avg(q[0], q[2]); /* hor1: above-left / below-left */
@@ -363,7 +365,7 @@ __device__ __forceinline__ const DBK_LDS uint32_t *ktab_setup_h265(uint32_t *lds
  *   with wave-uniform branches.
  * MODE 0 = filter, MODE 1 = diagnostic copy (same loads/stores, no arithmetic).
  */
-template <bool CHROMA, int MODE, bool NT, int PATH, bool QPMAP>
+template <bool CHROMA, int MODE, bool NT, int PATH, bool QPMAP, int CF = 1 /* chroma_format_idc of a spec-exact chroma plane */>
 __device__ __forceinline__ void packed_body(const DbkArgs &a, int by, int f, int bx, bool active, int by0,
                                             const DbkH265Args *hx = nullptr /* MODE 2 only */,
                                             uint32_t *ktab_lds = nullptr /* QPMAP luma: LDS for the workgroup's operand table */)
@@ -537,13 +539,13 @@ __device__ __forceinline__ void packed_body(const DbkArgs &a, int by, int f, int
         dbk::H265Seg sg;
         if constexpr (QPMAP) {
             int qpl[4];
-            block_qpl4_dev<CHROMA>(a, f, by, active ? bx : 0, qpl);
+            block_qpl4_dev<CHROMA, CF>(a, f, by, active ? bx : 0, qpl);
             const dbk::H265Prm prm = {hx->tc_off, hx->beta_off, hx->c_qp_offset, 0, 255};
             if constexpr (KT) {
                 if constexpr (PATH != 3) ktab = ktab_setup_h265(ktab_lds, 0);
                 dbk::h265_seg_rows(entry, qpl, prm, ktab, sg);
             } else {
-                dbk::h265_seg_params<CHROMA>(entry, qpl, prm, sg);
+                dbk::h265_seg_params<CHROMA, CF>(entry, qpl, prm, sg);
             }
         } else { /* one QP: beta is a scalar and tc one of two scalars picked by the bS */
 #pragma unroll
@@ -635,7 +637,7 @@ __device__ __forceinline__ void packed_body(const DbkArgs &a, int by, int f, int
  * they are (no widening needed), so twice the bytes per pixel at the same instruction count: this is
  * the variant that runs into the HBM roof (BASELINE config 5).
  */
-template <int MODE, bool NT, bool EDGE, bool QPMAP, bool CHROMA = false, bool WIDE = false>
+template <int MODE, bool NT, bool EDGE, bool QPMAP, bool CHROMA = false, bool WIDE = false, int CF = 1>
 __device__ __forceinline__ void packed16_body(const DbkArgs &a, int by, int f, int bx, bool active,
                                               const DbkH265Args *hx = nullptr /* MODE 2 (spec-exact) only */,
                                               uint32_t *ktab_lds = nullptr /* QPMAP luma: LDS for the workgroup's operand table */)
@@ -694,10 +696,10 @@ __device__ __forceinline__ void packed16_body(const DbkArgs &a, int by, int f, i
         dbk::H265Seg sg;
         if constexpr (QPMAP) {
             int qpl[4];
-            block_qpl4_dev<CHROMA>(a, f, by, active ? bx : 0, qpl);
+            block_qpl4_dev<CHROMA, CF>(a, f, by, active ? bx : 0, qpl);
             const dbk::H265Prm prm = {hx->tc_off, hx->beta_off, hx->c_qp_offset, a.shift, a.max_v};
             if constexpr (KT) dbk::h265_seg_rows(entry, qpl, prm, ktab_setup_h265(ktab_lds, a.shift), sg);
-            else dbk::h265_seg_params<CHROMA>(entry, qpl, prm, sg);
+            else dbk::h265_seg_params<CHROMA, CF>(entry, qpl, prm, sg);
         } else {
 #pragma unroll
             for (int i = 0; i < 4; i++) {
@@ -866,7 +868,7 @@ __global__ __launch_bounds__(1024) void dbk_packed_kernel(const DbkArgs a)
 }
 
 /* spec-exact mode (H.265 8.7.2), 8-bit samples, packed-int16 arithmetic: same mapping and memory path */
-template <bool CHROMA, bool LINEAR, bool QPMAP>
+template <bool CHROMA, bool LINEAR, bool QPMAP, int CF = 1>
 __device__ __forceinline__ void packed_h265_dispatch(const DbkH265Args &h)
 {
     const DbkArgs &a = h.base;
@@ -877,14 +879,30 @@ __device__ __forceinline__ void packed_h265_dispatch(const DbkH265Args &h)
     }
     WaveCoords c;
     if (!wave_coords<LINEAR>(a, c)) return;
-    if (c.interior) packed_body<CHROMA, 2, false, 0, QPMAP>(a, c.by, c.f, c.bx, true, c.by0, &h, kt);
-    else if (c.rows_in) packed_body<CHROMA, 2, false, LINEAR ? 1 : 3, QPMAP>(a, c.by, c.f, c.bx, c.active, c.by0, &h, kt);
-    else packed_body<CHROMA, 2, false, 2, QPMAP>(a, c.by, c.f, c.bx, c.active, c.by0, &h, kt);
+    if (c.interior) packed_body<CHROMA, 2, false, 0, QPMAP, CF>(a, c.by, c.f, c.bx, true, c.by0, &h, kt);
+    else if (c.rows_in) packed_body<CHROMA, 2, false, LINEAR ? 1 : 3, QPMAP, CF>(a, c.by, c.f, c.bx, c.active, c.by0, &h, kt);
+    else packed_body<CHROMA, 2, false, 2, QPMAP, CF>(a, c.by, c.f, c.bx, c.active, c.by0, &h, kt);
 }
 template <bool CHROMA, bool LINEAR, bool QPMAP>
 __global__ __launch_bounds__(1024) void dbk_packed_h265_kernel(const DbkH265Args h)
 {
     packed_h265_dispatch<CHROMA, LINEAR, QPMAP>(h);
+}
+/* QP-map chroma planes of 4:2:2 (CF 2) / 4:4:4 (CF 3) pictures: the format's map positions and QpC rule (one-QP planes of
+ * every format take the kernels above: with one QP the format is only in the launcher's scalar tc) */
+template <bool LINEAR, int CF>
+__global__ __launch_bounds__(1024) void dbk_packed_h265_cf_kernel(const DbkH265Args h)
+{
+    packed_h265_dispatch<true, LINEAR, true, CF>(h);
+}
+template <bool LINEAR, int CF>
+__global__ __launch_bounds__(1024) void dbk_packed16_h265_cf_kernel(const DbkH265Args h)
+{
+    const DbkArgs &a = h.base;
+    WaveCoords c;
+    if (!wave_coords<LINEAR>(a, c)) return;
+    if (c.interior) packed16_body<2, false, false, true, true, false, CF>(a, c.by, c.f, c.bx, true, &h, nullptr);
+    else packed16_body<2, false, true, true, true, false, CF>(a, c.by, c.f, c.bx, c.active, &h, nullptr);
 }
 /* ------------------------------------------------------------------------------------------ */
 /* one launch for the planes of a 4:2:0 frame                                */
@@ -1325,6 +1343,18 @@ bool dbk_packed_h265_supports(const DbkH265Args &h, int sample_bytes, bool chrom
 
 hipError_t dbk_launch_packed_h265(const DbkH265Args &h, int sample_bytes, bool chroma, hipStream_t stream)
 {
+    return dbk_launch_packed_h265_cf(h, sample_bytes, chroma, 1, stream);
+}
+
+/* QpC of a one-QP chroma plane: Table 8-10 for 4:2:0, Min(qPi, 51) for the other formats (dbk::h265_chroma_qp_cf) */
+static int chroma_qp_of_format(int qpi, int chroma_format)
+{
+    return chroma_format == 1 ? dbk::h265_chroma_qp(qpi) : dbk::h265_chroma_qp_cf<3>(qpi);
+}
+
+hipError_t dbk_launch_packed_h265_cf(const DbkH265Args &h, int sample_bytes, bool chroma, int chroma_format, hipStream_t stream)
+{
+    if (chroma && chroma_format != 1 && chroma_format != 2 && chroma_format != 3) return hipErrorInvalidValue;
     if (h.base.n_frames <= 0 || h.base.nbx <= 0 || h.base.nby <= 0) return hipSuccess;
     DbkH265Args g = h;
     dim3 grid, block;
@@ -1336,11 +1366,27 @@ hipError_t dbk_launch_packed_h265(const DbkH265Args &h, int sample_bytes, bool c
         g.beta_s = dbk::h265_beta(cl(qp + h.beta_off, 0, 51)) << sh;
         if (chroma) {
             g.tc_bs1 = 0;
-            g.tc_bs2 = dbk::h265_tc(cl(dbk::h265_chroma_qp(qp + h.c_qp_offset) + 2 + h.tc_off, 0, 53)) << sh;
+            g.tc_bs2 = dbk::h265_tc(cl(chroma_qp_of_format(qp + h.c_qp_offset, chroma_format) + 2 + h.tc_off, 0, 53)) << sh;
         } else {
             g.tc_bs1 = dbk::h265_tc(cl(qp + h.tc_off, 0, 53)) << sh;
             g.tc_bs2 = dbk::h265_tc(cl(qp + 2 + h.tc_off, 0, 53)) << sh;
         }
+    }
+    if (chroma && g.base.qp_map && chroma_format != 1) { /* QP-map chroma of 4:2:2 / 4:4:4: the format's kernels */
+#define DBK_H265_CF_LAUNCH(LIN, CF)                                                                     \
+    do {                                                                                                \
+        if (sample_bytes == 2) DBK_LAUNCH((dbk_packed16_h265_cf_kernel<LIN, CF>), grid, block, stream, g); \
+        else DBK_LAUNCH((dbk_packed_h265_cf_kernel<LIN, CF>), grid, block, stream, g);                  \
+    } while (0)
+        if (linear) {
+            if (chroma_format == 2) DBK_H265_CF_LAUNCH(true, 2);
+            else DBK_H265_CF_LAUNCH(true, 3);
+        } else {
+            if (chroma_format == 2) DBK_H265_CF_LAUNCH(false, 2);
+            else DBK_H265_CF_LAUNCH(false, 3);
+        }
+#undef DBK_H265_CF_LAUNCH
+        return hipGetLastError();
     }
 #define DBK_H265_LAUNCH(C, LIN)                                                                                       \
     do {                                                                                                              \
@@ -1402,14 +1448,14 @@ static unsigned fused_grid(int plane_w, int plane_h, int n_frames, int sample_by
 }
 
 /* the scalar-QP operands of the packed spec-exact kernels, as dbk_launch_packed_h265 derives them */
-static void fused_h265_scalars(DbkH265Args &d, bool chroma)
+static void fused_h265_scalars(DbkH265Args &d, bool chroma, int chroma_format = 1)
 {
     auto cl = [](int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); };
     const int sh = d.base.shift, qp = d.qp;
     d.beta_s = dbk::h265_beta(cl(qp + d.beta_off, 0, 51)) << sh;
     if (chroma) {
         d.tc_bs1 = 0;
-        d.tc_bs2 = dbk::h265_tc(cl(dbk::h265_chroma_qp(qp + d.c_qp_offset) + 2 + d.tc_off, 0, 53)) << sh;
+        d.tc_bs2 = dbk::h265_tc(cl(chroma_qp_of_format(qp + d.c_qp_offset, chroma_format) + 2 + d.tc_off, 0, 53)) << sh;
     } else {
         d.tc_bs1 = dbk::h265_tc(cl(qp + d.tc_off, 0, 53)) << sh;
         d.tc_bs2 = dbk::h265_tc(cl(qp + 2 + d.tc_off, 0, 53)) << sh;
@@ -1447,13 +1493,37 @@ hipError_t dbk_launch_deblock_sao(const DbkArgs &d, const DbkSaoArgs &s, int sam
 
 hipError_t dbk_launch_deblock_sao_h265(const DbkH265Args &h, const DbkSaoArgs &s, int sample_bytes, bool chroma, hipStream_t stream)
 {
+    return dbk_launch_deblock_sao_h265_cf(h, s, sample_bytes, chroma, 1, stream);
+}
+
+/* one-QP chroma planes of 4:2:2 / 4:4:4 pictures take the 4:2:0 kernels: with one QP the format enters only through QpC in the
+ * scalar tc (4:2:2 chroma CTBs arrive as square ones: dbk_launch_sao_rows_x2); with a QP map they take the _cf kernels */
+static bool fused_format_ok(int chroma_format)
+{
+    return chroma_format >= 1 && chroma_format <= 3;
+}
+
+hipError_t dbk_launch_deblock_sao_h265_cf(const DbkH265Args &h, const DbkSaoArgs &s, int sample_bytes, bool chroma, int chroma_format,
+                                          hipStream_t stream)
+{
+    if (!fused_format_ok(chroma_format)) return hipErrorInvalidValue;
     if (h.base.n_frames <= 0 || h.base.nbx <= 0 || h.base.nby <= 0) return hipSuccess;
     DbkFusedH265Args fa;
     fa.d = h;
     fa.s = s;
-    fused_h265_scalars(fa.d, chroma);
+    fused_h265_scalars(fa.d, chroma, chroma_format);
     const bool qm = h.base.qp_map != nullptr;
     const dim3 grid(fused_grid(h.base.plane_w, h.base.plane_h, h.base.n_frames, sample_bytes, fa.g), 1, 1);
+    if (chroma && qm && chroma_format != 1) {
+        if (sample_bytes == 1) {
+            if (chroma_format == 2) DBK_LAUNCH_LDS((dbk_sao_fused_h265_cf_kernel<2>), grid, dim3(kFusedThreads), kFusedLds, stream, fa);
+            else DBK_LAUNCH_LDS((dbk_sao_fused_h265_cf_kernel<3>), grid, dim3(kFusedThreads), kFusedLds, stream, fa);
+        } else {
+            if (chroma_format == 2) DBK_LAUNCH_LDS((dbk_sao_fused16_h265_cf_kernel<2>), grid, dim3(kFused16Threads), kFused16Lds, stream, fa);
+            else DBK_LAUNCH_LDS((dbk_sao_fused16_h265_cf_kernel<3>), grid, dim3(kFused16Threads), kFused16Lds, stream, fa);
+        }
+        return hipGetLastError();
+    }
     if (sample_bytes == 1) {
         if (chroma) DBK_FUSED_LAUNCH(qm, dbk_sao_fused_h265_kernel, kFusedThreads, kFusedLds, true);
         else DBK_FUSED_LAUNCH(qm, dbk_sao_fused_h265_kernel, kFusedThreads, kFusedLds, false);
@@ -1491,6 +1561,13 @@ hipError_t dbk_launch_deblock_sao_multi(const DbkArgs *d, const DbkSaoArgs *s, i
 
 hipError_t dbk_launch_deblock_sao_multi_h265(const DbkH265Args *h, const DbkSaoArgs *s, int n, int sample_bytes, hipStream_t stream)
 {
+    return dbk_launch_deblock_sao_multi_h265_cf(h, s, n, sample_bytes, 1, stream);
+}
+
+hipError_t dbk_launch_deblock_sao_multi_h265_cf(const DbkH265Args *h, const DbkSaoArgs *s, int n, int sample_bytes, int chroma_format,
+                                                hipStream_t stream)
+{
+    if (!fused_format_ok(chroma_format)) return hipErrorInvalidValue;
     if (n < 2 || n > 3) return hipErrorInvalidValue;
     if (h[0].base.n_frames <= 0) return hipSuccess;
     DbkFusedMultiH265Args m;
@@ -1500,7 +1577,7 @@ hipError_t dbk_launch_deblock_sao_multi_h265(const DbkH265Args *h, const DbkSaoA
         if (i < n) {
             m.pl[i].d = h[i];
             m.pl[i].s = s[i];
-            fused_h265_scalars(m.pl[i].d, i > 0);
+            fused_h265_scalars(m.pl[i].d, i > 0, chroma_format);
             total += fused_grid(h[i].base.plane_w, h[i].base.plane_h, h[i].base.n_frames, sample_bytes, m.pl[i].g);
         }
         m.wg_end[i] = total;
@@ -1508,6 +1585,18 @@ hipError_t dbk_launch_deblock_sao_multi_h265(const DbkH265Args *h, const DbkSaoA
     const dim3 grid(total, 1, 1);
     const DbkFusedMultiH265Args &fa = m;
     const bool qm = h[0].base.qp_map != nullptr; /* the caller checked: all planes with a map, or none */
+    if (qm && chroma_format != 1) { /* QP-map planes of 4:2:2 / 4:4:4 */
+#define DBK_FUSED_CF_LAUNCH(CF)                                                                                                      \
+    do {                                                                                                                             \
+        if (sample_bytes == 1) DBK_LAUNCH_LDS((dbk_sao_fused_multi_h265_cf_kernel<1, false, CF>), grid, dim3(kFusedThreads), kFusedLds, stream, fa); \
+        else if (h[0].base.max_v > 2047) DBK_LAUNCH_LDS((dbk_sao_fused_multi_h265_cf_kernel<2, true, CF>), grid, dim3(kFused16Threads), kFused16Lds, stream, fa); \
+        else DBK_LAUNCH_LDS((dbk_sao_fused_multi_h265_cf_kernel<2, false, CF>), grid, dim3(kFused16Threads), kFused16Lds, stream, fa); \
+    } while (0)
+        if (chroma_format == 2) DBK_FUSED_CF_LAUNCH(2);
+        else DBK_FUSED_CF_LAUNCH(3);
+#undef DBK_FUSED_CF_LAUNCH
+        return hipGetLastError();
+    }
     if (sample_bytes == 1) DBK_FUSED_LAUNCH(qm, dbk_sao_fused_multi_h265_kernel, kFusedThreads, kFusedLds, 1, false);
     else if (h[0].base.max_v > 2047) DBK_FUSED_LAUNCH(qm, dbk_sao_fused_multi_h265_kernel, kFused16Threads, kFused16Lds, 2, true);
     else DBK_FUSED_LAUNCH(qm, dbk_sao_fused_multi_h265_kernel, kFused16Threads, kFused16Lds, 2, false);

@@ -346,7 +346,8 @@ DBK_HD void packed_filter_block_h265(uint32_t (&L)[8], uint32_t (&R)[8], const H
 }
 
 /* per-segment tc / beta from qPL, the bS and the offsets (8.7.2.5.3 luma, 8.7.2.5.5 chroma); 8-bit samples */
-template <bool CHROMA>
+/* CF = chroma_format_idc of a chroma plane (deblock_h265.h ChromaFmt): QpC by Table 8-10 for 1, Min(qPi, 51) for 2 and 3 */
+template <bool CHROMA, int CF = 1>
 DBK_HD void h265_seg_params(const int (&entry)[4], const int (&qpl)[4], const H265Prm &p, H265Seg &s)
 {
 #pragma unroll
@@ -355,7 +356,8 @@ DBK_HD void h265_seg_params(const int (&entry)[4], const int (&qpl)[4], const H2
         s.entry[i] = entry[i];
         if constexpr (CHROMA) {
             s.beta[i] = 0;
-            s.tc[i] = h265_tc(clampi(h265_chroma_qp(qpl[i] + p.c_qp_offset) + 2 + p.tc_off, 0, 53)) << p.shift;
+            if constexpr (CF == 1) s.tc[i] = h265_tc(clampi(h265_chroma_qp(qpl[i] + p.c_qp_offset) + 2 + p.tc_off, 0, 53)) << p.shift;
+            else s.tc[i] = h265_tc(clampi(h265_chroma_qp_cf<CF>(qpl[i] + p.c_qp_offset) + 2 + p.tc_off, 0, 53)) << p.shift;
         } else {
             s.beta[i] = h265_beta(clampi(qpl[i] + p.beta_off, 0, 51)) << p.shift;
             s.tc[i] = h265_tc(clampi(qpl[i] + 2 * (bs - 1) + p.tc_off, 0, 53)) << p.shift;

@@ -33,7 +33,8 @@ constexpr int kFusedQuads = kFusedTile / 64;          /* 64 x 64 quadrants: kFus
 constexpr int kFusedQuadsX = kFusedTileW / 64;
 constexpr int kFusedLds = (kFusedTile + 8) * kFusedPitch;
 
-template <bool CHROMA, int MODE, bool QPMAP> /* MODE 0 = reference-exact deblocking, 2 = spec-exact (H.265 8.7.2); QPMAP = QP per map unit */
+template <bool CHROMA, int MODE, bool QPMAP, int CF = 1> /* MODE 0 = reference-exact deblocking, 2 = spec-exact (H.265 8.7.2); QPMAP = QP per map unit;
+                                                          CF = chroma_format_idc of a spec-exact chroma plane with a QP map */
 __device__ __forceinline__ void fused_body(const DbkArgs &a, const DbkH265Args *hx, const DbkSaoArgs &s, const DbkFusedGrid &g, uint8_t *tile,
                                            uint32_t id /* workgroup number inside this plane's part of the grid */)
 {
@@ -110,10 +111,10 @@ __device__ __forceinline__ void fused_body(const DbkArgs &a, const DbkH265Args *
         dbk::H265Seg sg;
         if constexpr (QPMAP) {
             int qpl[4];
-            block_qpl4_dev<CHROMA>(a, f, by, active ? bx : 0, qpl);
+            block_qpl4_dev<CHROMA, CF>(a, f, by, active ? bx : 0, qpl);
             const dbk::H265Prm prm = {hx->tc_off, hx->beta_off, hx->c_qp_offset, 0, 255};
             if constexpr (KT) dbk::h265_seg_rows(entry, qpl, prm, ktab_setup_h265(ktab_lds, 0), sg);
-            else dbk::h265_seg_params<CHROMA>(entry, qpl, prm, sg);
+            else dbk::h265_seg_params<CHROMA, CF>(entry, qpl, prm, sg);
         } else {
 #pragma unroll
             for (int i = 0; i < 4; i++) {
@@ -199,7 +200,7 @@ constexpr int kFused16Threads = 320;
 constexpr int kFused16Quads = kFused16Tile / 64;       /* 2 x 2 SAO waves */
 constexpr int kFused16Lds = (kFused16Tile + 8) * kFused16Pitch;
 
-template <bool CHROMA, int MODE, bool WIDE, bool QPMAP>
+template <bool CHROMA, int MODE, bool WIDE, bool QPMAP, int CF = 1>
 __device__ __forceinline__ void fused_body16(const DbkArgs &a, const DbkH265Args *hx, const DbkSaoArgs &s, const DbkFusedGrid &g, uint8_t *tile,
                                              uint32_t id)
 {
@@ -255,9 +256,9 @@ __device__ __forceinline__ void fused_body16(const DbkArgs &a, const DbkH265Args
         dbk::H265Seg sg;
         if constexpr (QPMAP) {
             int qpl[4];
-            block_qpl4_dev<CHROMA>(a, f, by, active ? bx : 0, qpl);
+            block_qpl4_dev<CHROMA, CF>(a, f, by, active ? bx : 0, qpl);
             const dbk::H265Prm prm = {hx->tc_off, hx->beta_off, hx->c_qp_offset, a.shift, a.max_v};
-            dbk::h265_seg_params<CHROMA>(entry, qpl, prm, sg);
+            dbk::h265_seg_params<CHROMA, CF>(entry, qpl, prm, sg);
         } else {
 #pragma unroll
             for (int i = 0; i < 4; i++) {
@@ -398,5 +399,35 @@ __global__ __launch_bounds__(SB == 1 ? kFusedThreads : kFused16Threads) void dbk
     } else {
         if (pl == 0) fused_body16<false, 2, WIDE, QPMAP>(fa.d.base, &fa.d, fa.s, fa.g, fused_tile, id);
         else fused_body16<true, 2, false, QPMAP>(fa.d.base, &fa.d, fa.s, fa.g, fused_tile, id);
+    }
+}
+
+/* QP-map planes of 4:2:2 (CF 2) / 4:4:4 (CF 3) pictures: chroma with the format's map positions and QpC rule (one-QP planes of
+ * every format take the kernels above; 4:2:2 SAO parameters arrive rewritten for square CTBs, dbk_launch_sao_rows_x2) */
+template <int CF>
+__global__ __launch_bounds__(kFusedThreads) void dbk_sao_fused_h265_cf_kernel(const DbkFusedH265Args fa)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t fused_tile[];
+    fused_body<true, 2, true, CF>(fa.d.base, &fa.d, fa.s, fa.g, fused_tile, blockIdx.x);
+}
+template <int CF>
+__global__ __launch_bounds__(kFused16Threads) void dbk_sao_fused16_h265_cf_kernel(const DbkFusedH265Args fa)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t fused_tile[];
+    fused_body16<true, 2, false, true, CF>(fa.d.base, &fa.d, fa.s, fa.g, fused_tile, blockIdx.x);
+}
+template <int SB, bool WIDE, int CF>
+__global__ __launch_bounds__(SB == 1 ? kFusedThreads : kFused16Threads) void dbk_sao_fused_multi_h265_cf_kernel(const DbkFusedMultiH265Args m)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t fused_tile[];
+    uint32_t id;
+    const int pl = fused_plane(m.wg_end, id);
+    const DbkFusedH265Args &fa = m.pl[pl];
+    if constexpr (SB == 1) {
+        if (pl == 0) fused_body<false, 2, true>(fa.d.base, &fa.d, fa.s, fa.g, fused_tile, id);
+        else fused_body<true, 2, true, CF>(fa.d.base, &fa.d, fa.s, fa.g, fused_tile, id);
+    } else {
+        if (pl == 0) fused_body16<false, 2, WIDE, true>(fa.d.base, &fa.d, fa.s, fa.g, fused_tile, id);
+        else fused_body16<true, 2, false, true, CF>(fa.d.base, &fa.d, fa.s, fa.g, fused_tile, id);
     }
 }

@@ -496,3 +496,39 @@ hipError_t dbk_launch_sao(const DbkSaoArgs &a, int sample_bytes, hipStream_t str
     }
     return hipGetLastError();
 }
+
+/* ---- rectangular CTBs (4:2:2 chroma: CtbSizeY / 2 wide, CtbSizeY tall) ----------------------------------------------------
+ * A CTB of (1 << L) x (1 << (L + 1)) samples is two square CTBs of (1 << L) one above the other with the same parameters, so
+ * the parameter rows are doubled once per call (a few KiB: one entry per CTB) and the square kernels -- plain SAO and the fused
+ * deblocking + SAO kernels, fast paths included -- run unchanged on the result. */
+namespace {
+__global__ __launch_bounds__(256) void sao_rows_x2_kernel(const DbkSaoCtb *src, int src_stride, long long src_frame_stride,
+                                                          DbkSaoCtb *dst, int cols, int rows, long long total)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    const long long per_frame = (long long)rows * cols;
+    const long long f = i / per_frame, k = i - f * per_frame;
+    const int r = (int)(k / cols), c = (int)(k - (long long)r * cols);
+    dst[i] = src[f * src_frame_stride + (long long)(r >> 1) * src_stride + c];
+}
+} /* namespace */
+
+size_t dbk_sao_rows_x2_entries(const DbkSaoArgs &a)
+{
+    const long long cols = (a.plane_w + (1 << a.ctb_log2) - 1) >> a.ctb_log2, rows = (a.plane_h + (1 << a.ctb_log2) - 1) >> a.ctb_log2;
+    return (size_t)(cols * rows * (a.params_frame_stride ? a.n_frames : 1));
+}
+
+hipError_t dbk_launch_sao_rows_x2(DbkSaoArgs &a, DbkSaoCtb *dst, hipStream_t stream)
+{
+    const int cols = (a.plane_w + (1 << a.ctb_log2) - 1) >> a.ctb_log2, rows = (a.plane_h + (1 << a.ctb_log2) - 1) >> a.ctb_log2;
+    const long long total = (long long)dbk_sao_rows_x2_entries(a);
+    if (total > 0)
+        hipLaunchKernelGGL(sao_rows_x2_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, a.params, a.params_stride,
+                           a.params_frame_stride, dst, cols, rows, total);
+    a.params = dst;
+    a.params_stride = cols;
+    a.params_frame_stride = a.params_frame_stride ? (long long)rows * cols : 0;
+    return hipGetLastError();
+}

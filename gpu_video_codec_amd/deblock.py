@@ -299,9 +299,12 @@ class Context:
 
     # -- spec-exact mode (H.265 clause 8.7.2) ------------------------------------------------------
     def filter_frame_h265(self, y, u=None, v=None, *, qp, bit_depth=8, units=None, vert_bs4=None, hor_bs4=None,
-                          qp_map=None, unit_log2=3, tc_offset_div2=0, beta_offset_div2=0, cb_qp_offset=0, cr_qp_offset=0):
+                          qp_map=None, unit_log2=3, tc_offset_div2=0, beta_offset_div2=0, cb_qp_offset=0, cr_qp_offset=0,
+                          chroma_format="420"):
         """hevc_deblocking_filter_h265 on host planes, in place.  Either `units` = (flags, mv0, mv1, ref0, ref1) per 4x4
-        luma unit (bS derived on the GPU, 8.7.2.4) or the 4-sample-granular luma bS arrays."""
+        luma unit (bS derived on the GPU, 8.7.2.4) or the 4-sample-granular luma bS arrays.  chroma_format '400' / '420' /
+        '422' / '444': u, v are (H / SubHeightC) x (W / SubWidthC) planes (none for '400'; '420' = the 4:2:0 entry)."""
+        cf = _lib.chroma_format_idc(chroma_format)
         fr = _lib.Frame()
         fr.height, fr.width = y.shape
         fr.bit_depth, fr.sample_bytes = bit_depth, y.dtype.itemsize
@@ -331,19 +334,32 @@ class Context:
             q.map, q.map_stride = m.ctypes.data, m.shape[1]
         prm = _lib.H265Params(tc_offset_div2, beta_offset_div2, cb_qp_offset, cr_qp_offset)
         tm = _lib.Timing()
-        rc = _lib.lib().hevc_deblocking_filter_h265(self.handle, C.byref(fr), None if un is None else C.byref(un),
-                                                    None if bs is None else C.byref(bs), C.byref(q), C.byref(prm), C.byref(tm))
+        if cf == _lib.CHROMA_420:
+            rc = _lib.lib().hevc_deblocking_filter_h265(self.handle, C.byref(fr), None if un is None else C.byref(un),
+                                                        None if bs is None else C.byref(bs), C.byref(q), C.byref(prm), C.byref(tm))
+        else:
+            rc = _lib.lib().hevcdbk_h265_filter_frame_cf(self.handle, C.byref(fr), cf, None if un is None else C.byref(un),
+                                                           None if bs is None else C.byref(bs), C.byref(q), C.byref(prm), C.byref(tm))
         _chk(rc, self.handle)
         return {"exec_s": tm.exec_s, "total_s": tm.total_s, "copy_s": tm.copy_s, "pipelined_s": tm.pipelined_s}
 
     def filter_device_h265(self, planes, qp, *, c_idx=0, tc_offset_div2=0, beta_offset_div2=0, cb_qp_offset=0, cr_qp_offset=0,
-                           variant=KERNEL_AUTO):
+                           variant=KERNEL_AUTO, chroma_format="420"):
+        """hevc_deblocking_filter_h265_device[_cf]: a plane of a picture in chroma_format '400' / '420' / '422' / '444'."""
+        cf = _lib.chroma_format_idc(chroma_format)
         prm = _lib.H265Params(tc_offset_div2, beta_offset_div2, cb_qp_offset, cr_qp_offset)
-        _chk(_lib.lib().hevc_deblocking_filter_h265_device(self.handle, C.byref(planes), c_idx, int(qp), C.byref(prm),
-                                                           variant, None), self.handle)
+        if cf == _lib.CHROMA_420:
+            rc = _lib.lib().hevc_deblocking_filter_h265_device(self.handle, C.byref(planes), c_idx, int(qp), C.byref(prm), variant, None)
+        else:
+            rc = _lib.lib().hevcdbk_h265_filter_device_cf(self.handle, C.byref(planes), c_idx, cf, int(qp), C.byref(prm),
+                                                                  variant, None)
+        _chk(rc, self.handle)
 
-    def derive_bs_h265(self, units, w, h, *, chroma=True):
-        """8.7.2.4 on the GPU from host arrays; returns (vert, hor[, chroma_vert, chroma_hor]) as host arrays."""
+    def derive_bs_h265(self, units, w, h, *, chroma=True, chroma_format="420"):
+        """8.7.2.4 on the GPU from host arrays; returns (vert, hor[, chroma_vert, chroma_hor]) as host arrays; the chroma
+        arrays in the geometry of chroma_format's chroma plane (none for '400')."""
+        cf = _lib.chroma_format_idc(chroma_format)
+        chroma = chroma and cf != _lib.CHROMA_400
         arrs = [np.ascontiguousarray(a, dt) for a, dt in zip(units, (np.uint16, np.int16, np.int16, np.int32, np.int32))]
         bufs = [self.alloc(a.nbytes) for a in arrs]
         for b, a in zip(bufs, arrs):
@@ -351,11 +367,16 @@ class Context:
         L = _lib.lib()
         sizes = [L.hevcdbk_h265_num_vert_bs(w, h), L.hevcdbk_h265_num_hor_bs(w, h)]
         if chroma:
-            sizes += [L.hevcdbk_h265_num_vert_bs(w // 2, h // 2), L.hevcdbk_h265_num_hor_bs(w // 2, h // 2)]
+            sx, sy = _lib.CHROMA_SUB[cf]
+            sizes += [L.hevcdbk_h265_num_vert_bs(w // sx, h // sy), L.hevcdbk_h265_num_hor_bs(w // sx, h // sy)]
         outs = [self.alloc(max(n, 1)) for n in sizes]
         un = _lib.H265Units(*[b.ptr for b in bufs])
-        rc = L.hevcdbk_h265_derive_bs_device(self.handle, C.byref(un), w, h, outs[0].ptr, outs[1].ptr,
-                                             outs[2].ptr if chroma else None, outs[3].ptr if chroma else None, None)
+        if cf == _lib.CHROMA_420:
+            rc = L.hevcdbk_h265_derive_bs_device(self.handle, C.byref(un), w, h, outs[0].ptr, outs[1].ptr,
+                                                 outs[2].ptr if chroma else None, outs[3].ptr if chroma else None, None)
+        else:
+            rc = L.hevcdbk_h265_derive_bs_device_cf(self.handle, C.byref(un), w, h, cf, outs[0].ptr, outs[1].ptr,
+                                                    outs[2].ptr if chroma else None, outs[3].ptr if chroma else None, None)
         _chk(rc, self.handle)
         self.synchronize()
         res = [o.download(n) for o, n in zip(outs, sizes)]
@@ -364,10 +385,18 @@ class Context:
         return res
 
     def sao_device(self, planes, params_ptr, params_stride, ctb_log2, *, params_frame_stride=0, keep_ptr=None, keep_stride=0,
-                   keep_frame_stride=0):
-        """hevc_sao_filter_device: H.265 8.7.3 on planes in HBM, src -> dst."""
-        _chk(_lib.lib().hevc_sao_filter_device(self.handle, C.byref(planes), params_ptr, params_stride, params_frame_stride,
-                                               ctb_log2, keep_ptr, keep_stride, keep_frame_stride, None), self.handle)
+                   keep_frame_stride=0, chroma_format="420", ctb_log2_h=None):
+        """hevc_sao_filter_device[_cf]: H.265 8.7.3 on planes in HBM, src -> dst.  ctb_log2 = log2 of this plane's CTB width;
+        its height follows from chroma_format (a 4:2:2 chroma plane, planes.is_chroma: twice the width) unless ctb_log2_h says."""
+        cf = _lib.chroma_format_idc(chroma_format)
+        lh = _ctb_log2_h(ctb_log2, ctb_log2_h, cf, planes.is_chroma)
+        if cf == _lib.CHROMA_420 and lh == ctb_log2:
+            rc = _lib.lib().hevc_sao_filter_device(self.handle, C.byref(planes), params_ptr, params_stride, params_frame_stride,
+                                                   ctb_log2, keep_ptr, keep_stride, keep_frame_stride, None)
+        else:
+            rc = _lib.lib().hevcdbk_sao_filter_device_cf(self.handle, C.byref(planes), params_ptr, params_stride, params_frame_stride,
+                                                      ctb_log2, lh, keep_ptr, keep_stride, keep_frame_stride, None)
+        _chk(rc, self.handle)
 
     def deblock_sao_device(self, planes, qp, params_ptr, params_stride, ctb_log2, *, params_frame_stride=0, keep_ptr=None,
                            keep_stride=0, keep_frame_stride=0, tc_table=None, beta_table=None, fused=_lib.FUSED_AUTO, stream=None):
@@ -380,19 +409,47 @@ class Context:
 
     def deblock_sao_h265_device(self, planes, qp, params_ptr, params_stride, ctb_log2, *, c_idx=0, tc_offset_div2=0,
                                 beta_offset_div2=0, cb_qp_offset=0, cr_qp_offset=0, params_frame_stride=0, keep_ptr=None,
-                                keep_stride=0, keep_frame_stride=0, fused=_lib.FUSED_AUTO):
-        """hevc_deblock_sao_h265_device: spec-exact deblocking (8.7.2) followed by SAO (8.7.3), src -> dst."""
+                                keep_stride=0, keep_frame_stride=0, fused=_lib.FUSED_AUTO, chroma_format="420", ctb_log2_h=None):
+        """hevc_deblock_sao_h265_device[_cf]: spec-exact deblocking (8.7.2) followed by SAO (8.7.3), src -> dst; chroma_format
+        and ctb_log2 / ctb_log2_h as for sao_device."""
+        cf = _lib.chroma_format_idc(chroma_format)
+        lh = _ctb_log2_h(ctb_log2, ctb_log2_h, cf, c_idx != 0)
         prm = _lib.H265Params(tc_offset_div2, beta_offset_div2, cb_qp_offset, cr_qp_offset)
-        _chk(_lib.lib().hevc_deblock_sao_h265_device(self.handle, C.byref(planes), c_idx, int(qp), C.byref(prm), params_ptr, params_stride,
-                                                     params_frame_stride, ctb_log2, keep_ptr, keep_stride, keep_frame_stride, fused,
-                                                     None), self.handle)
+        if cf == _lib.CHROMA_420 and lh == ctb_log2:
+            rc = _lib.lib().hevc_deblock_sao_h265_device(self.handle, C.byref(planes), c_idx, int(qp), C.byref(prm), params_ptr,
+                                                         params_stride, params_frame_stride, ctb_log2, keep_ptr, keep_stride,
+                                                         keep_frame_stride, fused, None)
+        else:
+            rc = _lib.lib().hevcdbk_h265_deblock_sao_device_cf(self.handle, C.byref(planes), c_idx, cf, int(qp), C.byref(prm), params_ptr,
+                                                            params_stride, params_frame_stride, ctb_log2, lh, keep_ptr, keep_stride,
+                                                            keep_frame_stride, fused, None)
+        _chk(rc, self.handle)
 
-    def deblock_sao_device_planes(self, planes_list, qp, sao_list, *, h265=None, fused=_lib.FUSED_AUTO, tc_table=None, beta_table=None):
+    def deblock_sao_device_planes(self, planes_list, qp, sao_list, *, h265=None, fused=_lib.FUSED_AUTO, tc_table=None, beta_table=None,
+                                  chroma_format="420"):
         """hevc_deblock_sao_device_planes / hevc_deblock_sao_h265_device_planes: deblocking + SAO of Y, U, V of a batch in one
         call (one launch where the fused kernel takes every plane).  sao_list[i] = (params_ptr, params_stride, ctb_log2) or a
         dict with the optional params_frame_stride / keep / keep_stride / keep_frame_stride; h265 = None (reference-exact
-        deblocking) or a dict of tc_offset_div2, beta_offset_div2, cb_qp_offset, cr_qp_offset (spec-exact)."""
+        deblocking) or a dict of tc_offset_div2, beta_offset_div2, cb_qp_offset, cr_qp_offset (spec-exact).  chroma_format
+        (spec-exact mode only): '400' / '420' / '422' / '444'; ctb_log2 = log2 of the plane's CTB width, its height follows
+        from the format (or a ctb_log2_h entry of the dict)."""
+        cf = _lib.chroma_format_idc(chroma_format)
+        if cf != _lib.CHROMA_420 and h265 is None:
+            raise ValueError("the reference-exact mode is 4:2:0 only: chroma_format needs h265=")
         arr = (_lib.DevicePlanes * len(planes_list))(*planes_list)
+        if cf != _lib.CHROMA_420 or any(isinstance(so, dict) and "ctb_log2_h" in so for so in sao_list):
+            spc = (_lib.SaoPlaneCf * len(sao_list))()
+            for i, so in enumerate(sao_list):
+                d = so if isinstance(so, dict) else {"params": so[0], "params_stride": so[1], "ctb_log2": so[2]}
+                spc[i].params, spc[i].params_stride, spc[i].ctb_log2_w = d["params"], d["params_stride"], d["ctb_log2"]
+                spc[i].ctb_log2_h = _ctb_log2_h(d["ctb_log2"], d.get("ctb_log2_h"), cf, i > 0)
+                spc[i].params_frame_stride = d.get("params_frame_stride", 0)
+                spc[i].keep, spc[i].keep_stride, spc[i].keep_frame_stride = d.get("keep"), d.get("keep_stride", 0), d.get("keep_frame_stride", 0)
+            prm = _lib.H265Params(h265.get("tc_offset_div2", 0), h265.get("beta_offset_div2", 0), h265.get("cb_qp_offset", 0),
+                                  h265.get("cr_qp_offset", 0))
+            _chk(_lib.lib().hevcdbk_h265_deblock_sao_device_planes_cf(self.handle, arr, len(planes_list), cf, int(qp), C.byref(prm), spc,
+                                                                   fused, None), self.handle)
+            return
         sp = (_lib.SaoPlane * len(sao_list))()
         for i, so in enumerate(sao_list):
             d = so if isinstance(so, dict) else {"params": so[0], "params_stride": so[1], "ctb_log2": so[2]}
@@ -449,8 +506,16 @@ class Context:
         return buf.value.decode().lower()
 
 
+def _ctb_log2_h(ctb_log2_w, ctb_log2_h, cf, chroma):
+    """log2 of a plane's CTB height: given, or from the format (4:2:2 chroma CTBs are twice as tall as wide, 6.5.1)"""
+    if ctb_log2_h is not None:
+        return int(ctb_log2_h)
+    return int(ctb_log2_w) + (1 if chroma and cf == _lib.CHROMA_422 else 0)
+
+
 class DeviceBatch:
-    """n_frames planes of identical geometry resident in HBM (src and dst), plus their bS arrays.
+    """n_frames planes of identical geometry resident in HBM (src and dst), plus their bS arrays -- any plane geometry: a
+    luma plane, or a chroma plane of any chroma format ((W / SubWidthC) x (H / SubHeightC), is_chroma=True).
     This is the layout bench.py times: frame f at base + f*frame_stride, tight pitch."""
 
     def __init__(self, ctx, plane_w, plane_h, n_frames, *, bit_depth=8, sample_bytes=None, is_chroma=False,

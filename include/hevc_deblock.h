@@ -359,7 +359,8 @@ HEVCDBK_API int hevcdbk_filter_yuv_file_multi(const int *devices, unsigned n_dev
  * bS arrays are 4-sample granular (the standard's unit):
  *   vert: (W/8+1) columns x (H/4) rows, entry (y4, bx) = the edge x = 8*bx over rows 4*y4 .. 4*y4+3
  *   hor:  (H/8+1) rows x (W/4) columns, entry (by, x4) = the edge y = 8*by over columns 4*x4 .. 4*x4+3
- * for a W x H plane; chroma planes (4:2:0) carry their own arrays in the chroma plane's geometry.  An entry holds the
+ * for a W x H plane; chroma planes carry their own arrays in the chroma plane's geometry (4:2:0 here; the other chroma
+ * formats: the _cf entries at the end of this header).  An entry holds the
  * bS in bits 1:0 and two flags: HEVCDBK_H265_KEEP_P / _KEEP_Q leave the P / Q samples unmodified (pcm_loop_filter_
  * disabled_flag with a PCM block, cu_transquant_bypass_flag: nDp / nDq = 0 in 8.7.2.5.7).  Edges on the picture boundary
  * are never filtered, whatever the arrays hold.
@@ -483,7 +484,7 @@ HEVCDBK_API int hevc_deblock_sao_h265_device(hevcdbk_context *ctx, const hevcdbk
                                              void *hip_stream);
 
 /*
- * The same for the planes of a 4:2:0 batch -- planes[0] luma, the others chroma, n_planes <= 3, one frame count -- in ONE
+ * The same for the planes of a 4:2:0 batch (other chroma formats: hevcdbk_h265_deblock_sao_device_planes_cf) -- planes[0] luma, the others chroma, n_planes <= 3, one frame count -- in ONE
  * call: where the fused kernel takes every plane (one sample width and bit depth) they go out as ONE launch, the planes'
  * tiles one after the other in the grid; otherwise plane by plane exactly as n_planes calls of the entries above would
  * (every plane is checked before the first launch).  sao[i] = the SAO operands of planes[i] (its own CTB grid: 4:2:0 chroma
@@ -505,6 +506,78 @@ HEVCDBK_API int hevc_deblock_sao_device_planes(hevcdbk_context *ctx, const hevcd
 HEVCDBK_API int hevc_deblock_sao_h265_device_planes(hevcdbk_context *ctx, const hevcdbk_device_planes *planes, unsigned n_planes,
                                                     unsigned qp, const hevcdbk_h265_params *h265_params,
                                                     const hevcdbk_sao_plane *sao, int fused, void *hip_stream);
+
+/* ==================================================================================================================
+ * Chroma formats of the spec-exact mode and SAO: 4:0:0, 4:2:0, 4:2:2, 4:4:4 (the RExt and Monochrome profiles).
+ *
+ * The entries above are the chroma_format_idc == 1 (4:2:0) case; the _cf entries below take the format as an operand
+ * (HEVCDBK_CHROMA_* = chroma_format_idc) and, with HEVCDBK_CHROMA_420, produce exactly what the entries above produce.
+ * SubWidthC x SubHeightC (Table 6-1) = 2x2 for 4:2:0, 2x1 for 4:2:2, 1x1 for 4:4:4; a chroma plane is
+ * (W / SubWidthC) x (H / SubHeightC) and every rule is stated in its own sample coordinates:
+ *   - chroma edges lie on the chroma plane's 8-sample grid (4:2:2: vertical edges every 16 luma columns, horizontal edges
+ *     every 8 luma rows); the plane's bS arrays have the usual 4-sample-granular layout of ITS geometry, entry =
+ *     the luma entry at (xDk * SubWidthC, yDm * SubHeightC) (8.7.2.5.5), only bS 2 filters;
+ *   - QpQ / QpP = QpY of the unit covering luma sample (x * SubWidthC, y * SubHeightC);
+ *   - QpC: Table 8-10 for 4:2:0, Min(qPi, 51) otherwise, qPi = ((QpQ + QpP + 1) >> 1) + cQpPicOffset (the pps offset
+ *     only, for every format: CuQpOffsetC does not enter the deblocking);
+ *   - SAO: the chroma CTB is (CtbSizeY / SubWidthC) x (CtbSizeY / SubHeightC): ctb_log2_w / ctb_log2_h (4:2:2 chroma:
+ *     ctb_log2_h = ctb_log2_w + 1, e.g. 32 x 64 for CtbSizeY 64); params_stride counts CTB columns of that width;
+ *     the keep map stays one byte per 8x8 samples of the plane;
+ *   - 4:0:0: luma only; a chroma plane, c_idx > 0 or chroma bS outputs are HEVCDBK_ERR_ARG;
+ *   - separate_colour_plane_flag = 1 (ChromaArrayType 0): each colour plane is coded as a monochrome picture, i.e. three
+ *     luma calls (c_idx 0, HEVCDBK_CHROMA_400 or any format), each with its own bS, QP and SAO operands.
+ * Kernels: every format, with one QP or a QP map, runs through the 32-bit kernel, the packed kernels and the fused
+ * deblocking + SAO kernel -- Y, Cb, Cr of a 4:2:2 or 4:4:4 batch in ONE deblocking + SAO launch (4:2:2: after one small
+ * launch that rewrites the chroma SAO parameters for square CTBs into a scratch owned by the context).  Parity: against a restatement of the standard in tests/, "parity
+ * unpinned" as for the rest of the spec-exact mode.
+ * ================================================================================================================== */
+#define HEVCDBK_CHROMA_400 0
+#define HEVCDBK_CHROMA_420 1
+#define HEVCDBK_CHROMA_422 2
+#define HEVCDBK_CHROMA_444 3
+
+/* hevcdbk_h265_derive_bs_device for a picture of format chroma_format_idc: the chroma outputs (may both be NULL; must be
+ * with 4:0:0) have the entry counts of the (width / SubWidthC) x (height / SubHeightC) plane */
+HEVCDBK_API int hevcdbk_h265_derive_bs_device_cf(hevcdbk_context *ctx, const hevcdbk_h265_units *units, unsigned width,
+                                                 unsigned height, int chroma_format_idc, uint8_t *vert_bs4, uint8_t *hor_bs4,
+                                                 uint8_t *chroma_vert_bs4, uint8_t *chroma_hor_bs4, void *hip_stream);
+/* hevc_deblocking_filter_h265_device for a plane of a picture of format chroma_format_idc (planes->plane_w / plane_h = this
+ * plane's geometry; the QP map is indexed at (x * SubWidthC, y * SubHeightC)); kernel variants as there */
+HEVCDBK_API int hevcdbk_h265_filter_device_cf(hevcdbk_context *ctx, const hevcdbk_device_planes *planes, int c_idx,
+                                                      int chroma_format_idc, unsigned qp, const hevcdbk_h265_params *params,
+                                                      int kernel_variant, void *hip_stream);
+/* hevc_deblocking_filter_h265 for a frame of format chroma_format_idc: chroma planes (W / SubWidthC) x (H / SubHeightC),
+ * multiples of 8 samples (else HEVCDBK_ERR_ARG; 4:2:0: HEVCDBK_ERR_DIMENSIONS as before); 4:0:0 frames carry no chroma
+ * plane.  The chroma bS arrays are gathered from the luma arrays in the format's geometry */
+HEVCDBK_API int hevcdbk_h265_filter_frame_cf(hevcdbk_context *ctx, hevcdbk_frame *frame, int chroma_format_idc,
+                                               const hevcdbk_h265_units *units, const hevcdbk_bs *bs4, const hevcdbk_qp *qp,
+                                               const hevcdbk_h265_params *params, hevcdbk_timing *timing);
+/* hevc_sao_filter_device with CTBs of (1 << ctb_log2_w) x (1 << ctb_log2_h) samples: ctb_log2_h = ctb_log2_w (square) or
+ * ctb_log2_w + 1 (4:2:2 chroma), 3..6 each */
+HEVCDBK_API int hevcdbk_sao_filter_device_cf(hevcdbk_context *ctx, const hevcdbk_device_planes *planes, const hevcdbk_sao_ctb *params,
+                                          unsigned params_stride, size_t params_frame_stride, unsigned ctb_log2_w,
+                                          unsigned ctb_log2_h, const uint8_t *keep, unsigned keep_stride,
+                                          size_t keep_frame_stride, void *hip_stream);
+HEVCDBK_API int hevcdbk_h265_deblock_sao_device_cf(hevcdbk_context *ctx, const hevcdbk_device_planes *planes, int c_idx,
+                                                int chroma_format_idc, unsigned qp, const hevcdbk_h265_params *h265_params,
+                                                const hevcdbk_sao_ctb *params, unsigned params_stride, size_t params_frame_stride,
+                                                unsigned ctb_log2_w, unsigned ctb_log2_h, const uint8_t *keep, unsigned keep_stride,
+                                                size_t keep_frame_stride, int fused, void *hip_stream);
+/* the planes of a batch in format chroma_format_idc (4:2:2 / 4:4:4: chroma planes in the format's geometry of planes[0], else
+ * HEVCDBK_ERR_ARG; 4:2:0 with square CTBs: exactly hevc_deblock_sao_h265_device_planes); Y + Cb + Cr go out as ONE
+ * deblocking + SAO launch where the fused kernel takes every plane, with one QP or a QP map */
+typedef struct {
+    const hevcdbk_sao_ctb *params; /* DEVICE memory */
+    unsigned params_stride;
+    size_t params_frame_stride;
+    unsigned ctb_log2_w, ctb_log2_h;
+    const uint8_t *keep;           /* DEVICE memory, may be NULL */
+    unsigned keep_stride;
+    size_t keep_frame_stride;
+} hevcdbk_sao_plane_cf;
+HEVCDBK_API int hevcdbk_h265_deblock_sao_device_planes_cf(hevcdbk_context *ctx, const hevcdbk_device_planes *planes, unsigned n_planes,
+                                                       int chroma_format_idc, unsigned qp, const hevcdbk_h265_params *h265_params,
+                                                       const hevcdbk_sao_plane_cf *sao, int fused, void *hip_stream);
 
 #ifdef __cplusplus
 }

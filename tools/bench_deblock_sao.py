@@ -20,7 +20,11 @@ def main():
     ap.add_argument("--types", default="mix")
     ap.add_argument("--diag", action="append", default=None,
                     help="diagnostic library with these knobs (csrc/hevcdbk_diag.h), e.g. noswz; may be given several times: one result per knob set")
+    ap.add_argument("--chroma-format", choices=["420", "422", "444"], default=None,
+                    help="--mode h265: Y + Cb + Cr of pictures of this format in one call (CtbSizeY 64) instead of luma planes")
     a = ap.parse_args()
+    if a.chroma_format and a.mode != "h265":
+        ap.error("--chroma-format needs --mode h265 (the reference-exact mode is 4:2:0 only)")
     if a.diag is not None:
         _lib.use_diagnostic_library(a.diag[0] or None)
     w, h, n = a.width, a.height, a.frames
@@ -47,13 +51,21 @@ def main():
         dh.upload(np.full(nh, 2, np.uint8))
         p.vert_bs, p.hor_bs, p.vert_bs_stride, p.hor_bs_stride = dv.ptr, dh.ptr, 0, 0
 
+    nbytes = 2 * n * w * h
+    if a.chroma_format:  # the planes of tools/bench_rext.py: bS 2 everywhere, seeded SAO parameters per plane
+        sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+        import bench_rext
+        yuv, sao, nbytes, _keep = bench_rext.setup(ctx, a.chroma_format, w, h, n, 8, np.random.RandomState(5))
+        h265 = {"tc_offset_div2": 0, "beta_offset_div2": 0, "cb_qp_offset": 0, "cr_qp_offset": 0}
+
     def call(fused):
-        if a.mode == "ref":
+        if a.chroma_format:
+            ctx.deblock_sao_device_planes(yuv, a.qp, sao, h265=h265, fused=fused, chroma_format=a.chroma_format)
+        elif a.mode == "ref":
             ctx.deblock_sao_device(p, a.qp, dp.ptr, cols, 6, fused=fused)
         else:
             ctx.deblock_sao_h265_device(p, a.qp, dp.ptr, cols, 6, fused=fused)
 
-    nbytes = 2 * n * w * h
     out = {}
     runs = [("fused", _lib.FUSED_ON, None), ("two_launches", _lib.FUSED_OFF, None), ("fused_again", _lib.FUSED_ON, None)]
     if a.diag is not None:
@@ -72,7 +84,8 @@ def main():
         ctx.synchronize()
         dt = (time.perf_counter() - t0) / a.steps
         out[name] = {"ms_per_step": dt * 1e3, "frames_per_s": n / dt, "frac_of_8TBps_read_once_write_once": nbytes / dt / 8e12}
-    print(json.dumps({"stage": "deblock+sao", "mode": a.mode, "workload": "%dx%d 8-bit luma x %d, QP %d, CTB types: %s" % (w, h, n, a.qp, a.types),
+    what = "luma" if not a.chroma_format else "Y+Cb+Cr %s" % a.chroma_format
+    print(json.dumps({"stage": "deblock+sao", "mode": a.mode, "workload": "%dx%d 8-bit %s x %d, QP %d, CTB types: %s" % (w, h, what, n, a.qp, a.types),
                       **out}))
 
 

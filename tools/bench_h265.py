@@ -19,10 +19,16 @@ def main():
                     help="QP per unit of (1 << LOG2) luma samples, qp-6 .. qp+6 (3..6; 0 = one QP): what a stream with cu_qp_delta has")
     ap.add_argument("--bs", choices=["2", "mixed"], default="2", help="bS 2 on every interior edge, or a seeded mix of 0 / 1 / 2 per 4-sample segment")
     ap.add_argument("--only", choices=["generic", "packed"], default=None)
+    ap.add_argument("--chroma-format", choices=["420", "422", "444"], default=None,
+                    help="time the Cb plane of a picture of this format (the QP map stays in luma units) instead of the luma plane")
     a = ap.parse_args()
-    w, h, n = a.width, a.height, a.frames
+    n = a.frames
+    fmt = a.chroma_format
+    sub = {None: (1, 1), "420": (2, 2), "422": (2, 1), "444": (1, 1)}[fmt]
+    w, h = a.width // sub[0], a.height // sub[1]  # the timed plane
     ctx = deblock.Context(0)
-    b = deblock.DeviceBatch(ctx, w, h, n, per_frame_bs=False)
+    b = deblock.DeviceBatch(ctx, w, h, n, per_frame_bs=False, is_chroma=fmt is not None)
+    kw = {} if fmt is None else {"c_idx": 1, "chroma_format": fmt}
     distinct = min(n, 8)
     src = np.stack([synth.blocky_plane(w, h, seed=7, frame=i) for i in range(distinct)])
     b.upload_all(np.concatenate([src] * (n // distinct + 1))[:n])
@@ -41,7 +47,7 @@ def main():
     p.vert_bs, p.hor_bs, p.vert_bs_stride, p.hor_bs_stride = dv.ptr, dh.ptr, 0, 0
     bytes_per_launch = n * (2 * w * h + vb.size + hb.size)
     if a.qp_map:
-        qmap = synth.ctu_qp_map(w, h, seed=29, lo=max(a.qp - 6, 0), hi=min(a.qp + 6, 51), ctu_log2=a.qp_map)
+        qmap = synth.ctu_qp_map(a.width, a.height, seed=29, lo=max(a.qp - 6, 0), hi=min(a.qp + 6, 51), ctu_log2=a.qp_map)
         dm = ctx.alloc(qmap.nbytes)
         dm.upload(qmap)
         p.qp_map, p.qp_map_stride, p.ctu_log2, p.qp_map_frame_stride = dm.ptr, qmap.shape[1], a.qp_map, 0
@@ -50,16 +56,16 @@ def main():
         if a.only and a.only != name:
             continue
         for _ in range(100):
-            ctx.filter_device_h265(p, a.qp, variant=variant)
+            ctx.filter_device_h265(p, a.qp, variant=variant, **kw)
         ctx.synchronize()
         t0 = time.perf_counter()
         for _ in range(a.steps):
-            ctx.filter_device_h265(p, a.qp, variant=variant)
+            ctx.filter_device_h265(p, a.qp, variant=variant, **kw)
         ctx.synchronize()
         dt = (time.perf_counter() - t0) / a.steps
         print(json.dumps({"mode": "h265", "kernel": name, "ms_per_launch": dt * 1e3, "frames_per_s": n / dt,
                           "GBps": bytes_per_launch / dt * 1e-9, "frac_of_8TBps": bytes_per_launch / dt / 8e12,
-                          "workload": "%dx%d 8-bit luma x %d, QP %d%s, bS %s" % (w, h, n, a.qp, " +-6 per %d x %d unit" % (1 << a.qp_map, 1 << a.qp_map) if a.qp_map else "", a.bs)}))
+                          "workload": "%dx%d 8-bit %s x %d, QP %d%s, bS %s" % (w, h, "luma" if fmt is None else "Cb of %s" % fmt, n, a.qp, " +-6 per %d x %d unit" % (1 << a.qp_map, 1 << a.qp_map) if a.qp_map else "", a.bs)}))
 
 
 if __name__ == "__main__":
