@@ -186,6 +186,10 @@ def random_sao_params(w, h, ctb_log2, seed, bit_depth=8):
     p["cls"] = np.where(band, rng.randint(0, 32, (rows, cols)), rng.randint(0, 4, (rows, cols)))
     lim = (1 << (min(bit_depth, 10) - 5)) - 1
     off = rng.randint(-lim, lim + 1, (rows, cols, 4))
+    if bit_depth > 10:
+        # SaoOffsetVal = offset << log2OffsetScale, log2OffsetScale = 0 .. Max(0, bitDepth - 10) (7.4.9.3.2), as far as the
+        # int8 entry holds it (<< 2 at most: +-124)
+        off = off << rng.randint(0, min(bit_depth - 10, 2) + 1, (rows, cols, 1))
     # edge offsets: the first two are non-negative, the last two non-positive (7.4.9.3.2); band offsets keep their signs
     eo = ~band
     off[eo, 0:2] = np.abs(off[eo, 0:2])

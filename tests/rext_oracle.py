@@ -158,6 +158,8 @@ def random_sao_params(w, h, ctb_log2_w, ctb_log2_h, rng, bit_depth=8):
     p["cls"] = np.where(band, rng.integers(0, 32, (rows, cols)), rng.integers(0, 4, (rows, cols)))
     lim = (1 << (min(bit_depth, 10) - 5)) - 1
     off = rng.integers(-lim, lim + 1, (rows, cols, 4))
+    if bit_depth > 10:  # log2OffsetScale 0 .. Max(0, bitDepth - 10), as far as the int8 entry holds the scaled value
+        off = off << rng.integers(0, min(bit_depth - 10, 2) + 1, (rows, cols, 1))
     eo = ~band
     off[eo, 0:2] = np.abs(off[eo, 0:2])
     off[eo, 2:4] = -np.abs(off[eo, 2:4])
