@@ -17,7 +17,12 @@ What it writes (all data, no reference source):
                                  (gpu_video_codec_amd.synth.blocky_yuv420), small and 4K,
   * ref_fresh.json            -- sha256 of reference outputs on the hard seeded inputs of fresh_cases()
                                  and the reference constructor's return codes on the files of ERROR_CASES
-                                 (tests/test_oracle.py checks the restatement against both).
+                                 (tests/test_oracle.py checks the restatement against both),
+  * ref_boundaries.json       -- sha256 of input and reference output of the boundary frames of boundary_cases():
+                                 segments solved onto every decision threshold (tests/ref_vectors.py), with their luma
+                                 bS override (tests/test_ref_boundaries_cpu.py checks the restatement against it).
+
+    python tests/golden/make_golden.py --boundaries   rewrites ref_boundaries.json alone.
 """
 import hashlib
 import json
@@ -90,6 +95,35 @@ def record_fresh():
     print("wrote", os.path.join(HERE, "ref_fresh.json"))
 
 
+# boundary frames: 8-bit 4:2:0, scalar QP, one luma wave each (tests/ref_vectors.py); sizes multiples of 16
+BOUNDARY_SIZES = [(16, 16), (48, 32), (112, 48), (528, 48)]
+BOUNDARY_QPS = [18, 27, 35, 42, 51]
+
+
+def boundary_cases():
+    """Seeded 8-bit 4:2:0 frames whose luma segments are solved onto the reference's decision thresholds, range extremes and
+    picture border (luma bS override: vertical-only, horizontal-only or mixed waves) and whose chroma segments sit on the
+    +-tc clips and Clip2 under the default chroma bS: yields (w, h, qp, wave, yuv bytes, vert bS, hor bS)."""
+    import numpy as np
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import ref_vectors as rv
+    rng = np.random.default_rng(29)
+    for i, (w, h) in enumerate(BOUNDARY_SIZES):
+        for j, qp in enumerate(BOUNDARY_QPS):
+            wave = rv.WAVES[(i + j) % 3]
+            y, u, v, vb, hb = rv.boundary_frame(w, h, qp, wave, rng)
+            yield w, h, qp, wave, oracle.join_yuv420(y, u, v), vb, hb
+
+
+def record_boundaries():
+    cases = [{"width": w, "height": h, "qp": qp, "wave": wave, "input_sha256": sha(buf),
+              "sha256": sha(oracle.ref_filter_yuv420(buf, w, h, qp, vb, hb, threads=1))}
+             for (w, h, qp, wave, buf, vb, hb) in boundary_cases()]
+    with open(os.path.join(HERE, "ref_boundaries.json"), "w") as fh:
+        json.dump({"cases": cases}, fh, indent=1)
+    print("wrote", os.path.join(HERE, "ref_boundaries.json"))
+
+
 def main():
     assert oracle.have_ref(), "build oracle/_ref first (make -C oracle ref)"
     man = {"images": {}, "synth": []}
@@ -125,7 +159,12 @@ def main():
         json.dump(man, fh, indent=1)
     print("wrote", os.path.join(HERE, "manifest.json"))
     record_fresh()
+    record_boundaries()
 
 
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["--boundaries"]:
+        assert oracle.have_ref(), "build oracle/_ref first (make -C oracle ref)"
+        record_boundaries()
+    else:
+        main()
