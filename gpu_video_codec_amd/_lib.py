@@ -43,6 +43,8 @@ EXPORTS = [
     "hevcdbk_last_frame_trace", "hevcdbk_device_malloc_probed",
     "hevcdbk_h265_derive_bs_device_cf", "hevcdbk_h265_filter_device_cf", "hevcdbk_h265_filter_frame_cf",
     "hevcdbk_sao_filter_device_cf", "hevcdbk_h265_deblock_sao_device_cf", "hevcdbk_h265_deblock_sao_device_planes_cf",
+    "hevcdbk_h265_sao_borders_device", "hevcdbk_sao_filter_device_nox", "hevcdbk_h265_deblock_sao_device_nox",
+    "hevcdbk_h265_deblock_sao_device_planes_nox",
 ]
 
 # chroma_format_idc of the spec-exact mode and SAO (HEVCDBK_CHROMA_*): 4:0:0, 4:2:0, 4:2:2, 4:4:4
@@ -98,6 +100,15 @@ class SaoPlaneCf(C.Structure):
     """hevcdbk_sao_plane_cf: SaoPlane with CTBs of (1 << ctb_log2_w) x (1 << ctb_log2_h) samples"""
     _fields_ = [("params", C.c_void_p), ("params_stride", C.c_uint), ("params_frame_stride", C.c_size_t), ("ctb_log2_w", C.c_uint),
                 ("ctb_log2_h", C.c_uint), ("keep", C.c_void_p), ("keep_stride", C.c_uint), ("keep_frame_stride", C.c_size_t)]
+
+
+class SaoBorders(C.Structure):
+    """hevcdbk_sao_borders: one byte per CTB of the picture's (luma) CTB grid, SAO_NOX_* bits (device pointer)"""
+    _fields_ = [("nox", C.c_void_p), ("stride", C.c_uint), ("frame_stride", C.c_size_t)]
+
+
+# HEVCDBK_SAO_NOX_*: the neighbouring CTB this CTB's samples must not look into (H.265 8.7.3.2)
+SAO_NOX_L, SAO_NOX_R, SAO_NOX_U, SAO_NOX_D, SAO_NOX_UL, SAO_NOX_UR, SAO_NOX_DL, SAO_NOX_DR = 1, 2, 4, 8, 16, 32, 64, 128
 
 
 class Replay(C.Structure):
@@ -251,6 +262,16 @@ def lib():
                                                       C.c_void_p, C.c_uint, C.c_size_t, C.c_int, C.c_void_p]
         L.hevcdbk_h265_deblock_sao_device_planes_cf.argtypes = [C.c_void_p, C.POINTER(DevicePlanes), C.c_uint, C.c_int, C.c_uint,
                                                              C.POINTER(H265Params), C.POINTER(SaoPlaneCf), C.c_int, C.c_void_p]
+        L.hevcdbk_h265_sao_borders_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_uint, C.c_uint,
+                                                      C.c_uint, C.c_void_p, C.c_uint, C.c_void_p]
+        L.hevcdbk_sao_filter_device_nox.argtypes = [C.c_void_p, C.POINTER(DevicePlanes), C.c_void_p, C.c_uint, C.c_size_t, C.c_uint,
+                                                    C.c_uint, C.c_void_p, C.c_uint, C.c_size_t, C.POINTER(SaoBorders), C.c_void_p]
+        L.hevcdbk_h265_deblock_sao_device_nox.argtypes = [C.c_void_p, C.POINTER(DevicePlanes), C.c_int, C.c_int, C.c_uint,
+                                                          C.POINTER(H265Params), C.c_void_p, C.c_uint, C.c_size_t, C.c_uint, C.c_uint,
+                                                          C.c_void_p, C.c_uint, C.c_size_t, C.c_int, C.POINTER(SaoBorders), C.c_void_p]
+        L.hevcdbk_h265_deblock_sao_device_planes_nox.argtypes = [C.c_void_p, C.POINTER(DevicePlanes), C.c_uint, C.c_int, C.c_uint,
+                                                                 C.POINTER(H265Params), C.POINTER(SaoPlaneCf), C.c_int,
+                                                                 C.POINTER(SaoBorders), C.c_void_p]
         L.hevc_deblock_sao_h265_device_planes.argtypes = [C.c_void_p, C.POINTER(DevicePlanes), C.c_uint, C.c_uint, C.POINTER(H265Params),
                                                           C.POINTER(SaoPlane), C.c_int, C.c_void_p]
         L.hevcdbk_set_host_threads.argtypes = [C.c_void_p, C.c_uint]

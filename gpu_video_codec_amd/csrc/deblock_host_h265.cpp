@@ -370,32 +370,43 @@ int deblock_sao_plane(hevcdbk_context *ctx, const hevcdbk_device_planes *p, unsi
     return tmp_done(ctx, s);
 }
 int deblock_sao_plane_h265(hevcdbk_context *ctx, const hevcdbk_device_planes *p, int c_idx, unsigned qp, const hevcdbk_h265_params *prm,
-                           DbkH265Args &h, DbkSaoArgs &sa, int fused, hipStream_t s)
+                           DbkH265Args &h, DbkSaoArgs &sa, int fused, hipStream_t s, const DbkSaoNox *nx = nullptr)
 {
     const bool can = dbk_packed_h265_supports(h, (int)p->sample_bytes, c_idx != 0) &&
                      dbk_deblock_sao_supports(h.base, sa, (int)p->sample_bytes, c_idx != 0);
     if (fused == HEVCDBK_FUSED_ON && !can) return HEVCDBK_ERR_UNSUPPORTED;
     if (can && fused != HEVCDBK_FUSED_OFF)
-        return hip_ok(ctx, dbk_launch_deblock_sao_h265(h, sa, (int)p->sample_bytes, c_idx != 0, s), "fused deblocking + SAO launch") ? HEVCDBK_OK : HEVCDBK_ERR_HIP;
+        return hip_ok(ctx, dbk_launch_deblock_sao_h265_cf(h, sa, (int)p->sample_bytes, c_idx != 0, 1, s, nx), "fused deblocking + SAO launch") ? HEVCDBK_OK : HEVCDBK_ERR_HIP;
     hevcdbk_device_planes first, second;
     if (int rc = tmp_planes(ctx, p, s, first, second)) return rc;
     if (int rc = h265_args(&first, c_idx, qp, prm, h)) return rc;
     if (int rc = launch_h265(ctx, h, (int)p->sample_bytes, c_idx != 0, HEVCDBK_KERNEL_AUTO, s)) return rc;
     sa.src = (const uint8_t *)second.src;
-    if (!hip_ok(ctx, dbk_launch_sao(sa, (int)p->sample_bytes, s), "SAO launch")) return HEVCDBK_ERR_HIP;
+    if (!hip_ok(ctx, dbk_launch_sao(sa, (int)p->sample_bytes, s, nx), "SAO launch")) return HEVCDBK_ERR_HIP;
     return tmp_done(ctx, s);
 }
 
 /* 4:2:2 chroma planes (ctb_log2_h[i] = sa[i].ctb_log2 + 1): their SAO parameters rewritten as those of square CTBs into the
  * context's scratch (dbk_launch_sao_rows_x2), so that every kernel after this sees square CTBs.  Like dev_tmp, the scratch is
  * fenced by an event: the next user waits for the last launch that read it (sao_done) */
-int sao_square_params(hevcdbk_context *ctx, DbkSaoArgs *sa, const unsigned *ctb_log2_h, unsigned n, hipStream_t s)
+/* the bytes of a 4:2:2 chroma plane's rows of CTBs, doubled like the parameters (dbk_launch_sao_nox_rows_x2) */
+size_t nox_x2_bytes(const DbkSaoArgs &a, const DbkSaoNox &nx)
 {
-    size_t entries = 0;
+    const size_t cols = (size_t)((a.plane_w + (1 << a.ctb_log2) - 1) >> a.ctb_log2), rows = (size_t)((a.plane_h + (1 << a.ctb_log2) - 1) >> a.ctb_log2);
+    return cols * rows * (nx.frame_stride ? (size_t)a.n_frames : 1);
+}
+
+/* nx (may be NULL): the planes' slice / tile boundary bytes, rewritten with the parameters into the same scratch */
+int sao_square_params(hevcdbk_context *ctx, DbkSaoArgs *sa, const unsigned *ctb_log2_h, unsigned n, hipStream_t s, DbkSaoNox *nx = nullptr)
+{
+    size_t entries = 0, nox_bytes = 0;
     for (unsigned i = 0; i < n; i++)
-        if (ctb_log2_h[i] != (unsigned)sa[i].ctb_log2) entries += dbk_sao_rows_x2_entries(sa[i]);
+        if (ctb_log2_h[i] != (unsigned)sa[i].ctb_log2) {
+            entries += dbk_sao_rows_x2_entries(sa[i]);
+            if (nx) nox_bytes += nox_x2_bytes(sa[i], nx[i]);
+        }
     if (entries == 0) return HEVCDBK_OK;
-    const size_t bytes = entries * sizeof(DbkSaoCtb);
+    const size_t bytes = entries * sizeof(DbkSaoCtb) + nox_bytes;
     if (!ctx->sao_ev) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->sao_ev, hipEventDisableTiming));
     if (ctx->sao_used) {
         if (ctx->dev_sao.cap < bytes) HIP_TRY(ctx, hipEventSynchronize(ctx->sao_ev)); /* about to free it */
@@ -403,8 +414,14 @@ int sao_square_params(hevcdbk_context *ctx, DbkSaoArgs *sa, const unsigned *ctb_
     }
     if (int rc = grow_device(ctx, ctx->dev_sao, bytes)) return rc;
     DbkSaoCtb *dst = (DbkSaoCtb *)ctx->dev_sao.p;
+    uint8_t *nox_dst = (uint8_t *)ctx->dev_sao.p + entries * sizeof(DbkSaoCtb);
     for (unsigned i = 0; i < n; i++)
         if (ctb_log2_h[i] != (unsigned)sa[i].ctb_log2) {
+            if (nx) {
+                const size_t nb = nox_x2_bytes(sa[i], nx[i]);
+                if (!hip_ok(ctx, dbk_launch_sao_nox_rows_x2(sa[i], nx[i], nox_dst, s), "SAO border launch")) return HEVCDBK_ERR_HIP;
+                nox_dst += nb;
+            }
             const size_t k = dbk_sao_rows_x2_entries(sa[i]);
             if (!hip_ok(ctx, dbk_launch_sao_rows_x2(sa[i], dst, s), "SAO parameter launch")) return HEVCDBK_ERR_HIP;
             dst += k;
@@ -427,38 +444,76 @@ bool fused_can(const DbkH265Args &h, const DbkSaoArgs &sa, const hevcdbk_device_
 
 /* deblock_sao_plane_h265 for a plane of a picture in chroma format cf (luma: cf 1), square CTBs (after sao_square_params) */
 int deblock_sao_plane_h265_cf(hevcdbk_context *ctx, const hevcdbk_device_planes *p, int c_idx, int cf, unsigned qp,
-                              const hevcdbk_h265_params *prm, DbkH265Args &h, DbkSaoArgs &sa, int fused, hipStream_t s)
+                              const hevcdbk_h265_params *prm, DbkH265Args &h, DbkSaoArgs &sa, int fused, hipStream_t s,
+                              const DbkSaoNox *nx = nullptr)
 {
-    if (cf == HEVCDBK_CHROMA_420 || c_idx == 0) return deblock_sao_plane_h265(ctx, p, c_idx, qp, prm, h, sa, fused, s);
+    if (cf == HEVCDBK_CHROMA_420 || c_idx == 0) return deblock_sao_plane_h265(ctx, p, c_idx, qp, prm, h, sa, fused, s, nx);
     const bool can = fused_can(h, sa, p, c_idx);
     if (fused == HEVCDBK_FUSED_ON && !can) return HEVCDBK_ERR_UNSUPPORTED;
     if (can && fused != HEVCDBK_FUSED_OFF)
-        return hip_ok(ctx, dbk_launch_deblock_sao_h265_cf(h, sa, (int)p->sample_bytes, true, cf, s), "fused deblocking + SAO launch")
+        return hip_ok(ctx, dbk_launch_deblock_sao_h265_cf(h, sa, (int)p->sample_bytes, true, cf, s, nx), "fused deblocking + SAO launch")
                    ? HEVCDBK_OK : HEVCDBK_ERR_HIP;
     hevcdbk_device_planes first, second;
     if (int rc = tmp_planes(ctx, p, s, first, second)) return rc;
     if (int rc = h265_args(&first, c_idx, qp, prm, h)) return rc;
     if (int rc = launch_h265(ctx, h, (int)p->sample_bytes, true, HEVCDBK_KERNEL_AUTO, s, cf)) return rc;
     sa.src = (const uint8_t *)second.src;
-    if (!hip_ok(ctx, dbk_launch_sao(sa, (int)p->sample_bytes, s), "SAO launch")) return HEVCDBK_ERR_HIP;
+    if (!hip_ok(ctx, dbk_launch_sao(sa, (int)p->sample_bytes, s, nx), "SAO launch")) return HEVCDBK_ERR_HIP;
     return tmp_done(ctx, s);
+}
+
+/* validates the slice / tile boundary operand of a plane whose SAO operands are `a` (before sao_square_params) and fills nx */
+int nox_args(const hevcdbk_sao_borders *b, const DbkSaoArgs &a, DbkSaoNox &nx)
+{
+    if (!b->nox || b->stride < (unsigned)((a.plane_w + (1 << a.ctb_log2) - 1) >> a.ctb_log2)) return HEVCDBK_ERR_ARG;
+    nx.nox = b->nox;
+    nx.stride = (int)b->stride;
+    nx.frame_stride = (long long)b->frame_stride;
+    return HEVCDBK_OK;
 }
 
 } /* namespace */
 
-int hevcdbk_sao_filter_device_cf(hevcdbk_context *ctx, const hevcdbk_device_planes *p, const hevcdbk_sao_ctb *params,
-                              unsigned params_stride, size_t params_frame_stride, unsigned ctb_log2_w, unsigned ctb_log2_h,
-                              const uint8_t *keep, unsigned keep_stride, size_t keep_frame_stride, void *hip_stream)
+int hevcdbk_sao_filter_device_nox(hevcdbk_context *ctx, const hevcdbk_device_planes *p, const hevcdbk_sao_ctb *params,
+                                  unsigned params_stride, size_t params_frame_stride, unsigned ctb_log2_w, unsigned ctb_log2_h,
+                                  const uint8_t *keep, unsigned keep_stride, size_t keep_frame_stride,
+                                  const hevcdbk_sao_borders *borders, void *hip_stream)
 {
     if (!ctx) return HEVCDBK_ERR_ARG;
     DbkSaoArgs a;
     if (int rc = sao_args_cf(p, params, params_stride, params_frame_stride, ctb_log2_w, ctb_log2_h, keep, keep_stride, keep_frame_stride, a))
         return rc;
+    DbkSaoNox nx, *nxp = nullptr; /* no operand: the kernels without it */
+    if (borders) {
+        if (int rc = nox_args(borders, a, nx)) return rc;
+        nxp = &nx;
+    }
     if (int rc = bind(ctx)) return rc;
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->compute;
-    if (int rc = sao_square_params(ctx, &a, &ctb_log2_h, 1, s)) return rc;
-    if (!hip_ok(ctx, dbk_launch_sao(a, (int)p->sample_bytes, s), "SAO launch")) return HEVCDBK_ERR_HIP;
+    if (int rc = sao_square_params(ctx, &a, &ctb_log2_h, 1, s, nxp)) return rc;
+    if (!hip_ok(ctx, dbk_launch_sao(a, (int)p->sample_bytes, s, nxp), "SAO launch")) return HEVCDBK_ERR_HIP;
     return ctb_log2_h != ctb_log2_w ? sao_done(ctx, s) : HEVCDBK_OK;
+}
+
+int hevcdbk_sao_filter_device_cf(hevcdbk_context *ctx, const hevcdbk_device_planes *p, const hevcdbk_sao_ctb *params,
+                              unsigned params_stride, size_t params_frame_stride, unsigned ctb_log2_w, unsigned ctb_log2_h,
+                              const uint8_t *keep, unsigned keep_stride, size_t keep_frame_stride, void *hip_stream)
+{
+    return hevcdbk_sao_filter_device_nox(ctx, p, params, params_stride, params_frame_stride, ctb_log2_w, ctb_log2_h, keep, keep_stride,
+                                         keep_frame_stride, nullptr, hip_stream);
+}
+
+int hevcdbk_h265_sao_borders_device(hevcdbk_context *ctx, const uint16_t *slice_idx, const uint8_t *slice_across, const uint16_t *tile_idx,
+                                    int loop_filter_across_tiles_enabled_flag, unsigned ctbs_x, unsigned ctbs_y, unsigned in_stride,
+                                    uint8_t *nox, unsigned nox_stride, void *hip_stream)
+{
+    if (!ctx || !slice_idx || !slice_across || !nox) return HEVCDBK_ERR_ARG;
+    if (ctbs_x == 0 || ctbs_y == 0 || ctbs_x > 65535 || ctbs_y > 65535 || in_stride < ctbs_x || nox_stride < ctbs_x) return HEVCDBK_ERR_ARG;
+    if (int rc = bind(ctx)) return rc;
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->compute;
+    const hipError_t e = dbk_launch_sao_borders(slice_idx, slice_across, tile_idx, loop_filter_across_tiles_enabled_flag != 0, (int)ctbs_x,
+                                                (int)ctbs_y, (int)in_stride, nox, (int)nox_stride, s);
+    return hip_ok(ctx, e, "SAO border derivation launch") ? HEVCDBK_OK : HEVCDBK_ERR_HIP;
 }
 
 int hevc_sao_filter_device(hevcdbk_context *ctx, const hevcdbk_device_planes *p, const hevcdbk_sao_ctb *params,
@@ -578,17 +633,32 @@ int hevcdbk_h265_deblock_sao_device_cf(hevcdbk_context *ctx, const hevcdbk_devic
                                     size_t params_frame_stride, unsigned ctb_log2_w, unsigned ctb_log2_h, const uint8_t *keep,
                                     unsigned keep_stride, size_t keep_frame_stride, int fused, void *hip_stream)
 {
+    return hevcdbk_h265_deblock_sao_device_nox(ctx, p, c_idx, chroma_format_idc, qp, prm, params, params_stride, params_frame_stride,
+                                               ctb_log2_w, ctb_log2_h, keep, keep_stride, keep_frame_stride, fused, nullptr, hip_stream);
+}
+
+int hevcdbk_h265_deblock_sao_device_nox(hevcdbk_context *ctx, const hevcdbk_device_planes *p, int c_idx, int chroma_format_idc, unsigned qp,
+                                        const hevcdbk_h265_params *prm, const hevcdbk_sao_ctb *params, unsigned params_stride,
+                                        size_t params_frame_stride, unsigned ctb_log2_w, unsigned ctb_log2_h, const uint8_t *keep,
+                                        unsigned keep_stride, size_t keep_frame_stride, int fused, const hevcdbk_sao_borders *borders,
+                                        void *hip_stream)
+{
     if (!ctx || (fused != HEVCDBK_FUSED_AUTO && fused != HEVCDBK_FUSED_OFF && fused != HEVCDBK_FUSED_ON)) return HEVCDBK_ERR_ARG;
     DbkSaoArgs sa;
     if (int rc = sao_args_cf(p, params, params_stride, params_frame_stride, ctb_log2_w, ctb_log2_h, keep, keep_stride, keep_frame_stride, sa))
         return rc;
     DbkH265Args h;
     if (int rc = h265_args_cf(p, c_idx, chroma_format_idc, qp, prm, h)) return rc;
+    DbkSaoNox nx, *nxp = nullptr; /* no operand: the kernels without it */
+    if (borders) {
+        if (int rc = nox_args(borders, sa, nx)) return rc;
+        nxp = &nx;
+    }
     if (fused == HEVCDBK_FUSED_ON && !fused_can(h, sa, p, c_idx)) return HEVCDBK_ERR_UNSUPPORTED; /* before any launch */
     if (int rc = bind(ctx)) return rc;
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->compute;
-    if (int rc = sao_square_params(ctx, &sa, &ctb_log2_h, 1, s)) return rc;
-    const int rc = deblock_sao_plane_h265_cf(ctx, p, c_idx, c_idx != 0 ? chroma_format_idc : 1, qp, prm, h, sa, fused, s);
+    if (int rc = sao_square_params(ctx, &sa, &ctb_log2_h, 1, s, nxp)) return rc;
+    const int rc = deblock_sao_plane_h265_cf(ctx, p, c_idx, c_idx != 0 ? chroma_format_idc : 1, qp, prm, h, sa, fused, s, nxp);
     if (ctb_log2_h != ctb_log2_w)
         if (int rc2 = sao_done(ctx, s)) return rc ? rc : rc2; /* the parameter launch is fenced whatever followed it */
     return rc;
@@ -598,12 +668,20 @@ int hevcdbk_h265_deblock_sao_device_planes_cf(hevcdbk_context *ctx, const hevcdb
                                            int chroma_format_idc, unsigned qp, const hevcdbk_h265_params *prm,
                                            const hevcdbk_sao_plane_cf *sao, int fused, void *hip_stream)
 {
+    return hevcdbk_h265_deblock_sao_device_planes_nox(ctx, planes, n_planes, chroma_format_idc, qp, prm, sao, fused, nullptr, hip_stream);
+}
+
+int hevcdbk_h265_deblock_sao_device_planes_nox(hevcdbk_context *ctx, const hevcdbk_device_planes *planes, unsigned n_planes,
+                                               int chroma_format_idc, unsigned qp, const hevcdbk_h265_params *prm,
+                                               const hevcdbk_sao_plane_cf *sao, int fused, const hevcdbk_sao_borders *borders,
+                                               void *hip_stream)
+{
     const int cf = chroma_format_idc;
     if (!ctx || !planes || !sao || n_planes == 0 || n_planes > 3 || cf < HEVCDBK_CHROMA_400 || cf > HEVCDBK_CHROMA_444 ||
         (fused != HEVCDBK_FUSED_AUTO && fused != HEVCDBK_FUSED_OFF && fused != HEVCDBK_FUSED_ON))
         return HEVCDBK_ERR_ARG;
     if (cf == HEVCDBK_CHROMA_400 && n_planes > 1) return HEVCDBK_ERR_ARG;
-    if (cf == HEVCDBK_CHROMA_420) { /* square CTBs: exactly the 4:2:0 entry, checks included */
+    if (cf == HEVCDBK_CHROMA_420 && !borders) { /* square CTBs: exactly the 4:2:0 entry, checks included */
         bool square = true;
         hevcdbk_sao_plane sq[3];
         for (unsigned i = 0; i < n_planes; i++) {
@@ -615,6 +693,7 @@ int hevcdbk_h265_deblock_sao_device_planes_cf(hevcdbk_context *ctx, const hevcdb
     }
     DbkH265Args h[3];
     DbkSaoArgs sa[3];
+    DbkSaoNox nx[3], *nxp = borders ? nx : nullptr; /* ONE operand for the picture: every plane's CTB grid is the luma grid sub-sampled */
     bool can[3] = {false, false, false}, rect = false;
     unsigned log2_h[3] = {0, 0, 0};
     bool one = n_planes >= 2 && fused != HEVCDBK_FUSED_OFF && !planes[0].is_chroma;
@@ -623,6 +702,8 @@ int hevcdbk_h265_deblock_sao_device_planes_cf(hevcdbk_context *ctx, const hevcdb
                                  sao[i].ctb_log2_h, sao[i].keep, sao[i].keep_stride, sao[i].keep_frame_stride, sa[i]))
             return rc;
         if (int rc = h265_args_cf(&planes[i], (int)i, cf, qp, prm, h[i])) return rc; /* c_idx = plane index: 0 Y, 1 Cb, 2 Cr */
+        if (borders)
+            if (int rc = nox_args(borders, sa[i], nx[i])) return rc;
         if (planes[i].n_frames != planes[0].n_frames) return HEVCDBK_ERR_ARG;
         /* chroma planes in the format's geometry of the luma plane (when planes[0] is the luma plane; 4:2:0 as its own entry) */
         if (i > 0 && !planes[0].is_chroma && cf != HEVCDBK_CHROMA_420 &&
@@ -639,15 +720,15 @@ int hevcdbk_h265_deblock_sao_device_planes_cf(hevcdbk_context *ctx, const hevcdb
             if (!can[i]) return HEVCDBK_ERR_UNSUPPORTED;
     if (int rc = bind(ctx)) return rc;
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->compute;
-    if (int rc = sao_square_params(ctx, sa, log2_h, n_planes, s)) return rc;
+    if (int rc = sao_square_params(ctx, sa, log2_h, n_planes, s, nxp)) return rc;
     int rc = HEVCDBK_OK;
     if (one) {
-        if (!hip_ok(ctx, dbk_launch_deblock_sao_multi_h265_cf(h, sa, (int)n_planes, (int)planes[0].sample_bytes, cf, s),
+        if (!hip_ok(ctx, dbk_launch_deblock_sao_multi_h265_cf(h, sa, (int)n_planes, (int)planes[0].sample_bytes, cf, s, nxp),
                     "fused deblocking + SAO launch"))
             rc = HEVCDBK_ERR_HIP;
     } else {
         for (unsigned i = 0; i < n_planes && rc == HEVCDBK_OK; i++)
-            rc = deblock_sao_plane_h265_cf(ctx, &planes[i], (int)i, i != 0 ? cf : 1, qp, prm, h[i], sa[i], fused, s);
+            rc = deblock_sao_plane_h265_cf(ctx, &planes[i], (int)i, i != 0 ? cf : 1, qp, prm, h[i], sa[i], fused, s, nxp ? &nxp[i] : nullptr);
     }
     if (rect)
         if (int rc2 = sao_done(ctx, s)) return rc ? rc : rc2; /* the parameter launch is fenced whatever followed it */

@@ -153,7 +153,24 @@ struct DbkSaoArgs {
     int keep_stride;
     long long keep_frame_stride;
 };
-hipError_t dbk_launch_sao(const DbkSaoArgs &a, int sample_bytes, hipStream_t stream);
+/* slice / tile boundaries SAO must not look across (H.265 8.7.3.2; hevcdbk_sao_borders of the C ABI): one byte per CTB of the
+ * plane's own CTB grid, HEVCDBK_SAO_NOX_* bits.  A kernel argument of its own, taken by the _nox kernels only: the kernels
+ * without the operand keep their argument layout, i.e. their machine code */
+struct DbkSaoNox {
+    const uint8_t *nox;
+    int stride;
+    long long frame_stride; /* bytes, 0 = shared */
+};
+/* nx == NULL: the kernels without the operand; else their _nox twins, which honour the bytes */
+hipError_t dbk_launch_sao(const DbkSaoArgs &a, int sample_bytes, hipStream_t stream, const DbkSaoNox *nx = nullptr);
+/* the bytes of the CTBs hevcdbk_h265_sao_borders_device describes: one lane per CTB */
+hipError_t dbk_launch_sao_borders(const uint16_t *slice_idx, const uint8_t *slice_across, const uint16_t *tile_idx, int tiles_across,
+                                  int ctbs_x, int ctbs_y, int in_stride, uint8_t *nox, int nox_stride, hipStream_t stream);
+/* the bytes of a 4:2:2 chroma plane's CTBs rewritten for square CTBs as dbk_launch_sao_rows_x2 rewrites the parameters (a = the
+ * plane BEFORE that call): every row twice, the upper half's neighbours below and the lower half's above being the CTB itself and
+ * its left / right neighbours; dst holds one byte per square CTB of the plane (times a.n_frames when nx.frame_stride is not 0);
+ * points nx at them */
+hipError_t dbk_launch_sao_nox_rows_x2(const DbkSaoArgs &a, DbkSaoNox &nx, uint8_t *dst, hipStream_t stream);
 /* CTBs of (1 << a.ctb_log2) x (2 << a.ctb_log2) samples (4:2:2 chroma): writes the parameters as those of square CTBs of
  * (1 << a.ctb_log2) -- every row twice -- into dst (dbk_sao_rows_x2_entries(a) entries, device memory) and points a at them */
 size_t dbk_sao_rows_x2_entries(const DbkSaoArgs &a);
@@ -196,8 +213,9 @@ hipError_t dbk_launch_deblock_sao_multi(const DbkArgs *d, const DbkSaoArgs *s, i
 hipError_t dbk_launch_deblock_sao_multi_h265(const DbkH265Args *h, const DbkSaoArgs *s, int n, int sample_bytes, hipStream_t stream);
 /* the same for the chroma planes of 4:2:2 / 4:4:4 pictures with one QP (QpC by Min(qPi, 51), folded into the scalar tc as above;
  * square CTBs: 4:2:2 parameters through dbk_launch_sao_rows_x2 first) */
+/* nx (one per plane for the multi launch) == NULL: the kernels without the operand; else their _nox twins */
 hipError_t dbk_launch_deblock_sao_h265_cf(const DbkH265Args &h, const DbkSaoArgs &s, int sample_bytes, bool chroma, int chroma_format,
-                                          hipStream_t stream);
+                                          hipStream_t stream, const DbkSaoNox *nx = nullptr);
 hipError_t dbk_launch_deblock_sao_multi_h265_cf(const DbkH265Args *h, const DbkSaoArgs *s, int n, int sample_bytes, int chroma_format,
-                                                hipStream_t stream);
+                                                hipStream_t stream, const DbkSaoNox *nx = nullptr);
 

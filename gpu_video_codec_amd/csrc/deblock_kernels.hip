@@ -1504,7 +1504,7 @@ static bool fused_format_ok(int chroma_format)
 }
 
 hipError_t dbk_launch_deblock_sao_h265_cf(const DbkH265Args &h, const DbkSaoArgs &s, int sample_bytes, bool chroma, int chroma_format,
-                                          hipStream_t stream)
+                                          hipStream_t stream, const DbkSaoNox *nxp)
 {
     if (!fused_format_ok(chroma_format)) return hipErrorInvalidValue;
     if (h.base.n_frames <= 0 || h.base.nbx <= 0 || h.base.nby <= 0) return hipSuccess;
@@ -1514,6 +1514,33 @@ hipError_t dbk_launch_deblock_sao_h265_cf(const DbkH265Args &h, const DbkSaoArgs
     fused_h265_scalars(fa.d, chroma, chroma_format);
     const bool qm = h.base.qp_map != nullptr;
     const dim3 grid(fused_grid(h.base.plane_w, h.base.plane_h, h.base.n_frames, sample_bytes, fa.g), 1, 1);
+    if (nxp) { /* the same grid and choice of kernel, the _nox twins (deblock_sao_fused.inc) */
+        const DbkSaoNox nx = *nxp;
+        const int cf = chroma && qm ? chroma_format : 1; /* the format enters the kernel through a chroma plane's QP map only */
+#define DBK_NOX8(C, Q, F) DBK_LAUNCH_LDS((dbk_sao_fused_h265_nox_kernel<C, Q, F>), grid, dim3(kFusedThreads), kFusedLds, stream, fa, nx)
+#define DBK_NOX16(C, W, Q, F) DBK_LAUNCH_LDS((dbk_sao_fused16_h265_nox_kernel<C, W, Q, F>), grid, dim3(kFused16Threads), kFused16Lds, stream, fa, nx)
+        if (sample_bytes == 1) {
+            if (cf == 2) DBK_NOX8(true, true, 2);
+            else if (cf == 3) DBK_NOX8(true, true, 3);
+            else if (chroma && qm) DBK_NOX8(true, true, 1);
+            else if (chroma) DBK_NOX8(true, false, 1);
+            else if (qm) DBK_NOX8(false, true, 1);
+            else DBK_NOX8(false, false, 1);
+        } else {
+            const bool wide = !chroma && h.base.max_v > 2047;
+            if (cf == 2) DBK_NOX16(true, false, true, 2);
+            else if (cf == 3) DBK_NOX16(true, false, true, 3);
+            else if (chroma && qm) DBK_NOX16(true, false, true, 1);
+            else if (chroma) DBK_NOX16(true, false, false, 1);
+            else if (wide && qm) DBK_NOX16(false, true, true, 1);
+            else if (wide) DBK_NOX16(false, true, false, 1);
+            else if (qm) DBK_NOX16(false, false, true, 1);
+            else DBK_NOX16(false, false, false, 1);
+        }
+#undef DBK_NOX8
+#undef DBK_NOX16
+        return hipGetLastError();
+    }
     if (chroma && qm && chroma_format != 1) {
         if (sample_bytes == 1) {
             if (chroma_format == 2) DBK_LAUNCH_LDS((dbk_sao_fused_h265_cf_kernel<2>), grid, dim3(kFusedThreads), kFusedLds, stream, fa);
@@ -1565,7 +1592,7 @@ hipError_t dbk_launch_deblock_sao_multi_h265(const DbkH265Args *h, const DbkSaoA
 }
 
 hipError_t dbk_launch_deblock_sao_multi_h265_cf(const DbkH265Args *h, const DbkSaoArgs *s, int n, int sample_bytes, int chroma_format,
-                                                hipStream_t stream)
+                                                hipStream_t stream, const DbkSaoNox *nxp)
 {
     if (!fused_format_ok(chroma_format)) return hipErrorInvalidValue;
     if (n < 2 || n > 3) return hipErrorInvalidValue;
@@ -1585,6 +1612,28 @@ hipError_t dbk_launch_deblock_sao_multi_h265_cf(const DbkH265Args *h, const DbkS
     const dim3 grid(total, 1, 1);
     const DbkFusedMultiH265Args &fa = m;
     const bool qm = h[0].base.qp_map != nullptr; /* the caller checked: all planes with a map, or none */
+    if (nxp) { /* the same grid and choice of kernel, the _nox twins */
+        DbkSaoNox3 nx = {};
+        for (int i = 0; i < n; i++) nx.pl[i] = nxp[i];
+        const int cf = qm ? chroma_format : 1;
+        const bool wide = h[0].base.max_v > 2047;
+#define DBK_NOXM(SB, W, Q, F)                                                                                                          \
+    DBK_LAUNCH_LDS((dbk_sao_fused_multi_h265_nox_kernel<SB, W, Q, F>), grid, dim3(SB == 1 ? kFusedThreads : kFused16Threads),          \
+                   SB == 1 ? kFusedLds : kFused16Lds, stream, fa, nx)
+#define DBK_NOXM_F(Q, F)                                                                                                               \
+    do {                                                                                                                               \
+        if (sample_bytes == 1) DBK_NOXM(1, false, Q, F);                                                                               \
+        else if (wide) DBK_NOXM(2, true, Q, F);                                                                                        \
+        else DBK_NOXM(2, false, Q, F);                                                                                                 \
+    } while (0)
+        if (cf == 2) DBK_NOXM_F(true, 2);
+        else if (cf == 3) DBK_NOXM_F(true, 3);
+        else if (qm) DBK_NOXM_F(true, 1);
+        else DBK_NOXM_F(false, 1);
+#undef DBK_NOXM_F
+#undef DBK_NOXM
+        return hipGetLastError();
+    }
     if (qm && chroma_format != 1) { /* QP-map planes of 4:2:2 / 4:4:4 */
 #define DBK_FUSED_CF_LAUNCH(CF)                                                                                                      \
     do {                                                                                                                             \

@@ -33,10 +33,11 @@ constexpr int kFusedQuads = kFusedTile / 64;          /* 64 x 64 quadrants: kFus
 constexpr int kFusedQuadsX = kFusedTileW / 64;
 constexpr int kFusedLds = (kFusedTile + 8) * kFusedPitch;
 
-template <bool CHROMA, int MODE, bool QPMAP, int CF = 1> /* MODE 0 = reference-exact deblocking, 2 = spec-exact (H.265 8.7.2); QPMAP = QP per map unit;
-                                                          CF = chroma_format_idc of a spec-exact chroma plane with a QP map */
+template <bool CHROMA, int MODE, bool QPMAP, int CF = 1, bool NOX = false> /* MODE 0 = reference-exact deblocking, 2 = spec-exact (H.265 8.7.2); QPMAP = QP per map unit;
+                                                          CF = chroma_format_idc of a spec-exact chroma plane with a QP map;
+                                                          NOX = stage 2 honours the slice / tile boundaries of nx (the _nox kernels) */
 __device__ __forceinline__ void fused_body(const DbkArgs &a, const DbkH265Args *hx, const DbkSaoArgs &s, const DbkFusedGrid &g, uint8_t *tile,
-                                           uint32_t id /* workgroup number inside this plane's part of the grid */)
+                                           uint32_t id /* workgroup number inside this plane's part of the grid */, const DbkSaoNox *nx = nullptr)
 {
     /* workgroups are dealt round-robin over the 8 XCDs (an observation used for speed only): renumber them so that each XCD
      * works through a contiguous range of tiles.  A tile's row pieces are 200 bytes at an odd alignment, so it shares 128-byte
@@ -152,6 +153,8 @@ __device__ __forceinline__ void fused_body(const DbkArgs &a, const DbkH265Args *
         constexpr int NROWS = decltype(nrows)::value;
         const int x = X0 + qx, ys = Y0 + qy;
         if (x >= s.plane_w || ys >= s.plane_h) return;
+        [[maybe_unused]] uint32_t nox_byte = 0u;
+        if constexpr (NOX) nox_byte = saonox::ctb_byte(*nx, f, x, ys, s.ctb_log2);
         const DbkSaoCtb c = s.params[(long long)f * s.params_frame_stride + (long long)(ys >> s.ctb_log2) * s.params_stride + (x >> s.ctb_log2)];
         const bool kept = s.keep && s.keep[(long long)f * s.keep_frame_stride + (long long)(ys >> 3) * s.keep_stride + (x >> 3)];
         /* image (x - 4, ys - 1 + i) is tile (qx, qy + 3 + i): the tile's origin is image (X0 - 4, Y0 - 4) */
@@ -169,6 +172,12 @@ __device__ __forceinline__ void fused_body(const DbkArgs &a, const DbkH265Args *
             w.y = hi;
             __builtin_amdgcn_raw_buffer_store_b64(w, rd, vout, r * (int)s.pitch, 0);
         };
+        if constexpr (NOX) { /* the block's mask of directions not to look in, the picture border among them (sao_packed.h) */
+            const uint32_t m = saonox::block_mask<NROWS>(nox_byte, x, ys, s.plane_w, s.plane_h, s.ctb_log2);
+            if (__builtin_amdgcn_ballot_w64(m != 0u) != 0ull) sao8::block<2, NROWS>(fetch, store, x, ys, s.plane_w, s.plane_h, c, kept, m);
+            else sao8::block<false, NROWS>(fetch, store, x, ys, s.plane_w, s.plane_h, c, kept);
+            return;
+        }
         const bool border = x == 0 || x + 8 == s.plane_w || ys == 0 || ys + NROWS >= s.plane_h;
         if (__builtin_amdgcn_ballot_w64(border) != 0ull) sao8::block<true, NROWS>(fetch, store, x, ys, s.plane_w, s.plane_h, c, kept);
         else sao8::block<false, NROWS>(fetch, store, x, ys, s.plane_w, s.plane_h, c, kept);
@@ -200,9 +209,9 @@ constexpr int kFused16Threads = 320;
 constexpr int kFused16Quads = kFused16Tile / 64;       /* 2 x 2 SAO waves */
 constexpr int kFused16Lds = (kFused16Tile + 8) * kFused16Pitch;
 
-template <bool CHROMA, int MODE, bool WIDE, bool QPMAP, int CF = 1>
+template <bool CHROMA, int MODE, bool WIDE, bool QPMAP, int CF = 1, bool NOX = false>
 __device__ __forceinline__ void fused_body16(const DbkArgs &a, const DbkH265Args *hx, const DbkSaoArgs &s, const DbkFusedGrid &g, uint8_t *tile,
-                                             uint32_t id)
+                                             uint32_t id, const DbkSaoNox *nx = nullptr)
 {
     const uint32_t logical = (id & 7u) * g.per_xcd + (id >> 3);
     if (logical >= g.total) return;
@@ -292,6 +301,8 @@ __device__ __forceinline__ void fused_body16(const DbkArgs &a, const DbkH265Args
         constexpr int NROWS = decltype(nrows)::value;
         const int x = X0 + qx, ys = Y0 + qy;
         if (x >= s.plane_w || ys >= s.plane_h) return;
+        [[maybe_unused]] uint32_t nox_byte = 0u;
+        if constexpr (NOX) nox_byte = saonox::ctb_byte(*nx, f, x, ys, s.ctb_log2);
         const DbkSaoCtb c = s.params[(long long)f * s.params_frame_stride + (long long)(ys >> s.ctb_log2) * s.params_stride + (x >> s.ctb_log2)];
         const bool kept = s.keep && s.keep[(long long)f * s.keep_frame_stride + (long long)(ys >> 3) * s.keep_stride + (x >> 3)];
         /* image (x - 4, ys - 1 + i) is tile (column qx, row qy + 3 + i): the tile's origin is image (X0 - 4, Y0 - 4) */
@@ -315,6 +326,14 @@ __device__ __forceinline__ void fused_body16(const DbkArgs &a, const DbkH265Args
              * scans the product's ISA for the sequence. */
             asm volatile("s_nop 1" : : "v"(w.x), "v"(w.y), "v"(w.z), "v"(w.w) : "memory"); /* reads w: nothing that overwrites it moves above */
         };
+        if constexpr (NOX) {
+            const uint32_t m = saonox::block_mask<NROWS>(nox_byte, x, ys, s.plane_w, s.plane_h, s.ctb_log2);
+            if (__builtin_amdgcn_ballot_w64(m != 0u) != 0ull)
+                sao16::block<2, NROWS>(fetch, store, x, ys, s.plane_w, s.plane_h, c, kept, s.max_v, s.band_shift, m);
+            else
+                sao16::block<false, NROWS>(fetch, store, x, ys, s.plane_w, s.plane_h, c, kept, s.max_v, s.band_shift);
+            return;
+        }
         const bool border = x == 0 || x + 8 == s.plane_w || ys == 0 || ys + NROWS >= s.plane_h;
         if (__builtin_amdgcn_ballot_w64(border) != 0ull)
             sao16::block<true, NROWS>(fetch, store, x, ys, s.plane_w, s.plane_h, c, kept, s.max_v, s.band_shift);
@@ -429,5 +448,41 @@ __global__ __launch_bounds__(SB == 1 ? kFusedThreads : kFused16Threads) void dbk
     } else {
         if (pl == 0) fused_body16<false, 2, WIDE, true>(fa.d.base, &fa.d, fa.s, fa.g, fused_tile, id);
         else fused_body16<true, 2, false, true, CF>(fa.d.base, &fa.d, fa.s, fa.g, fused_tile, id);
+    }
+}
+
+/* ---- the spec-exact kernels with the slice / tile boundaries SAO must not look across (H.265 8.7.3.2): the kernels above plus one
+ * argument, DbkSaoNox (one per plane for the multi-plane launch).  Kernels of their own names, so that every kernel without the
+ * operand keeps its argument layout and machine code; CF 1 = 4:2:0 and every one-QP plane (fused_body's CF enters through the QP
+ * map only) ---- */
+template <bool CHROMA, bool QPMAP, int CF>
+__global__ __launch_bounds__(kFusedThreads) void dbk_sao_fused_h265_nox_kernel(const DbkFusedH265Args fa, const DbkSaoNox nx)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t fused_tile[];
+    fused_body<CHROMA, 2, QPMAP, CF, true>(fa.d.base, &fa.d, fa.s, fa.g, fused_tile, blockIdx.x, &nx);
+}
+template <bool CHROMA, bool WIDE, bool QPMAP, int CF>
+__global__ __launch_bounds__(kFused16Threads) void dbk_sao_fused16_h265_nox_kernel(const DbkFusedH265Args fa, const DbkSaoNox nx)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t fused_tile[];
+    fused_body16<CHROMA, 2, WIDE, QPMAP, CF, true>(fa.d.base, &fa.d, fa.s, fa.g, fused_tile, blockIdx.x, &nx);
+}
+struct DbkSaoNox3 {
+    DbkSaoNox pl[3];
+};
+template <int SB, bool WIDE, bool QPMAP, int CF>
+__global__ __launch_bounds__(SB == 1 ? kFusedThreads : kFused16Threads) void dbk_sao_fused_multi_h265_nox_kernel(const DbkFusedMultiH265Args m,
+                                                                                                                 const DbkSaoNox3 nx)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t fused_tile[];
+    uint32_t id;
+    const int pl = fused_plane(m.wg_end, id);
+    const DbkFusedH265Args &fa = m.pl[pl];
+    if constexpr (SB == 1) {
+        if (pl == 0) fused_body<false, 2, QPMAP, 1, true>(fa.d.base, &fa.d, fa.s, fa.g, fused_tile, id, &nx.pl[0]);
+        else fused_body<true, 2, QPMAP, CF, true>(fa.d.base, &fa.d, fa.s, fa.g, fused_tile, id, &nx.pl[pl]);
+    } else {
+        if (pl == 0) fused_body16<false, 2, WIDE, QPMAP, 1, true>(fa.d.base, &fa.d, fa.s, fa.g, fused_tile, id, &nx.pl[0]);
+        else fused_body16<true, 2, false, QPMAP, CF, true>(fa.d.base, &fa.d, fa.s, fa.g, fused_tile, id, &nx.pl[pl]);
     }
 }

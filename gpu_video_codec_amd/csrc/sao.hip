@@ -94,117 +94,27 @@ __device__ __forceinline__ bool sao_strip(const DbkFusedGrid &g, int &wx, int &w
  * CTB parameters and the keep flag are fetched once, and the edge classifier slides a three-row window down the block, so a
  * row is loaded once per lane (10 rows for 8 rows of output) instead of three times per output row.
  */
-template <typename T, bool SWZ, bool PK16 = false> /* PK16: 16-bit containers up to 12 bit take the packed block procedure in waves off the border */
+/* the CTB bit that speaks for the neighbouring CTB (dcx, dcy), each -1 / 0 / 1; (0, 0) = the CTB itself: nothing */
+__device__ __forceinline__ uint32_t sao_nox_bit(int dcx, int dcy)
+{
+    using namespace saonox;
+    return dcy < 0 ? (dcx < 0 ? UL : (dcx > 0 ? UR : U)) : (dcy > 0 ? (dcx < 0 ? DL : (dcx > 0 ? DR : D)) : (dcx < 0 ? L : (dcx > 0 ? R : 0u)));
+}
+
+/* PK16: 16-bit containers up to 12 bit take the packed block procedure in waves off the border.  The body is written once
+ * (sao_kernel_body.inc) for the kernel and its _nox twin */
+template <typename T, bool SWZ, bool PK16 = false>
 __global__ __launch_bounds__(256) void sao_kernel(const DbkSaoArgs a, const DbkFusedGrid g)
 {
-    /* a wave = the 8 x 8 blocks of one 64 x 64 region: with 64-sample CTBs every lane of a wave has the same SAO type and the
-     * wave runs ONE of the three paths; a row-shaped wave (512 x 8) would span eight CTBs and run all of them */
-    int wx, wy, f;
-    if (!sao_strip<SWZ>(g, wx, wy, f)) return;
-    const int wv = threadIdx.x >> 6, l = threadIdx.x & 63;
-    const int x = (wx * 4 + wv) * 64 + (l & 7) * 8;
-    const int y0 = wy * 64 + (l >> 3) * 8;
-    if (x >= a.plane_w || y0 >= a.plane_h) return;
-    const uint8_t *src = a.src + (long long)f * a.frame_stride;
-    uint8_t *dst = a.dst + (long long)f * a.frame_stride;
-    const DbkSaoCtb c = a.params[(long long)f * a.params_frame_stride + (long long)(y0 >> a.ctb_log2) * a.params_stride + (x >> a.ctb_log2)];
-    const bool kept = a.keep && a.keep[(long long)f * a.keep_frame_stride + (long long)(y0 >> 3) * a.keep_stride + (x >> 3)];
-    if constexpr (PK16 && sizeof(T) == 2) {
-        /* no lane of the wave on the picture border (nearly every wave): the packed 16-bit block procedure of the fused kernels
-         * (sao_packed.h, sao16: the samples already are int16 pairs) on rows addressed through buffer resources, as the 8-bit
-         * kernel below does; a region's row piece is a whole 128-byte line here, so the wave keeps its 64 x 64 shape */
-        const bool border = x == 0 || x + 8 == a.plane_w || y0 == 0 || y0 + 8 >= a.plane_h;
-        if (__builtin_amdgcn_ballot_w64(border) == 0ull) {
-            typedef uint32_t u32x4b __attribute__((ext_vector_type(4)));
-            const uint32_t plane_bytes = (uint32_t)a.pitch * (uint32_t)a.plane_h; /* < 2^31: checked by the launcher */
-            const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(src), 0, plane_bytes, 0x00020000);
-            const __amdgpu_buffer_rsrc_t rd = __builtin_amdgcn_make_buffer_rsrc(dst, 0, plane_bytes, 0x00020000);
-            const int sp = __builtin_amdgcn_readfirstlane((int)a.pitch);
-            const uint32_t vrow = (uint32_t)y0 * (uint32_t)a.pitch + (uint32_t)x * 2u;
-            const uint32_t vup = vrow - (uint32_t)a.pitch; /* raw row 0 = image row y0 - 1 */
-            auto fetch = [&](int j, auto halo) {
-                sao16::Raw q;
-                const u32x4b m = __builtin_amdgcn_raw_buffer_load_b128(rs, vup, j * sp, 0); /* samples x .. x+7 */
-                q.d[0] = q.d[7] = 0u;
-                q.d[2] = m.x; q.d[3] = m.y; q.d[4] = m.z; q.d[5] = m.w;
-                if constexpr (decltype(halo)::value) {
-                    q.d[1] = __builtin_amdgcn_raw_buffer_load_b32(rs, vup - 4u, j * sp, 0);  /* s[-2], s[-1] */
-                    q.d[6] = __builtin_amdgcn_raw_buffer_load_b32(rs, vup + 16u, j * sp, 0); /* s8, s9 */
-                } else {
-                    q.d[1] = q.d[6] = 0u;
-                }
-                return q;
-            };
-            auto store = [&](int r, uint32_t d0, uint32_t d1, uint32_t d2, uint32_t d3) {
-                u32x4b w;
-                w.x = d0; w.y = d1; w.z = d2; w.w = d3;
-                __builtin_amdgcn_raw_buffer_store_b128(w, rd, vrow, r * sp, 0);
-                /* the wait states of the fused 16-bit kernel's stores (deblock_sao_fused.inc): a 16-byte buffer store with an SGPR
-                 * offset followed at once by a VALU write of its data registers */
-                asm volatile("s_nop 1" : : "v"(w.x), "v"(w.y), "v"(w.z), "v"(w.w) : "memory");
-            };
-            sao16::block<false, 8>(fetch, store, x, y0, a.plane_w, a.plane_h, c, kept, a.max_v, a.band_shift);
-            return;
-        }
-    }
-    if (kept || c.type == 0 || c.type > 2) {
-#pragma unroll
-        for (int r = 0; r < 8; r++) {
-            int o[8];
-            load8<T>(src + (long long)(y0 + r) * a.pitch, x, o);
-            store8<T>(dst + (long long)(y0 + r) * a.pitch, x, o);
-        }
-        return;
-    }
-    if (c.type == 1) { /* band offset: bandTable[(k + sao_band_position) & 31] = k + 1 */
-#pragma unroll
-        for (int r = 0; r < 8; r++) {
-            int o[8];
-            load8<T>(src + (long long)(y0 + r) * a.pitch, x, o);
-#pragma unroll
-            for (int i = 0; i < 8; i++) {
-                const int k = ((o[i] >> a.band_shift) - (int)c.cls) & 31;
-                const int off = k == 0 ? c.offset[0] : (k == 1 ? c.offset[1] : (k == 2 ? c.offset[2] : (k == 3 ? c.offset[3] : 0)));
-                const int v = o[i] + off;
-                o[i] = v < 0 ? 0 : (v > a.max_v ? a.max_v : v);
-            }
-            store8<T>(dst + (long long)(y0 + r) * a.pitch, x, o);
-        }
-        return;
-    }
-    /* edge offset, Table 8-13: class 0 (-1,0)/(1,0); 1 (0,-1)/(0,1); 2 (-1,-1)/(1,1); 3 (1,-1)/(-1,1) */
-    const int cls = c.cls & 3;
-    const int dxa = cls == 1 ? 0 : (cls == 3 ? 1 : -1);
-    const bool vertical = cls != 0; /* neighbours in the rows above and below */
-    auto row_at = [&](int y) { return src + (long long)(y < 0 ? 0 : (y >= a.plane_h ? a.plane_h - 1 : y)) * a.pitch; };
-    int up[10], mid[10], dn[10];
-    load10<T>(row_at(y0 - 1), x, a.plane_w, up);
-    load10<T>(row_at(y0), x, a.plane_w, mid);
-#pragma unroll
-    for (int r = 0; r < 8; r++) {
-        const int y = y0 + r;
-        load10<T>(row_at(y + 1), x, a.plane_w, dn);
-        const bool rows_ok = !vertical || (y > 0 && y < a.plane_h - 1);
-        int o[8];
-#pragma unroll
-        for (int i = 0; i < 8; i++) {
-            const int rec = mid[1 + i];
-            const int xa = x + i + dxa, xb = x + i - dxa;
-            const bool ok = rows_ok && xa >= 0 && xa < a.plane_w && xb >= 0 && xb < a.plane_w;
-            const int (&ra)[10] = vertical ? up : mid;
-            const int (&rb)[10] = vertical ? dn : mid;
-            const int na = dxa < 0 ? ra[i] : (dxa == 0 ? ra[1 + i] : ra[2 + i]);
-            const int nb = dxa < 0 ? rb[2 + i] : (dxa == 0 ? rb[1 + i] : rb[i]);
-            const int e = 2 + sgn(rec - na) + sgn(rec - nb);
-            /* raw 0 -> SaoOffsetVal[1], 1 -> [2], 2 -> none, 3 -> [3], 4 -> [4] */
-            const int off = e == 0 ? c.offset[0] : (e == 1 ? c.offset[1] : (e == 3 ? c.offset[2] : (e == 4 ? c.offset[3] : 0)));
-            const int v = rec + (ok ? off : 0);
-            o[i] = v < 0 ? 0 : (v > a.max_v ? a.max_v : v);
-        }
-        store8<T>(dst + (long long)y * a.pitch, x, o);
-#pragma unroll
-        for (int i = 0; i < 10; i++) { up[i] = mid[i]; mid[i] = dn[i]; }
-    }
+    constexpr bool NOX = false;
+    [[maybe_unused]] const DbkSaoNox nx = {};
+#include "sao_kernel_body.inc"
+}
+template <typename T, bool SWZ, bool PK16 = false>
+__global__ __launch_bounds__(256) void sao_nox_kernel(const DbkSaoArgs a, const DbkFusedGrid g, const DbkSaoNox nx)
+{
+    constexpr bool NOX = true;
+#include "sao_kernel_body.inc"
 }
 
 /* ------------------------------------------------------------------------------------------ */
@@ -262,17 +172,17 @@ __device__ __forceinline__ uint32_t sao_apply(uint32_t rec, uint32_t idx, uint32
 }
 __device__ __forceinline__ uint32_t sao_edge_idx(uint32_t rec, uint32_t a, uint32_t b) { return sao8::edge_idx(rec, a, b); }
 
-template <bool BORDER>
+template <int BORDER> /* 0 = off the border; 1 = the picture border from x, y0; 2 = the block's mask m (saonox::block_mask) */
 __device__ __forceinline__ void sao8_edge_block(const DbkSaoArgs &a, const uint8_t *src, uint8_t *dst, int x, int y0, int cls,
-                                                uint32_t tab_lo, uint32_t tab_hi)
+                                                uint32_t tab_lo, uint32_t tab_hi, uint32_t m = 0u)
 {
     auto row_at = [&](int y) { return src + (long long)(y < 0 ? 0 : (y >= a.plane_h ? a.plane_h - 1 : y)) * a.pitch; };
     const bool horizontal = cls != 1; /* neighbours to the left / right take part: the halo dwords are needed */
     const bool vertical = cls != 0;   /* neighbours in the rows above / below take part */
     SaoRow up, mid, dn;
     if (horizontal) {
-        up = sao_load_row<true, !BORDER>(row_at(y0 - 1), x, a.plane_w);
-        mid = sao_load_row<true, !BORDER>(row_at(y0), x, a.plane_w);
+        up = sao_load_row<true, BORDER == 0>(row_at(y0 - 1), x, a.plane_w);
+        mid = sao_load_row<true, BORDER == 0>(row_at(y0), x, a.plane_w);
     } else {
         up = sao_load_row<false, false>(row_at(y0 - 1), x, a.plane_w);
         mid = sao_load_row<false, false>(row_at(y0), x, a.plane_w);
@@ -280,7 +190,7 @@ __device__ __forceinline__ void sao8_edge_block(const DbkSaoArgs &a, const uint8
 #pragma unroll
     for (int r = 0; r < 8; r++) {
         const int y = y0 + r;
-        dn = horizontal ? sao_load_row<true, !BORDER>(row_at(y + 1), x, a.plane_w) : sao_load_row<false, false>(row_at(y + 1), x, a.plane_w);
+        dn = horizontal ? sao_load_row<true, BORDER == 0>(row_at(y + 1), x, a.plane_w) : sao_load_row<false, false>(row_at(y + 1), x, a.plane_w);
         uint32_t i0, i1, i2, i3; /* indices of E0, O0, E1, O1 */
         if (cls == 0) {          /* (-1, 0) / (1, 0) */
             i0 = sao_edge_idx(mid.E0, mid.lE0, mid.O0);
@@ -303,7 +213,13 @@ __device__ __forceinline__ void sao8_edge_block(const DbkSaoArgs &a, const uint8
             i2 = sao_edge_idx(mid.E1, up.O1, dn.lE1);
             i3 = sao_edge_idx(mid.O1, up.rO1, dn.E1);
         }
-        if constexpr (BORDER) { /* a neighbour outside the picture: edgeIdx 0 (8.7.3.2) */
+        if constexpr (BORDER == 2) { /* a neighbour outside the picture, or across a slice / tile boundary not to be crossed */
+            if (cls == 0) saonox::mask_row<0, 8>(m, r, i0, i1, i2, i3);
+            else if (cls == 1) saonox::mask_row<1, 8>(m, r, i0, i1, i2, i3);
+            else if (cls == 2) saonox::mask_row<2, 8>(m, r, i0, i1, i2, i3);
+            else saonox::mask_row<3, 8>(m, r, i0, i1, i2, i3);
+        }
+        if constexpr (BORDER == 1) { /* a neighbour outside the picture: edgeIdx 0 (8.7.3.2) */
             if (vertical && (y == 0 || y == a.plane_h - 1)) i0 = i1 = i2 = i3 = 0x00020002u | sao8::kSel;
             if (horizontal && x == 0) i0 = (i0 & 0xffff0000u) | 0x0c02u;                       /* sample 0: low half of E0 */
             if (horizontal && x + 8 == a.plane_w) i3 = (i3 & 0x0000ffffu) | 0x0c020000u;  /* sample 7: high half of O1 */
@@ -319,118 +235,24 @@ __device__ __forceinline__ void sao8_edge_block(const DbkSaoArgs &a, const uint8
     }
 }
 
+/* the body is written once (sao8_kernel_body.inc) for the kernel and its _nox twin, as for sao_kernel */
 template <bool SWZ, int WAVES>
 __global__ __launch_bounds__(64 * WAVES) void sao8_kernel(const DbkSaoArgs a, const DbkFusedGrid g)
 {
-    int wx, wy, f;
-    if (!sao_strip<SWZ>(g, wx, wy, f)) return;
-    const int wv = threadIdx.x >> 6, l = threadIdx.x & 63;
-    /* Lane -> 8 x 8 block.  A wave takes one 64 x 64 region, i.e. with 64-sample CTBs one CTB and ONE path; its row pieces are
-     * then 64 bytes, half a cache line.  Where the two CTBs of an aligned pair (waves 2k, 2k + 1 of the workgroup) take the
-     * same path -- both edge offset of one class, or neither edge offset: SAO parameters are merged from the left / above
-     * neighbour in most CTBs of a real stream -- the two waves split the pair the other way: each takes 32 rows of BOTH CTBs
-     * (16 blocks across, 4 down), whole 128-byte lines, still one path per wave.  (Round 3 measured the wide shape for every
-     * pair: +8 % where the paths agree, -7 % where they differ; per pair it only ever takes the gain.) */
-    int x = (wx * WAVES + wv) * 64 + (l & 7) * 8;
-    int y0 = wy * 64 + (l >> 3) * 8;
-    bool zero_band = false;
-    if constexpr (WAVES % 2 == 0) {
-        const int px = (wx * WAVES + (wv & ~1)) * 64, py = wy * 64; /* the pair's origin */
-        if (a.ctb_log2 == 6 && px + 128 <= a.plane_w && py + 64 <= a.plane_h) {
-            const DbkSaoCtb *pc = a.params + (long long)f * a.params_frame_stride + (long long)(py >> 6) * a.params_stride + (px >> 6);
-            /* "not applied" and band offset count as one path: in a wide wave the former runs as a band offset of zeros (below) */
-            const bool e0 = pc[0].type == 2, e1 = pc[1].type == 2;
-            const bool same = e0 == e1 && (!e0 || ((pc[0].cls ^ pc[1].cls) & 3) == 0);
-            if (__builtin_amdgcn_readfirstlane(same ? 1 : 0)) { /* uniform by construction: every lane looked at the same two entries */
-                x = px + (l & 15) * 8;
-                y0 = py + (wv & 1) * 32 + (l >> 4) * 8;
-                /* one CTB band offset, the other not applied: see below */
-                zero_band = __builtin_amdgcn_readfirstlane((!e0 && (pc[0].type == 1) != (pc[1].type == 1)) ? 1 : 0) != 0;
-            }
-        }
-    }
-    if (x >= a.plane_w || y0 >= a.plane_h) return;
-    const uint8_t *src = a.src + (long long)f * a.frame_stride;
-    uint8_t *dst = a.dst + (long long)f * a.frame_stride;
-    const DbkSaoCtb c = a.params[(long long)f * a.params_frame_stride + (long long)(y0 >> a.ctb_log2) * a.params_stride + (x >> a.ctb_log2)];
-    const bool kept = a.keep && a.keep[(long long)f * a.keep_frame_stride + (long long)(y0 >> 3) * a.keep_stride + (x >> 3)];
-    const bool border = x == 0 || x + 8 == a.plane_w || y0 == 0 || y0 + 8 >= a.plane_h;
-    if (__builtin_amdgcn_ballot_w64(border) == 0ull) {
-        /* no lane of the wave touches the picture border (nearly every wave): the shared block procedure (sao_packed.h, the
-         * edge class resolved once per block) on rows addressed through buffer resources -- a lane's byte offset once, the
-         * row in the scalar offset, no per-row 64-bit address arithmetic and no clamping of row numbers */
-        const uint32_t plane_bytes = (uint32_t)a.pitch * (uint32_t)a.plane_h; /* < 2^31: checked by the launcher */
-        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(src), 0, plane_bytes, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rd = __builtin_amdgcn_make_buffer_rsrc(dst, 0, plane_bytes, 0x00020000);
-        const int sp = __builtin_amdgcn_readfirstlane((int)a.pitch);
-        const uint32_t vrow = (uint32_t)y0 * (uint32_t)a.pitch + (uint32_t)x; /* (x, y0); y0 >= 8 and x >= 8 here */
-        const uint32_t vup = vrow - (uint32_t)a.pitch;                         /* raw row 0 = image row y0 - 1 */
-        auto fetch = [&](int j, auto halo) {
-            SaoRaw q;
-            if constexpr (decltype(halo)::value) {
-                const sao_u32x4b v = __builtin_amdgcn_raw_buffer_load_b128(rs, vup - 4u, j * sp, 0);
-                q.lh = v.x; q.cx = v.y; q.cy = v.z; q.rh = v.w;
-            } else {
-                const sao_u32x2b v = __builtin_amdgcn_raw_buffer_load_b64(rs, vup, j * sp, 0);
-                q.lh = q.rh = 0u;
-                q.cx = v.x; q.cy = v.y;
-            }
-            return q;
-        };
-        auto store = [&](int r, uint32_t lo, uint32_t hi) {
-            sao_u32x2b w;
-            w.x = lo;
-            w.y = hi;
-            __builtin_amdgcn_raw_buffer_store_b64(w, rd, vrow, r * sp, 0);
-        };
-        if (zero_band) {
-            /* a wide wave over one band-offset CTB and one without SAO: the latter's blocks (and kept ones) run as a band offset
-             * of zeros (rec + 0, clipped: the same bytes) so that the two CTBs' lanes issue the SAME loads and stores -- whole
-             * lines -- instead of each half of the wave its own.  (A pair without SAO in either CTB keeps the plain copy:
-             * the arithmetic costs 5 % there.) */
-            DbkSaoCtb z = c;
-            if (kept || c.type != 1) {
-                z.type = 1; z.cls = 0;
-                z.offset[0] = z.offset[1] = z.offset[2] = z.offset[3] = 0;
-            }
-            sao8::block<false, 8>(fetch, store, x, y0, a.plane_w, a.plane_h, z, false);
-            return;
-        }
-        sao8::block<false, 8>(fetch, store, x, y0, a.plane_w, a.plane_h, c, kept);
-        return;
-    }
-    if (kept || c.type == 0 || c.type > 2) {
-#pragma unroll
-        for (int r = 0; r < 8; r++)
-            *reinterpret_cast<uint2 *>(dst + (long long)(y0 + r) * a.pitch + x) =
-                *reinterpret_cast<const uint2 *>(src + (long long)(y0 + r) * a.pitch + x);
-        return;
-    }
-    auto b = [](int v) { return (uint32_t)(v + 128) & 0xffu; };
-    if (c.type == 1) { /* band offset: bandTable[(k + sao_band_position) & 31] = k + 1; index min(k, 4), entry 4 = no offset */
-        const uint32_t tab_lo = b(c.offset[0]) | (b(c.offset[1]) << 8) | (b(c.offset[2]) << 16) | (b(c.offset[3]) << 24), tab_hi = b(0);
-        const spk pos = s_splat((int)c.cls);
-        auto band = [&](uint32_t rec) {
-            return sao_apply(rec, sao8::band_sel(rec, 3, pos), tab_lo, tab_hi); /* 8 bit: bandShift = bitDepth - 5 = 3 */
-        };
-#pragma unroll
-        for (int r = 0; r < 8; r++) {
-            const SaoRow m = sao_load_row<false, false>(src + (long long)(y0 + r) * a.pitch, x, a.plane_w);
-            uint2 out;
-            out.x = band(m.E0) | (band(m.O0) << 8);
-            out.y = band(m.E1) | (band(m.O1) << 8);
-            *reinterpret_cast<uint2 *>(dst + (long long)(y0 + r) * a.pitch + x) = out;
-        }
-        return;
-    }
-    /* edge offset: index 0 -> SaoOffsetVal[1], 1 -> [2], 2 -> none, 3 -> [3], 4 -> [4] */
-    const uint32_t tab_lo = b(c.offset[0]) | (b(c.offset[1]) << 8) | (b(0) << 16) | (b(c.offset[2]) << 24), tab_hi = b(c.offset[3]);
-    sao8_edge_block<true>(a, src, dst, x, y0, c.cls & 3, tab_lo, tab_hi); /* a wave with a lane on the picture border */
+    constexpr bool NOX = false;
+    [[maybe_unused]] const DbkSaoNox nx = {};
+#include "sao8_kernel_body.inc"
+}
+template <bool SWZ, int WAVES>
+__global__ __launch_bounds__(64 * WAVES) void sao8_nox_kernel(const DbkSaoArgs a, const DbkFusedGrid g, const DbkSaoNox nx)
+{
+    constexpr bool NOX = true;
+#include "sao8_kernel_body.inc"
 }
 
 } /* namespace */
 
-hipError_t dbk_launch_sao(const DbkSaoArgs &a, int sample_bytes, hipStream_t stream)
+hipError_t dbk_launch_sao(const DbkSaoArgs &a, int sample_bytes, hipStream_t stream, const DbkSaoNox *nxp)
 {
     if (a.n_frames <= 0 || a.plane_w <= 0 || a.plane_h <= 0) return hipSuccess;
     int waves = 4; /* 64 x 64 regions (waves) side by side in one workgroup */
@@ -472,6 +294,29 @@ hipError_t dbk_launch_sao(const DbkSaoArgs &a, int sample_bytes, hipStream_t str
         g.per_xcd = (uint32_t)((total + 7) / 8);
     }
     const dim3 grid = swz ? dim3(g.per_xcd * 8u, 1, 1) : grid3;
+    if (nxp) { /* the same grid and choice of kernel, the _nox twins */
+        const DbkSaoNox nx = *nxp;
+        if (sample_bytes == 1 && aligned8) {
+#ifdef HEVCDBK_DIAG
+            if (waves == 1 && swz) hipLaunchKernelGGL((sao8_nox_kernel<true, 1>), grid, block, 0, stream, a, g, nx);
+            else if (waves == 2 && swz) hipLaunchKernelGGL((sao8_nox_kernel<true, 2>), grid, block, 0, stream, a, g, nx);
+            else
+#endif
+            if (swz) hipLaunchKernelGGL((sao8_nox_kernel<true, 4>), grid, block, 0, stream, a, g, nx);
+            else hipLaunchKernelGGL((sao8_nox_kernel<false, 4>), grid, block, 0, stream, a, g, nx);
+        } else if (sample_bytes == 1) {
+            if (swz) hipLaunchKernelGGL((sao_nox_kernel<uint8_t, true>), grid, block, 0, stream, a, g, nx);
+            else hipLaunchKernelGGL((sao_nox_kernel<uint8_t, false>), grid, block, 0, stream, a, g, nx);
+        } else {
+            const bool pk16 = a.max_v <= 4095 && a.band_shift >= 3 && (1 << (a.band_shift + 5)) - 1 == a.max_v && a.pitch % 4 == 0 &&
+                              a.frame_stride % 4 == 0 && ((uintptr_t)a.src % 4) == 0 && ((uintptr_t)a.dst % 4) == 0 && a.plane_w % 8 == 0 &&
+                              a.plane_h % 8 == 0 && (unsigned long long)a.pitch * (unsigned long long)a.plane_h < (1ull << 31);
+            if (swz && pk16) hipLaunchKernelGGL((sao_nox_kernel<uint16_t, true, true>), grid, block, 0, stream, a, g, nx);
+            else if (swz) hipLaunchKernelGGL((sao_nox_kernel<uint16_t, true>), grid, block, 0, stream, a, g, nx);
+            else hipLaunchKernelGGL((sao_nox_kernel<uint16_t, false>), grid, block, 0, stream, a, g, nx);
+        }
+        return hipGetLastError();
+    }
     /* 8-bit planes whose rows and frames are 8-byte aligned take the packed kernel (every lane moves 8 bytes at once) */
     if (sample_bytes == 1 && aligned8) {
 #ifdef HEVCDBK_DIAG
@@ -530,5 +375,75 @@ hipError_t dbk_launch_sao_rows_x2(DbkSaoArgs &a, DbkSaoCtb *dst, hipStream_t str
     a.params = dst;
     a.params_stride = cols;
     a.params_frame_stride = a.params_frame_stride ? (long long)rows * cols : 0;
+    return hipGetLastError();
+}
+
+/* ---- slice / tile boundaries SAO must not look across (H.265 8.7.3.2) ------------------------------------------------------
+ * One lane per CTB: for each of the eight neighbouring CTBs inside the picture, the bit is set when that CTB lies in another
+ * slice whose order and flags forbid it -- the neighbour's slice earlier in decoding order and THIS slice's
+ * slice_loop_filter_across_slices_enabled_flag 0, or later and the NEIGHBOUR's flag 0 -- or in another tile while
+ * loop_filter_across_tiles_enabled_flag is 0. */
+namespace {
+__global__ __launch_bounds__(256) void sao_borders_kernel(const uint16_t *slice_idx, const uint8_t *slice_across, const uint16_t *tile_idx,
+                                                          int tiles_across, int ctbs_x, int ctbs_y, int in_stride, uint8_t *nox, int nox_stride)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= ctbs_x * ctbs_y) return;
+    const int cy = i / ctbs_x, cx = i - cy * ctbs_x;
+    const long long at = (long long)cy * in_stride + cx;
+    const unsigned s = slice_idx[at], fl = slice_across[at], t = tile_idx ? tile_idx[at] : 0u;
+    uint32_t b = 0u;
+#pragma unroll
+    for (int dy = -1; dy <= 1; dy++)
+#pragma unroll
+        for (int dx = -1; dx <= 1; dx++) {
+            if ((dx == 0 && dy == 0) || cx + dx < 0 || cx + dx >= ctbs_x || cy + dy < 0 || cy + dy >= ctbs_y) continue;
+            const long long n = at + (long long)dy * in_stride + dx;
+            const unsigned s2 = slice_idx[n];
+            const bool by_slice = (s2 < s && fl == 0u) || (s < s2 && slice_across[n] == 0u);
+            const bool by_tile = !tiles_across && tile_idx && tile_idx[n] != t;
+            if (by_slice || by_tile) b |= sao_nox_bit(dx, dy);
+        }
+    nox[(long long)cy * nox_stride + cx] = (uint8_t)b;
+}
+
+/* the bytes of CTBs of (1 << L) x (2 << L) samples as those of the square CTBs they are halves of: what lies below the upper half
+ * is the CTB itself (D cleared) and, diagonally, the left / right CTB (DL := L, DR := R); the lower half likewise upwards */
+__global__ __launch_bounds__(256) void sao_nox_rows_x2_kernel(const uint8_t *src, int src_stride, long long src_frame_stride, uint8_t *dst,
+                                                              int cols, int rows, long long total)
+{
+    using namespace saonox;
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    const long long per_frame = (long long)rows * cols;
+    const long long f = i / per_frame, k = i - f * per_frame;
+    const int r = (int)(k / cols), c = (int)(k - (long long)r * cols);
+    const uint32_t b = src[f * src_frame_stride + (long long)(r >> 1) * src_stride + c];
+    const uint32_t l = (b & L) ? 1u : 0u, rr = (b & R) ? 1u : 0u;
+    dst[i] = (uint8_t)((r & 1) ? ((b & ~(U | UL | UR)) | (l ? UL : 0u) | (rr ? UR : 0u)) : ((b & ~(D | DL | DR)) | (l ? DL : 0u) | (rr ? DR : 0u)));
+}
+} /* namespace */
+
+hipError_t dbk_launch_sao_borders(const uint16_t *slice_idx, const uint8_t *slice_across, const uint16_t *tile_idx, int tiles_across,
+                                  int ctbs_x, int ctbs_y, int in_stride, uint8_t *nox, int nox_stride, hipStream_t stream)
+{
+    const int total = ctbs_x * ctbs_y;
+    if (total <= 0) return hipSuccess;
+    hipLaunchKernelGGL(sao_borders_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, slice_idx, slice_across, tile_idx,
+                       tiles_across, ctbs_x, ctbs_y, in_stride, nox, nox_stride);
+    return hipGetLastError();
+}
+
+hipError_t dbk_launch_sao_nox_rows_x2(const DbkSaoArgs &a, DbkSaoNox &nx, uint8_t *dst, hipStream_t stream)
+{
+    const int cols = (a.plane_w + (1 << a.ctb_log2) - 1) >> a.ctb_log2, rows = (a.plane_h + (1 << a.ctb_log2) - 1) >> a.ctb_log2;
+    const bool per_frame = nx.frame_stride != 0;
+    const long long total = (long long)cols * rows * (per_frame ? a.n_frames : 1);
+    if (total > 0)
+        hipLaunchKernelGGL(sao_nox_rows_x2_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, nx.nox, nx.stride,
+                           nx.frame_stride, dst, cols, rows, total);
+    nx.nox = dst;
+    nx.stride = cols;
+    nx.frame_stride = per_frame ? (long long)rows * cols : 0;
     return hipGetLastError();
 }

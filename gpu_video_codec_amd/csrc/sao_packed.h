@@ -11,6 +11,72 @@
 
 #include "deblock_kernels.h"
 
+/*
+ * Slice and tile boundaries that SAO must not look across (H.265 8.7.3.2; DbkSaoNox): a lane's block of 8 x NROWS samples gets
+ * an 8-bit mask of the directions in which its neighbouring samples must not be looked at -- outside the picture, or in another
+ * CTB whose bit the block's CTB carries.  The eight regions around a block (left and right column, row above and below, four
+ * corner samples) lie in one CTB each; for a corner that is the diagonal CTB only when the block sits in that corner of its CTB,
+ * else the CTB above / below or left / right, else the block's own.
+ */
+namespace saonox {
+constexpr uint32_t L = 0x01u, R = 0x02u, U = 0x04u, D = 0x08u, UL = 0x10u, UR = 0x20u, DL = 0x40u, DR = 0x80u;
+
+/* the byte of the CTB holding sample (x, y0) of frame f.  Asked for next to the CTB's SAO parameters -- ahead of them -- so that
+ * the two requests are in flight together: the wave's ballot over the masks waits for the byte */
+__device__ __forceinline__ uint32_t ctb_byte(const DbkSaoNox &n, int f, int x, int y0, int ctb_log2)
+{
+    return n.nox[(long long)f * n.frame_stride + (long long)(y0 >> ctb_log2) * n.stride + (x >> ctb_log2)];
+}
+
+template <int NROWS> /* b = ctb_byte of the block's CTB */
+__device__ __forceinline__ uint32_t block_mask(uint32_t b, int x, int y0, int w, int h, int ctb_log2)
+{
+    const int cm = (1 << ctb_log2) - 1;
+    const bool pl = x == 0, pr = x + 8 >= w, pt = y0 == 0, pb = y0 + NROWS >= h;                               /* the picture's border */
+    const bool cl = (x & cm) == 0, cr = ((x + 8) & cm) == 0, ct = (y0 & cm) == 0, cb = ((y0 + NROWS) & cm) == 0; /* the CTB's */
+    const bool l = pl || (cl && (b & L)), r = pr || (cr && (b & R)), u = pt || (ct && (b & U)), d = pb || (cb && (b & D));
+    auto corner = [&](bool px, bool py, bool cx, bool cy, uint32_t diag, bool side_x, bool side_y) {
+        if (px || py) return true;
+        if (cx && cy) return (b & diag) != 0u;
+        return cx ? side_x : (cy ? side_y : false);
+    };
+    uint32_t m = (l ? L : 0u) | (r ? R : 0u) | (u ? U : 0u) | (d ? D : 0u);
+    if (corner(pl, pt, cl, ct, UL, l, u)) m |= UL;
+    if (corner(pr, pt, cr, ct, UR, r, u)) m |= UR;
+    if (corner(pl, pb, cl, cb, DL, l, d)) m |= DL;
+    if (corner(pr, pb, cr, cb, DR, r, d)) m |= DR;
+    return m;
+}
+
+/* row r of a block with mask m, class CLS: the selectors of the samples that must not be offset forced to "none".  Both packed
+ * layouts keep sample 0 in the low half of i0 and sample 7 in the high half of i3; samples 1..6 -- the rest -- share their fate:
+ * their neighbours lie in the row above / below only */
+template <int CLS, int NROWS>
+__device__ __forceinline__ void mask_row(uint32_t m, int r, uint32_t &i0, uint32_t &i1, uint32_t &i2, uint32_t &i3)
+{
+    constexpr uint32_t none = 0x0c020c02u; /* index 2 in both halves + the selector constant (sao8::kSel) */
+    const bool top = r == 0, bot = r == NROWS - 1;
+    const bool vert = CLS != 0 && ((top && (m & U)) || (bot && (m & D)));
+    bool s0, s7;
+    if constexpr (CLS == 0) { s0 = m & L; s7 = m & R; }
+    else if constexpr (CLS == 1) { s0 = s7 = vert; }
+    else if constexpr (CLS == 2) { /* (-1, -1) / (1, 1) */
+        s0 = (m & (top ? UL : L)) || (bot && (m & D));
+        s7 = (top && (m & U)) || (m & (bot ? DR : R));
+    } else {                       /* (1, -1) / (-1, 1) */
+        s0 = (top && (m & U)) || (m & (bot ? DL : L));
+        s7 = (m & (top ? UR : R)) || (bot && (m & D));
+    }
+    if (vert) {
+        i0 = (i0 & 0x0000ffffu) | (none & 0xffff0000u);
+        i1 = i2 = none;
+        i3 = (i3 & 0xffff0000u) | (none & 0x0000ffffu);
+    }
+    if (s0) i0 = (i0 & 0xffff0000u) | (none & 0x0000ffffu);
+    if (s7) i3 = (i3 & 0x0000ffffu) | (none & 0xffff0000u);
+}
+} /* namespace saonox */
+
 namespace sao8 {
 
 struct SaoRow {
@@ -87,12 +153,13 @@ __device__ __forceinline__ uint32_t band_sel(uint32_t rec, int shift, spk pos)
 }
 
 /* the NROWS (8) output rows of an edge-offset block from its NROWS + 2 (ten) raw rows, class CLS of Table 8-13: 0 (-1,0)/(1,0); 1 (0,-1)/(0,1);
- * 2 (-1,-1)/(1,1); 3 (1,-1)/(-1,1).  BORDER: the block may touch the picture border (x, y0 = its position, w x h the picture):
- * a sample with a neighbour outside the picture gets no offset (8.7.3.2), whatever the raw rows hold there.
+ * 2 (-1,-1)/(1,1); 3 (1,-1)/(-1,1).  BORDER 1: the block may touch the picture border (x, y0 = its position, w x h the picture):
+ * a sample with a neighbour outside the picture gets no offset (8.7.3.2), whatever the raw rows hold there; BORDER 2: the same
+ * for every direction of the block's mask m (saonox::block_mask: picture border, slice and tile boundaries).
  * store(r, lo, hi) takes output row r as its two dwords. */
-template <int CLS, bool BORDER, int NROWS, typename Fetch, typename Store>
+template <int CLS, int BORDER, int NROWS, typename Fetch, typename Store>
 __device__ __forceinline__ void edge_rows(const Fetch &fetch, const Store &store, int x, int y0, int w, int h, uint32_t tab_lo,
-                                          uint32_t tab_hi)
+                                          uint32_t tab_hi, uint32_t m = 0u)
 {
     constexpr bool horizontal = CLS != 1, vertical = CLS != 0;
     constexpr std::bool_constant<horizontal> halo{}; /* tells the fetch functor whether the samples left / right of the block are looked at */
@@ -123,7 +190,8 @@ __device__ __forceinline__ void edge_rows(const Fetch &fetch, const Store &store
             i2 = edge_idx(mid.E1, up.O1, dn.lE1);
             i3 = edge_idx(mid.O1, up.rO1, dn.E1);
         }
-        if constexpr (BORDER) {
+        if constexpr (BORDER == 2) saonox::mask_row<CLS, NROWS>(m, r, i0, i1, i2, i3);
+        if constexpr (BORDER == 1) {
             if (vertical && (y == 0 || y == h - 1)) i0 = i1 = i2 = i3 = 0x00020002u | sao8::kSel;
             if (horizontal && x == 0) i0 = (i0 & 0xffff0000u) | 0x0c02u;              /* sample 0: low half of E0 */
             if (horizontal && x + 8 == w) i3 = (i3 & 0x0000ffffu) | 0x0c020000u; /* sample 7: high half of O1 */
@@ -143,8 +211,8 @@ __device__ __forceinline__ void edge_rows(const Fetch &fetch, const Store &store
  * samples -- one CTB of 64, i.e. ONE path per wave; NROWS = 2: a wave covers 32 x 32 samples, one CTB of 32 (every chroma CTB
  * of a 4:2:0 picture with 64-sample luma CTBs) -- the same, where 8-row lanes would spread a wave over four CTBs and run every
  * path that occurs among them with a quarter of its lanes. */
-template <bool BORDER, int NROWS = 8, typename Fetch, typename Store>
-__device__ __forceinline__ void block(const Fetch &fetch, const Store &store, int x, int y0, int w, int h, const DbkSaoCtb &c, bool kept)
+template <int BORDER, int NROWS = 8, typename Fetch, typename Store>
+__device__ __forceinline__ void block(const Fetch &fetch, const Store &store, int x, int y0, int w, int h, const DbkSaoCtb &c, bool kept, uint32_t m = 0u)
 {
     if (kept || c.type == 0 || c.type > 2) {
 #pragma unroll
@@ -171,10 +239,10 @@ __device__ __forceinline__ void block(const Fetch &fetch, const Store &store, in
     /* edge offset: index 0 -> SaoOffsetVal[1], 1 -> [2], 2 -> none, 3 -> [3], 4 -> [4] */
     const uint32_t tab_lo = b(c.offset[0]) | (b(c.offset[1]) << 8) | (b(0) << 16) | (b(c.offset[2]) << 24), tab_hi = b(c.offset[3]);
     const int cls = c.cls & 3;
-    if (cls == 0) edge_rows<0, BORDER, NROWS>(fetch, store, x, y0, w, h, tab_lo, tab_hi);
-    else if (cls == 1) edge_rows<1, BORDER, NROWS>(fetch, store, x, y0, w, h, tab_lo, tab_hi);
-    else if (cls == 2) edge_rows<2, BORDER, NROWS>(fetch, store, x, y0, w, h, tab_lo, tab_hi);
-    else edge_rows<3, BORDER, NROWS>(fetch, store, x, y0, w, h, tab_lo, tab_hi);
+    if (cls == 0) edge_rows<0, BORDER, NROWS>(fetch, store, x, y0, w, h, tab_lo, tab_hi, m);
+    else if (cls == 1) edge_rows<1, BORDER, NROWS>(fetch, store, x, y0, w, h, tab_lo, tab_hi, m);
+    else if (cls == 2) edge_rows<2, BORDER, NROWS>(fetch, store, x, y0, w, h, tab_lo, tab_hi, m);
+    else edge_rows<3, BORDER, NROWS>(fetch, store, x, y0, w, h, tab_lo, tab_hi, m);
 }
 
 } /* namespace sao8 */
@@ -230,8 +298,8 @@ __device__ __forceinline__ uint32_t apply(uint32_t rec, uint32_t idx /* + sao8::
 }
 using sao8::edge_idx;
 
-template <int CLS, bool BORDER, int NROWS, typename Fetch, typename Store>
-__device__ __forceinline__ void edge_rows(const Fetch &fetch, const Store &store, int x, int y0, int w, int h, const Tab &t)
+template <int CLS, int BORDER, int NROWS, typename Fetch, typename Store>
+__device__ __forceinline__ void edge_rows(const Fetch &fetch, const Store &store, int x, int y0, int w, int h, const Tab &t, uint32_t m = 0u)
 {
     constexpr bool horizontal = CLS != 1, vertical = CLS != 0;
     constexpr std::bool_constant<horizontal> halo{};
@@ -262,7 +330,8 @@ __device__ __forceinline__ void edge_rows(const Fetch &fetch, const Store &store
             i2 = edge_idx(mid.P2, up.L3, dn.L2);
             i3 = edge_idx(mid.P3, up.R3, dn.L3);
         }
-        if constexpr (BORDER) { /* a neighbour outside the picture: edgeIdx 0 (8.7.3.2) */
+        if constexpr (BORDER == 2) saonox::mask_row<CLS, NROWS>(m, r, i0, i1, i2, i3);
+        if constexpr (BORDER == 1) { /* a neighbour outside the picture: edgeIdx 0 (8.7.3.2) */
             if (vertical && (y == 0 || y == h - 1)) i0 = i1 = i2 = i3 = 0x00020002u | sao8::kSel;
             if (horizontal && x == 0) i0 = (i0 & 0xffff0000u) | 0x0c02u;              /* sample 0: low half of P0 */
             if (horizontal && x + 8 == w) i3 = (i3 & 0x0000ffffu) | 0x0c020000u; /* sample 7: high half of P3 */
@@ -275,9 +344,9 @@ __device__ __forceinline__ void edge_rows(const Fetch &fetch, const Store &store
 
 /* one block of 8 x NROWS 16-bit samples (NROWS = 8, or 2 for 32-sample CTBs: see sao8::block); fetch(i) = raw row i = image
  * row y0 - 1 + i; store(r, four dwords) */
-template <bool BORDER, int NROWS = 8, typename Fetch, typename Store>
+template <int BORDER, int NROWS = 8, typename Fetch, typename Store>
 __device__ __forceinline__ void block(const Fetch &fetch, const Store &store, int x, int y0, int w, int h, const DbkSaoCtb &c, bool kept,
-                                      int max_v, int band_shift)
+                                      int max_v, int band_shift, uint32_t m = 0u)
 {
     if (kept || c.type == 0 || c.type > 2) {
 #pragma unroll
@@ -309,10 +378,10 @@ __device__ __forceinline__ void block(const Fetch &fetch, const Store &store, in
     t.lo = b(c.offset[0]) | (b(c.offset[1]) << 8) | (0x80u << 16) | (b(c.offset[2]) << 24);
     t.hi = b(c.offset[3]);
     const int cls = c.cls & 3;
-    if (cls == 0) edge_rows<0, BORDER, NROWS>(fetch, store, x, y0, w, h, t);
-    else if (cls == 1) edge_rows<1, BORDER, NROWS>(fetch, store, x, y0, w, h, t);
-    else if (cls == 2) edge_rows<2, BORDER, NROWS>(fetch, store, x, y0, w, h, t);
-    else edge_rows<3, BORDER, NROWS>(fetch, store, x, y0, w, h, t);
+    if (cls == 0) edge_rows<0, BORDER, NROWS>(fetch, store, x, y0, w, h, t, m);
+    else if (cls == 1) edge_rows<1, BORDER, NROWS>(fetch, store, x, y0, w, h, t, m);
+    else if (cls == 2) edge_rows<2, BORDER, NROWS>(fetch, store, x, y0, w, h, t, m);
+    else edge_rows<3, BORDER, NROWS>(fetch, store, x, y0, w, h, t, m);
 }
 
 } /* namespace sao16 */

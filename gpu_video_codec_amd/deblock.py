@@ -384,12 +384,46 @@ class Context:
             b.free()
         return res
 
+    def derive_sao_borders(self, slice_idx, slice_across, tile_idx=None, *, tiles_across=True):
+        """hevcdbk_h265_sao_borders_device from host arrays of one entry per CTB (slice_idx: index of the CTB's slice in decoding
+        order; slice_across: that slice's slice_loop_filter_across_slices_enabled_flag; tile_idx: None = one tile;
+        tiles_across = loop_filter_across_tiles_enabled_flag); returns the bytes (CTB rows, CTB columns) as a host array --
+        upload them and hand them on as borders=SaoBorders(ptr, stride, frame_stride)."""
+        si = np.ascontiguousarray(slice_idx, np.uint16)
+        sa = np.ascontiguousarray(slice_across, np.uint8)
+        if si.ndim != 2 or sa.shape != si.shape:
+            raise ValueError("slice_idx and slice_across must be 2-D arrays of one shape")
+        arrs = [si, sa]
+        if tile_idx is not None:
+            arrs.append(np.ascontiguousarray(tile_idx, np.uint16))
+            if arrs[2].shape != si.shape:
+                raise ValueError("tile_idx must have the shape of slice_idx")
+        rows, cols = si.shape
+        bufs = [self.alloc(max(a.nbytes, 1)) for a in arrs]
+        for b, a in zip(bufs, arrs):
+            b.upload(a)
+        out = self.alloc(max(rows * cols, 1))
+        rc = _lib.lib().hevcdbk_h265_sao_borders_device(self.handle, bufs[0].ptr, bufs[1].ptr, bufs[2].ptr if tile_idx is not None else None,
+                                                        int(bool(tiles_across)), cols, rows, cols, out.ptr, cols, None)
+        _chk(rc, self.handle)
+        self.synchronize()
+        res = out.download(rows * cols).reshape(rows, cols)
+        for b in bufs + [out]:
+            b.free()
+        return res
+
     def sao_device(self, planes, params_ptr, params_stride, ctb_log2, *, params_frame_stride=0, keep_ptr=None, keep_stride=0,
-                   keep_frame_stride=0, chroma_format="420", ctb_log2_h=None):
+                   keep_frame_stride=0, chroma_format="420", ctb_log2_h=None, borders=None):
         """hevc_sao_filter_device[_cf]: H.265 8.7.3 on planes in HBM, src -> dst.  ctb_log2 = log2 of this plane's CTB width;
-        its height follows from chroma_format (a 4:2:2 chroma plane, planes.is_chroma: twice the width) unless ctb_log2_h says."""
+        its height follows from chroma_format (a 4:2:2 chroma plane, planes.is_chroma: twice the width) unless ctb_log2_h says.
+        borders: a _lib.SaoBorders (slice / tile boundaries not to be looked across, 8.7.3.2: hevcdbk_sao_filter_device_nox)."""
         cf = _lib.chroma_format_idc(chroma_format)
         lh = _ctb_log2_h(ctb_log2, ctb_log2_h, cf, planes.is_chroma)
+        if borders is not None:
+            _chk(_lib.lib().hevcdbk_sao_filter_device_nox(self.handle, C.byref(planes), params_ptr, params_stride, params_frame_stride,
+                                                          ctb_log2, lh, keep_ptr, keep_stride, keep_frame_stride, C.byref(borders), None),
+                 self.handle)
+            return
         if cf == _lib.CHROMA_420 and lh == ctb_log2:
             rc = _lib.lib().hevc_sao_filter_device(self.handle, C.byref(planes), params_ptr, params_stride, params_frame_stride,
                                                    ctb_log2, keep_ptr, keep_stride, keep_frame_stride, None)
@@ -409,12 +443,18 @@ class Context:
 
     def deblock_sao_h265_device(self, planes, qp, params_ptr, params_stride, ctb_log2, *, c_idx=0, tc_offset_div2=0,
                                 beta_offset_div2=0, cb_qp_offset=0, cr_qp_offset=0, params_frame_stride=0, keep_ptr=None,
-                                keep_stride=0, keep_frame_stride=0, fused=_lib.FUSED_AUTO, chroma_format="420", ctb_log2_h=None):
-        """hevc_deblock_sao_h265_device[_cf]: spec-exact deblocking (8.7.2) followed by SAO (8.7.3), src -> dst; chroma_format
-        and ctb_log2 / ctb_log2_h as for sao_device."""
+                                keep_stride=0, keep_frame_stride=0, fused=_lib.FUSED_AUTO, chroma_format="420", ctb_log2_h=None,
+                                borders=None):
+        """hevc_deblock_sao_h265_device[_cf]: spec-exact deblocking (8.7.2) followed by SAO (8.7.3), src -> dst; chroma_format,
+        ctb_log2 / ctb_log2_h and borders (hevcdbk_h265_deblock_sao_device_nox) as for sao_device."""
         cf = _lib.chroma_format_idc(chroma_format)
         lh = _ctb_log2_h(ctb_log2, ctb_log2_h, cf, c_idx != 0)
         prm = _lib.H265Params(tc_offset_div2, beta_offset_div2, cb_qp_offset, cr_qp_offset)
+        if borders is not None:
+            _chk(_lib.lib().hevcdbk_h265_deblock_sao_device_nox(self.handle, C.byref(planes), c_idx, cf, int(qp), C.byref(prm), params_ptr,
+                                                                params_stride, params_frame_stride, ctb_log2, lh, keep_ptr, keep_stride,
+                                                                keep_frame_stride, fused, C.byref(borders), None), self.handle)
+            return
         if cf == _lib.CHROMA_420 and lh == ctb_log2:
             rc = _lib.lib().hevc_deblock_sao_h265_device(self.handle, C.byref(planes), c_idx, int(qp), C.byref(prm), params_ptr,
                                                          params_stride, params_frame_stride, ctb_log2, keep_ptr, keep_stride,
@@ -426,18 +466,21 @@ class Context:
         _chk(rc, self.handle)
 
     def deblock_sao_device_planes(self, planes_list, qp, sao_list, *, h265=None, fused=_lib.FUSED_AUTO, tc_table=None, beta_table=None,
-                                  chroma_format="420"):
+                                  chroma_format="420", borders=None):
         """hevc_deblock_sao_device_planes / hevc_deblock_sao_h265_device_planes: deblocking + SAO of Y, U, V of a batch in one
         call (one launch where the fused kernel takes every plane).  sao_list[i] = (params_ptr, params_stride, ctb_log2) or a
         dict with the optional params_frame_stride / keep / keep_stride / keep_frame_stride; h265 = None (reference-exact
         deblocking) or a dict of tc_offset_div2, beta_offset_div2, cb_qp_offset, cr_qp_offset (spec-exact).  chroma_format
         (spec-exact mode only): '400' / '420' / '422' / '444'; ctb_log2 = log2 of the plane's CTB width, its height follows
-        from the format (or a ctb_log2_h entry of the dict)."""
+        from the format (or a ctb_log2_h entry of the dict).  borders (spec-exact mode only): ONE _lib.SaoBorders for the
+        picture (hevcdbk_h265_deblock_sao_device_planes_nox)."""
         cf = _lib.chroma_format_idc(chroma_format)
         if cf != _lib.CHROMA_420 and h265 is None:
             raise ValueError("the reference-exact mode is 4:2:0 only: chroma_format needs h265=")
+        if borders is not None and h265 is None:
+            raise ValueError("the reference-exact mode has no slice / tile boundaries: borders needs h265=")
         arr = (_lib.DevicePlanes * len(planes_list))(*planes_list)
-        if cf != _lib.CHROMA_420 or any(isinstance(so, dict) and "ctb_log2_h" in so for so in sao_list):
+        if borders is not None or cf != _lib.CHROMA_420 or any(isinstance(so, dict) and "ctb_log2_h" in so for so in sao_list):
             spc = (_lib.SaoPlaneCf * len(sao_list))()
             for i, so in enumerate(sao_list):
                 d = so if isinstance(so, dict) else {"params": so[0], "params_stride": so[1], "ctb_log2": so[2]}
@@ -447,6 +490,10 @@ class Context:
                 spc[i].keep, spc[i].keep_stride, spc[i].keep_frame_stride = d.get("keep"), d.get("keep_stride", 0), d.get("keep_frame_stride", 0)
             prm = _lib.H265Params(h265.get("tc_offset_div2", 0), h265.get("beta_offset_div2", 0), h265.get("cb_qp_offset", 0),
                                   h265.get("cr_qp_offset", 0))
+            if borders is not None:
+                _chk(_lib.lib().hevcdbk_h265_deblock_sao_device_planes_nox(self.handle, arr, len(planes_list), cf, int(qp), C.byref(prm), spc,
+                                                                           fused, C.byref(borders), None), self.handle)
+                return
             _chk(_lib.lib().hevcdbk_h265_deblock_sao_device_planes_cf(self.handle, arr, len(planes_list), cf, int(qp), C.byref(prm), spc,
                                                                    fused, None), self.handle)
             return

@@ -579,6 +579,67 @@ HEVCDBK_API int hevcdbk_h265_deblock_sao_device_planes_cf(hevcdbk_context *ctx, 
                                                        int chroma_format_idc, unsigned qp, const hevcdbk_h265_params *h265_params,
                                                        const hevcdbk_sao_plane_cf *sao, int fused, void *hip_stream);
 
+/* ==================================================================================================================
+ * SAO at slice and tile boundaries that in-loop filtering must not cross (ITU-T H.265 8.7.3.2).
+ *
+ * For a sample of an edge-offset CTB, edgeIdx is 0 -- the sample is copied -- when either of its two neighbours
+ * (Table 8-13) lies outside the picture, OR belongs to a different slice and (the neighbour earlier in decoding order and
+ * slice_loop_filter_across_slices_enabled_flag of the CURRENT sample's slice is 0, or the neighbour later and that flag of
+ * the NEIGHBOUR's slice is 0), OR belongs to a different tile while loop_filter_across_tiles_enabled_flag is 0.  Slices and
+ * tiles are made of whole CTBs, so every such boundary is a CTB border: the operand is one byte per CTB with one bit per
+ * neighbouring CTB that this CTB's samples must not look into.  A CTB's byte speaks for the samples inside that CTB only
+ * (it is never reconciled with the neighbour's byte); bits that point outside the picture are ignored; band offset, the
+ * keep map and the picture-border rule are as in the entries above.  One CTB grid -- the luma one -- serves every plane of
+ * a picture: the chroma CTBs are the luma CTBs sub-sampled.  Deblocking takes its share of the same syntax elements
+ * through the units' HEVCDBK_U_NOX_LEFT / _TOP flags.  The reference has no SAO at all (main.cu:41-43 ends at
+ * DeblockingFilter); parity against the per-sample restatement in tests/ only ("parity unpinned").
+ * ================================================================================================================== */
+#define HEVCDBK_SAO_NOX_L  0x01u /* the CTB left of this one must not be read by this CTB's samples */
+#define HEVCDBK_SAO_NOX_R  0x02u
+#define HEVCDBK_SAO_NOX_U  0x04u
+#define HEVCDBK_SAO_NOX_D  0x08u
+#define HEVCDBK_SAO_NOX_UL 0x10u
+#define HEVCDBK_SAO_NOX_UR 0x20u
+#define HEVCDBK_SAO_NOX_DL 0x40u
+#define HEVCDBK_SAO_NOX_DR 0x80u
+typedef struct hevcdbk_sao_borders { /* DEVICE memory; one CTB grid for all planes of a picture (the luma CTB grid) */
+    const uint8_t *nox;              /* nox[cy * stride + cx] */
+    unsigned stride;
+    size_t frame_stride;             /* bytes between the frames of a batch, 0 = shared */
+} hevcdbk_sao_borders;
+
+/*
+ * The bytes from what a decoder holds per CTB (DEVICE arrays, row stride in_stride entries): slice_idx = index of the CTB's
+ * slice (not slice segment) in decoding order, slice_across = that slice's slice_loop_filter_across_slices_enabled_flag,
+ * tile_idx = index of its tile (NULL = one tile).  One small launch, asynchronous like hevcdbk_h265_derive_bs_device;
+ * callers that already hold the bits skip it.  Bits that point outside the picture come out 0.
+ */
+HEVCDBK_API int hevcdbk_h265_sao_borders_device(hevcdbk_context *ctx, const uint16_t *slice_idx, const uint8_t *slice_across,
+                                                const uint16_t *tile_idx, int loop_filter_across_tiles_enabled_flag,
+                                                unsigned ctbs_x, unsigned ctbs_y, unsigned in_stride, uint8_t *nox,
+                                                unsigned nox_stride, void *hip_stream);
+/*
+ * The _cf entries with the operand.  borders == NULL is the _cf entry itself (the same launches); a non-NULL operand -- nox
+ * non-NULL, stride at least the plane's CTB columns, else HEVCDBK_ERR_ARG -- runs the _nox twins of the same kernels, in
+ * which a wave takes the masked form only where one of its lanes has a direction not to look in.  4:2:2 chroma (CTBs twice
+ * as tall as wide): the bytes are rewritten for square CTBs together with the parameters.  The planes entry takes ONE
+ * operand for the picture.
+ */
+HEVCDBK_API int hevcdbk_sao_filter_device_nox(hevcdbk_context *ctx, const hevcdbk_device_planes *planes, const hevcdbk_sao_ctb *params,
+                                              unsigned params_stride, size_t params_frame_stride, unsigned ctb_log2_w,
+                                              unsigned ctb_log2_h, const uint8_t *keep, unsigned keep_stride,
+                                              size_t keep_frame_stride, const hevcdbk_sao_borders *borders, void *hip_stream);
+HEVCDBK_API int hevcdbk_h265_deblock_sao_device_nox(hevcdbk_context *ctx, const hevcdbk_device_planes *planes, int c_idx,
+                                                    int chroma_format_idc, unsigned qp, const hevcdbk_h265_params *h265_params,
+                                                    const hevcdbk_sao_ctb *params, unsigned params_stride,
+                                                    size_t params_frame_stride, unsigned ctb_log2_w, unsigned ctb_log2_h,
+                                                    const uint8_t *keep, unsigned keep_stride, size_t keep_frame_stride, int fused,
+                                                    const hevcdbk_sao_borders *borders, void *hip_stream);
+HEVCDBK_API int hevcdbk_h265_deblock_sao_device_planes_nox(hevcdbk_context *ctx, const hevcdbk_device_planes *planes,
+                                                           unsigned n_planes, int chroma_format_idc, unsigned qp,
+                                                           const hevcdbk_h265_params *h265_params, const hevcdbk_sao_plane_cf *sao,
+                                                           int fused, const hevcdbk_sao_borders *borders, void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

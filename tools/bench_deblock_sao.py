@@ -22,15 +22,22 @@ def main():
                     help="diagnostic library with these knobs (csrc/hevcdbk_diag.h), e.g. noswz; may be given several times: one result per knob set")
     ap.add_argument("--chroma-format", choices=["420", "422", "444"], default=None,
                     help="--mode h265: Y + Cb + Cr of pictures of this format in one call (CtbSizeY 64) instead of luma planes")
+    ap.add_argument("--bit-depth", type=int, default=8, help="luma planes: 8, or 10 / 12 in 16-bit containers")
+    ap.add_argument("--borders", choices=["none", "zero", "decoder", "every-ctb"], default=None,
+                    help="--mode h265: slice / tile boundaries SAO must not look across (the _nox entries; tools/sao_border_layouts.py): the fused "
+                         "call without the operand, with this layout and without it again take turns in this one process on the same buffers")
+    ap.add_argument("--rounds", type=int, default=3, help="--borders: rounds of turns; the median of each variant is reported")
     a = ap.parse_args()
+    if a.borders is not None and a.mode != "h265":
+        ap.error("--borders needs --mode h265 (the reference-exact mode has no slices or tiles)")
     if a.chroma_format and a.mode != "h265":
         ap.error("--chroma-format needs --mode h265 (the reference-exact mode is 4:2:0 only)")
     if a.diag is not None:
         _lib.use_diagnostic_library(a.diag[0] or None)
     w, h, n = a.width, a.height, a.frames
     ctx = deblock.Context(0)
-    b = deblock.DeviceBatch(ctx, w, h, n, per_frame_bs=False)
-    src = np.stack([synth.blocky_plane(w, h, seed=7, frame=i) for i in range(4)])
+    b = deblock.DeviceBatch(ctx, w, h, n, bit_depth=a.bit_depth, per_frame_bs=False)
+    src = np.stack([synth.blocky_plane(w, h, seed=7, frame=i, bit_depth=a.bit_depth) for i in range(4)])
     b.upload_all(np.concatenate([src] * (n // 4 + 1))[:n])
     rng = np.random.RandomState(5)
     rows, cols = (h + 63) // 64, (w + 63) // 64
@@ -51,20 +58,47 @@ def main():
         dh.upload(np.full(nh, 2, np.uint8))
         p.vert_bs, p.hor_bs, p.vert_bs_stride, p.hor_bs_stride = dv.ptr, dh.ptr, 0, 0
 
-    nbytes = 2 * n * w * h
+    nbytes = 2 * n * w * h * b.sb
     if a.chroma_format:  # the planes of tools/bench_rext.py: bS 2 everywhere, seeded SAO parameters per plane
         sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
         import bench_rext
         yuv, sao, nbytes, _keep = bench_rext.setup(ctx, a.chroma_format, w, h, n, 8, np.random.RandomState(5))
         h265 = {"tc_offset_div2": 0, "beta_offset_div2": 0, "cb_qp_offset": 0, "cr_qp_offset": 0}
 
-    def call(fused):
+    def call(fused, borders=None):
         if a.chroma_format:
-            ctx.deblock_sao_device_planes(yuv, a.qp, sao, h265=h265, fused=fused, chroma_format=a.chroma_format)
+            ctx.deblock_sao_device_planes(yuv, a.qp, sao, h265=h265, fused=fused, chroma_format=a.chroma_format, borders=borders)
         elif a.mode == "ref":
             ctx.deblock_sao_device(p, a.qp, dp.ptr, cols, 6, fused=fused)
         else:
-            ctx.deblock_sao_h265_device(p, a.qp, dp.ptr, cols, 6, fused=fused)
+            ctx.deblock_sao_h265_device(p, a.qp, dp.ptr, cols, 6, fused=fused, borders=borders)
+
+    what = "luma" if not a.chroma_format else "Y+Cb+Cr %s" % a.chroma_format
+    if a.borders is not None:  # none / the layout / none again, taking turns; `spread` = the distance between the two runs without the operand
+        sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+        import sao_border_layouts as sbl
+        bo, _buf, share = sbl.device_borders(ctx, a.borders, rows, cols)
+        variants = [("none", None), (a.borders, bo), ("none_again", None)]
+        ms = {k: [] for k, _ in variants}
+        for _ in range(300):  # settle the clocks
+            call(_lib.FUSED_ON)
+        ctx.synchronize()
+        for _ in range(a.rounds):
+            for k, bb in variants:
+                for _ in range(20):
+                    call(_lib.FUSED_ON, bb)
+                ctx.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(a.steps):
+                    call(_lib.FUSED_ON, bb)
+                ctx.synchronize()
+                ms[k].append((time.perf_counter() - t0) / a.steps * 1e3)
+        med = {k: float(np.median(v)) for k, v in ms.items()}
+        print(json.dumps({"stage": "deblock+sao", "mode": a.mode, "borders": a.borders, "masked_region_share": share, "ms": med, "rounds_ms": ms,
+                          "spread_ms": abs(med["none"] - med["none_again"]),
+                          "frac_of_8TBps_read_once_write_once": {k: nbytes / (v * 1e-3) / 8e12 for k, v in med.items()},
+                          "workload": "%dx%d %d-bit %s x %d, QP %d, CTB types: %s" % (w, h, a.bit_depth, what, n, a.qp, a.types)}))
+        return
 
     out = {}
     runs = [("fused", _lib.FUSED_ON, None), ("two_launches", _lib.FUSED_OFF, None), ("fused_again", _lib.FUSED_ON, None)]
@@ -84,7 +118,6 @@ def main():
         ctx.synchronize()
         dt = (time.perf_counter() - t0) / a.steps
         out[name] = {"ms_per_step": dt * 1e3, "frames_per_s": n / dt, "frac_of_8TBps_read_once_write_once": nbytes / dt / 8e12}
-    what = "luma" if not a.chroma_format else "Y+Cb+Cr %s" % a.chroma_format
     print(json.dumps({"stage": "deblock+sao", "mode": a.mode, "workload": "%dx%d 8-bit %s x %d, QP %d, CTB types: %s" % (w, h, what, n, a.qp, a.types),
                       **out}))
 

@@ -17,6 +17,10 @@ def main():
     ap.add_argument("--types", default="mix", help="mix (one third off / band / edge), off, band, edge: the SAO type of every CTB")
     ap.add_argument("--ctb-log2", type=int, default=6, help="CTB size (6 = 64 samples; 5 = 32: the chroma planes of 4:2:0, or a stream with 32-sample CTBs)")
     ap.add_argument("--merge", action="store_true", help="merge the parameters from the left (p 0.5) / upper (p 0.25) CTB, as a stream's SAO merge flags do")
+    ap.add_argument("--borders", choices=["none", "zero", "decoder", "every-ctb"], default=None,
+                    help="slice / tile boundaries not to be looked across (hevcdbk_sao_filter_device_nox; tools/sao_border_layouts.py): the entry "
+                         "without the operand, this layout and the entry without it again take turns in this one process on the same buffers")
+    ap.add_argument("--rounds", type=int, default=3, help="--borders: rounds of turns; the median of each variant is reported")
     ap.add_argument("--diag", default=None, help="run on libhevcdbk_diag.so with these knobs (noswz = the plain 3-D strip numbering)")
     a = ap.parse_args()
     if a.diag is not None:
@@ -42,6 +46,8 @@ def main():
     dp = ctx.alloc(prm.nbytes)
     dp.upload(prm.view(np.uint8).ravel())
     p = b.planes()
+    if a.borders is not None:
+        return ab_borders(a, ctx, p, dp, rows, cols, 2 * n * w * h * sb)
     for _ in range(100):
         ctx.sao_device(p, dp.ptr, cols, a.ctb_log2)
     ctx.synchronize()
@@ -53,6 +59,33 @@ def main():
     nbytes = 2 * n * w * h * sb
     print(json.dumps({"stage": "sao", "ms_per_launch": dt * 1e3, "frames_per_s": n / dt, "GBps": nbytes / dt * 1e-9,
                       "frac_of_8TBps": nbytes / dt / 8e12, "workload": "%dx%d %d-bit luma x %d, %d-sample CTBs, types: %s" % (w, h, bd, n, cs, a.types), "diag": a.diag}))
+
+
+def ab_borders(a, ctx, p, dp, rows, cols, nbytes):
+    """none / the layout / none again, taking turns; `spread` = the distance between the two runs without the operand"""
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import sao_border_layouts as sbl
+    b, _buf, share = sbl.device_borders(ctx, a.borders, rows, cols)
+    variants = [("none", None), (a.borders, b), ("none_again", None)]
+    ms = {k: [] for k, _ in variants}
+    for _ in range(300):  # settle the clocks
+        ctx.sao_device(p, dp.ptr, cols, a.ctb_log2)
+    ctx.synchronize()
+    for _ in range(a.rounds):
+        for k, bb in variants:
+            for _ in range(20):
+                ctx.sao_device(p, dp.ptr, cols, a.ctb_log2, borders=bb)
+            ctx.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(a.steps):
+                ctx.sao_device(p, dp.ptr, cols, a.ctb_log2, borders=bb)
+            ctx.synchronize()
+            ms[k].append((time.perf_counter() - t0) / a.steps * 1e3)
+    med = {k: float(np.median(v)) for k, v in ms.items()}
+    print(json.dumps({"stage": "sao", "borders": a.borders, "masked_region_share": share, "ms": med, "rounds_ms": ms,
+                      "spread_ms": abs(med["none"] - med["none_again"]),
+                      "frac_of_8TBps": {k: nbytes / (v * 1e-3) / 8e12 for k, v in med.items()},
+                      "workload": "%dx%d %d-bit luma x %d, %d-sample CTBs, types: %s" % (a.width, a.height, a.bit_depth, a.frames, 1 << a.ctb_log2, a.types)}))
 
 
 if __name__ == "__main__":
