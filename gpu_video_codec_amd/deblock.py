@@ -595,6 +595,7 @@ class DeviceBatch:
         self.hor.upload(np.tile(dh, nb))
         self.qp_map = None
         self.map_stride = 0
+        self.map_frame_stride = 0
         self.ctu_log2 = 6
 
     def _pitched(self, a, fill=0):
@@ -621,11 +622,27 @@ class DeviceBatch:
         self.vert.upload(np.ascontiguousarray(vert, np.uint8), f * self.nv)
         self.hor.upload(np.ascontiguousarray(hor, np.uint8), f * self.nh)
 
-    def set_qp_map(self, qmap, ctu_log2=6):
+    def set_qp_map(self, qmap, ctu_log2=6, frame_stride=None):
+        """qmap: one (rows, cols) map for every frame, or (n_frames, rows, cols) = one map per frame, laid out tight or, with
+        frame_stride (entries, >= rows * cols), with a gap between the frames' maps (left as allocated)"""
         m = np.ascontiguousarray(qmap, np.uint8)
-        self.qp_map = self.ctx.alloc(m.nbytes)
-        self.qp_map.upload(m)
-        self.map_stride, self.ctu_log2 = m.shape[1], ctu_log2
+        if m.ndim == 2:
+            if frame_stride is not None:
+                raise ValueError("frame_stride needs one map per frame")
+            self.qp_map = self.ctx.alloc(m.nbytes)
+            self.qp_map.upload(m)
+            self.map_frame_stride = 0
+        else:
+            if m.ndim != 3 or m.shape[0] != self.n:
+                raise ValueError("qmap must be (rows, cols) or (n_frames, rows, cols)")
+            size = m.shape[1] * m.shape[2]
+            self.map_frame_stride = size if frame_stride is None else int(frame_stride)
+            if self.map_frame_stride < size:
+                raise ValueError("frame_stride is smaller than one map")
+            self.qp_map = self.ctx.alloc(self.map_frame_stride * (self.n - 1) + size)
+            for f in range(self.n):
+                self.qp_map.upload(m[f], f * self.map_frame_stride)
+        self.map_stride, self.ctu_log2 = m.shape[-1], ctu_log2
 
     def planes(self):
         p = _lib.DevicePlanes()
@@ -638,6 +655,7 @@ class DeviceBatch:
         p.hor_bs_stride = self.nh if self.per_frame_bs else 0
         if self.qp_map is not None:
             p.qp_map, p.qp_map_stride, p.ctu_log2 = self.qp_map.ptr, self.map_stride, self.ctu_log2
+            p.qp_map_frame_stride = self.map_frame_stride
         return p
 
     def download_frame(self, f, which="dst", with_padding=False):
