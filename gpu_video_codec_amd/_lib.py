@@ -45,6 +45,8 @@ EXPORTS = [
     "hevcdbk_sao_filter_device_cf", "hevcdbk_h265_deblock_sao_device_cf", "hevcdbk_h265_deblock_sao_device_planes_cf",
     "hevcdbk_h265_sao_borders_device", "hevcdbk_sao_filter_device_nox", "hevcdbk_h265_deblock_sao_device_nox",
     "hevcdbk_h265_deblock_sao_device_planes_nox",
+    "hevcdbk_h265_slice_offsets_device", "hevcdbk_h265_filter_device_sl", "hevcdbk_h265_deblock_sao_device_sl",
+    "hevcdbk_h265_deblock_sao_device_planes_sl",
 ]
 
 # chroma_format_idc of the spec-exact mode and SAO (HEVCDBK_CHROMA_*): 4:0:0, 4:2:0, 4:2:2, 4:4:4
@@ -105,6 +107,12 @@ class SaoPlaneCf(C.Structure):
 class SaoBorders(C.Structure):
     """hevcdbk_sao_borders: one byte per CTB of the picture's (luma) CTB grid, SAO_NOX_* bits (device pointer)"""
     _fields_ = [("nox", C.c_void_p), ("stride", C.c_uint), ("frame_stride", C.c_size_t)]
+
+
+class SliceOffsets(C.Structure):
+    """hevcdbk_h265_slice_offsets: (slice_beta_offset_div2, slice_tc_offset_div2) as two int8 per CTB of the picture's (luma) CTB
+    grid (device pointer, 2-byte aligned); with it the two offsets of H265Params are not used"""
+    _fields_ = [("offs", C.c_void_p), ("stride", C.c_uint), ("frame_stride", C.c_size_t), ("ctb_log2", C.c_uint)]
 
 
 # HEVCDBK_SAO_NOX_*: the neighbouring CTB this CTB's samples must not look into (H.265 8.7.3.2)
@@ -272,6 +280,17 @@ def lib():
         L.hevcdbk_h265_deblock_sao_device_planes_nox.argtypes = [C.c_void_p, C.POINTER(DevicePlanes), C.c_uint, C.c_int, C.c_uint,
                                                                  C.POINTER(H265Params), C.POINTER(SaoPlaneCf), C.c_int,
                                                                  C.POINTER(SaoBorders), C.c_void_p]
+        L.hevcdbk_h265_slice_offsets_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint, C.c_void_p, C.c_uint, C.c_uint, C.c_uint,
+                                                        C.c_void_p, C.c_uint, C.c_void_p]
+        L.hevcdbk_h265_filter_device_sl.argtypes = [C.c_void_p, C.POINTER(DevicePlanes), C.c_int, C.c_int, C.c_uint,
+                                                    C.POINTER(H265Params), C.c_int, C.POINTER(SliceOffsets), C.c_void_p]
+        L.hevcdbk_h265_deblock_sao_device_sl.argtypes = [C.c_void_p, C.POINTER(DevicePlanes), C.c_int, C.c_int, C.c_uint,
+                                                         C.POINTER(H265Params), C.c_void_p, C.c_uint, C.c_size_t, C.c_uint, C.c_uint,
+                                                         C.c_void_p, C.c_uint, C.c_size_t, C.c_int, C.POINTER(SaoBorders),
+                                                         C.POINTER(SliceOffsets), C.c_void_p]
+        L.hevcdbk_h265_deblock_sao_device_planes_sl.argtypes = [C.c_void_p, C.POINTER(DevicePlanes), C.c_uint, C.c_int, C.c_uint,
+                                                                C.POINTER(H265Params), C.POINTER(SaoPlaneCf), C.c_int,
+                                                                C.POINTER(SaoBorders), C.POINTER(SliceOffsets), C.c_void_p]
         L.hevc_deblock_sao_h265_device_planes.argtypes = [C.c_void_p, C.POINTER(DevicePlanes), C.c_uint, C.c_uint, C.POINTER(H265Params),
                                                           C.POINTER(SaoPlane), C.c_int, C.c_void_p]
         L.hevcdbk_set_host_threads.argtypes = [C.c_void_p, C.c_uint]

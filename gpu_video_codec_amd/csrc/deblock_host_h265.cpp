@@ -735,4 +735,198 @@ int hevcdbk_h265_deblock_sao_device_planes_nox(hevcdbk_context *ctx, const hevcd
     return rc;
 }
 
+/* ---- per-slice deblocking offsets (H.265 8.7.2.5.3 / 8.7.2.5.5: the pair of the slice that holds q0,0) -------------------- */
+
+namespace {
+
+/* validates the operand against the LUMA picture of plane p (c_idx 0: the plane itself; else scaled by the format) and fills sl */
+int sl_args(const hevcdbk_h265_slice_offsets *so, const hevcdbk_device_planes *p, int c_idx, int cf, DbkSlOffs &sl)
+{
+    if (!so->offs || (uintptr_t)so->offs % 2 != 0 || so->frame_stride % 2 != 0 || so->ctb_log2 < 4 || so->ctb_log2 > 6) return HEVCDBK_ERR_ARG;
+    const unsigned long long lw = (unsigned long long)p->plane_w * (c_idx ? sub_w(cf) : 1u), lh = (unsigned long long)p->plane_h * (c_idx ? sub_h(cf) : 1u);
+    const unsigned long long cols = (lw + (1u << so->ctb_log2) - 1) >> so->ctb_log2, rows = (lh + (1u << so->ctb_log2) - 1) >> so->ctb_log2;
+    if (so->stride < cols || so->stride >= (1u << 23)) return HEVCDBK_ERR_ARG; /* 2 * stride is a 24-bit multiplicand of the kernels */
+    const unsigned long long bytes = 2ull * so->stride * rows;
+    if (bytes > 0x7fffffffull || rows >= (1u << 24)) return HEVCDBK_ERR_ARG;
+    sl.offs = so->offs;
+    sl.stride = (int)so->stride;
+    sl.frame_stride = (long long)so->frame_stride;
+    sl.ctb_log2 = (int)so->ctb_log2;
+    sl.n_bytes = (uint32_t)bytes;
+    return HEVCDBK_OK;
+}
+
+/* the deblocking launch of a plane with the operand: the kernel families of launch_h265, each one's _sl twin */
+int launch_h265_sl(hevcdbk_context *ctx, const DbkH265Args &h0, const DbkSlOffs &sl, int sample_bytes, int c_idx, int cf, int variant,
+                   hipStream_t s)
+{
+    const int map = variant & HEVCDBK_MAP_MASK; /* as in launch_h265 */
+    variant &= ~HEVCDBK_MAP_MASK;
+    if (map != HEVCDBK_MAP_AUTO && map != HEVCDBK_MAP_ROWS && map != HEVCDBK_MAP_LINEAR) return HEVCDBK_ERR_ARG;
+    if (variant != HEVCDBK_KERNEL_PACKED && variant != HEVCDBK_KERNEL_GENERIC && variant != HEVCDBK_KERNEL_AUTO) return HEVCDBK_ERR_ARG;
+    DbkH265Args h = h0;
+    h.base.map_override = map == HEVCDBK_MAP_ROWS ? 1 : (map == HEVCDBK_MAP_LINEAR ? 2 : 0);
+    const bool pack = dbk_packed_h265_supports(h, sample_bytes, c_idx != 0);
+    if (variant == HEVCDBK_KERNEL_PACKED && !pack) return HEVCDBK_ERR_UNSUPPORTED;
+    hipError_t e;
+    if (variant != HEVCDBK_KERNEL_GENERIC && pack) e = dbk_launch_packed_h265_sl(h, sl, sample_bytes, c_idx != 0, c_idx ? cf : 1, s);
+    else e = dbk_launch_h265_sl(h, sl, sample_bytes, c_idx ? cf : 0, s);
+    return hip_ok(ctx, e, "kernel launch") ? HEVCDBK_OK : HEVCDBK_ERR_HIP;
+}
+
+/* launch_h265_sl's argument errors, for the entries that check everything before they bind the device */
+int check_variant_sl(const DbkH265Args &h, int sample_bytes, int c_idx, int variant)
+{
+    const int map = variant & HEVCDBK_MAP_MASK;
+    variant &= ~HEVCDBK_MAP_MASK;
+    if (map != HEVCDBK_MAP_AUTO && map != HEVCDBK_MAP_ROWS && map != HEVCDBK_MAP_LINEAR) return HEVCDBK_ERR_ARG;
+    if (variant != HEVCDBK_KERNEL_PACKED && variant != HEVCDBK_KERNEL_GENERIC && variant != HEVCDBK_KERNEL_AUTO) return HEVCDBK_ERR_ARG;
+    if (variant == HEVCDBK_KERNEL_PACKED && !dbk_packed_h265_supports(h, sample_bytes, c_idx != 0)) return HEVCDBK_ERR_UNSUPPORTED;
+    return HEVCDBK_OK;
+}
+
+/* deblocking + SAO of one plane with the operand: the fused kernel where it applies (and is not switched off), else the two
+ * launches through the context's scratch plane (square CTBs: after sao_square_params) */
+int deblock_sao_plane_h265_sl(hevcdbk_context *ctx, const hevcdbk_device_planes *p, int c_idx, int cf, unsigned qp,
+                              const hevcdbk_h265_params *prm, DbkH265Args &h, DbkSaoArgs &sa, const DbkSlOffs &sl, int fused, hipStream_t s,
+                              const DbkSaoNox *nx)
+{
+    const bool can = fused_can(h, sa, p, c_idx);
+    if (fused == HEVCDBK_FUSED_ON && !can) return HEVCDBK_ERR_UNSUPPORTED;
+    if (can && fused != HEVCDBK_FUSED_OFF)
+        return hip_ok(ctx, dbk_launch_deblock_sao_h265_sl(h, sa, sl, (int)p->sample_bytes, c_idx != 0, c_idx ? cf : 1, s, nx),
+                      "fused deblocking + SAO launch") ? HEVCDBK_OK : HEVCDBK_ERR_HIP;
+    hevcdbk_device_planes first, second;
+    if (int rc = tmp_planes(ctx, p, s, first, second)) return rc;
+    if (int rc = h265_args(&first, c_idx, qp, prm, h)) return rc;
+    if (int rc = launch_h265_sl(ctx, h, sl, (int)p->sample_bytes, c_idx, cf, HEVCDBK_KERNEL_AUTO, s)) return rc;
+    sa.src = (const uint8_t *)second.src;
+    if (!hip_ok(ctx, dbk_launch_sao(sa, (int)p->sample_bytes, s, nx), "SAO launch")) return HEVCDBK_ERR_HIP;
+    return tmp_done(ctx, s);
+}
+
+} /* namespace */
+
+int hevcdbk_h265_slice_offsets_device(hevcdbk_context *ctx, const uint16_t *slice_idx, unsigned in_stride, const int8_t *slice_table,
+                                      unsigned n_slices, unsigned ctbs_x, unsigned ctbs_y, int8_t *offs, unsigned offs_stride,
+                                      void *hip_stream)
+{
+    if (!ctx || !slice_idx || !offs || (uintptr_t)offs % 2 != 0 || (n_slices != 0 && !slice_table)) return HEVCDBK_ERR_ARG;
+    if (ctbs_x == 0 || ctbs_y == 0 || ctbs_x > 65535 || ctbs_y > 65535 || (unsigned long long)ctbs_x * ctbs_y > (1ull << 30) || /* one lane per CTB, numbered in an int */
+        in_stride < ctbs_x || offs_stride < ctbs_x)
+        return HEVCDBK_ERR_ARG;
+    if (int rc = bind(ctx)) return rc;
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->compute;
+    const hipError_t e = dbk_launch_h265_slice_offsets(slice_idx, (int)in_stride, slice_table, n_slices, (int)ctbs_x, (int)ctbs_y, offs,
+                                                       (int)offs_stride, s);
+    return hip_ok(ctx, e, "slice offset derivation launch") ? HEVCDBK_OK : HEVCDBK_ERR_HIP;
+}
+
+int hevcdbk_h265_filter_device_sl(hevcdbk_context *ctx, const hevcdbk_device_planes *planes, int c_idx, int chroma_format_idc, unsigned qp,
+                                  const hevcdbk_h265_params *params, int kernel_variant, const hevcdbk_h265_slice_offsets *slice_offsets,
+                                  void *hip_stream)
+{
+    if (!slice_offsets) /* no operand: the kernels without it */
+        return hevcdbk_h265_filter_device_cf(ctx, planes, c_idx, chroma_format_idc, qp, params, kernel_variant, hip_stream);
+    if (!ctx) return HEVCDBK_ERR_ARG;
+    DbkH265Args h;
+    if (int rc = h265_args_cf(planes, c_idx, chroma_format_idc, qp, params, h)) return rc;
+    DbkSlOffs sl;
+    if (int rc = sl_args(slice_offsets, planes, c_idx, chroma_format_idc, sl)) return rc;
+    if (int rc = check_variant_sl(h, (int)planes->sample_bytes, c_idx, kernel_variant)) return rc;
+    if (int rc = bind(ctx)) return rc;
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->compute;
+    return launch_h265_sl(ctx, h, sl, (int)planes->sample_bytes, c_idx, chroma_format_idc, kernel_variant, s);
+}
+
+int hevcdbk_h265_deblock_sao_device_sl(hevcdbk_context *ctx, const hevcdbk_device_planes *p, int c_idx, int chroma_format_idc, unsigned qp,
+                                       const hevcdbk_h265_params *prm, const hevcdbk_sao_ctb *params, unsigned params_stride,
+                                       size_t params_frame_stride, unsigned ctb_log2_w, unsigned ctb_log2_h, const uint8_t *keep,
+                                       unsigned keep_stride, size_t keep_frame_stride, int fused, const hevcdbk_sao_borders *borders,
+                                       const hevcdbk_h265_slice_offsets *slice_offsets, void *hip_stream)
+{
+    if (!slice_offsets)
+        return hevcdbk_h265_deblock_sao_device_nox(ctx, p, c_idx, chroma_format_idc, qp, prm, params, params_stride, params_frame_stride,
+                                                   ctb_log2_w, ctb_log2_h, keep, keep_stride, keep_frame_stride, fused, borders, hip_stream);
+    if (!ctx || (fused != HEVCDBK_FUSED_AUTO && fused != HEVCDBK_FUSED_OFF && fused != HEVCDBK_FUSED_ON)) return HEVCDBK_ERR_ARG;
+    DbkSaoArgs sa;
+    if (int rc = sao_args_cf(p, params, params_stride, params_frame_stride, ctb_log2_w, ctb_log2_h, keep, keep_stride, keep_frame_stride, sa))
+        return rc;
+    DbkH265Args h;
+    if (int rc = h265_args_cf(p, c_idx, chroma_format_idc, qp, prm, h)) return rc;
+    DbkSaoNox nx, *nxp = nullptr;
+    if (borders) {
+        if (int rc = nox_args(borders, sa, nx)) return rc;
+        nxp = &nx;
+    }
+    DbkSlOffs sl;
+    if (int rc = sl_args(slice_offsets, p, c_idx, chroma_format_idc, sl)) return rc;
+    if (fused == HEVCDBK_FUSED_ON && !fused_can(h, sa, p, c_idx)) return HEVCDBK_ERR_UNSUPPORTED; /* before any launch */
+    if (int rc = bind(ctx)) return rc;
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->compute;
+    if (int rc = sao_square_params(ctx, &sa, &ctb_log2_h, 1, s, nxp)) return rc;
+    const int rc = deblock_sao_plane_h265_sl(ctx, p, c_idx, chroma_format_idc, qp, prm, h, sa, sl, fused, s, nxp);
+    if (ctb_log2_h != ctb_log2_w)
+        if (int rc2 = sao_done(ctx, s)) return rc ? rc : rc2; /* the parameter launch is fenced whatever followed it */
+    return rc;
+}
+
+int hevcdbk_h265_deblock_sao_device_planes_sl(hevcdbk_context *ctx, const hevcdbk_device_planes *planes, unsigned n_planes,
+                                              int chroma_format_idc, unsigned qp, const hevcdbk_h265_params *prm,
+                                              const hevcdbk_sao_plane_cf *sao, int fused, const hevcdbk_sao_borders *borders,
+                                              const hevcdbk_h265_slice_offsets *slice_offsets, void *hip_stream)
+{
+    if (!slice_offsets)
+        return hevcdbk_h265_deblock_sao_device_planes_nox(ctx, planes, n_planes, chroma_format_idc, qp, prm, sao, fused, borders, hip_stream);
+    const int cf = chroma_format_idc;
+    if (!ctx || !planes || !sao || n_planes == 0 || n_planes > 3 || cf < HEVCDBK_CHROMA_400 || cf > HEVCDBK_CHROMA_444 ||
+        (fused != HEVCDBK_FUSED_AUTO && fused != HEVCDBK_FUSED_OFF && fused != HEVCDBK_FUSED_ON))
+        return HEVCDBK_ERR_ARG;
+    if (cf == HEVCDBK_CHROMA_400 && n_planes > 1) return HEVCDBK_ERR_ARG;
+    DbkH265Args h[3];
+    DbkSaoArgs sa[3];
+    DbkSaoNox nx[3], *nxp = borders ? nx : nullptr;
+    DbkSlOffs sl[3]; /* ONE operand for the picture: every plane looks its CTBs up on the luma grid */
+    bool can[3] = {false, false, false}, rect = false;
+    unsigned log2_h[3] = {0, 0, 0};
+    bool one = n_planes >= 2 && fused != HEVCDBK_FUSED_OFF && !planes[0].is_chroma;
+    for (unsigned i = 0; i < n_planes; i++) {
+        if (int rc = sao_args_cf(&planes[i], sao[i].params, sao[i].params_stride, sao[i].params_frame_stride, sao[i].ctb_log2_w,
+                                 sao[i].ctb_log2_h, sao[i].keep, sao[i].keep_stride, sao[i].keep_frame_stride, sa[i]))
+            return rc;
+        if (int rc = h265_args_cf(&planes[i], (int)i, cf, qp, prm, h[i])) return rc; /* c_idx = plane index: 0 Y, 1 Cb, 2 Cr */
+        if (borders)
+            if (int rc = nox_args(borders, sa[i], nx[i])) return rc;
+        if (int rc = sl_args(slice_offsets, &planes[i], (int)i, cf, sl[i])) return rc;
+        if (planes[i].n_frames != planes[0].n_frames) return HEVCDBK_ERR_ARG;
+        if (i > 0 && !planes[0].is_chroma && cf != HEVCDBK_CHROMA_420 &&
+            (planes[i].plane_w * sub_w(cf) != planes[0].plane_w || planes[i].plane_h * sub_h(cf) != planes[0].plane_h))
+            return HEVCDBK_ERR_ARG;
+        log2_h[i] = sao[i].ctb_log2_h;
+        rect = rect || sao[i].ctb_log2_h != sao[i].ctb_log2_w;
+        can[i] = fused_can(h[i], sa[i], &planes[i], (int)i);
+        /* one launch: as in the _nox entry, and one luma picture behind all planes (the kernel takes ONE operand) */
+        one = one && (i == 0 || planes[i].is_chroma) && planes[i].sample_bytes == planes[0].sample_bytes &&
+              planes[i].bit_depth == planes[0].bit_depth && (h[i].base.qp_map != nullptr) == (h[0].base.qp_map != nullptr) && can[i] &&
+              sl[i].n_bytes == sl[0].n_bytes;
+    }
+    if (!one && fused == HEVCDBK_FUSED_ON)
+        for (unsigned i = 0; i < n_planes; i++)
+            if (!can[i]) return HEVCDBK_ERR_UNSUPPORTED;
+    if (int rc = bind(ctx)) return rc;
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->compute;
+    if (int rc = sao_square_params(ctx, sa, log2_h, n_planes, s, nxp)) return rc;
+    int rc = HEVCDBK_OK;
+    if (one) {
+        if (!hip_ok(ctx, dbk_launch_deblock_sao_multi_h265_sl(h, sa, sl[0], (int)n_planes, (int)planes[0].sample_bytes, cf, s, nxp),
+                    "fused deblocking + SAO launch"))
+            rc = HEVCDBK_ERR_HIP;
+    }
+    for (unsigned i = 0; !one && i < n_planes && rc == HEVCDBK_OK; i++)
+        rc = deblock_sao_plane_h265_sl(ctx, &planes[i], (int)i, cf, qp, prm, h[i], sa[i], sl[i], fused, s, nxp ? &nxp[i] : nullptr);
+    if (rect)
+        if (int rc2 = sao_done(ctx, s)) return rc ? rc : rc2;
+    return rc;
+}
+
 } /* extern "C" */

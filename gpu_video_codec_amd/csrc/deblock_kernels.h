@@ -219,3 +219,29 @@ hipError_t dbk_launch_deblock_sao_h265_cf(const DbkH265Args &h, const DbkSaoArgs
 hipError_t dbk_launch_deblock_sao_multi_h265_cf(const DbkH265Args *h, const DbkSaoArgs *s, int n, int sample_bytes, int chroma_format,
                                                 hipStream_t stream, const DbkSaoNox *nx = nullptr);
 
+/* ---- per-slice deblocking offsets of the spec-exact mode (hevcdbk_h265_slice_offsets of the C ABI), deblock_sl.hip ---- */
+/* slice_beta_offset_div2 / slice_tc_offset_div2 per CTB of the LUMA grid (one grid for every plane of the picture).  A kernel
+ * argument of its own, taken by the _sl kernels only: the kernels without the operand keep their argument layout, i.e. their
+ * machine code.  With it h.tc_off / h.beta_off are not used. */
+struct DbkSlOffs {
+    const int8_t *offs;     /* offs[2 * (cy * stride + cx)] = beta, [.. + 1] = tc; 2-byte aligned */
+    int stride;             /* CTBs per row, 2 * stride < 2^24 */
+    long long frame_stride; /* bytes, 0 = shared */
+    int ctb_log2;           /* CtbLog2SizeY */
+    uint32_t n_bytes;       /* one frame's array: 2 * stride * CTB rows (the kernels' buffer range) */
+};
+/* the 32-bit kernel with the operand: chroma_format 0 = the luma plane, 1..3 = a chroma plane of a picture of that format */
+hipError_t dbk_launch_h265_sl(const DbkH265Args &h, const DbkSlOffs &sl, int sample_bytes, int chroma_format, hipStream_t stream);
+/* the packed kernels' and the fused deblocking + SAO kernels' _sl twins (deblock_kernels.hip): the operands dbk_packed_h265_supports
+ * / dbk_deblock_sao_supports accept, one QP or a QP map, every chroma format; grids and blocks as without the operand.  nx may be
+ * NULL (one per plane for the multi launch otherwise); ONE DbkSlOffs serves all planes of the multi launch */
+hipError_t dbk_launch_packed_h265_sl(const DbkH265Args &h, const DbkSlOffs &sl, int sample_bytes, bool chroma, int chroma_format,
+                                     hipStream_t stream);
+hipError_t dbk_launch_deblock_sao_h265_sl(const DbkH265Args &h, const DbkSaoArgs &s, const DbkSlOffs &sl, int sample_bytes, bool chroma,
+                                          int chroma_format, hipStream_t stream, const DbkSaoNox *nx);
+hipError_t dbk_launch_deblock_sao_multi_h265_sl(const DbkH265Args *h, const DbkSaoArgs *s, const DbkSlOffs &sl, int n, int sample_bytes,
+                                                int chroma_format, hipStream_t stream, const DbkSaoNox *nx);
+/* the operand from the decoder's per-CTB slice indices and a table of n_slices (beta, tc) pairs: one lane per CTB */
+hipError_t dbk_launch_h265_slice_offsets(const uint16_t *slice_idx, int in_stride, const int8_t *table, unsigned n_slices, int ctbs_x,
+                                         int ctbs_y, int8_t *offs, int offs_stride, hipStream_t stream);
+

@@ -22,6 +22,8 @@
 #include "deblock_kernels.h"
 #include "deblock_packed.h"
 #include "deblock_packed_h265.h"
+#include "deblock_sl_dev.h"
+#include "deblock_sl_packed.h"
 #include "deblock_packed16.h"
 #include "sao_packed.h"
 
@@ -317,6 +319,25 @@ __device__ __forceinline__ void block_qpl4_dev(const DbkArgs &a, int f, int by, 
     qpl[3] = dbk::seg_qp_avg(q[1], q[3]); /* hor2: above-right / below-right */
 }
 
+/* per-slice offsets (the _sl kernels, deblock_sl.h): the block's four segment QPs and four offset pairs.  The three pair loads go
+ * out first, then the map loads (a one-QP launch has no map: its qPL is the launch's scalar, and no dummy map is read); nothing
+ * waits before all of them are under way */
+template <bool CHROMA, int CF>
+__device__ __forceinline__ void sl_block_operands(const DbkArgs &a, const DbkH265Args *hx, const DbkSlOffs *sl, int f, int by, int bx,
+                                                  int (&qpl)[4], int (&tc_off)[4], int (&beta_off)[4])
+{
+    constexpr int sx = CHROMA ? (CF == 3 ? 1 : 2) : 1, sy = CHROMA ? (CF == 1 ? 2 : 1) : 1;
+    unsigned ar, bl, br;
+    dbk_sl_load_pairs<sx, sy>(*sl, f, bx, by, a.plane_w * sx, a.plane_h * sy, ar, bl, br);
+    if (a.qp_map) { /* wave-uniform */
+        block_qpl4_dev<CHROMA, CF>(a, f, by, bx, qpl);
+    } else {
+#pragma unroll
+        for (int i = 0; i < 4; i++) qpl[i] = hx->qp;
+    }
+    dbk::h265_sl_seg_offs(ar, bl, br, tc_off, beta_off);
+}
+
 template <bool CHROMA>
 __device__ __forceinline__ dbk::QsTable block_qp_tab(const DbkArgs &a, int f, int by, int bx, const DBK_LDS uint32_t *tab)
 {
@@ -365,10 +386,12 @@ __device__ __forceinline__ const DBK_LDS uint32_t *ktab_setup_h265(uint32_t *lds
  *   with wave-uniform branches.
  * MODE 0 = filter, MODE 1 = diagnostic copy (same loads/stores, no arithmetic).
  */
-template <bool CHROMA, int MODE, bool NT, int PATH, bool QPMAP, int CF = 1 /* chroma_format_idc of a spec-exact chroma plane */>
+template <bool CHROMA, int MODE, bool NT, int PATH, bool QPMAP, int CF = 1 /* chroma_format_idc of a spec-exact chroma plane */,
+          bool SL = false /* MODE 2 with QPMAP: per-slice offsets from sl (the _sl kernels); the map itself may be absent */>
 __device__ __forceinline__ void packed_body(const DbkArgs &a, int by, int f, int bx, bool active, int by0,
                                             const DbkH265Args *hx = nullptr /* MODE 2 only */,
-                                            uint32_t *ktab_lds = nullptr /* QPMAP luma: LDS for the workgroup's operand table */)
+                                            uint32_t *ktab_lds = nullptr /* QPMAP luma: LDS for the workgroup's operand table */,
+                                            [[maybe_unused]] const DbkSlOffs *sl = nullptr /* SL only */)
 {
     /* QP-map luma launches: every wave of the workgroup passes ktab_setup() exactly once -- AFTER its row, bS and map loads have
      * been issued, so that the table's construction (the first 54 lanes of the workgroup; the others wait at the barrier)
@@ -537,7 +560,17 @@ __device__ __forceinline__ void packed_body(const DbkArgs &a, int by, int f, int
         int entry[4];
         load_bs_buffer_h265<PATH>(a, f, by, bx, active, entry);
         dbk::H265Seg sg;
-        if constexpr (QPMAP) {
+        if constexpr (QPMAP && SL) {
+            int qpl[4], tc_off[4], beta_off[4];
+            sl_block_operands<CHROMA, CF>(a, hx, sl, f, by, active ? bx : 0, qpl, tc_off, beta_off);
+            const dbk::H265Prm prm = {0, 0, hx->c_qp_offset, 0, 255};
+            if constexpr (KT) {
+                if constexpr (PATH != 3) ktab = ktab_setup_h265(ktab_lds, 0);
+                dbk::h265_seg_rows_sl(entry, qpl, prm, ktab, tc_off, beta_off, sg);
+            } else {
+                dbk::h265_seg_params_sl<CHROMA, CF>(entry, qpl, prm, tc_off, beta_off, sg);
+            }
+        } else if constexpr (QPMAP) {
             int qpl[4];
             block_qpl4_dev<CHROMA, CF>(a, f, by, active ? bx : 0, qpl);
             const dbk::H265Prm prm = {hx->tc_off, hx->beta_off, hx->c_qp_offset, 0, 255};
@@ -637,10 +670,11 @@ __device__ __forceinline__ void packed_body(const DbkArgs &a, int by, int f, int
  * they are (no widening needed), so twice the bytes per pixel at the same instruction count: this is
  * the variant that runs into the HBM roof (BASELINE config 5).
  */
-template <int MODE, bool NT, bool EDGE, bool QPMAP, bool CHROMA = false, bool WIDE = false, int CF = 1>
+template <int MODE, bool NT, bool EDGE, bool QPMAP, bool CHROMA = false, bool WIDE = false, int CF = 1, bool SL = false /* packed_body */>
 __device__ __forceinline__ void packed16_body(const DbkArgs &a, int by, int f, int bx, bool active,
                                               const DbkH265Args *hx = nullptr /* MODE 2 (spec-exact) only */,
-                                              uint32_t *ktab_lds = nullptr /* QPMAP luma: LDS for the workgroup's operand table */)
+                                              uint32_t *ktab_lds = nullptr /* QPMAP luma: LDS for the workgroup's operand table */,
+                                              [[maybe_unused]] const DbkSlOffs *sl = nullptr /* SL only */)
 {
     constexpr bool KT = QPMAP && !CHROMA && (MODE == 0 || MODE == 2); /* packed_body: built after the loads have been issued */
     const bool lv = active && bx > 0;
@@ -694,7 +728,13 @@ __device__ __forceinline__ void packed16_body(const DbkArgs &a, int by, int f, i
         int entry[4];
         load_bs_buffer_h265<EDGE ? 2 : 0>(a, f, by, bx, active, entry);
         dbk::H265Seg sg;
-        if constexpr (QPMAP) {
+        if constexpr (QPMAP && SL) {
+            int qpl[4], tc_off[4], beta_off[4];
+            sl_block_operands<CHROMA, CF>(a, hx, sl, f, by, active ? bx : 0, qpl, tc_off, beta_off);
+            const dbk::H265Prm prm = {0, 0, hx->c_qp_offset, a.shift, a.max_v};
+            if constexpr (KT) dbk::h265_seg_rows_sl(entry, qpl, prm, ktab_setup_h265(ktab_lds, a.shift), tc_off, beta_off, sg);
+            else dbk::h265_seg_params_sl<CHROMA, CF>(entry, qpl, prm, tc_off, beta_off, sg);
+        } else if constexpr (QPMAP) {
             int qpl[4];
             block_qpl4_dev<CHROMA, CF>(a, f, by, active ? bx : 0, qpl);
             const dbk::H265Prm prm = {hx->tc_off, hx->beta_off, hx->c_qp_offset, a.shift, a.max_v};
@@ -868,8 +908,8 @@ __global__ __launch_bounds__(1024) void dbk_packed_kernel(const DbkArgs a)
 }
 
 /* spec-exact mode (H.265 8.7.2), 8-bit samples, packed-int16 arithmetic: same mapping and memory path */
-template <bool CHROMA, bool LINEAR, bool QPMAP, int CF = 1>
-__device__ __forceinline__ void packed_h265_dispatch(const DbkH265Args &h)
+template <bool CHROMA, bool LINEAR, bool QPMAP, int CF = 1, bool SL = false>
+__device__ __forceinline__ void packed_h265_dispatch(const DbkH265Args &h, const DbkSlOffs *sl = nullptr)
 {
     const DbkArgs &a = h.base;
     uint32_t *kt = nullptr;
@@ -879,9 +919,9 @@ __device__ __forceinline__ void packed_h265_dispatch(const DbkH265Args &h)
     }
     WaveCoords c;
     if (!wave_coords<LINEAR>(a, c)) return;
-    if (c.interior) packed_body<CHROMA, 2, false, 0, QPMAP, CF>(a, c.by, c.f, c.bx, true, c.by0, &h, kt);
-    else if (c.rows_in) packed_body<CHROMA, 2, false, LINEAR ? 1 : 3, QPMAP, CF>(a, c.by, c.f, c.bx, c.active, c.by0, &h, kt);
-    else packed_body<CHROMA, 2, false, 2, QPMAP, CF>(a, c.by, c.f, c.bx, c.active, c.by0, &h, kt);
+    if (c.interior) packed_body<CHROMA, 2, false, 0, QPMAP, CF, SL>(a, c.by, c.f, c.bx, true, c.by0, &h, kt, sl);
+    else if (c.rows_in) packed_body<CHROMA, 2, false, LINEAR ? 1 : 3, QPMAP, CF, SL>(a, c.by, c.f, c.bx, c.active, c.by0, &h, kt, sl);
+    else packed_body<CHROMA, 2, false, 2, QPMAP, CF, SL>(a, c.by, c.f, c.bx, c.active, c.by0, &h, kt, sl);
 }
 template <bool CHROMA, bool LINEAR, bool QPMAP>
 __global__ __launch_bounds__(1024) void dbk_packed_h265_kernel(const DbkH265Args h)
@@ -903,6 +943,29 @@ __global__ __launch_bounds__(1024) void dbk_packed16_h265_cf_kernel(const DbkH26
     if (!wave_coords<LINEAR>(a, c)) return;
     if (c.interior) packed16_body<2, false, false, true, true, false, CF>(a, c.by, c.f, c.bx, true, &h, nullptr);
     else packed16_body<2, false, true, true, true, false, CF>(a, c.by, c.f, c.bx, c.active, &h, nullptr);
+}
+/* The packed kernels with per-slice offsets (DbkSlOffs, an argument of their own: the kernels above keep their layout and machine
+ * code).  Always the per-lane form -- the QP-map kernels' operand table for luma, their per-lane tc for chroma -- whose two
+ * indices of Table 8-12 take the offsets of the CTB that holds q0,0 of the segment; a one-QP launch runs it with a constant qPL.
+ * CF = chroma_format_idc of a chroma plane (its map positions, its CTB positions and its QpC rule); luma: CF 1. */
+template <bool CHROMA, bool LINEAR, int CF>
+__global__ __launch_bounds__(1024) void dbk_packed_h265_sl_kernel(const DbkH265Args h, const DbkSlOffs sl)
+{
+    packed_h265_dispatch<CHROMA, LINEAR, true, CF, true>(h, &sl);
+}
+template <bool CHROMA, bool LINEAR, bool WIDE, int CF>
+__global__ __launch_bounds__(1024) void dbk_packed16_h265_sl_kernel(const DbkH265Args h, const DbkSlOffs sl)
+{
+    const DbkArgs &a = h.base;
+    uint32_t *kt = nullptr;
+    if constexpr (!CHROMA) {
+        __shared__ uint32_t ktab[dbk::kKTabDwords];
+        kt = ktab;
+    }
+    WaveCoords c;
+    if (!wave_coords<LINEAR>(a, c)) return;
+    if (c.interior) packed16_body<2, false, false, true, CHROMA, WIDE, CF, true>(a, c.by, c.f, c.bx, true, &h, kt, &sl);
+    else packed16_body<2, false, true, true, CHROMA, WIDE, CF, true>(a, c.by, c.f, c.bx, c.active, &h, kt, &sl);
 }
 /* ------------------------------------------------------------------------------------------ */
 /* one launch for the planes of a 4:2:0 frame                                */
@@ -1649,5 +1712,107 @@ hipError_t dbk_launch_deblock_sao_multi_h265_cf(const DbkH265Args *h, const DbkS
     if (sample_bytes == 1) DBK_FUSED_LAUNCH(qm, dbk_sao_fused_multi_h265_kernel, kFusedThreads, kFusedLds, 1, false);
     else if (h[0].base.max_v > 2047) DBK_FUSED_LAUNCH(qm, dbk_sao_fused_multi_h265_kernel, kFused16Threads, kFused16Lds, 2, true);
     else DBK_FUSED_LAUNCH(qm, dbk_sao_fused_multi_h265_kernel, kFused16Threads, kFused16Lds, 2, false);
+    return hipGetLastError();
+}
+
+/* ---- per-slice deblocking offsets: the packed and fused kernels' _sl twins (grids and blocks as without the operand) ---- */
+
+hipError_t dbk_launch_packed_h265_sl(const DbkH265Args &h, const DbkSlOffs &sl, int sample_bytes, bool chroma, int chroma_format,
+                                     hipStream_t stream)
+{
+    if (chroma && chroma_format != 1 && chroma_format != 2 && chroma_format != 3) return hipErrorInvalidValue;
+    if (h.base.n_frames <= 0 || h.base.nbx <= 0 || h.base.nby <= 0) return hipSuccess;
+    DbkH265Args g = h;
+    dim3 grid, block;
+    const bool linear = plan_packed(h.base, g.base, grid, block);
+    const int cf = chroma ? chroma_format : 1;
+    const bool wide = !chroma && g.base.max_v > 2047; /* 12-bit luma */
+#define DBK_SL_LAUNCH(C, LIN, F)                                                                                        \
+    do {                                                                                                                \
+        if (sample_bytes == 2 && wide) DBK_LAUNCH((dbk_packed16_h265_sl_kernel<C, LIN, !C, F>), grid, block, stream, g, sl); \
+        else if (sample_bytes == 2) DBK_LAUNCH((dbk_packed16_h265_sl_kernel<C, LIN, false, F>), grid, block, stream, g, sl); \
+        else DBK_LAUNCH((dbk_packed_h265_sl_kernel<C, LIN, F>), grid, block, stream, g, sl);                           \
+    } while (0)
+#define DBK_SL_LAUNCH_F(LIN)                          \
+    do {                                              \
+        if (!chroma) DBK_SL_LAUNCH(false, LIN, 1);    \
+        else if (cf == 1) DBK_SL_LAUNCH(true, LIN, 1); \
+        else if (cf == 2) DBK_SL_LAUNCH(true, LIN, 2); \
+        else DBK_SL_LAUNCH(true, LIN, 3);             \
+    } while (0)
+    if (linear) DBK_SL_LAUNCH_F(true);
+    else DBK_SL_LAUNCH_F(false);
+#undef DBK_SL_LAUNCH_F
+#undef DBK_SL_LAUNCH
+    return hipGetLastError();
+}
+
+hipError_t dbk_launch_deblock_sao_h265_sl(const DbkH265Args &h, const DbkSaoArgs &s, const DbkSlOffs &sl, int sample_bytes, bool chroma,
+                                          int chroma_format, hipStream_t stream, const DbkSaoNox *nxp)
+{
+    if (!fused_format_ok(chroma_format)) return hipErrorInvalidValue;
+    if (h.base.n_frames <= 0 || h.base.nbx <= 0 || h.base.nby <= 0) return hipSuccess;
+    DbkFusedH265Args fa;
+    fa.d = h;
+    fa.s = s;
+    const dim3 grid(fused_grid(h.base.plane_w, h.base.plane_h, h.base.n_frames, sample_bytes, fa.g), 1, 1);
+    const DbkSaoNox nx = nxp ? *nxp : DbkSaoNox{nullptr, 0, 0}; /* no bytes: no direction is forbidden */
+    const int cf = chroma ? chroma_format : 1;
+#define DBK_SL8(C, F) DBK_LAUNCH_LDS((dbk_sao_fused_h265_sl_kernel<C, F>), grid, dim3(kFusedThreads), kFusedLds, stream, fa, nx, sl)
+#define DBK_SL16(C, W, F) DBK_LAUNCH_LDS((dbk_sao_fused16_h265_sl_kernel<C, W, F>), grid, dim3(kFused16Threads), kFused16Lds, stream, fa, nx, sl)
+    if (sample_bytes == 1) {
+        if (!chroma) DBK_SL8(false, 1);
+        else if (cf == 1) DBK_SL8(true, 1);
+        else if (cf == 2) DBK_SL8(true, 2);
+        else DBK_SL8(true, 3);
+    } else {
+        if (!chroma && h.base.max_v > 2047) DBK_SL16(false, true, 1);
+        else if (!chroma) DBK_SL16(false, false, 1);
+        else if (cf == 1) DBK_SL16(true, false, 1);
+        else if (cf == 2) DBK_SL16(true, false, 2);
+        else DBK_SL16(true, false, 3);
+    }
+#undef DBK_SL8
+#undef DBK_SL16
+    return hipGetLastError();
+}
+
+hipError_t dbk_launch_deblock_sao_multi_h265_sl(const DbkH265Args *h, const DbkSaoArgs *s, const DbkSlOffs &sl, int n, int sample_bytes,
+                                                int chroma_format, hipStream_t stream, const DbkSaoNox *nxp)
+{
+    if (!fused_format_ok(chroma_format)) return hipErrorInvalidValue;
+    if (n < 2 || n > 3) return hipErrorInvalidValue;
+    if (h[0].base.n_frames <= 0) return hipSuccess;
+    DbkFusedMultiH265Args m;
+    std::memset(&m, 0, sizeof(m));
+    unsigned total = 0;
+    for (int i = 0; i < 3; i++) {
+        if (i < n) {
+            m.pl[i].d = h[i];
+            m.pl[i].s = s[i];
+            total += fused_grid(h[i].base.plane_w, h[i].base.plane_h, h[i].base.n_frames, sample_bytes, m.pl[i].g);
+        }
+        m.wg_end[i] = total;
+    }
+    const dim3 grid(total, 1, 1);
+    const DbkFusedMultiH265Args &fa = m;
+    DbkSaoNox3 nx = {};
+    if (nxp)
+        for (int i = 0; i < n; i++) nx.pl[i] = nxp[i];
+    const bool wide = h[0].base.max_v > 2047;
+#define DBK_SLM(SB, W, F)                                                                                                            \
+    DBK_LAUNCH_LDS((dbk_sao_fused_multi_h265_sl_kernel<SB, W, F>), grid, dim3(SB == 1 ? kFusedThreads : kFused16Threads),            \
+                   SB == 1 ? kFusedLds : kFused16Lds, stream, fa, nx, sl)
+#define DBK_SLM_F(F)                                    \
+    do {                                                \
+        if (sample_bytes == 1) DBK_SLM(1, false, F);    \
+        else if (wide) DBK_SLM(2, true, F);             \
+        else DBK_SLM(2, false, F);                      \
+    } while (0)
+    if (chroma_format == 1) DBK_SLM_F(1);
+    else if (chroma_format == 2) DBK_SLM_F(2);
+    else DBK_SLM_F(3);
+#undef DBK_SLM_F
+#undef DBK_SLM
     return hipGetLastError();
 }

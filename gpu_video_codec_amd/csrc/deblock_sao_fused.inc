@@ -33,11 +33,14 @@ constexpr int kFusedQuads = kFusedTile / 64;          /* 64 x 64 quadrants: kFus
 constexpr int kFusedQuadsX = kFusedTileW / 64;
 constexpr int kFusedLds = (kFusedTile + 8) * kFusedPitch;
 
-template <bool CHROMA, int MODE, bool QPMAP, int CF = 1, bool NOX = false> /* MODE 0 = reference-exact deblocking, 2 = spec-exact (H.265 8.7.2); QPMAP = QP per map unit;
+template <bool CHROMA, int MODE, bool QPMAP, int CF = 1, bool NOX = false, bool SL = false> /* MODE 0 = reference-exact deblocking, 2 = spec-exact (H.265 8.7.2); QPMAP = QP per map unit;
                                                           CF = chroma_format_idc of a spec-exact chroma plane with a QP map;
-                                                          NOX = stage 2 honours the slice / tile boundaries of nx (the _nox kernels) */
+                                                          NOX = stage 2 honours the slice / tile boundaries of nx (the _nox kernels);
+                                                          SL = per-slice deblocking offsets from sl (the _sl kernels: MODE 2, QPMAP and NOX set,
+                                                          the map and the bytes of nx may be absent) */
 __device__ __forceinline__ void fused_body(const DbkArgs &a, const DbkH265Args *hx, const DbkSaoArgs &s, const DbkFusedGrid &g, uint8_t *tile,
-                                           uint32_t id /* workgroup number inside this plane's part of the grid */, const DbkSaoNox *nx = nullptr)
+                                           uint32_t id /* workgroup number inside this plane's part of the grid */, const DbkSaoNox *nx = nullptr,
+                                           [[maybe_unused]] const DbkSlOffs *sl = nullptr)
 {
     /* workgroups are dealt round-robin over the 8 XCDs (an observation used for speed only): renumber them so that each XCD
      * works through a contiguous range of tiles.  A tile's row pieces are 200 bytes at an odd alignment, so it shares 128-byte
@@ -110,7 +113,13 @@ __device__ __forceinline__ void fused_body(const DbkArgs &a, const DbkH265Args *
         int entry[4];
         load_bs_buffer_h265<2>(a, f, by, bx, active, entry);
         dbk::H265Seg sg;
-        if constexpr (QPMAP) {
+        if constexpr (QPMAP && SL) {
+            int qpl[4], tc_off[4], beta_off[4];
+            sl_block_operands<CHROMA, CF>(a, hx, sl, f, by, active ? bx : 0, qpl, tc_off, beta_off);
+            const dbk::H265Prm prm = {0, 0, hx->c_qp_offset, 0, 255};
+            if constexpr (KT) dbk::h265_seg_rows_sl(entry, qpl, prm, ktab_setup_h265(ktab_lds, 0), tc_off, beta_off, sg);
+            else dbk::h265_seg_params_sl<CHROMA, CF>(entry, qpl, prm, tc_off, beta_off, sg);
+        } else if constexpr (QPMAP) {
             int qpl[4];
             block_qpl4_dev<CHROMA, CF>(a, f, by, active ? bx : 0, qpl);
             const dbk::H265Prm prm = {hx->tc_off, hx->beta_off, hx->c_qp_offset, 0, 255};
@@ -154,7 +163,8 @@ __device__ __forceinline__ void fused_body(const DbkArgs &a, const DbkH265Args *
         const int x = X0 + qx, ys = Y0 + qy;
         if (x >= s.plane_w || ys >= s.plane_h) return;
         [[maybe_unused]] uint32_t nox_byte = 0u;
-        if constexpr (NOX) nox_byte = saonox::ctb_byte(*nx, f, x, ys, s.ctb_log2);
+        if constexpr (NOX && SL) nox_byte = nx->nox ? saonox::ctb_byte(*nx, f, x, ys, s.ctb_log2) : 0u; /* no bytes: nothing forbidden */
+        else if constexpr (NOX) nox_byte = saonox::ctb_byte(*nx, f, x, ys, s.ctb_log2);
         const DbkSaoCtb c = s.params[(long long)f * s.params_frame_stride + (long long)(ys >> s.ctb_log2) * s.params_stride + (x >> s.ctb_log2)];
         const bool kept = s.keep && s.keep[(long long)f * s.keep_frame_stride + (long long)(ys >> 3) * s.keep_stride + (x >> 3)];
         /* image (x - 4, ys - 1 + i) is tile (qx, qy + 3 + i): the tile's origin is image (X0 - 4, Y0 - 4) */
@@ -209,9 +219,9 @@ constexpr int kFused16Threads = 320;
 constexpr int kFused16Quads = kFused16Tile / 64;       /* 2 x 2 SAO waves */
 constexpr int kFused16Lds = (kFused16Tile + 8) * kFused16Pitch;
 
-template <bool CHROMA, int MODE, bool WIDE, bool QPMAP, int CF = 1, bool NOX = false>
+template <bool CHROMA, int MODE, bool WIDE, bool QPMAP, int CF = 1, bool NOX = false, bool SL = false>
 __device__ __forceinline__ void fused_body16(const DbkArgs &a, const DbkH265Args *hx, const DbkSaoArgs &s, const DbkFusedGrid &g, uint8_t *tile,
-                                             uint32_t id, const DbkSaoNox *nx = nullptr)
+                                             uint32_t id, const DbkSaoNox *nx = nullptr, [[maybe_unused]] const DbkSlOffs *sl = nullptr)
 {
     const uint32_t logical = (id & 7u) * g.per_xcd + (id >> 3);
     if (logical >= g.total) return;
@@ -263,7 +273,12 @@ __device__ __forceinline__ void fused_body16(const DbkArgs &a, const DbkH265Args
         int entry[4];
         load_bs_buffer_h265<2>(a, f, by, bx, active, entry);
         dbk::H265Seg sg;
-        if constexpr (QPMAP) {
+        if constexpr (QPMAP && SL) {
+            int qpl[4], tc_off[4], beta_off[4];
+            sl_block_operands<CHROMA, CF>(a, hx, sl, f, by, active ? bx : 0, qpl, tc_off, beta_off);
+            const dbk::H265Prm prm = {0, 0, hx->c_qp_offset, a.shift, a.max_v};
+            dbk::h265_seg_params_sl<CHROMA, CF>(entry, qpl, prm, tc_off, beta_off, sg);
+        } else if constexpr (QPMAP) {
             int qpl[4];
             block_qpl4_dev<CHROMA, CF>(a, f, by, active ? bx : 0, qpl);
             const dbk::H265Prm prm = {hx->tc_off, hx->beta_off, hx->c_qp_offset, a.shift, a.max_v};
@@ -302,7 +317,8 @@ __device__ __forceinline__ void fused_body16(const DbkArgs &a, const DbkH265Args
         const int x = X0 + qx, ys = Y0 + qy;
         if (x >= s.plane_w || ys >= s.plane_h) return;
         [[maybe_unused]] uint32_t nox_byte = 0u;
-        if constexpr (NOX) nox_byte = saonox::ctb_byte(*nx, f, x, ys, s.ctb_log2);
+        if constexpr (NOX && SL) nox_byte = nx->nox ? saonox::ctb_byte(*nx, f, x, ys, s.ctb_log2) : 0u; /* no bytes: nothing forbidden */
+        else if constexpr (NOX) nox_byte = saonox::ctb_byte(*nx, f, x, ys, s.ctb_log2);
         const DbkSaoCtb c = s.params[(long long)f * s.params_frame_stride + (long long)(ys >> s.ctb_log2) * s.params_stride + (x >> s.ctb_log2)];
         const bool kept = s.keep && s.keep[(long long)f * s.keep_frame_stride + (long long)(ys >> 3) * s.keep_stride + (x >> 3)];
         /* image (x - 4, ys - 1 + i) is tile (column qx, row qy + 3 + i): the tile's origin is image (X0 - 4, Y0 - 4) */
@@ -484,5 +500,40 @@ __global__ __launch_bounds__(SB == 1 ? kFusedThreads : kFused16Threads) void dbk
     } else {
         if (pl == 0) fused_body16<false, 2, WIDE, QPMAP, 1, true>(fa.d.base, &fa.d, fa.s, fa.g, fused_tile, id, &nx.pl[0]);
         else fused_body16<true, 2, false, QPMAP, CF, true>(fa.d.base, &fa.d, fa.s, fa.g, fused_tile, id, &nx.pl[pl]);
+    }
+}
+
+/* ---- the spec-exact kernels with per-slice deblocking offsets (deblock_sl.h): the _nox kernels plus one argument, DbkSlOffs -- ONE
+ * for all planes of the multi-plane launch, whose CTB grid is the luma grid.  Kernels of their own names again.  They take the
+ * boundary bytes as well, which may be absent (nx.nox == NULL: stage 2 then masks the picture border only, the same bytes as the
+ * kernels without the operand), and always run stage 1 in the per-lane form, with a constant qPL where the plane has no QP map:
+ * neither choice is a template dimension, so there is one kernel per plane kind and format ---- */
+template <bool CHROMA, int CF>
+__global__ __launch_bounds__(kFusedThreads) void dbk_sao_fused_h265_sl_kernel(const DbkFusedH265Args fa, const DbkSaoNox nx, const DbkSlOffs sl)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t fused_tile[];
+    fused_body<CHROMA, 2, true, CF, true, true>(fa.d.base, &fa.d, fa.s, fa.g, fused_tile, blockIdx.x, &nx, &sl);
+}
+template <bool CHROMA, bool WIDE, int CF>
+__global__ __launch_bounds__(kFused16Threads) void dbk_sao_fused16_h265_sl_kernel(const DbkFusedH265Args fa, const DbkSaoNox nx, const DbkSlOffs sl)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t fused_tile[];
+    fused_body16<CHROMA, 2, WIDE, true, CF, true, true>(fa.d.base, &fa.d, fa.s, fa.g, fused_tile, blockIdx.x, &nx, &sl);
+}
+template <int SB, bool WIDE, int CF>
+__global__ __launch_bounds__(SB == 1 ? kFusedThreads : kFused16Threads) void dbk_sao_fused_multi_h265_sl_kernel(const DbkFusedMultiH265Args m,
+                                                                                                                const DbkSaoNox3 nx,
+                                                                                                                const DbkSlOffs sl)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t fused_tile[];
+    uint32_t id;
+    const int pl = fused_plane(m.wg_end, id);
+    const DbkFusedH265Args &fa = m.pl[pl];
+    if constexpr (SB == 1) {
+        if (pl == 0) fused_body<false, 2, true, 1, true, true>(fa.d.base, &fa.d, fa.s, fa.g, fused_tile, id, &nx.pl[0], &sl);
+        else fused_body<true, 2, true, CF, true, true>(fa.d.base, &fa.d, fa.s, fa.g, fused_tile, id, &nx.pl[pl], &sl);
+    } else {
+        if (pl == 0) fused_body16<false, 2, WIDE, true, 1, true, true>(fa.d.base, &fa.d, fa.s, fa.g, fused_tile, id, &nx.pl[0], &sl);
+        else fused_body16<true, 2, false, true, CF, true, true>(fa.d.base, &fa.d, fa.s, fa.g, fused_tile, id, &nx.pl[pl], &sl);
     }
 }

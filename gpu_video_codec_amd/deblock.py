@@ -344,11 +344,16 @@ class Context:
         return {"exec_s": tm.exec_s, "total_s": tm.total_s, "copy_s": tm.copy_s, "pipelined_s": tm.pipelined_s}
 
     def filter_device_h265(self, planes, qp, *, c_idx=0, tc_offset_div2=0, beta_offset_div2=0, cb_qp_offset=0, cr_qp_offset=0,
-                           variant=KERNEL_AUTO, chroma_format="420"):
-        """hevc_deblocking_filter_h265_device[_cf]: a plane of a picture in chroma_format '400' / '420' / '422' / '444'."""
+                           variant=KERNEL_AUTO, chroma_format="420", slice_offsets=None):
+        """hevc_deblocking_filter_h265_device[_cf]: a plane of a picture in chroma_format '400' / '420' / '422' / '444'.
+        slice_offsets: a _lib.SliceOffsets (per-CTB slice_beta_offset_div2 / slice_tc_offset_div2, hevcdbk_h265_filter_device_sl);
+        with it tc_offset_div2 / beta_offset_div2 are not used."""
         cf = _lib.chroma_format_idc(chroma_format)
         prm = _lib.H265Params(tc_offset_div2, beta_offset_div2, cb_qp_offset, cr_qp_offset)
-        if cf == _lib.CHROMA_420:
+        if slice_offsets is not None:
+            rc = _lib.lib().hevcdbk_h265_filter_device_sl(self.handle, C.byref(planes), c_idx, cf, int(qp), C.byref(prm), variant,
+                                                          C.byref(slice_offsets), None)
+        elif cf == _lib.CHROMA_420:
             rc = _lib.lib().hevc_deblocking_filter_h265_device(self.handle, C.byref(planes), c_idx, int(qp), C.byref(prm), variant, None)
         else:
             rc = _lib.lib().hevcdbk_h265_filter_device_cf(self.handle, C.byref(planes), c_idx, cf, int(qp), C.byref(prm),
@@ -412,6 +417,30 @@ class Context:
             b.free()
         return res
 
+    def derive_slice_offsets(self, slice_idx, slice_table):
+        """hevcdbk_h265_slice_offsets_device from host arrays: slice_idx (CTB rows, CTB columns) = index of the CTB's slice in
+        decoding order, slice_table (n_slices, 2) = (slice_beta_offset_div2, slice_tc_offset_div2) per slice; returns the pairs
+        (CTB rows, CTB columns, 2) as a host int8 array -- upload them and hand them on as
+        slice_offsets=SliceOffsets(ptr, stride, frame_stride, ctb_log2)."""
+        si = np.ascontiguousarray(slice_idx, np.uint16)
+        tb = np.ascontiguousarray(slice_table, np.int8)
+        if si.ndim != 2 or tb.ndim != 2 or tb.shape[1] != 2:
+            raise ValueError("slice_idx must be 2-D and slice_table (n_slices, 2)")
+        rows, cols = si.shape
+        bufs = [self.alloc(max(si.nbytes, 1)), self.alloc(max(tb.nbytes, 1))]
+        bufs[0].upload(si)
+        if tb.nbytes:
+            bufs[1].upload(tb)
+        out = self.alloc(max(2 * rows * cols, 1))
+        rc = _lib.lib().hevcdbk_h265_slice_offsets_device(self.handle, bufs[0].ptr, cols, bufs[1].ptr, tb.shape[0], cols, rows, out.ptr,
+                                                          cols, None)
+        _chk(rc, self.handle)
+        self.synchronize()
+        res = out.download(2 * rows * cols).view(np.int8).reshape(rows, cols, 2)
+        for b in bufs + [out]:
+            b.free()
+        return res
+
     def sao_device(self, planes, params_ptr, params_stride, ctb_log2, *, params_frame_stride=0, keep_ptr=None, keep_stride=0,
                    keep_frame_stride=0, chroma_format="420", ctb_log2_h=None, borders=None):
         """hevc_sao_filter_device[_cf]: H.265 8.7.3 on planes in HBM, src -> dst.  ctb_log2 = log2 of this plane's CTB width;
@@ -444,12 +473,19 @@ class Context:
     def deblock_sao_h265_device(self, planes, qp, params_ptr, params_stride, ctb_log2, *, c_idx=0, tc_offset_div2=0,
                                 beta_offset_div2=0, cb_qp_offset=0, cr_qp_offset=0, params_frame_stride=0, keep_ptr=None,
                                 keep_stride=0, keep_frame_stride=0, fused=_lib.FUSED_AUTO, chroma_format="420", ctb_log2_h=None,
-                                borders=None):
+                                borders=None, slice_offsets=None):
         """hevc_deblock_sao_h265_device[_cf]: spec-exact deblocking (8.7.2) followed by SAO (8.7.3), src -> dst; chroma_format,
-        ctb_log2 / ctb_log2_h and borders (hevcdbk_h265_deblock_sao_device_nox) as for sao_device."""
+        ctb_log2 / ctb_log2_h and borders (hevcdbk_h265_deblock_sao_device_nox) as for sao_device; slice_offsets as for
+        filter_device_h265 (hevcdbk_h265_deblock_sao_device_sl)."""
         cf = _lib.chroma_format_idc(chroma_format)
         lh = _ctb_log2_h(ctb_log2, ctb_log2_h, cf, c_idx != 0)
         prm = _lib.H265Params(tc_offset_div2, beta_offset_div2, cb_qp_offset, cr_qp_offset)
+        if slice_offsets is not None:
+            _chk(_lib.lib().hevcdbk_h265_deblock_sao_device_sl(self.handle, C.byref(planes), c_idx, cf, int(qp), C.byref(prm), params_ptr,
+                                                               params_stride, params_frame_stride, ctb_log2, lh, keep_ptr, keep_stride,
+                                                               keep_frame_stride, fused, None if borders is None else C.byref(borders),
+                                                               C.byref(slice_offsets), None), self.handle)
+            return
         if borders is not None:
             _chk(_lib.lib().hevcdbk_h265_deblock_sao_device_nox(self.handle, C.byref(planes), c_idx, cf, int(qp), C.byref(prm), params_ptr,
                                                                 params_stride, params_frame_stride, ctb_log2, lh, keep_ptr, keep_stride,
@@ -466,21 +502,24 @@ class Context:
         _chk(rc, self.handle)
 
     def deblock_sao_device_planes(self, planes_list, qp, sao_list, *, h265=None, fused=_lib.FUSED_AUTO, tc_table=None, beta_table=None,
-                                  chroma_format="420", borders=None):
+                                  chroma_format="420", borders=None, slice_offsets=None):
         """hevc_deblock_sao_device_planes / hevc_deblock_sao_h265_device_planes: deblocking + SAO of Y, U, V of a batch in one
         call (one launch where the fused kernel takes every plane).  sao_list[i] = (params_ptr, params_stride, ctb_log2) or a
         dict with the optional params_frame_stride / keep / keep_stride / keep_frame_stride; h265 = None (reference-exact
         deblocking) or a dict of tc_offset_div2, beta_offset_div2, cb_qp_offset, cr_qp_offset (spec-exact).  chroma_format
         (spec-exact mode only): '400' / '420' / '422' / '444'; ctb_log2 = log2 of the plane's CTB width, its height follows
         from the format (or a ctb_log2_h entry of the dict).  borders (spec-exact mode only): ONE _lib.SaoBorders for the
-        picture (hevcdbk_h265_deblock_sao_device_planes_nox)."""
+        picture (hevcdbk_h265_deblock_sao_device_planes_nox).  slice_offsets (spec-exact mode only): ONE _lib.SliceOffsets for the
+        picture (hevcdbk_h265_deblock_sao_device_planes_sl)."""
         cf = _lib.chroma_format_idc(chroma_format)
         if cf != _lib.CHROMA_420 and h265 is None:
             raise ValueError("the reference-exact mode is 4:2:0 only: chroma_format needs h265=")
         if borders is not None and h265 is None:
             raise ValueError("the reference-exact mode has no slice / tile boundaries: borders needs h265=")
+        if slice_offsets is not None and h265 is None:
+            raise ValueError("the reference-exact mode has no slices: slice_offsets needs h265=")
         arr = (_lib.DevicePlanes * len(planes_list))(*planes_list)
-        if borders is not None or cf != _lib.CHROMA_420 or any(isinstance(so, dict) and "ctb_log2_h" in so for so in sao_list):
+        if borders is not None or slice_offsets is not None or cf != _lib.CHROMA_420 or any(isinstance(so, dict) and "ctb_log2_h" in so for so in sao_list):
             spc = (_lib.SaoPlaneCf * len(sao_list))()
             for i, so in enumerate(sao_list):
                 d = so if isinstance(so, dict) else {"params": so[0], "params_stride": so[1], "ctb_log2": so[2]}
@@ -490,6 +529,11 @@ class Context:
                 spc[i].keep, spc[i].keep_stride, spc[i].keep_frame_stride = d.get("keep"), d.get("keep_stride", 0), d.get("keep_frame_stride", 0)
             prm = _lib.H265Params(h265.get("tc_offset_div2", 0), h265.get("beta_offset_div2", 0), h265.get("cb_qp_offset", 0),
                                   h265.get("cr_qp_offset", 0))
+            if slice_offsets is not None:
+                _chk(_lib.lib().hevcdbk_h265_deblock_sao_device_planes_sl(self.handle, arr, len(planes_list), cf, int(qp), C.byref(prm), spc,
+                                                                          fused, None if borders is None else C.byref(borders),
+                                                                          C.byref(slice_offsets), None), self.handle)
+                return
             if borders is not None:
                 _chk(_lib.lib().hevcdbk_h265_deblock_sao_device_planes_nox(self.handle, arr, len(planes_list), cf, int(qp), C.byref(prm), spc,
                                                                            fused, C.byref(borders), None), self.handle)

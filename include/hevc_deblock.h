@@ -640,6 +640,62 @@ HEVCDBK_API int hevcdbk_h265_deblock_sao_device_planes_nox(hevcdbk_context *ctx,
                                                            const hevcdbk_h265_params *h265_params, const hevcdbk_sao_plane_cf *sao,
                                                            int fused, const hevcdbk_sao_borders *borders, void *hip_stream);
 
+/* ==================================================================================================================
+ * Per-slice deblocking offsets (ITU-T H.265 8.7.2.5.3 luma, 8.7.2.5.5 chroma).
+ *
+ * With deblocking_filter_override_enabled_flag a stream may set slice_beta_offset_div2 / slice_tc_offset_div2 in every slice, and
+ * the standard takes both from the slice that holds sample q0,0 of each edge segment.  hevcdbk_h265_params carries one pair per
+ * call; this operand carries one pair per CTB.  Rule: for every edge segment, luma and chroma, the beta and tC indices use the pair
+ * of the CTB that holds the segment's q0,0; for a chroma plane that CTB is found at luma position (x * SubWidthC, y *
+ * SubHeightC); chroma uses the tC offset only.  Slices are made of whole CTBs of at least 16 samples and edges lie on the 8-sample
+ * grid, so one pair per CTB is exact.  With the operand present, tc_offset_div2 and beta_offset_div2 of hevcdbk_h265_params are
+ * NOT USED (they are still range-checked); its cb_qp_offset / cr_qp_offset (cQpPicOffset) stay per call.  Values outside -6..6
+ * are the caller's error: the indices are clipped as the standard clips them (0..51 and 0..53), so nothing is read out of range.
+ * slice_deblocking_filter_disabled_flag goes through HEVCDBK_U_DBK_OFF, and slice_cb_qp_offset never enters deblocking.
+ * Parity: against a composition of uniform-offset runs of the oracles in tests/ ("parity unpinned").
+ * ================================================================================================================== */
+typedef struct hevcdbk_h265_slice_offsets {  /* DEVICE memory; the LUMA CTB grid serves every plane of the picture */
+    const int8_t *offs;    /* offs[2*(cy*stride+cx)] = slice_beta_offset_div2, [.. + 1] = slice_tc_offset_div2 of the slice holding the CTB;
+                              2-byte aligned (a pair is read as one 16-bit word) */
+    unsigned stride;       /* CTBs per row of the array, >= the picture's CTB columns */
+    size_t frame_stride;   /* bytes between the frames of a batch, 0 = shared; a multiple of 2 */
+    unsigned ctb_log2;     /* CtbLog2SizeY, 4..6 */
+} hevcdbk_h265_slice_offsets;
+
+/*
+ * The pairs from what a decoder holds (DEVICE arrays): slice_idx = index of the CTB's slice in decoding order, one uint16_t per
+ * CTB, row stride in_stride entries -- the array hevcdbk_h265_sao_borders_device takes; slice_table = int8_t[n_slices][2], beta
+ * then tC.  A slice_idx >= n_slices yields (0, 0).  One small launch, asynchronous like its siblings; callers that already hold
+ * the pairs skip it.  offs: 2 * offs_stride bytes per CTB row, 2-byte aligned.
+ */
+HEVCDBK_API int hevcdbk_h265_slice_offsets_device(hevcdbk_context *ctx, const uint16_t *slice_idx, unsigned in_stride,
+                                                  const int8_t *slice_table, unsigned n_slices, unsigned ctbs_x, unsigned ctbs_y,
+                                                  int8_t *offs, unsigned offs_stride, void *hip_stream);
+/*
+ * The _cf / _nox entries with the operand appended.  slice_offsets == NULL is the existing entry itself: the same kernels, grids
+ * and blocks.  A non-NULL operand with offs == NULL (or misaligned), stride below the picture's CTB columns or ctb_log2 outside
+ * 4..6 returns HEVCDBK_ERR_ARG before anything is enqueued.  With the operand every kernel family runs as its _sl twin -- the 32-bit
+ * kernel, the packed kernels (8-bit and 16-bit containers) and the fused deblocking + SAO kernels, single plane and Y + Cb + Cr in
+ * one launch -- for every chroma format, with one QP or a QP map, on the operands the family takes without it: kernel_variant and
+ * `fused` mean what they mean there, and HEVCDBK_ERR_UNSUPPORTED comes back exactly where the entry without the operand returns
+ * it.  The twins always run the per-lane (QP-map) form, a one-QP call with a constant qPL; no dummy map is needed.  `borders` of
+ * the two deblocking + SAO entries may be NULL.  The planes entry takes ONE operand for the picture.  The host-frame operators
+ * (hevc_deblocking_filter_h265, hevcdbk_h265_filter_frame_cf) and the reference-exact mode take no per-slice offsets.
+ */
+HEVCDBK_API int hevcdbk_h265_filter_device_sl(hevcdbk_context *ctx, const hevcdbk_device_planes *planes, int c_idx, int chroma_format_idc,
+                                              unsigned qp, const hevcdbk_h265_params *params, int kernel_variant,
+                                              const hevcdbk_h265_slice_offsets *slice_offsets, void *hip_stream);
+HEVCDBK_API int hevcdbk_h265_deblock_sao_device_sl(hevcdbk_context *ctx, const hevcdbk_device_planes *planes, int c_idx,
+                                                   int chroma_format_idc, unsigned qp, const hevcdbk_h265_params *h265_params,
+                                                   const hevcdbk_sao_ctb *params, unsigned params_stride, size_t params_frame_stride,
+                                                   unsigned ctb_log2_w, unsigned ctb_log2_h, const uint8_t *keep, unsigned keep_stride,
+                                                   size_t keep_frame_stride, int fused, const hevcdbk_sao_borders *borders,
+                                                   const hevcdbk_h265_slice_offsets *slice_offsets, void *hip_stream);
+HEVCDBK_API int hevcdbk_h265_deblock_sao_device_planes_sl(hevcdbk_context *ctx, const hevcdbk_device_planes *planes, unsigned n_planes,
+                                                          int chroma_format_idc, unsigned qp, const hevcdbk_h265_params *h265_params,
+                                                          const hevcdbk_sao_plane_cf *sao, int fused, const hevcdbk_sao_borders *borders,
+                                                          const hevcdbk_h265_slice_offsets *slice_offsets, void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -26,10 +26,16 @@ def main():
     ap.add_argument("--borders", choices=["none", "zero", "decoder", "every-ctb"], default=None,
                     help="--mode h265: slice / tile boundaries SAO must not look across (the _nox entries; tools/sao_border_layouts.py): the fused "
                          "call without the operand, with this layout and without it again take turns in this one process on the same buffers")
-    ap.add_argument("--rounds", type=int, default=3, help="--borders: rounds of turns; the median of each variant is reported")
+    ap.add_argument("--slice-offsets", action="store_true",
+                    help="--mode h265: per-slice deblocking offsets (the _sl entries, CtbSizeY 64): the fused call without the operand, with one pair "
+                         "everywhere, with a slice every 8 CTB rows with differing pairs, and without it again take turns in this one process; "
+                         "with --borders every one of the four carries that layout (the _nox kernels are then the yardstick)")
+    ap.add_argument("--rounds", type=int, default=3, help="--borders / --slice-offsets: rounds of turns; the median of each variant is reported")
     a = ap.parse_args()
     if a.borders is not None and a.mode != "h265":
         ap.error("--borders needs --mode h265 (the reference-exact mode has no slices or tiles)")
+    if a.slice_offsets and a.mode != "h265":
+        ap.error("--slice-offsets needs --mode h265")
     if a.chroma_format and a.mode != "h265":
         ap.error("--chroma-format needs --mode h265 (the reference-exact mode is 4:2:0 only)")
     if a.diag is not None:
@@ -65,16 +71,17 @@ def main():
         yuv, sao, nbytes, _keep = bench_rext.setup(ctx, a.chroma_format, w, h, n, 8, np.random.RandomState(5))
         h265 = {"tc_offset_div2": 0, "beta_offset_div2": 0, "cb_qp_offset": 0, "cr_qp_offset": 0}
 
-    def call(fused, borders=None):
+    def call(fused, borders=None, slice_offsets=None):
         if a.chroma_format:
-            ctx.deblock_sao_device_planes(yuv, a.qp, sao, h265=h265, fused=fused, chroma_format=a.chroma_format, borders=borders)
+            ctx.deblock_sao_device_planes(yuv, a.qp, sao, h265=h265, fused=fused, chroma_format=a.chroma_format, borders=borders,
+                                          slice_offsets=slice_offsets)
         elif a.mode == "ref":
             ctx.deblock_sao_device(p, a.qp, dp.ptr, cols, 6, fused=fused)
         else:
-            ctx.deblock_sao_h265_device(p, a.qp, dp.ptr, cols, 6, fused=fused, borders=borders)
+            ctx.deblock_sao_h265_device(p, a.qp, dp.ptr, cols, 6, fused=fused, borders=borders, slice_offsets=slice_offsets)
 
     what = "luma" if not a.chroma_format else "Y+Cb+Cr %s" % a.chroma_format
-    if a.borders is not None:  # none / the layout / none again, taking turns; `spread` = the distance between the two runs without the operand
+    if a.borders is not None and not a.slice_offsets:  # none / the layout / none again, taking turns; `spread` = the distance between the two runs without the operand
         sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
         import sao_border_layouts as sbl
         bo, _buf, share = sbl.device_borders(ctx, a.borders, rows, cols)
@@ -97,6 +104,36 @@ def main():
         print(json.dumps({"stage": "deblock+sao", "mode": a.mode, "borders": a.borders, "masked_region_share": share, "ms": med, "rounds_ms": ms,
                           "spread_ms": abs(med["none"] - med["none_again"]),
                           "frac_of_8TBps_read_once_write_once": {k: nbytes / (v * 1e-3) / 8e12 for k, v in med.items()},
+                          "workload": "%dx%d %d-bit %s x %d, QP %d, CTB types: %s" % (w, h, a.bit_depth, what, n, a.qp, a.types)}))
+        return
+
+    if a.slice_offsets:  # none / uniform / decoder / none again, taking turns (as --borders)
+        sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+        import bench_h265
+        ops = bench_h265.slice_offset_operands(ctx, rows, cols)
+        bo = None
+        if a.borders is not None:
+            import sao_border_layouts as sbl
+            bo, _buf, _share = sbl.device_borders(ctx, a.borders, rows, cols)
+        variants = [("none", None), ("uniform", ops["uniform"]), ("decoder", ops["decoder"]), ("none_again", None)]
+        ms = {k: [] for k, _ in variants}
+        for _ in range(300):  # settle the clocks
+            call(_lib.FUSED_ON)
+        ctx.synchronize()
+        for _ in range(a.rounds):
+            for k, so in variants:
+                for _ in range(20):
+                    call(_lib.FUSED_ON, bo, so)
+                ctx.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(a.steps):
+                    call(_lib.FUSED_ON, bo, so)
+                ctx.synchronize()
+                ms[k].append((time.perf_counter() - t0) / a.steps * 1e3)
+        med = {k: float(np.median(v)) for k, v in ms.items()}
+        print(json.dumps({"stage": "deblock+sao", "mode": a.mode, "slice_offsets": True, "borders": a.borders, "ms": med, "rounds_ms": ms,
+                          "spread_ms": abs(med["none"] - med["none_again"]),
+                          "ratio_to_none": {k: med[k] / med["none"] for k in ("uniform", "decoder", "none_again")},
                           "workload": "%dx%d %d-bit %s x %d, QP %d, CTB types: %s" % (w, h, a.bit_depth, what, n, a.qp, a.types)}))
         return
 

@@ -40,6 +40,11 @@ def functions(path):
             t = ln.split("//")[0].strip()
             if t:
                 out[func].append(t)
+    # objdump marks a run of zero bytes with "...": as the LAST line of a function that is the padding behind it, which depends on what
+    # the linker places next, and is dropped; anywhere else it stays and is compared
+    for ins in out.values():
+        while ins and ins[-1] == "...":
+            ins.pop()
     return {f: relabel(ins) for f, ins in out.items()}
 
 
