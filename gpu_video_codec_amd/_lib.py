@@ -47,6 +47,8 @@ EXPORTS = [
     "hevcdbk_h265_deblock_sao_device_planes_nox",
     "hevcdbk_h265_slice_offsets_device", "hevcdbk_h265_filter_device_sl", "hevcdbk_h265_deblock_sao_device_sl",
     "hevcdbk_h265_deblock_sao_device_planes_sl",
+    "hevcdbk_h265_derive_bs_device_g4", "hevcdbk_h265_filter_device_g4", "hevcdbk_sao_filter_device_g4",
+    "hevcdbk_h265_deblock_sao_device_g4", "hevcdbk_h265_deblock_sao_device_planes_g4",
 ]
 
 # chroma_format_idc of the spec-exact mode and SAO (HEVCDBK_CHROMA_*): 4:0:0, 4:2:0, 4:2:2, 4:4:4
@@ -291,6 +293,12 @@ def lib():
         L.hevcdbk_h265_deblock_sao_device_planes_sl.argtypes = [C.c_void_p, C.POINTER(DevicePlanes), C.c_uint, C.c_int, C.c_uint,
                                                                 C.POINTER(H265Params), C.POINTER(SaoPlaneCf), C.c_int,
                                                                 C.POINTER(SaoBorders), C.POINTER(SliceOffsets), C.c_void_p]
+        # the _g4 entries (planes sized in multiples of 4): the signatures of the entries they extend
+        L.hevcdbk_h265_derive_bs_device_g4.argtypes = L.hevcdbk_h265_derive_bs_device_cf.argtypes
+        L.hevcdbk_h265_filter_device_g4.argtypes = L.hevcdbk_h265_filter_device_sl.argtypes
+        L.hevcdbk_sao_filter_device_g4.argtypes = L.hevcdbk_sao_filter_device_nox.argtypes
+        L.hevcdbk_h265_deblock_sao_device_g4.argtypes = L.hevcdbk_h265_deblock_sao_device_sl.argtypes
+        L.hevcdbk_h265_deblock_sao_device_planes_g4.argtypes = L.hevcdbk_h265_deblock_sao_device_planes_sl.argtypes
         L.hevc_deblock_sao_h265_device_planes.argtypes = [C.c_void_p, C.POINTER(DevicePlanes), C.c_uint, C.c_uint, C.POINTER(H265Params),
                                                           C.POINTER(SaoPlane), C.c_int, C.c_void_p]
         L.hevcdbk_set_host_threads.argtypes = [C.c_void_p, C.c_uint]

@@ -227,6 +227,26 @@ DBK_HD void load_block_bs_h265(const uint8_t *vert, const uint8_t *hor, int bx, 
     entry[3] = (hedge && bx < nbx - 1) ? hor[by * hstride + 2 * bx] : 0;
 }
 
+/*
+ * The same for a plane whose width and height are multiples of 4 (the _g4 entries: the chroma planes of a 1920x1080 4:2:0 picture
+ * are 960x540).  The arrays keep their layouts with floor division and nbx = plane_w/8 + 1, nby = plane_h/8 + 1 as before, but the
+ * last block of a row (bx = plane_w/8) of a plane 8k+4 samples wide has its right half INSIDE the picture and its vertical edge
+ * x = 8k is an ordinary edge.  So "this half is inside" and "this edge is not the picture boundary" are statements about the plane
+ * size: 8 bx < plane_w, 8 by < plane_h.  For multiples of 8 they say what bx < nbx - 1, by < nby - 1 say above.
+ */
+DBK_HD bool g4_right_in(int bx, int plane_w) { return 8 * bx < plane_w; }  /* columns 4..7 of block bx inside the picture */
+DBK_HD bool g4_below_in(int by, int plane_h) { return 8 * by < plane_h; }  /* rows 4..7 of block by inside the picture */
+DBK_HD void load_block_bs_h265_g4(const uint8_t *vert, const uint8_t *hor, int bx, int by, int plane_w, int plane_h, int vstride,
+                                  int hstride, int (&entry)[4])
+{
+    const bool rin = g4_right_in(bx, plane_w), bin = g4_below_in(by, plane_h);
+    const bool vedge = bx > 0 && rin, hedge = by > 0 && bin;
+    entry[0] = (vedge && by > 0) ? vert[(2 * by - 1) * vstride + bx] : 0;
+    entry[1] = (vedge && bin) ? vert[(2 * by) * vstride + bx] : 0;
+    entry[2] = (hedge && bx > 0) ? hor[by * hstride + 2 * bx - 1] : 0;
+    entry[3] = (hedge && rin) ? hor[by * hstride + 2 * bx] : 0;
+}
+
 /* qPL = (QpQ + QpP + 1) >> 1 of the four segments of the block whose (0,0) is plane sample (x0, y0): QpY of the coding
  * units holding q0,0 / p0,0 of line 0 (8.7.2.5.3); chroma positions are doubled (sc = 2).  map == NULL: scalar qp. */
 DBK_HD void h265_block_qpl(const uint8_t *map, int map_stride, int unit_log2, int sc, int lw, int lh, int x0, int y0, int qp,

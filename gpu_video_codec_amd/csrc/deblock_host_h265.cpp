@@ -62,7 +62,33 @@ namespace {
 inline unsigned sub_w(int cf) { return cf == HEVCDBK_CHROMA_444 ? 1u : 2u; }
 inline unsigned sub_h(int cf) { return cf == HEVCDBK_CHROMA_420 ? 2u : 1u; }
 
-int h265_args(const hevcdbk_device_planes *planes, int c_idx, unsigned qp, const hevcdbk_h265_params *prm, DbkH265Args &h)
+/* a plane size: 0 = multiples of 8 (what every entry takes), 1 = multiples of 4 and at least 8 with one of them not a multiple of 8
+ * (a "g4 plane": the _g4 entries), -1 = anything else */
+int g4_kind(unsigned w, unsigned h)
+{
+    if (w < 8 || h < 8 || w % 4 != 0 || h % 4 != 0) return -1;
+    return (w % 8 != 0 || h % 8 != 0) ? 1 : 0;
+}
+
+/* planes_to_args for the _g4 entries: a g4 plane passes every check planes_to_args makes of a plane -- on its size rounded down to
+ * multiples of 8, which is still a plane -- and then gets its own geometry: the block counts and the vertical array's stride are
+ * plane / 8 + 1 with floor division, as for every plane */
+int planes_to_args_g4(const hevcdbk_device_planes *p, unsigned qp, DbkArgs &a)
+{
+    if (!p || g4_kind(p->plane_w, p->plane_h) != 1) return planes_to_args(p, qp, nullptr, a);
+    hevcdbk_device_planes q = *p;
+    q.plane_w = p->plane_w & ~7u;
+    q.plane_h = p->plane_h & ~7u;
+    if (int rc = planes_to_args(&q, qp, nullptr, a)) return rc;
+    if (p->pitch < (size_t)p->plane_w * p->sample_bytes) return HEVCDBK_ERR_ARG;
+    a.plane_w = (int)p->plane_w;
+    a.plane_h = (int)p->plane_h;
+    a.nbx = a.vstride = (int)(p->plane_w / 8 + 1);
+    a.nby = (int)(p->plane_h / 8 + 1);
+    return HEVCDBK_OK;
+}
+
+int h265_args(const hevcdbk_device_planes *planes, int c_idx, unsigned qp, const hevcdbk_h265_params *prm, DbkH265Args &h, bool g4 = false)
 {
     if (!planes || c_idx < 0 || c_idx > 2 || (c_idx != 0) != (planes->is_chroma != 0)) return HEVCDBK_ERR_ARG;
     const hevcdbk_h265_params zero = {0, 0, 0, 0};
@@ -71,7 +97,8 @@ int h265_args(const hevcdbk_device_planes *planes, int c_idx, unsigned qp, const
         prm->cb_qp_offset < -12 || prm->cb_qp_offset > 12 || prm->cr_qp_offset < -12 || prm->cr_qp_offset > 12)
         return HEVCDBK_ERR_ARG;
     if (planes->qp_map && (planes->ctu_log2 < 3 || planes->ctu_log2 > 8)) return HEVCDBK_ERR_ARG;
-    if (int rc = planes_to_args(planes, qp, nullptr, h.base)) return rc;
+    if (int rc = g4 ? planes_to_args_g4(planes, qp, h.base) : planes_to_args(planes, qp, nullptr, h.base)) return rc;
+    if (g4 && c_idx == 0 && g4_kind(planes->plane_w, planes->plane_h) != 0) return HEVCDBK_ERR_DIMENSIONS; /* HEVC has no such luma plane */
     h.base.hstride = (int)(planes->plane_w / 4);
     h.base.n_vert = (int)hevcdbk_h265_num_vert_bs(planes->plane_w, planes->plane_h);
     h.base.n_hor = (int)hevcdbk_h265_num_hor_bs(planes->plane_w, planes->plane_h);
@@ -83,11 +110,12 @@ int h265_args(const hevcdbk_device_planes *planes, int c_idx, unsigned qp, const
 }
 
 /* h265_args with the picture's chroma format: 4:0:0 has no chroma plane */
-int h265_args_cf(const hevcdbk_device_planes *planes, int c_idx, int cf, unsigned qp, const hevcdbk_h265_params *prm, DbkH265Args &h)
+int h265_args_cf(const hevcdbk_device_planes *planes, int c_idx, int cf, unsigned qp, const hevcdbk_h265_params *prm, DbkH265Args &h,
+                 bool g4 = false)
 {
     if (cf < HEVCDBK_CHROMA_400 || cf > HEVCDBK_CHROMA_444) return HEVCDBK_ERR_ARG;
     if (cf == HEVCDBK_CHROMA_400 && (c_idx != 0 || (planes && planes->is_chroma))) return HEVCDBK_ERR_ARG;
-    return h265_args(planes, c_idx, qp, prm, h);
+    return h265_args(planes, c_idx, qp, prm, h, g4);
 }
 
 /* cf = chroma_format_idc of a chroma plane (1 for luma: the format does not enter luma) */
@@ -291,15 +319,18 @@ static_assert(sizeof(hevcdbk_sao_ctb) == sizeof(DbkSaoCtb) && sizeof(DbkSaoCtb) 
 namespace {
 
 /* validates the SAO operands of `p` and fills `a` (src / dst as in `p`) */
+/* g4 (the _g4 entries): sizes that are multiples of 4 and at least 8; the keep map by ceiling, its last byte of a row / column
+ * speaking for 4 samples */
 int sao_args(const hevcdbk_device_planes *p, const hevcdbk_sao_ctb *params, unsigned params_stride, size_t params_frame_stride,
-             unsigned ctb_log2, const uint8_t *keep, unsigned keep_stride, size_t keep_frame_stride, DbkSaoArgs &a)
+             unsigned ctb_log2, const uint8_t *keep, unsigned keep_stride, size_t keep_frame_stride, DbkSaoArgs &a, bool g4 = false)
 {
     if (!p || !p->src || !p->dst || p->src == p->dst || !params) return HEVCDBK_ERR_ARG;
     if (bad_depth(p->bit_depth, p->sample_bytes)) return HEVCDBK_ERR_ARG;
-    if (p->plane_w == 0 || p->plane_h == 0 || p->plane_w % 8 != 0 || p->plane_h % 8 != 0) return HEVCDBK_ERR_DIMENSIONS;
+    if (g4 ? g4_kind(p->plane_w, p->plane_h) < 0 : (p->plane_w == 0 || p->plane_h == 0 || p->plane_w % 8 != 0 || p->plane_h % 8 != 0))
+        return HEVCDBK_ERR_DIMENSIONS;
     if (ctb_log2 < 3 || ctb_log2 > 6) return HEVCDBK_ERR_ARG;
     if (params_stride < ((p->plane_w + (1u << ctb_log2) - 1) >> ctb_log2)) return HEVCDBK_ERR_ARG;
-    if (keep && keep_stride < p->plane_w / 8) return HEVCDBK_ERR_ARG;
+    if (keep && keep_stride < (p->plane_w + 7) / 8) return HEVCDBK_ERR_ARG;
     const size_t align = 4 * p->sample_bytes;
     if (p->pitch % align != 0 || p->frame_stride % align != 0 || (uintptr_t)p->src % align != 0 || (uintptr_t)p->dst % align != 0)
         return HEVCDBK_ERR_UNSUPPORTED;
@@ -319,11 +350,11 @@ int sao_args(const hevcdbk_device_planes *p, const hevcdbk_sao_ctb *params, unsi
 /* sao_args for CTBs of (1 << ctb_log2_w) x (1 << ctb_log2_h) samples: square, or twice as tall as wide (4:2:2 chroma) */
 int sao_args_cf(const hevcdbk_device_planes *p, const hevcdbk_sao_ctb *params, unsigned params_stride, size_t params_frame_stride,
                 unsigned ctb_log2_w, unsigned ctb_log2_h, const uint8_t *keep, unsigned keep_stride, size_t keep_frame_stride,
-                DbkSaoArgs &a)
+                DbkSaoArgs &a, bool g4 = false)
 {
     if (ctb_log2_h != ctb_log2_w && ctb_log2_h != ctb_log2_w + 1) return HEVCDBK_ERR_ARG;
     if (ctb_log2_h < 3 || ctb_log2_h > 6) return HEVCDBK_ERR_ARG;
-    return sao_args(p, params, params_stride, params_frame_stride, ctb_log2_w, keep, keep_stride, keep_frame_stride, a);
+    return sao_args(p, params, params_stride, params_frame_stride, ctb_log2_w, keep, keep_stride, keep_frame_stride, a, g4);
 }
 
 /* the two-launch form of deblocking + SAO: the deblocked planes go through ctx->dev_tmp (same pitch and frame stride).
@@ -924,6 +955,232 @@ int hevcdbk_h265_deblock_sao_device_planes_sl(hevcdbk_context *ctx, const hevcdb
     }
     for (unsigned i = 0; !one && i < n_planes && rc == HEVCDBK_OK; i++)
         rc = deblock_sao_plane_h265_sl(ctx, &planes[i], (int)i, cf, qp, prm, h[i], sa[i], sl[i], fused, s, nxp ? &nxp[i] : nullptr);
+    if (rect)
+        if (int rc2 = sao_done(ctx, s)) return rc ? rc : rc2;
+    return rc;
+}
+
+/* ---- planes whose sizes are multiples of 4, not 8: the chroma planes of 1920x1080 (960x540), 640x360, ... (the _g4 entries) ------- */
+
+namespace {
+
+/* "no per-slice offsets" for the _g4 kernels: an array of no bytes, every pair of which reads (0, 0) */
+const DbkSlOffs kNoSlOffs = {nullptr, 0, 0, 4, 0u};
+
+/* the operand of a _g4 launch: the caller's array -- then the call's own pair, which the kernels add, is zero (8.7.2.5.3: the pair is
+ * the slice's) -- or none */
+int sl_args_g4(const hevcdbk_h265_slice_offsets *so, const hevcdbk_device_planes *p, int c_idx, int cf, DbkH265Args &h, DbkSlOffs &sl)
+{
+    if (!so) {
+        sl = kNoSlOffs;
+        return HEVCDBK_OK;
+    }
+    if (int rc = sl_args(so, p, c_idx, cf, sl)) return rc;
+    h.tc_off = h.beta_off = 0;
+    return HEVCDBK_OK;
+}
+
+/* the deblocking launch of a g4 chroma plane: the families of launch_h265_sl, each one's _g4 twin */
+int launch_h265_g4(hevcdbk_context *ctx, const DbkH265Args &h0, const DbkSlOffs &sl, int sample_bytes, int cf, int variant, hipStream_t s)
+{
+    const int map = variant & HEVCDBK_MAP_MASK;
+    variant &= ~HEVCDBK_MAP_MASK;
+    DbkH265Args h = h0;
+    h.base.map_override = map == HEVCDBK_MAP_ROWS ? 1 : (map == HEVCDBK_MAP_LINEAR ? 2 : 0);
+    const bool pack = dbk_packed_h265_supports(h, sample_bytes, true);
+    if (variant == HEVCDBK_KERNEL_PACKED && !pack) return HEVCDBK_ERR_UNSUPPORTED;
+    hipError_t e;
+    if (variant != HEVCDBK_KERNEL_GENERIC && pack) e = dbk_launch_packed_h265_g4(h, sl, sample_bytes, cf, s);
+    else e = dbk_launch_h265_g4(h, sl, sample_bytes, cf, s);
+    return hip_ok(ctx, e, "kernel launch") ? HEVCDBK_OK : HEVCDBK_ERR_HIP;
+}
+
+/* deblocking + SAO of one g4 chroma plane: deblock_sao_plane_h265_sl with the _g4 kernels (square CTBs: after sao_square_params) */
+int deblock_sao_plane_h265_g4(hevcdbk_context *ctx, const hevcdbk_device_planes *p, int c_idx, int cf, unsigned qp,
+                              const hevcdbk_h265_params *prm, DbkH265Args &h, DbkSaoArgs &sa, const DbkSlOffs &sl, int fused, hipStream_t s,
+                              const DbkSaoNox *nx)
+{
+    const bool can = fused_can(h, sa, p, c_idx);
+    if (fused == HEVCDBK_FUSED_ON && !can) return HEVCDBK_ERR_UNSUPPORTED;
+    if (can && fused != HEVCDBK_FUSED_OFF)
+        return hip_ok(ctx, dbk_launch_deblock_sao_h265_g4(h, sa, sl, (int)p->sample_bytes, cf, s, nx), "fused deblocking + SAO launch")
+                   ? HEVCDBK_OK : HEVCDBK_ERR_HIP;
+    hevcdbk_device_planes first, second;
+    if (int rc = tmp_planes(ctx, p, s, first, second)) return rc;
+    const int tc_off = h.tc_off, beta_off = h.beta_off; /* zero with per-slice offsets (sl_args_g4) */
+    if (int rc = h265_args(&first, c_idx, qp, prm, h, true)) return rc;
+    h.tc_off = tc_off;
+    h.beta_off = beta_off;
+    if (int rc = launch_h265_g4(ctx, h, sl, (int)p->sample_bytes, cf, HEVCDBK_KERNEL_AUTO, s)) return rc;
+    sa.src = (const uint8_t *)second.src;
+    if (!hip_ok(ctx, dbk_launch_sao_g4(sa, (int)p->sample_bytes, s, nx), "SAO launch")) return HEVCDBK_ERR_HIP;
+    return tmp_done(ctx, s);
+}
+
+} /* namespace */
+
+int hevcdbk_h265_derive_bs_device_g4(hevcdbk_context *ctx, const hevcdbk_h265_units *u, unsigned width, unsigned height,
+                                     int chroma_format_idc, uint8_t *vert_bs4, uint8_t *hor_bs4, uint8_t *chroma_vert_bs4,
+                                     uint8_t *chroma_hor_bs4, void *hip_stream)
+{
+    const int cf = chroma_format_idc;
+    if (!ctx || !u || !u->flags || !u->mv0 || !u->mv1 || !u->ref0 || !u->ref1 || !vert_bs4 || !hor_bs4) return HEVCDBK_ERR_ARG;
+    if (cf < HEVCDBK_CHROMA_400 || cf > HEVCDBK_CHROMA_444) return HEVCDBK_ERR_ARG;
+    if ((chroma_vert_bs4 != nullptr) != (chroma_hor_bs4 != nullptr)) return HEVCDBK_ERR_ARG;
+    if (cf == HEVCDBK_CHROMA_400 && chroma_vert_bs4) return HEVCDBK_ERR_ARG;
+    if (width == 0 || height == 0 || width % 8 != 0 || height % 8 != 0) return HEVCDBK_ERR_DIMENSIONS;
+    /* the chroma planes of a picture of multiples of 8 are multiples of 4 in every format: what is left to ask is "at least 8" */
+    if (chroma_vert_bs4 && g4_kind(width / sub_w(cf), height / sub_h(cf)) < 0) return HEVCDBK_ERR_DIMENSIONS;
+    if (int rc = bind(ctx)) return rc;
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->compute;
+    hipError_t e;
+    if (cf == HEVCDBK_CHROMA_420) { /* the launches of hevcdbk_h265_derive_bs_device: the gathers divide with floor */
+        e = dbk_launch_h265_bs(u->flags, u->mv0, u->mv1, u->ref0, u->ref1, (int)width, (int)height, vert_bs4, hor_bs4, chroma_vert_bs4,
+                               chroma_hor_bs4, s);
+    } else {
+        e = dbk_launch_h265_bs(u->flags, u->mv0, u->mv1, u->ref0, u->ref1, (int)width, (int)height, vert_bs4, hor_bs4, nullptr, nullptr, s);
+        if (e == hipSuccess && chroma_vert_bs4)
+            e = dbk_launch_h265_chroma_bs_cf(vert_bs4, hor_bs4, (int)width, (int)height, cf, chroma_vert_bs4, chroma_hor_bs4, s);
+    }
+    return hip_ok(ctx, e, "bS derivation launch") ? HEVCDBK_OK : HEVCDBK_ERR_HIP;
+}
+
+int hevcdbk_h265_filter_device_g4(hevcdbk_context *ctx, const hevcdbk_device_planes *planes, int c_idx, int chroma_format_idc, unsigned qp,
+                                  const hevcdbk_h265_params *params, int kernel_variant, const hevcdbk_h265_slice_offsets *slice_offsets,
+                                  void *hip_stream)
+{
+    if (!planes || g4_kind(planes->plane_w, planes->plane_h) != 1) /* multiples of 8, or no plane at all: the entry this one extends */
+        return hevcdbk_h265_filter_device_sl(ctx, planes, c_idx, chroma_format_idc, qp, params, kernel_variant, slice_offsets, hip_stream);
+    if (!ctx) return HEVCDBK_ERR_ARG;
+    DbkH265Args h;
+    if (int rc = h265_args_cf(planes, c_idx, chroma_format_idc, qp, params, h, true)) return rc;
+    DbkSlOffs sl;
+    if (int rc = sl_args_g4(slice_offsets, planes, c_idx, chroma_format_idc, h, sl)) return rc;
+    if (int rc = check_variant_sl(h, (int)planes->sample_bytes, c_idx, kernel_variant)) return rc;
+    if (int rc = bind(ctx)) return rc;
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->compute;
+    return launch_h265_g4(ctx, h, sl, (int)planes->sample_bytes, chroma_format_idc, kernel_variant, s);
+}
+
+int hevcdbk_sao_filter_device_g4(hevcdbk_context *ctx, const hevcdbk_device_planes *p, const hevcdbk_sao_ctb *params,
+                                 unsigned params_stride, size_t params_frame_stride, unsigned ctb_log2_w, unsigned ctb_log2_h,
+                                 const uint8_t *keep, unsigned keep_stride, size_t keep_frame_stride,
+                                 const hevcdbk_sao_borders *borders, void *hip_stream)
+{
+    if (!p || g4_kind(p->plane_w, p->plane_h) != 1)
+        return hevcdbk_sao_filter_device_nox(ctx, p, params, params_stride, params_frame_stride, ctb_log2_w, ctb_log2_h, keep, keep_stride,
+                                             keep_frame_stride, borders, hip_stream);
+    if (!ctx) return HEVCDBK_ERR_ARG;
+    DbkSaoArgs a;
+    if (int rc = sao_args_cf(p, params, params_stride, params_frame_stride, ctb_log2_w, ctb_log2_h, keep, keep_stride, keep_frame_stride, a, true))
+        return rc;
+    DbkSaoNox nx, *nxp = nullptr;
+    if (borders) {
+        if (int rc = nox_args(borders, a, nx)) return rc;
+        nxp = &nx;
+    }
+    if (int rc = bind(ctx)) return rc;
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->compute;
+    if (int rc = sao_square_params(ctx, &a, &ctb_log2_h, 1, s, nxp)) return rc;
+    if (!hip_ok(ctx, dbk_launch_sao_g4(a, (int)p->sample_bytes, s, nxp), "SAO launch")) return HEVCDBK_ERR_HIP;
+    return ctb_log2_h != ctb_log2_w ? sao_done(ctx, s) : HEVCDBK_OK;
+}
+
+int hevcdbk_h265_deblock_sao_device_g4(hevcdbk_context *ctx, const hevcdbk_device_planes *p, int c_idx, int chroma_format_idc, unsigned qp,
+                                       const hevcdbk_h265_params *prm, const hevcdbk_sao_ctb *params, unsigned params_stride,
+                                       size_t params_frame_stride, unsigned ctb_log2_w, unsigned ctb_log2_h, const uint8_t *keep,
+                                       unsigned keep_stride, size_t keep_frame_stride, int fused, const hevcdbk_sao_borders *borders,
+                                       const hevcdbk_h265_slice_offsets *slice_offsets, void *hip_stream)
+{
+    if (!p || g4_kind(p->plane_w, p->plane_h) != 1)
+        return hevcdbk_h265_deblock_sao_device_sl(ctx, p, c_idx, chroma_format_idc, qp, prm, params, params_stride, params_frame_stride,
+                                                  ctb_log2_w, ctb_log2_h, keep, keep_stride, keep_frame_stride, fused, borders, slice_offsets,
+                                                  hip_stream);
+    if (!ctx || (fused != HEVCDBK_FUSED_AUTO && fused != HEVCDBK_FUSED_OFF && fused != HEVCDBK_FUSED_ON)) return HEVCDBK_ERR_ARG;
+    DbkSaoArgs sa;
+    if (int rc = sao_args_cf(p, params, params_stride, params_frame_stride, ctb_log2_w, ctb_log2_h, keep, keep_stride, keep_frame_stride, sa, true))
+        return rc;
+    DbkH265Args h;
+    if (int rc = h265_args_cf(p, c_idx, chroma_format_idc, qp, prm, h, true)) return rc;
+    DbkSaoNox nx, *nxp = nullptr;
+    if (borders) {
+        if (int rc = nox_args(borders, sa, nx)) return rc;
+        nxp = &nx;
+    }
+    DbkSlOffs sl;
+    if (int rc = sl_args_g4(slice_offsets, p, c_idx, chroma_format_idc, h, sl)) return rc;
+    if (fused == HEVCDBK_FUSED_ON && !fused_can(h, sa, p, c_idx)) return HEVCDBK_ERR_UNSUPPORTED; /* before any launch */
+    if (int rc = bind(ctx)) return rc;
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->compute;
+    if (int rc = sao_square_params(ctx, &sa, &ctb_log2_h, 1, s, nxp)) return rc;
+    const int rc = deblock_sao_plane_h265_g4(ctx, p, c_idx, chroma_format_idc, qp, prm, h, sa, sl, fused, s, nxp);
+    if (ctb_log2_h != ctb_log2_w)
+        if (int rc2 = sao_done(ctx, s)) return rc ? rc : rc2; /* the parameter launch is fenced whatever followed it */
+    return rc;
+}
+
+int hevcdbk_h265_deblock_sao_device_planes_g4(hevcdbk_context *ctx, const hevcdbk_device_planes *planes, unsigned n_planes,
+                                              int chroma_format_idc, unsigned qp, const hevcdbk_h265_params *prm,
+                                              const hevcdbk_sao_plane_cf *sao, int fused, const hevcdbk_sao_borders *borders,
+                                              const hevcdbk_h265_slice_offsets *slice_offsets, void *hip_stream)
+{
+    const int cf = chroma_format_idc;
+    bool any_g4 = false;
+    if (planes && n_planes >= 1 && n_planes <= 3)
+        for (unsigned i = 0; i < n_planes; i++) any_g4 = any_g4 || g4_kind(planes[i].plane_w, planes[i].plane_h) == 1;
+    if (!any_g4) /* multiples of 8 (or operands no entry takes): the entry this one extends */
+        return hevcdbk_h265_deblock_sao_device_planes_sl(ctx, planes, n_planes, cf, qp, prm, sao, fused, borders, slice_offsets, hip_stream);
+    if (!ctx || !sao || cf < HEVCDBK_CHROMA_400 || cf > HEVCDBK_CHROMA_444 ||
+        (fused != HEVCDBK_FUSED_AUTO && fused != HEVCDBK_FUSED_OFF && fused != HEVCDBK_FUSED_ON))
+        return HEVCDBK_ERR_ARG;
+    if (cf == HEVCDBK_CHROMA_400 && n_planes > 1) return HEVCDBK_ERR_ARG;
+    DbkH265Args h[3];
+    DbkSaoArgs sa[3];
+    DbkSaoNox nx[3], *nxp = borders ? nx : nullptr;
+    DbkSlOffs sl[3];
+    bool can[3] = {false, false, false}, rect = false;
+    unsigned log2_h[3] = {0, 0, 0};
+    bool one = n_planes >= 2 && fused != HEVCDBK_FUSED_OFF && !planes[0].is_chroma;
+    for (unsigned i = 0; i < n_planes; i++) {
+        if (int rc = sao_args_cf(&planes[i], sao[i].params, sao[i].params_stride, sao[i].params_frame_stride, sao[i].ctb_log2_w,
+                                 sao[i].ctb_log2_h, sao[i].keep, sao[i].keep_stride, sao[i].keep_frame_stride, sa[i], true))
+            return rc;
+        if (int rc = h265_args_cf(&planes[i], (int)i, cf, qp, prm, h[i], true)) return rc; /* c_idx = plane index; a g4 luma plane is refused here */
+        if (borders)
+            if (int rc = nox_args(borders, sa[i], nx[i])) return rc;
+        if (int rc = sl_args_g4(slice_offsets, &planes[i], (int)i, cf, h[i], sl[i])) return rc;
+        if (planes[i].n_frames != planes[0].n_frames) return HEVCDBK_ERR_ARG;
+        /* the chroma planes in the format's geometry of the luma plane */
+        if (i > 0 && (planes[i].plane_w * sub_w(cf) != planes[0].plane_w || planes[i].plane_h * sub_h(cf) != planes[0].plane_h))
+            return HEVCDBK_ERR_ARG;
+        log2_h[i] = sao[i].ctb_log2_h;
+        rect = rect || sao[i].ctb_log2_h != sao[i].ctb_log2_w;
+        can[i] = fused_can(h[i], sa[i], &planes[i], (int)i);
+        one = one && (i == 0 || planes[i].is_chroma) && planes[i].sample_bytes == planes[0].sample_bytes &&
+              planes[i].bit_depth == planes[0].bit_depth && (h[i].base.qp_map != nullptr) == (h[0].base.qp_map != nullptr) && can[i] &&
+              sl[i].n_bytes == sl[0].n_bytes;
+    }
+    if (!one && fused == HEVCDBK_FUSED_ON)
+        for (unsigned i = 0; i < n_planes; i++)
+            if (!can[i]) return HEVCDBK_ERR_UNSUPPORTED;
+    if (int rc = bind(ctx)) return rc;
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->compute;
+    if (int rc = sao_square_params(ctx, sa, log2_h, n_planes, s, nxp)) return rc;
+    int rc = HEVCDBK_OK;
+    if (one) {
+        if (!hip_ok(ctx, dbk_launch_deblock_sao_multi_h265_g4(h, sa, sl[0], (int)n_planes, (int)planes[0].sample_bytes, cf, s, nxp),
+                    "fused deblocking + SAO launch"))
+            rc = HEVCDBK_ERR_HIP;
+    }
+    for (unsigned i = 0; !one && i < n_planes && rc == HEVCDBK_OK; i++) {
+        const DbkSaoNox *nxi = nxp ? &nxp[i] : nullptr;
+        if (g4_kind(planes[i].plane_w, planes[i].plane_h) == 1)
+            rc = deblock_sao_plane_h265_g4(ctx, &planes[i], (int)i, cf, qp, prm, h[i], sa[i], sl[i], fused, s, nxi);
+        else if (slice_offsets) /* the luma plane: what the entry this one extends runs for it */
+            rc = deblock_sao_plane_h265_sl(ctx, &planes[i], (int)i, cf, qp, prm, h[i], sa[i], sl[i], fused, s, nxi);
+        else
+            rc = deblock_sao_plane_h265_cf(ctx, &planes[i], (int)i, i != 0 ? cf : 1, qp, prm, h[i], sa[i], fused, s, nxi);
+    }
     if (rect)
         if (int rc2 = sao_done(ctx, s)) return rc ? rc : rc2;
     return rc;

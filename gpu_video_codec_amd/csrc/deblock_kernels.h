@@ -245,3 +245,18 @@ hipError_t dbk_launch_deblock_sao_multi_h265_sl(const DbkH265Args *h, const DbkS
 hipError_t dbk_launch_h265_slice_offsets(const uint16_t *slice_idx, int in_stride, const int8_t *table, unsigned n_slices, int ctbs_x,
                                          int ctbs_y, int8_t *offs, int offs_stride, hipStream_t stream);
 
+/* ---- planes whose sizes are multiples of 4, not 8 (the _g4 entries of the C ABI: the chroma planes of a 1920x1080 4:2:0 picture are
+ * 960x540).  nbx = plane_w / 8 + 1 and nby = plane_h / 8 + 1 as ever, but the last block of a row / the last block row may have its
+ * second half inside the picture (deblock_h265.h load_block_bs_h265_g4).  Kernels of their own names, built on the most general
+ * forms -- the _sl kernels for deblocking, the _nox kernels for SAO: sl.n_bytes == 0 is "no per-slice offsets" (every pair reads 0)
+ * and h.tc_off / h.beta_off, which the _g4 kernels ADD to the pairs, carry the call's own offsets (zeros when sl has bytes);
+ * nx == NULL or nx->nox == NULL is "no boundary bytes".  Chroma planes only (chroma_format 1..3) ---- */
+hipError_t dbk_launch_h265_g4(const DbkH265Args &h, const DbkSlOffs &sl, int sample_bytes, int chroma_format, hipStream_t stream);
+hipError_t dbk_launch_packed_h265_g4(const DbkH265Args &h, const DbkSlOffs &sl, int sample_bytes, int chroma_format, hipStream_t stream);
+/* SAO of a plane of any kind whose sizes are multiples of 4 */
+hipError_t dbk_launch_sao_g4(const DbkSaoArgs &a, int sample_bytes, hipStream_t stream, const DbkSaoNox *nx);
+hipError_t dbk_launch_deblock_sao_h265_g4(const DbkH265Args &h, const DbkSaoArgs &s, const DbkSlOffs &sl, int sample_bytes, int chroma_format,
+                                          hipStream_t stream, const DbkSaoNox *nx);
+/* plane 0 = the luma plane (multiples of 8), the others its chroma planes */
+hipError_t dbk_launch_deblock_sao_multi_h265_g4(const DbkH265Args *h, const DbkSaoArgs *s, const DbkSlOffs &sl, int n, int sample_bytes,
+                                                int chroma_format, hipStream_t stream, const DbkSaoNox *nx);

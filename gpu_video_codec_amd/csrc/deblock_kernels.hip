@@ -232,9 +232,17 @@ __device__ __forceinline__ dbk::BlockBs load_bs_buffer_rowedge(const DbkArgs &a,
     return b;
 }
 
+/* The _g4 kernels (planes whose sizes are multiples of 4, deblock_h265.h load_block_bs_h265_g4): "columns 4..7 of block bx / rows
+ * 4..7 of block by lie inside the picture", which is also "the edge x = 8 bx / y = 8 by is not the picture boundary", is a statement
+ * about the plane size there.  Every other kernel keeps its statement about the block counts (bx < nbx - 1, by < nby - 1) word for
+ * word, in the other branch of an `if constexpr`: rewording it through a helper changed the operand order of two scalar
+ * instructions in 86 existing kernels (tools/kernel_symbol_diff.py) */
+__device__ __forceinline__ bool g4_right(const DbkArgs &a, int bx) { return dbk::g4_right_in(bx, a.plane_w); }
+__device__ __forceinline__ bool g4_below(const DbkArgs &a, int by) { return dbk::g4_below_in(by, a.plane_h); }
+
 /* spec-exact mode: the four 4-sample-granular bS bytes of a lane's block (deblock_h265.h load_block_bs_h265); edges on
  * the picture boundary and halves outside the picture read 0 through an out-of-range offset */
-template <int PATH>
+template <int PATH, bool G4 = false>
 __device__ __forceinline__ void load_bs_buffer_h265(const DbkArgs &a, int f, int by, int bx, bool active, int (&entry)[4])
 {
     const __amdgpu_buffer_rsrc_t rv = __builtin_amdgcn_make_buffer_rsrc(
@@ -247,6 +255,16 @@ __device__ __forceinline__ void load_bs_buffer_h265(const DbkArgs &a, int f, int
         entry[2] = __builtin_amdgcn_raw_buffer_load_b8(rh, (uint32_t)(2 * bx - 1), by * a.hstride, 0);
         entry[3] = __builtin_amdgcn_raw_buffer_load_b8(rh, (uint32_t)(2 * bx), by * a.hstride, 0);
     } else {
+        if constexpr (G4) {
+            const bool rin = g4_right(a, bx), bin = g4_below(a, by);
+            const bool vedge = active && bx > 0 && rin, hedge = active && by > 0 && bin;
+            const uint32_t iv = (uint32_t)(2 * by * a.vstride + bx), ih = (uint32_t)(by * a.hstride + 2 * bx);
+            entry[0] = __builtin_amdgcn_raw_buffer_load_b8(rv, (vedge && by > 0) ? iv - (uint32_t)a.vstride : kOob, 0, 0);
+            entry[1] = __builtin_amdgcn_raw_buffer_load_b8(rv, (vedge && bin) ? iv : kOob, 0, 0);
+            entry[2] = __builtin_amdgcn_raw_buffer_load_b8(rh, (hedge && bx > 0) ? ih - 1u : kOob, 0, 0);
+            entry[3] = __builtin_amdgcn_raw_buffer_load_b8(rh, (hedge && rin) ? ih : kOob, 0, 0);
+            return;
+        }
         const bool vedge = active && bx > 0 && bx < a.nbx - 1, hedge = active && by > 0 && by < a.nby - 1;
         const uint32_t iv = (uint32_t)(2 * by * a.vstride + bx), ih = (uint32_t)(by * a.hstride + 2 * bx);
         entry[0] = __builtin_amdgcn_raw_buffer_load_b8(rv, (vedge && by > 0) ? iv - (uint32_t)a.vstride : kOob, 0, 0);
@@ -322,7 +340,7 @@ __device__ __forceinline__ void block_qpl4_dev(const DbkArgs &a, int f, int by, 
 /* per-slice offsets (the _sl kernels, deblock_sl.h): the block's four segment QPs and four offset pairs.  The three pair loads go
  * out first, then the map loads (a one-QP launch has no map: its qPL is the launch's scalar, and no dummy map is read); nothing
  * waits before all of them are under way */
-template <bool CHROMA, int CF>
+template <bool CHROMA, int CF, bool G4 = false /* the _g4 kernels: the launch's own pair (hx->tc_off / beta_off) is added; a call with the operand hands in zeros there, a call without it an array of no bytes */>
 __device__ __forceinline__ void sl_block_operands(const DbkArgs &a, const DbkH265Args *hx, const DbkSlOffs *sl, int f, int by, int bx,
                                                   int (&qpl)[4], int (&tc_off)[4], int (&beta_off)[4])
 {
@@ -336,6 +354,13 @@ __device__ __forceinline__ void sl_block_operands(const DbkArgs &a, const DbkH26
         for (int i = 0; i < 4; i++) qpl[i] = hx->qp;
     }
     dbk::h265_sl_seg_offs(ar, bl, br, tc_off, beta_off);
+    if constexpr (G4) {
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            tc_off[i] += hx->tc_off;
+            beta_off[i] += hx->beta_off;
+        }
+    }
 }
 
 template <bool CHROMA>
@@ -387,7 +412,8 @@ __device__ __forceinline__ const DBK_LDS uint32_t *ktab_setup_h265(uint32_t *lds
  * MODE 0 = filter, MODE 1 = diagnostic copy (same loads/stores, no arithmetic).
  */
 template <bool CHROMA, int MODE, bool NT, int PATH, bool QPMAP, int CF = 1 /* chroma_format_idc of a spec-exact chroma plane */,
-          bool SL = false /* MODE 2 with QPMAP: per-slice offsets from sl (the _sl kernels); the map itself may be absent */>
+          bool SL = false /* MODE 2 with QPMAP: per-slice offsets from sl (the _sl kernels); the map itself may be absent */,
+          bool G4 = false /* with SL: a plane whose sizes are multiples of 4 (the _g4 kernels, g4_right / g4_below) */>
 __device__ __forceinline__ void packed_body(const DbkArgs &a, int by, int f, int bx, bool active, int by0,
                                             const DbkH265Args *hx = nullptr /* MODE 2 only */,
                                             uint32_t *ktab_lds = nullptr /* QPMAP luma: LDS for the workgroup's operand table */,
@@ -425,10 +451,14 @@ __device__ __forceinline__ void packed_body(const DbkArgs &a, int by, int f, int
     const bool shifted = MODE == 1 && a.diag_xshift != 0;
     if (shifted) active = active && bx < a.nbx - 1;
     const bool lv = shifted ? active : (active && bx > 0);
-    const bool rv = shifted ? active : (active && bx < a.nbx - 1);
+    bool rv;
+    if constexpr (G4) rv = active && g4_right(a, bx);
+    else rv = shifted ? active : (active && bx < a.nbx - 1);
 #else
     const bool lv = active && bx > 0;            /* cols 0..3 inside the image */
-    const bool rv = active && bx < a.nbx - 1;    /* cols 4..7 inside the image */
+    bool rv;                                     /* cols 4..7 inside the image */
+    if constexpr (G4) rv = active && g4_right(a, bx);
+    else rv = active && bx < a.nbx - 1;
 #endif
     const int y0 = by * 8 - 4;
 #ifdef HEVCDBK_DIAG
@@ -558,11 +588,11 @@ __device__ __forceinline__ void packed_body(const DbkArgs &a, int by, int f, int
 #endif
     else if constexpr (MODE == 2) { /* spec-exact mode, H.265 8.7.2 */
         int entry[4];
-        load_bs_buffer_h265<PATH>(a, f, by, bx, active, entry);
+        load_bs_buffer_h265<PATH, G4>(a, f, by, bx, active, entry);
         dbk::H265Seg sg;
         if constexpr (QPMAP && SL) {
             int qpl[4], tc_off[4], beta_off[4];
-            sl_block_operands<CHROMA, CF>(a, hx, sl, f, by, active ? bx : 0, qpl, tc_off, beta_off);
+            sl_block_operands<CHROMA, CF, G4>(a, hx, sl, f, by, active ? bx : 0, qpl, tc_off, beta_off);
             const dbk::H265Prm prm = {0, 0, hx->c_qp_offset, 0, 255};
             if constexpr (KT) {
                 if constexpr (PATH != 3) ktab = ktab_setup_h265(ktab_lds, 0);
@@ -670,7 +700,8 @@ __device__ __forceinline__ void packed_body(const DbkArgs &a, int by, int f, int
  * they are (no widening needed), so twice the bytes per pixel at the same instruction count: this is
  * the variant that runs into the HBM roof (BASELINE config 5).
  */
-template <int MODE, bool NT, bool EDGE, bool QPMAP, bool CHROMA = false, bool WIDE = false, int CF = 1, bool SL = false /* packed_body */>
+template <int MODE, bool NT, bool EDGE, bool QPMAP, bool CHROMA = false, bool WIDE = false, int CF = 1, bool SL = false /* packed_body */,
+          bool G4 = false /* packed_body */>
 __device__ __forceinline__ void packed16_body(const DbkArgs &a, int by, int f, int bx, bool active,
                                               const DbkH265Args *hx = nullptr /* MODE 2 (spec-exact) only */,
                                               uint32_t *ktab_lds = nullptr /* QPMAP luma: LDS for the workgroup's operand table */,
@@ -678,7 +709,9 @@ __device__ __forceinline__ void packed16_body(const DbkArgs &a, int by, int f, i
 {
     constexpr bool KT = QPMAP && !CHROMA && (MODE == 0 || MODE == 2); /* packed_body: built after the loads have been issued */
     const bool lv = active && bx > 0;
-    const bool rv = active && bx < a.nbx - 1;
+    bool rv;
+    if constexpr (G4) rv = active && g4_right(a, bx);
+    else rv = active && bx < a.nbx - 1;
     const int y0 = by * 8 - 4;
 #ifdef HEVCDBK_DIAG
     const uint32_t xoff = (uint32_t)(bx * 16 - 8) + (MODE == 1 ? (uint32_t)a.diag_xshift : 0u);
@@ -726,11 +759,11 @@ __device__ __forceinline__ void packed16_body(const DbkArgs &a, int by, int f, i
         }
     } else if constexpr (MODE == 2) { /* spec-exact mode, H.265 8.7.2 */
         int entry[4];
-        load_bs_buffer_h265<EDGE ? 2 : 0>(a, f, by, bx, active, entry);
+        load_bs_buffer_h265<EDGE ? 2 : 0, G4>(a, f, by, bx, active, entry);
         dbk::H265Seg sg;
         if constexpr (QPMAP && SL) {
             int qpl[4], tc_off[4], beta_off[4];
-            sl_block_operands<CHROMA, CF>(a, hx, sl, f, by, active ? bx : 0, qpl, tc_off, beta_off);
+            sl_block_operands<CHROMA, CF, G4>(a, hx, sl, f, by, active ? bx : 0, qpl, tc_off, beta_off);
             const dbk::H265Prm prm = {0, 0, hx->c_qp_offset, a.shift, a.max_v};
             if constexpr (KT) dbk::h265_seg_rows_sl(entry, qpl, prm, ktab_setup_h265(ktab_lds, a.shift), tc_off, beta_off, sg);
             else dbk::h265_seg_params_sl<CHROMA, CF>(entry, qpl, prm, tc_off, beta_off, sg);
@@ -801,7 +834,7 @@ struct WaveCoords {
  *   lines at their common boundary, and their partial writes then merge in one XCD's L2.
  *   Divisions are exact multiply-high by host-computed reciprocals (dividend < 2^32 / divisor).
  */
-template <bool LINEAR>
+template <bool LINEAR, bool G4 = false /* the _g4 kernels: the last block of a row / the last block row may be whole (g4_right / g4_below) */>
 __device__ __forceinline__ bool wave_coords(const DbkArgs &a, WaveCoords &c)
 {
     const int lane = (int)(threadIdx.x & 63u);
@@ -812,6 +845,12 @@ __device__ __forceinline__ bool wave_coords(const DbkArgs &a, WaveCoords &c)
         const int wave_bx0 = __builtin_amdgcn_readfirstlane(c.bx) & ~63;
         c.active = c.bx < a.nbx;
         c.by0 = c.by;
+        if constexpr (G4) {
+            /* the wave's last lane has its right half inside the picture (then so has every lane, and every lane owns a block) */
+            c.rows_in = c.by > 0 && g4_below(a, c.by);
+            c.interior = wave_bx0 > 0 && g4_right(a, wave_bx0 + 63) && c.rows_in;
+            return true;
+        }
         c.rows_in = c.by > 0 && c.by < a.nby - 1;
         c.interior = wave_bx0 > 0 && wave_bx0 + 64 <= a.nbx - 1 && c.rows_in;
         return true;
@@ -827,6 +866,11 @@ __device__ __forceinline__ bool wave_coords(const DbkArgs &a, WaveCoords &c)
         c.interior = bx0 >= 1u && bx0 + 63u <= (uint32_t)a.nbx - 2u && by0 >= 1u && by0 + 2u <= (uint32_t)a.nby;
         c.by0 = (int)by0;
         c.rows_in = by0 >= 1u && __umulhi(t0 + 63u, a.magic_nbx) + 2u <= (uint32_t)a.nby; /* last lane's row <= nby-2 */
+        if constexpr (G4) {
+            /* one block row (8 (bx0 + 63) < plane_w puts the last lane's block inside it), every half and every row inside the picture */
+            c.interior = bx0 >= 1u && g4_right(a, (int)bx0 + 63) && by0 >= 1u && g4_below(a, (int)by0);
+            c.rows_in = by0 >= 1u && g4_below(a, (int)__umulhi(t0 + 63u, a.magic_nbx)); /* the last lane's rows are inside */
+        }
         if (c.interior) {
             c.by = (int)by0;
             c.bx = (int)bx0 + lane;
@@ -908,7 +952,7 @@ __global__ __launch_bounds__(1024) void dbk_packed_kernel(const DbkArgs a)
 }
 
 /* spec-exact mode (H.265 8.7.2), 8-bit samples, packed-int16 arithmetic: same mapping and memory path */
-template <bool CHROMA, bool LINEAR, bool QPMAP, int CF = 1, bool SL = false>
+template <bool CHROMA, bool LINEAR, bool QPMAP, int CF = 1, bool SL = false, bool G4 = false>
 __device__ __forceinline__ void packed_h265_dispatch(const DbkH265Args &h, const DbkSlOffs *sl = nullptr)
 {
     const DbkArgs &a = h.base;
@@ -918,10 +962,10 @@ __device__ __forceinline__ void packed_h265_dispatch(const DbkH265Args &h, const
         kt = ktab;
     }
     WaveCoords c;
-    if (!wave_coords<LINEAR>(a, c)) return;
-    if (c.interior) packed_body<CHROMA, 2, false, 0, QPMAP, CF, SL>(a, c.by, c.f, c.bx, true, c.by0, &h, kt, sl);
-    else if (c.rows_in) packed_body<CHROMA, 2, false, LINEAR ? 1 : 3, QPMAP, CF, SL>(a, c.by, c.f, c.bx, c.active, c.by0, &h, kt, sl);
-    else packed_body<CHROMA, 2, false, 2, QPMAP, CF, SL>(a, c.by, c.f, c.bx, c.active, c.by0, &h, kt, sl);
+    if (!wave_coords<LINEAR, G4>(a, c)) return;
+    if (c.interior) packed_body<CHROMA, 2, false, 0, QPMAP, CF, SL, G4>(a, c.by, c.f, c.bx, true, c.by0, &h, kt, sl);
+    else if (c.rows_in) packed_body<CHROMA, 2, false, LINEAR ? 1 : 3, QPMAP, CF, SL, G4>(a, c.by, c.f, c.bx, c.active, c.by0, &h, kt, sl);
+    else packed_body<CHROMA, 2, false, 2, QPMAP, CF, SL, G4>(a, c.by, c.f, c.bx, c.active, c.by0, &h, kt, sl);
 }
 template <bool CHROMA, bool LINEAR, bool QPMAP>
 __global__ __launch_bounds__(1024) void dbk_packed_h265_kernel(const DbkH265Args h)
@@ -966,6 +1010,23 @@ __global__ __launch_bounds__(1024) void dbk_packed16_h265_sl_kernel(const DbkH26
     if (!wave_coords<LINEAR>(a, c)) return;
     if (c.interior) packed16_body<2, false, false, true, CHROMA, WIDE, CF, true>(a, c.by, c.f, c.bx, true, &h, kt, &sl);
     else packed16_body<2, false, true, true, CHROMA, WIDE, CF, true>(a, c.by, c.f, c.bx, c.active, &h, kt, &sl);
+}
+/* The _sl kernels for chroma planes whose sizes are multiples of 4 (the _g4 entries; g4_right / g4_below): kernels of their own
+ * names once more.  The last block of a row is a full 8-byte / 16-byte row access, the last block row eight valid rows, and a wave
+ * that holds them can be an interior wave.  A call without per-slice offsets hands in an array of no bytes (sl_block_operands). */
+template <bool LINEAR, int CF>
+__global__ __launch_bounds__(1024) void dbk_packed_h265_g4_kernel(const DbkH265Args h, const DbkSlOffs sl)
+{
+    packed_h265_dispatch<true, LINEAR, true, CF, true, true>(h, &sl);
+}
+template <bool LINEAR, int CF>
+__global__ __launch_bounds__(1024) void dbk_packed16_h265_g4_kernel(const DbkH265Args h, const DbkSlOffs sl)
+{
+    const DbkArgs &a = h.base;
+    WaveCoords c;
+    if (!wave_coords<LINEAR, true>(a, c)) return;
+    if (c.interior) packed16_body<2, false, false, true, true, false, CF, true, true>(a, c.by, c.f, c.bx, true, &h, nullptr, &sl);
+    else packed16_body<2, false, true, true, true, false, CF, true, true>(a, c.by, c.f, c.bx, c.active, &h, nullptr, &sl);
 }
 /* ------------------------------------------------------------------------------------------ */
 /* one launch for the planes of a 4:2:0 frame                                */
@@ -1747,10 +1808,38 @@ hipError_t dbk_launch_packed_h265_sl(const DbkH265Args &h, const DbkSlOffs &sl, 
     return hipGetLastError();
 }
 
-hipError_t dbk_launch_deblock_sao_h265_sl(const DbkH265Args &h, const DbkSaoArgs &s, const DbkSlOffs &sl, int sample_bytes, bool chroma,
-                                          int chroma_format, hipStream_t stream, const DbkSaoNox *nxp)
+/* ---- chroma planes whose sizes are multiples of 4 (the _g4 entries): the _sl twins' twins, grids and blocks unchanged ---- */
+
+hipError_t dbk_launch_packed_h265_g4(const DbkH265Args &h, const DbkSlOffs &sl, int sample_bytes, int chroma_format, hipStream_t stream)
 {
-    if (!fused_format_ok(chroma_format)) return hipErrorInvalidValue;
+    if (chroma_format != 1 && chroma_format != 2 && chroma_format != 3) return hipErrorInvalidValue;
+    if (h.base.n_frames <= 0 || h.base.nbx <= 0 || h.base.nby <= 0) return hipSuccess;
+    DbkH265Args g = h;
+    dim3 grid, block;
+    const bool linear = plan_packed(h.base, g.base, grid, block);
+#define DBK_G4_LAUNCH(LIN, F)                                                                                      \
+    do {                                                                                                           \
+        if (sample_bytes == 2) DBK_LAUNCH((dbk_packed16_h265_g4_kernel<LIN, F>), grid, block, stream, g, sl);      \
+        else DBK_LAUNCH((dbk_packed_h265_g4_kernel<LIN, F>), grid, block, stream, g, sl);                          \
+    } while (0)
+#define DBK_G4_LAUNCH_F(LIN)                               \
+    do {                                                   \
+        if (chroma_format == 1) DBK_G4_LAUNCH(LIN, 1);     \
+        else if (chroma_format == 2) DBK_G4_LAUNCH(LIN, 2); \
+        else DBK_G4_LAUNCH(LIN, 3);                        \
+    } while (0)
+    if (linear) DBK_G4_LAUNCH_F(true);
+    else DBK_G4_LAUNCH_F(false);
+#undef DBK_G4_LAUNCH_F
+#undef DBK_G4_LAUNCH
+    return hipGetLastError();
+}
+
+/* g4: the _g4 kernels (a chroma plane, or the planes of a picture whose chroma planes have sizes that are multiples of 4) */
+static hipError_t launch_deblock_sao_h265_sl(const DbkH265Args &h, const DbkSaoArgs &s, const DbkSlOffs &sl, int sample_bytes, bool chroma,
+                                             int chroma_format, hipStream_t stream, const DbkSaoNox *nxp, bool g4)
+{
+    if (!fused_format_ok(chroma_format) || (g4 && !chroma)) return hipErrorInvalidValue;
     if (h.base.n_frames <= 0 || h.base.nbx <= 0 || h.base.nby <= 0) return hipSuccess;
     DbkFusedH265Args fa;
     fa.d = h;
@@ -1758,6 +1847,22 @@ hipError_t dbk_launch_deblock_sao_h265_sl(const DbkH265Args &h, const DbkSaoArgs
     const dim3 grid(fused_grid(h.base.plane_w, h.base.plane_h, h.base.n_frames, sample_bytes, fa.g), 1, 1);
     const DbkSaoNox nx = nxp ? *nxp : DbkSaoNox{nullptr, 0, 0}; /* no bytes: no direction is forbidden */
     const int cf = chroma ? chroma_format : 1;
+    if (g4) {
+#define DBK_G48(F) DBK_LAUNCH_LDS((dbk_sao_fused_h265_g4_kernel<F>), grid, dim3(kFusedThreads), kFusedLds, stream, fa, nx, sl)
+#define DBK_G416(F) DBK_LAUNCH_LDS((dbk_sao_fused16_h265_g4_kernel<F>), grid, dim3(kFused16Threads), kFused16Lds, stream, fa, nx, sl)
+        if (sample_bytes == 1) {
+            if (cf == 1) DBK_G48(1);
+            else if (cf == 2) DBK_G48(2);
+            else DBK_G48(3);
+        } else {
+            if (cf == 1) DBK_G416(1);
+            else if (cf == 2) DBK_G416(2);
+            else DBK_G416(3);
+        }
+#undef DBK_G48
+#undef DBK_G416
+        return hipGetLastError();
+    }
 #define DBK_SL8(C, F) DBK_LAUNCH_LDS((dbk_sao_fused_h265_sl_kernel<C, F>), grid, dim3(kFusedThreads), kFusedLds, stream, fa, nx, sl)
 #define DBK_SL16(C, W, F) DBK_LAUNCH_LDS((dbk_sao_fused16_h265_sl_kernel<C, W, F>), grid, dim3(kFused16Threads), kFused16Lds, stream, fa, nx, sl)
     if (sample_bytes == 1) {
@@ -1777,8 +1882,19 @@ hipError_t dbk_launch_deblock_sao_h265_sl(const DbkH265Args &h, const DbkSaoArgs
     return hipGetLastError();
 }
 
-hipError_t dbk_launch_deblock_sao_multi_h265_sl(const DbkH265Args *h, const DbkSaoArgs *s, const DbkSlOffs &sl, int n, int sample_bytes,
-                                                int chroma_format, hipStream_t stream, const DbkSaoNox *nxp)
+hipError_t dbk_launch_deblock_sao_h265_sl(const DbkH265Args &h, const DbkSaoArgs &s, const DbkSlOffs &sl, int sample_bytes, bool chroma,
+                                          int chroma_format, hipStream_t stream, const DbkSaoNox *nxp)
+{
+    return launch_deblock_sao_h265_sl(h, s, sl, sample_bytes, chroma, chroma_format, stream, nxp, false);
+}
+hipError_t dbk_launch_deblock_sao_h265_g4(const DbkH265Args &h, const DbkSaoArgs &s, const DbkSlOffs &sl, int sample_bytes, int chroma_format,
+                                          hipStream_t stream, const DbkSaoNox *nxp)
+{
+    return launch_deblock_sao_h265_sl(h, s, sl, sample_bytes, true, chroma_format, stream, nxp, true);
+}
+
+static hipError_t launch_deblock_sao_multi_h265_sl(const DbkH265Args *h, const DbkSaoArgs *s, const DbkSlOffs &sl, int n, int sample_bytes,
+                                                   int chroma_format, hipStream_t stream, const DbkSaoNox *nxp, bool g4)
 {
     if (!fused_format_ok(chroma_format)) return hipErrorInvalidValue;
     if (n < 2 || n > 3) return hipErrorInvalidValue;
@@ -1801,8 +1917,14 @@ hipError_t dbk_launch_deblock_sao_multi_h265_sl(const DbkH265Args *h, const DbkS
         for (int i = 0; i < n; i++) nx.pl[i] = nxp[i];
     const bool wide = h[0].base.max_v > 2047;
 #define DBK_SLM(SB, W, F)                                                                                                            \
-    DBK_LAUNCH_LDS((dbk_sao_fused_multi_h265_sl_kernel<SB, W, F>), grid, dim3(SB == 1 ? kFusedThreads : kFused16Threads),            \
-                   SB == 1 ? kFusedLds : kFused16Lds, stream, fa, nx, sl)
+    do {                                                                                                                             \
+        if (g4)                                                                                                                      \
+            DBK_LAUNCH_LDS((dbk_sao_fused_multi_h265_g4_kernel<SB, W, F>), grid, dim3(SB == 1 ? kFusedThreads : kFused16Threads),    \
+                           SB == 1 ? kFusedLds : kFused16Lds, stream, fa, nx, sl);                                                   \
+        else                                                                                                                         \
+            DBK_LAUNCH_LDS((dbk_sao_fused_multi_h265_sl_kernel<SB, W, F>), grid, dim3(SB == 1 ? kFusedThreads : kFused16Threads),    \
+                           SB == 1 ? kFusedLds : kFused16Lds, stream, fa, nx, sl);                                                   \
+    } while (0)
 #define DBK_SLM_F(F)                                    \
     do {                                                \
         if (sample_bytes == 1) DBK_SLM(1, false, F);    \
@@ -1815,4 +1937,15 @@ hipError_t dbk_launch_deblock_sao_multi_h265_sl(const DbkH265Args *h, const DbkS
 #undef DBK_SLM_F
 #undef DBK_SLM
     return hipGetLastError();
+}
+
+hipError_t dbk_launch_deblock_sao_multi_h265_sl(const DbkH265Args *h, const DbkSaoArgs *s, const DbkSlOffs &sl, int n, int sample_bytes,
+                                                int chroma_format, hipStream_t stream, const DbkSaoNox *nxp)
+{
+    return launch_deblock_sao_multi_h265_sl(h, s, sl, n, sample_bytes, chroma_format, stream, nxp, false);
+}
+hipError_t dbk_launch_deblock_sao_multi_h265_g4(const DbkH265Args *h, const DbkSaoArgs *s, const DbkSlOffs &sl, int n, int sample_bytes,
+                                                int chroma_format, hipStream_t stream, const DbkSaoNox *nxp)
+{
+    return launch_deblock_sao_multi_h265_sl(h, s, sl, n, sample_bytes, chroma_format, stream, nxp, true);
 }

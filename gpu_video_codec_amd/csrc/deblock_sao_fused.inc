@@ -33,11 +33,13 @@ constexpr int kFusedQuads = kFusedTile / 64;          /* 64 x 64 quadrants: kFus
 constexpr int kFusedQuadsX = kFusedTileW / 64;
 constexpr int kFusedLds = (kFusedTile + 8) * kFusedPitch;
 
-template <bool CHROMA, int MODE, bool QPMAP, int CF = 1, bool NOX = false, bool SL = false> /* MODE 0 = reference-exact deblocking, 2 = spec-exact (H.265 8.7.2); QPMAP = QP per map unit;
+template <bool CHROMA, int MODE, bool QPMAP, int CF = 1, bool NOX = false, bool SL = false, bool G4 = false> /* MODE 0 = reference-exact deblocking, 2 = spec-exact (H.265 8.7.2); QPMAP = QP per map unit;
                                                           CF = chroma_format_idc of a spec-exact chroma plane with a QP map;
                                                           NOX = stage 2 honours the slice / tile boundaries of nx (the _nox kernels);
                                                           SL = per-slice deblocking offsets from sl (the _sl kernels: MODE 2, QPMAP and NOX set,
-                                                          the map and the bytes of nx may be absent) */
+                                                          the map and the bytes of nx may be absent);
+                                                          G4 = with SL: a plane whose sizes are multiples of 4 (the _g4 kernels: g4_right /
+                                                          g4_below in stage 1, partial blocks of 4 columns / 4 rows in stage 2) */
 __device__ __forceinline__ void fused_body(const DbkArgs &a, const DbkH265Args *hx, const DbkSaoArgs &s, const DbkFusedGrid &g, uint8_t *tile,
                                            uint32_t id /* workgroup number inside this plane's part of the grid */, const DbkSaoNox *nx = nullptr,
                                            [[maybe_unused]] const DbkSlOffs *sl = nullptr)
@@ -58,8 +60,15 @@ __device__ __forceinline__ void fused_body(const DbkArgs &a, const DbkH265Args *
     const bool in_tile = t < kFusedBlocksX * kFusedBlocks;
     const int bx = (X0 >> 3) + lbx, by = (Y0 >> 3) + lby;
     const bool active = in_tile && bx < a.nbx && by < a.nby;
-    const bool lv = active && bx > 0, rv = active && bx < a.nbx - 1;
-    const bool full = lv && rv && by > 0 && by < a.nby - 1; /* all 8 rows and both halves inside the picture */
+    const bool lv = active && bx > 0;
+    bool rv, full; /* full: all 8 rows and both halves inside the picture */
+    if constexpr (G4) {
+        rv = active && g4_right(a, bx);
+        full = lv && rv && by > 0 && g4_below(a, by);
+    } else {
+        rv = active && bx < a.nbx - 1;
+        full = lv && rv && by > 0 && by < a.nby - 1;
+    }
     const int y0 = by * 8 - 4;
     const uint32_t xoff = (uint32_t)(bx * 8 - 4);
     const uint32_t plane_bytes = (uint32_t)a.pitch * (uint32_t)a.plane_h;
@@ -111,11 +120,11 @@ __device__ __forceinline__ void fused_body(const DbkArgs &a, const DbkH265Args *
         }
     } else {
         int entry[4];
-        load_bs_buffer_h265<2>(a, f, by, bx, active, entry);
+        load_bs_buffer_h265<2, G4>(a, f, by, bx, active, entry);
         dbk::H265Seg sg;
         if constexpr (QPMAP && SL) {
             int qpl[4], tc_off[4], beta_off[4];
-            sl_block_operands<CHROMA, CF>(a, hx, sl, f, by, active ? bx : 0, qpl, tc_off, beta_off);
+            sl_block_operands<CHROMA, CF, G4>(a, hx, sl, f, by, active ? bx : 0, qpl, tc_off, beta_off);
             const dbk::H265Prm prm = {0, 0, hx->c_qp_offset, 0, 255};
             if constexpr (KT) dbk::h265_seg_rows_sl(entry, qpl, prm, ktab_setup_h265(ktab_lds, 0), tc_off, beta_off, sg);
             else dbk::h265_seg_params_sl<CHROMA, CF>(entry, qpl, prm, tc_off, beta_off, sg);
@@ -176,6 +185,33 @@ __device__ __forceinline__ void fused_body(const DbkArgs &a, const DbkH265Args *
             return q;
         };
         const uint32_t vout = (uint32_t)ys * (uint32_t)s.pitch + (uint32_t)x;
+        if constexpr (G4) {
+            /* the last block of a row may be 4 samples wide, the last one of a column 4 rows tall (NROWS 8 only: a plane's height
+             * is a multiple of 4).  Such a block is on the picture border, so its wave takes the masked procedure anyway: the
+             * narrow block has the picture's edge behind sample 3 (saonox::W4) and stores its low dword alone, the short one runs
+             * the procedure for 4 rows */
+            const bool w4 = x + 8 > s.plane_w, h4 = NROWS == 8 && ys + 8 > s.plane_h;
+            const bool any_w4 = __builtin_amdgcn_ballot_w64(w4) != 0ull;
+            auto store4 = [&](int r, uint32_t lo, uint32_t hi) {
+                u32x2 w;
+                w.x = lo;
+                w.y = hi;
+                __builtin_amdgcn_raw_buffer_store_b64(w, rd, w4 ? kOob : vout, r * (int)s.pitch, 0);
+                if (any_w4) __builtin_amdgcn_raw_buffer_store_b32(lo, rd, w4 ? vout : kOob, r * (int)s.pitch, 0);
+            };
+            const uint32_t m = (h4 ? saonox::block_mask<4>(nox_byte, x, ys, s.plane_w, s.plane_h, s.ctb_log2)
+                                   : saonox::block_mask<NROWS>(nox_byte, x, ys, s.plane_w, s.plane_h, s.ctb_log2)) |
+                               (w4 ? saonox::W4 : 0u);
+            if (__builtin_amdgcn_ballot_w64(m != 0u) == 0ull) {
+                sao8::block<false, NROWS>(fetch, store4, x, ys, s.plane_w, s.plane_h, c, kept);
+            } else if constexpr (NROWS == 8) {
+                if (h4) sao8::block<2, 4, true>(fetch, store4, x, ys, s.plane_w, s.plane_h, c, kept, m);
+                else sao8::block<2, 8, true>(fetch, store4, x, ys, s.plane_w, s.plane_h, c, kept, m);
+            } else {
+                sao8::block<2, NROWS, true>(fetch, store4, x, ys, s.plane_w, s.plane_h, c, kept, m);
+            }
+            return;
+        }
         auto store = [&](int r, uint32_t lo, uint32_t hi) {
             u32x2 w;
             w.x = lo;
@@ -219,7 +255,7 @@ constexpr int kFused16Threads = 320;
 constexpr int kFused16Quads = kFused16Tile / 64;       /* 2 x 2 SAO waves */
 constexpr int kFused16Lds = (kFused16Tile + 8) * kFused16Pitch;
 
-template <bool CHROMA, int MODE, bool WIDE, bool QPMAP, int CF = 1, bool NOX = false, bool SL = false>
+template <bool CHROMA, int MODE, bool WIDE, bool QPMAP, int CF = 1, bool NOX = false, bool SL = false, bool G4 = false /* fused_body */>
 __device__ __forceinline__ void fused_body16(const DbkArgs &a, const DbkH265Args *hx, const DbkSaoArgs &s, const DbkFusedGrid &g, uint8_t *tile,
                                              uint32_t id, const DbkSaoNox *nx = nullptr, [[maybe_unused]] const DbkSlOffs *sl = nullptr)
 {
@@ -235,8 +271,15 @@ __device__ __forceinline__ void fused_body16(const DbkArgs &a, const DbkH265Args
     const bool in_tile = t < kFused16Blocks * kFused16Blocks;
     const int bx = (X0 >> 3) + lbx, by = (Y0 >> 3) + lby;
     const bool active = in_tile && bx < a.nbx && by < a.nby;
-    const bool lv = active && bx > 0, rv = active && bx < a.nbx - 1;
-    const bool full = lv && rv && by > 0 && by < a.nby - 1;
+    const bool lv = active && bx > 0;
+    bool rv, full;
+    if constexpr (G4) {
+        rv = active && g4_right(a, bx);
+        full = lv && rv && by > 0 && g4_below(a, by);
+    } else {
+        rv = active && bx < a.nbx - 1;
+        full = lv && rv && by > 0 && by < a.nby - 1;
+    }
     const int y0 = by * 8 - 4;
     const uint32_t xoff = (uint32_t)(bx * 16 - 8);
     const uint32_t plane_bytes = (uint32_t)a.pitch * (uint32_t)a.plane_h;
@@ -271,11 +314,11 @@ __device__ __forceinline__ void fused_body16(const DbkArgs &a, const DbkH265Args
         else dbk::packed_filter_luma_block16<WIDE, !QPMAP>(W, bs, q, a.max_v);
     } else {
         int entry[4];
-        load_bs_buffer_h265<2>(a, f, by, bx, active, entry);
+        load_bs_buffer_h265<2, G4>(a, f, by, bx, active, entry);
         dbk::H265Seg sg;
         if constexpr (QPMAP && SL) {
             int qpl[4], tc_off[4], beta_off[4];
-            sl_block_operands<CHROMA, CF>(a, hx, sl, f, by, active ? bx : 0, qpl, tc_off, beta_off);
+            sl_block_operands<CHROMA, CF, G4>(a, hx, sl, f, by, active ? bx : 0, qpl, tc_off, beta_off);
             const dbk::H265Prm prm = {0, 0, hx->c_qp_offset, a.shift, a.max_v};
             dbk::h265_seg_params_sl<CHROMA, CF>(entry, qpl, prm, tc_off, beta_off, sg);
         } else if constexpr (QPMAP) {
@@ -330,6 +373,33 @@ __device__ __forceinline__ void fused_body16(const DbkArgs &a, const DbkH265Args
             return q;
         };
         const uint32_t vout = (uint32_t)ys * (uint32_t)s.pitch + (uint32_t)x * 2u;
+        if constexpr (G4) { /* partial blocks as in fused_body: the narrow one stores its first 8 bytes alone */
+            const bool w4 = x + 8 > s.plane_w, h4 = NROWS == 8 && ys + 8 > s.plane_h;
+            const bool any_w4 = __builtin_amdgcn_ballot_w64(w4) != 0ull;
+            auto store4 = [&](int r, uint32_t d0, uint32_t d1, uint32_t d2, uint32_t d3) {
+                u32x4 w;
+                w.x = d0; w.y = d1; w.z = d2; w.w = d3;
+                __builtin_amdgcn_raw_buffer_store_b128(w, rd, w4 ? kOob : vout, r * (int)s.pitch, 0);
+                if (any_w4) {
+                    u32x2 h;
+                    h.x = d0; h.y = d1;
+                    __builtin_amdgcn_raw_buffer_store_b64(h, rd, w4 ? vout : kOob, r * (int)s.pitch, 0);
+                }
+                asm volatile("s_nop 1" : : "v"(w.x), "v"(w.y), "v"(w.z), "v"(w.w) : "memory"); /* the wait states of `store` below */
+            };
+            const uint32_t m = (h4 ? saonox::block_mask<4>(nox_byte, x, ys, s.plane_w, s.plane_h, s.ctb_log2)
+                                   : saonox::block_mask<NROWS>(nox_byte, x, ys, s.plane_w, s.plane_h, s.ctb_log2)) |
+                               (w4 ? saonox::W4 : 0u);
+            if (__builtin_amdgcn_ballot_w64(m != 0u) == 0ull) {
+                sao16::block<false, NROWS>(fetch, store4, x, ys, s.plane_w, s.plane_h, c, kept, s.max_v, s.band_shift);
+            } else if constexpr (NROWS == 8) {
+                if (h4) sao16::block<2, 4, true>(fetch, store4, x, ys, s.plane_w, s.plane_h, c, kept, s.max_v, s.band_shift, m);
+                else sao16::block<2, 8, true>(fetch, store4, x, ys, s.plane_w, s.plane_h, c, kept, s.max_v, s.band_shift, m);
+            } else {
+                sao16::block<2, NROWS, true>(fetch, store4, x, ys, s.plane_w, s.plane_h, c, kept, s.max_v, s.band_shift, m);
+            }
+            return;
+        }
         auto store = [&](int r, uint32_t d0, uint32_t d1, uint32_t d2, uint32_t d3) {
             u32x4 w;
             w.x = d0; w.y = d1; w.z = d2; w.w = d3;
@@ -535,5 +605,39 @@ __global__ __launch_bounds__(SB == 1 ? kFusedThreads : kFused16Threads) void dbk
     } else {
         if (pl == 0) fused_body16<false, 2, WIDE, true, 1, true, true>(fa.d.base, &fa.d, fa.s, fa.g, fused_tile, id, &nx.pl[0], &sl);
         else fused_body16<true, 2, false, true, CF, true, true>(fa.d.base, &fa.d, fa.s, fa.g, fused_tile, id, &nx.pl[pl], &sl);
+    }
+}
+
+/* ---- the _sl kernels for planes whose sizes are multiples of 4 (the _g4 entries; deblock_h265.h load_block_bs_h265_g4): kernels of
+ * their own names once more.  Chroma planes only have such sizes; in the multi-plane launch the luma plane runs the same body, for
+ * which its multiple-of-8 size is the special case and which adds the launch's own (beta, tC) pair to the per-slice ones
+ * (sl_block_operands): a call without per-slice offsets hands in an array of no bytes ---- */
+template <int CF>
+__global__ __launch_bounds__(kFusedThreads) void dbk_sao_fused_h265_g4_kernel(const DbkFusedH265Args fa, const DbkSaoNox nx, const DbkSlOffs sl)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t fused_tile[];
+    fused_body<true, 2, true, CF, true, true, true>(fa.d.base, &fa.d, fa.s, fa.g, fused_tile, blockIdx.x, &nx, &sl);
+}
+template <int CF>
+__global__ __launch_bounds__(kFused16Threads) void dbk_sao_fused16_h265_g4_kernel(const DbkFusedH265Args fa, const DbkSaoNox nx, const DbkSlOffs sl)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t fused_tile[];
+    fused_body16<true, 2, false, true, CF, true, true, true>(fa.d.base, &fa.d, fa.s, fa.g, fused_tile, blockIdx.x, &nx, &sl);
+}
+template <int SB, bool WIDE, int CF>
+__global__ __launch_bounds__(SB == 1 ? kFusedThreads : kFused16Threads) void dbk_sao_fused_multi_h265_g4_kernel(const DbkFusedMultiH265Args m,
+                                                                                                                const DbkSaoNox3 nx,
+                                                                                                                const DbkSlOffs sl)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t fused_tile[];
+    uint32_t id;
+    const int pl = fused_plane(m.wg_end, id);
+    const DbkFusedH265Args &fa = m.pl[pl];
+    if constexpr (SB == 1) {
+        if (pl == 0) fused_body<false, 2, true, 1, true, true, true>(fa.d.base, &fa.d, fa.s, fa.g, fused_tile, id, &nx.pl[0], &sl);
+        else fused_body<true, 2, true, CF, true, true, true>(fa.d.base, &fa.d, fa.s, fa.g, fused_tile, id, &nx.pl[pl], &sl);
+    } else {
+        if (pl == 0) fused_body16<false, 2, WIDE, true, 1, true, true, true>(fa.d.base, &fa.d, fa.s, fa.g, fused_tile, id, &nx.pl[0], &sl);
+        else fused_body16<true, 2, false, true, CF, true, true, true>(fa.d.base, &fa.d, fa.s, fa.g, fused_tile, id, &nx.pl[pl], &sl);
     }
 }

@@ -101,12 +101,114 @@ __device__ __forceinline__ uint32_t sao_nox_bit(int dcx, int dcy)
     return dcy < 0 ? (dcx < 0 ? UL : (dcx > 0 ? UR : U)) : (dcy > 0 ? (dcx < 0 ? DL : (dcx > 0 ? DR : D)) : (dcx < 0 ? L : (dcx > 0 ? R : 0u)));
 }
 
+
+/* One block of the _g4 kernels (planes whose sizes are multiples of 4, not 8): 8 or 4 columns by 8 or 4 rows at (x, y0), the short
+ * ones being the last of their row / column of blocks.  The per-sample procedure of sao_kernel_body.inc with every position tested
+ * against the picture (a neighbour outside plane_w x plane_h: no offset, 8.7.3.2) and against the CTB's boundary byte `nox`
+ * (0 = nothing forbidden); a narrow block moves 4 samples per row -- nothing beyond plane_w is read or written -- a short one 4 rows */
+template <typename T>
+__device__ __forceinline__ void sao_block_g4(const DbkSaoArgs &a, uint32_t nox, const uint8_t *src, uint8_t *dst, int x, int y0,
+                                             const DbkSaoCtb &c, bool kept)
+{
+    using W = typename Q4<T>::W;
+    const bool w8 = x + 8 <= a.plane_w;
+    const int nr = y0 + 8 <= a.plane_h ? 8 : 4;
+    auto ld8 = [&](const uint8_t *row, int (&o)[8]) {
+        int c0[4], c1[4];
+        Q4<T>::unpack(*reinterpret_cast<const W *>(row + (size_t)x * sizeof(T)), c0);
+        Q4<T>::unpack(*reinterpret_cast<const W *>(row + (size_t)(w8 ? x + 4 : x) * sizeof(T)), c1); /* narrow: never used */
+#pragma unroll
+        for (int i = 0; i < 4; i++) { o[i] = c0[i]; o[4 + i] = c1[i]; }
+    };
+    auto st8 = [&](uint8_t *row, const int (&o)[8]) {
+        const int lo[4] = {o[0], o[1], o[2], o[3]}, hi[4] = {o[4], o[5], o[6], o[7]};
+        *reinterpret_cast<W *>(row + (size_t)x * sizeof(T)) = Q4<T>::pack(lo);
+        if (w8) *reinterpret_cast<W *>(row + (size_t)(x + 4) * sizeof(T)) = Q4<T>::pack(hi);
+    };
+    if (kept || c.type == 0 || c.type > 2) {
+#pragma unroll
+        for (int r = 0; r < 8; r++)
+            if (r < nr) {
+                int o[8];
+                ld8(src + (long long)(y0 + r) * a.pitch, o);
+                st8(dst + (long long)(y0 + r) * a.pitch, o);
+            }
+        return;
+    }
+    if (c.type == 1) { /* band offset: bandTable[(k + sao_band_position) & 31] = k + 1 */
+#pragma unroll
+        for (int r = 0; r < 8; r++)
+            if (r < nr) {
+                int o[8];
+                ld8(src + (long long)(y0 + r) * a.pitch, o);
+#pragma unroll
+                for (int i = 0; i < 8; i++) {
+                    const int k = ((o[i] >> a.band_shift) - (int)c.cls) & 31;
+                    const int off = k == 0 ? c.offset[0] : (k == 1 ? c.offset[1] : (k == 2 ? c.offset[2] : (k == 3 ? c.offset[3] : 0)));
+                    const int v = o[i] + off;
+                    o[i] = v < 0 ? 0 : (v > a.max_v ? a.max_v : v);
+                }
+                st8(dst + (long long)(y0 + r) * a.pitch, o);
+            }
+        return;
+    }
+    /* edge offset, Table 8-13: class 0 (-1,0)/(1,0); 1 (0,-1)/(0,1); 2 (-1,-1)/(1,1); 3 (1,-1)/(-1,1) */
+    const int cls = c.cls & 3;
+    const int dxa = cls == 1 ? 0 : (cls == 3 ? 1 : -1);
+    const bool vertical = cls != 0;
+    const int dya = vertical ? -1 : 0;
+    auto row_at = [&](int y) { return src + (long long)(y < 0 ? 0 : (y >= a.plane_h ? a.plane_h - 1 : y)) * a.pitch; };
+    /* samples x-1 .. x+8 of a row; positions outside the row hold junk that no sample inside the picture uses */
+    auto ld10 = [&](const uint8_t *row, int (&o)[10]) {
+        int m[8], l[4], r[4];
+        ld8(row, m);
+        Q4<T>::unpack(*reinterpret_cast<const W *>(row + (size_t)(x >= 4 ? x - 4 : 0) * sizeof(T)), l);
+        Q4<T>::unpack(*reinterpret_cast<const W *>(row + (size_t)(x + 12 <= a.plane_w ? x + 8 : a.plane_w - 4) * sizeof(T)), r);
+        o[0] = l[3];
+#pragma unroll
+        for (int i = 0; i < 8; i++) o[1 + i] = m[i];
+        o[9] = r[0];
+    };
+    int up[10], mid[10], dn[10];
+    ld10(row_at(y0 - 1), up);
+    ld10(row_at(y0), mid);
+#pragma unroll
+    for (int r = 0; r < 8; r++) {
+        if (r < nr) {
+            const int y = y0 + r;
+            ld10(row_at(y + 1), dn);
+            const bool rows_ok = !vertical || (y > 0 && y < a.plane_h - 1);
+            int o[8];
+#pragma unroll
+            for (int i = 0; i < 8; i++) {
+                const int rec = mid[1 + i];
+                const int xa = x + i + dxa, xb = x + i - dxa;
+                bool ok = rows_ok && xa >= 0 && xa < a.plane_w && xb >= 0 && xb < a.plane_w;
+                const int L2 = a.ctb_log2, cx = (x + i) >> L2, cy = y >> L2; /* per sample: the CTB either neighbour lies in, against the byte */
+                ok = ok && !(nox & (sao_nox_bit((xa >> L2) - cx, ((y + dya) >> L2) - cy) | sao_nox_bit((xb >> L2) - cx, ((y - dya) >> L2) - cy)));
+                const int (&ra)[10] = vertical ? up : mid;
+                const int (&rb)[10] = vertical ? dn : mid;
+                const int na = dxa < 0 ? ra[i] : (dxa == 0 ? ra[1 + i] : ra[2 + i]);
+                const int nb = dxa < 0 ? rb[2 + i] : (dxa == 0 ? rb[1 + i] : rb[i]);
+                const int e = 2 + sgn(rec - na) + sgn(rec - nb);
+                const int off = e == 0 ? c.offset[0] : (e == 1 ? c.offset[1] : (e == 3 ? c.offset[2] : (e == 4 ? c.offset[3] : 0)));
+                const int v = rec + (ok ? off : 0);
+                o[i] = v < 0 ? 0 : (v > a.max_v ? a.max_v : v);
+            }
+            st8(dst + (long long)y * a.pitch, o);
+#pragma unroll
+            for (int i = 0; i < 10; i++) { up[i] = mid[i]; mid[i] = dn[i]; }
+        }
+    }
+}
+
 /* PK16: 16-bit containers up to 12 bit take the packed block procedure in waves off the border.  The body is written once
  * (sao_kernel_body.inc) for the kernel and its _nox twin */
 template <typename T, bool SWZ, bool PK16 = false>
 __global__ __launch_bounds__(256) void sao_kernel(const DbkSaoArgs a, const DbkFusedGrid g)
 {
     constexpr bool NOX = false;
+    [[maybe_unused]] constexpr bool G4 = false;
     [[maybe_unused]] const DbkSaoNox nx = {};
 #include "sao_kernel_body.inc"
 }
@@ -114,6 +216,15 @@ template <typename T, bool SWZ, bool PK16 = false>
 __global__ __launch_bounds__(256) void sao_nox_kernel(const DbkSaoArgs a, const DbkFusedGrid g, const DbkSaoNox nx)
 {
     constexpr bool NOX = true;
+    [[maybe_unused]] constexpr bool G4 = false;
+#include "sao_kernel_body.inc"
+}
+/* planes whose sizes are multiples of 4, not 8 (the _g4 entries): the _nox twin's twin; nx.nox may be NULL */
+template <typename T, bool SWZ, bool PK16 = false>
+__global__ __launch_bounds__(256) void sao_g4_kernel(const DbkSaoArgs a, const DbkFusedGrid g, const DbkSaoNox nx)
+{
+    constexpr bool NOX = true;
+    [[maybe_unused]] constexpr bool G4 = true;
 #include "sao_kernel_body.inc"
 }
 
@@ -240,6 +351,7 @@ template <bool SWZ, int WAVES>
 __global__ __launch_bounds__(64 * WAVES) void sao8_kernel(const DbkSaoArgs a, const DbkFusedGrid g)
 {
     constexpr bool NOX = false;
+    [[maybe_unused]] constexpr bool G4 = false;
     [[maybe_unused]] const DbkSaoNox nx = {};
 #include "sao8_kernel_body.inc"
 }
@@ -247,6 +359,14 @@ template <bool SWZ, int WAVES>
 __global__ __launch_bounds__(64 * WAVES) void sao8_nox_kernel(const DbkSaoArgs a, const DbkFusedGrid g, const DbkSaoNox nx)
 {
     constexpr bool NOX = true;
+    [[maybe_unused]] constexpr bool G4 = false;
+#include "sao8_kernel_body.inc"
+}
+template <bool SWZ, int WAVES>
+__global__ __launch_bounds__(64 * WAVES) void sao8_g4_kernel(const DbkSaoArgs a, const DbkFusedGrid g, const DbkSaoNox nx)
+{
+    constexpr bool NOX = true;
+    [[maybe_unused]] constexpr bool G4 = true;
 #include "sao8_kernel_body.inc"
 }
 
@@ -338,6 +458,44 @@ hipError_t dbk_launch_sao(const DbkSaoArgs &a, int sample_bytes, hipStream_t str
         if (swz && pk16) hipLaunchKernelGGL((sao_kernel<uint16_t, true, true>), grid, block, 0, stream, a, g);
         else if (swz) hipLaunchKernelGGL((sao_kernel<uint16_t, true>), grid, block, 0, stream, a, g);
         else hipLaunchKernelGGL((sao_kernel<uint16_t, false>), grid, block, 0, stream, a, g);
+    }
+    return hipGetLastError();
+}
+
+/* planes whose sizes are multiples of 4 (the _g4 entries): dbk_launch_sao's grid and choice of kernel without its demand for multiples
+ * of 8, the _g4 kernels; nxp == NULL: no boundary bytes */
+hipError_t dbk_launch_sao_g4(const DbkSaoArgs &a, int sample_bytes, hipStream_t stream, const DbkSaoNox *nxp)
+{
+    if (a.n_frames <= 0 || a.plane_w <= 0 || a.plane_h <= 0) return hipSuccess;
+    const bool small = (unsigned long long)a.pitch * (unsigned long long)a.plane_h < (1ull << 31); /* 32-bit buffer offsets */
+    const bool aligned8 = a.pitch % 8 == 0 && a.frame_stride % 8 == 0 && ((uintptr_t)a.src % 8) == 0 && ((uintptr_t)a.dst % 8) == 0 &&
+                          a.max_v == 255 && a.band_shift == 3 && small;
+    const dim3 block(256, 1, 1), grid3((a.plane_w + 255) / 256, (a.plane_h + 63) / 64, a.n_frames);
+    DbkFusedGrid g = {};
+    const unsigned long long tx = grid3.x, tpf = tx * grid3.y, total = tpf * (unsigned long long)a.n_frames;
+    const bool swz = total + 8 < (1ull << 31) && (total + 8) * tpf < (1ull << 32) && tpf * tx < (1ull << 32);
+    if (swz) {
+        g.tiles_x = (uint32_t)tx;
+        g.tiles_per_frame = (uint32_t)tpf;
+        g.total = (uint32_t)total;
+        g.magic_tpf = tpf <= 1 ? 0u : (uint32_t)((1ull << 32) / tpf + 1ull);
+        g.magic_tx = tx <= 1 ? 0u : (uint32_t)((1ull << 32) / tx + 1ull);
+        g.per_xcd = (uint32_t)((total + 7) / 8);
+    }
+    const dim3 grid = swz ? dim3(g.per_xcd * 8u, 1, 1) : grid3;
+    const DbkSaoNox nx = nxp ? *nxp : DbkSaoNox{nullptr, 0, 0};
+    if (sample_bytes == 1 && aligned8) {
+        if (swz) hipLaunchKernelGGL((sao8_g4_kernel<true, 4>), grid, block, 0, stream, a, g, nx);
+        else hipLaunchKernelGGL((sao8_g4_kernel<false, 4>), grid, block, 0, stream, a, g, nx);
+    } else if (sample_bytes == 1) {
+        if (swz) hipLaunchKernelGGL((sao_g4_kernel<uint8_t, true>), grid, block, 0, stream, a, g, nx);
+        else hipLaunchKernelGGL((sao_g4_kernel<uint8_t, false>), grid, block, 0, stream, a, g, nx);
+    } else {
+        const bool pk16 = a.max_v <= 4095 && a.band_shift >= 3 && (1 << (a.band_shift + 5)) - 1 == a.max_v && a.pitch % 4 == 0 &&
+                          a.frame_stride % 4 == 0 && ((uintptr_t)a.src % 4) == 0 && ((uintptr_t)a.dst % 4) == 0 && small;
+        if (swz && pk16) hipLaunchKernelGGL((sao_g4_kernel<uint16_t, true, true>), grid, block, 0, stream, a, g, nx);
+        else if (swz) hipLaunchKernelGGL((sao_g4_kernel<uint16_t, true>), grid, block, 0, stream, a, g, nx);
+        else hipLaunchKernelGGL((sao_g4_kernel<uint16_t, false>), grid, block, 0, stream, a, g, nx);
     }
     return hipGetLastError();
 }

@@ -1,5 +1,6 @@
 /* sao8_kernel_body.inc -- the body of sao8_kernel / sao8_nox_kernel, included by sao.hip once for the kernel without the slice / tile boundary operand (NOX false: nx is
- * not looked at) and once for its _nox twin (NOX true; H.265 8.7.3.2).  Written once and compiled into two kernels of their own
+ * not looked at) and once for its _nox twin (NOX true; H.265 8.7.3.2), and a third time for the _nox twin's _g4 twin (G4 true: a plane
+ * whose sizes are multiples of 4, whose boundary bytes may be absent).  Written once and compiled into two kernels of their own
  * argument lists, so that the kernel without the operand is the same machine code with or without the twin beside it (a shared
  * __device__ body taking the arguments by reference was compiled to other code than the kernel had before). */
     int wx, wy, f;
@@ -33,7 +34,8 @@
     const uint8_t *src = a.src + (long long)f * a.frame_stride;
     uint8_t *dst = a.dst + (long long)f * a.frame_stride;
     [[maybe_unused]] uint32_t nox_byte = 0u;
-    if constexpr (NOX) nox_byte = saonox::ctb_byte(nx, f, x, y0, a.ctb_log2);
+    if constexpr (NOX && G4) nox_byte = nx.nox ? saonox::ctb_byte(nx, f, x, y0, a.ctb_log2) : 0u; /* no bytes: nothing forbidden */
+    else if constexpr (NOX) nox_byte = saonox::ctb_byte(nx, f, x, y0, a.ctb_log2);
     const DbkSaoCtb c = a.params[(long long)f * a.params_frame_stride + (long long)(y0 >> a.ctb_log2) * a.params_stride + (x >> a.ctb_log2)];
     const bool kept = a.keep && a.keep[(long long)f * a.keep_frame_stride + (long long)(y0 >> 3) * a.keep_stride + (x >> 3)];
     bool border = x == 0 || x + 8 == a.plane_w || y0 == 0 || y0 + 8 >= a.plane_h;
@@ -85,6 +87,15 @@
         }
         sao8::block<false, 8>(fetch, store, x, y0, a.plane_w, a.plane_h, c, kept);
         return;
+    }
+    if constexpr (G4) {
+        /* a wave that holds a block of 4 columns or 4 rows (the last column / row of blocks of a plane whose size is a multiple
+         * of 4, not 8: border blocks all of them): the masked per-sample procedure for the whole wave.  Every other wave --
+         * the border waves of whole blocks among them -- runs what it runs for a multiple of 8 */
+        if (__builtin_amdgcn_ballot_w64(x + 8 > a.plane_w || y0 + 8 > a.plane_h) != 0ull) {
+            sao_block_g4<uint8_t>(a, nox_byte, src, dst, x, y0, c, kept);
+            return;
+        }
     }
     if (kept || c.type == 0 || c.type > 2) {
 #pragma unroll

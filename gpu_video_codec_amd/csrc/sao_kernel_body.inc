@@ -1,5 +1,6 @@
 /* sao_kernel_body.inc -- the body of sao_kernel / sao_nox_kernel, included by sao.hip once for the kernel without the slice / tile boundary operand (NOX false: nx is
- * not looked at) and once for its _nox twin (NOX true; H.265 8.7.3.2).  Written once and compiled into two kernels of their own
+ * not looked at) and once for its _nox twin (NOX true; H.265 8.7.3.2), and a third time for the _nox twin's _g4 twin (G4 true: a plane
+ * whose sizes are multiples of 4, whose boundary bytes may be absent).  Written once and compiled into two kernels of their own
  * argument lists, so that the kernel without the operand is the same machine code with or without the twin beside it (a shared
  * __device__ body taking the arguments by reference was compiled to other code than the kernel had before). */
     /* a wave = the 8 x 8 blocks of one 64 x 64 region: with 64-sample CTBs every lane of a wave has the same SAO type and the
@@ -19,7 +20,8 @@
          * (sao_packed.h, sao16: the samples already are int16 pairs) on rows addressed through buffer resources, as the 8-bit
          * kernel below does; a region's row piece is a whole 128-byte line here, so the wave keeps its 64 x 64 shape */
         bool border = x == 0 || x + 8 == a.plane_w || y0 == 0 || y0 + 8 >= a.plane_h;
-        if constexpr (NOX) border = saonox::block_mask<8>(saonox::ctb_byte(nx, f, x, y0, a.ctb_log2), x, y0, a.plane_w, a.plane_h, a.ctb_log2) != 0u; /* the picture border included */
+        if constexpr (NOX && G4) border = saonox::block_mask<8>(nx.nox ? saonox::ctb_byte(nx, f, x, y0, a.ctb_log2) : 0u, x, y0, a.plane_w, a.plane_h, a.ctb_log2) != 0u; /* a block of 4 columns / rows is a border block */
+        else if constexpr (NOX) border = saonox::block_mask<8>(saonox::ctb_byte(nx, f, x, y0, a.ctb_log2), x, y0, a.plane_w, a.plane_h, a.ctb_log2) != 0u; /* the picture border included */
         if (__builtin_amdgcn_ballot_w64(border) == 0ull) {
             typedef uint32_t u32x4b __attribute__((ext_vector_type(4)));
             const uint32_t plane_bytes = (uint32_t)a.pitch * (uint32_t)a.plane_h; /* < 2^31: checked by the launcher */
@@ -52,6 +54,10 @@
             sao16::block<false, 8>(fetch, store, x, y0, a.plane_w, a.plane_h, c, kept, a.max_v, a.band_shift);
             return;
         }
+    }
+    if constexpr (G4) { /* the same procedure for blocks of 8 or 4 columns and rows (sao_block_g4) */
+        sao_block_g4<T>(a, nx.nox ? saonox::ctb_byte(nx, f, x, y0, a.ctb_log2) : 0u, src, dst, x, y0, c, kept);
+        return;
     }
     if (kept || c.type == 0 || c.type > 2) {
 #pragma unroll

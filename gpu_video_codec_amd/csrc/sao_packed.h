@@ -20,6 +20,9 @@
  */
 namespace saonox {
 constexpr uint32_t L = 0x01u, R = 0x02u, U = 0x04u, D = 0x08u, UL = 0x10u, UR = 0x20u, DL = 0x40u, DR = 0x80u;
+/* a block mask's own bit (never in a CTB's byte), looked at by the _g4 kernels only: the block is 4 samples wide -- the last block of
+ * a row of a plane whose width is a multiple of 4, not 8 -- so the picture ends behind its sample 3 */
+constexpr uint32_t W4 = 0x100u;
 
 /* the byte of the CTB holding sample (x, y0) of frame f.  Asked for next to the CTB's SAO parameters -- ahead of them -- so that
  * the two requests are in flight together: the wave's ballot over the masks waits for the byte */
@@ -51,7 +54,7 @@ __device__ __forceinline__ uint32_t block_mask(uint32_t b, int x, int y0, int w,
 /* row r of a block with mask m, class CLS: the selectors of the samples that must not be offset forced to "none".  Both packed
  * layouts keep sample 0 in the low half of i0 and sample 7 in the high half of i3; samples 1..6 -- the rest -- share their fate:
  * their neighbours lie in the row above / below only */
-template <int CLS, int NROWS>
+template <int CLS, int NROWS, bool G4 = false>
 __device__ __forceinline__ void mask_row(uint32_t m, int r, uint32_t &i0, uint32_t &i1, uint32_t &i2, uint32_t &i3)
 {
     constexpr uint32_t none = 0x0c020c02u; /* index 2 in both halves + the selector constant (sao8::kSel) */
@@ -74,6 +77,11 @@ __device__ __forceinline__ void mask_row(uint32_t m, int r, uint32_t &i0, uint32
     }
     if (s0) i0 = (i0 & 0xffff0000u) | (none & 0x0000ffffu);
     if (s7) i3 = (i3 & 0x0000ffffu) | (none & 0xffff0000u);
+    if constexpr (G4 && CLS != 1) {
+        /* a block of 4 samples: sample 3 (the high half of i1 in both layouts) has a neighbour of every class but the vertical one
+         * at x + 4, outside the picture; the vertical class is covered by `vert`.  Samples 4..7 are not stored */
+        if (m & W4) i1 = (i1 & 0x0000ffffu) | (none & 0xffff0000u);
+    }
 }
 } /* namespace saonox */
 
@@ -157,7 +165,7 @@ __device__ __forceinline__ uint32_t band_sel(uint32_t rec, int shift, spk pos)
  * a sample with a neighbour outside the picture gets no offset (8.7.3.2), whatever the raw rows hold there; BORDER 2: the same
  * for every direction of the block's mask m (saonox::block_mask: picture border, slice and tile boundaries).
  * store(r, lo, hi) takes output row r as its two dwords. */
-template <int CLS, int BORDER, int NROWS, typename Fetch, typename Store>
+template <int CLS, int BORDER, int NROWS, bool G4 = false, typename Fetch, typename Store>
 __device__ __forceinline__ void edge_rows(const Fetch &fetch, const Store &store, int x, int y0, int w, int h, uint32_t tab_lo,
                                           uint32_t tab_hi, uint32_t m = 0u)
 {
@@ -190,7 +198,7 @@ __device__ __forceinline__ void edge_rows(const Fetch &fetch, const Store &store
             i2 = edge_idx(mid.E1, up.O1, dn.lE1);
             i3 = edge_idx(mid.O1, up.rO1, dn.E1);
         }
-        if constexpr (BORDER == 2) saonox::mask_row<CLS, NROWS>(m, r, i0, i1, i2, i3);
+        if constexpr (BORDER == 2) saonox::mask_row<CLS, NROWS, G4>(m, r, i0, i1, i2, i3);
         if constexpr (BORDER == 1) {
             if (vertical && (y == 0 || y == h - 1)) i0 = i1 = i2 = i3 = 0x00020002u | sao8::kSel;
             if (horizontal && x == 0) i0 = (i0 & 0xffff0000u) | 0x0c02u;              /* sample 0: low half of E0 */
@@ -211,7 +219,7 @@ __device__ __forceinline__ void edge_rows(const Fetch &fetch, const Store &store
  * samples -- one CTB of 64, i.e. ONE path per wave; NROWS = 2: a wave covers 32 x 32 samples, one CTB of 32 (every chroma CTB
  * of a 4:2:0 picture with 64-sample luma CTBs) -- the same, where 8-row lanes would spread a wave over four CTBs and run every
  * path that occurs among them with a quarter of its lanes. */
-template <int BORDER, int NROWS = 8, typename Fetch, typename Store>
+template <int BORDER, int NROWS = 8, bool G4 = false /* the _g4 kernels: m may carry saonox::W4 */, typename Fetch, typename Store>
 __device__ __forceinline__ void block(const Fetch &fetch, const Store &store, int x, int y0, int w, int h, const DbkSaoCtb &c, bool kept, uint32_t m = 0u)
 {
     if (kept || c.type == 0 || c.type > 2) {
@@ -239,10 +247,10 @@ __device__ __forceinline__ void block(const Fetch &fetch, const Store &store, in
     /* edge offset: index 0 -> SaoOffsetVal[1], 1 -> [2], 2 -> none, 3 -> [3], 4 -> [4] */
     const uint32_t tab_lo = b(c.offset[0]) | (b(c.offset[1]) << 8) | (b(0) << 16) | (b(c.offset[2]) << 24), tab_hi = b(c.offset[3]);
     const int cls = c.cls & 3;
-    if (cls == 0) edge_rows<0, BORDER, NROWS>(fetch, store, x, y0, w, h, tab_lo, tab_hi, m);
-    else if (cls == 1) edge_rows<1, BORDER, NROWS>(fetch, store, x, y0, w, h, tab_lo, tab_hi, m);
-    else if (cls == 2) edge_rows<2, BORDER, NROWS>(fetch, store, x, y0, w, h, tab_lo, tab_hi, m);
-    else edge_rows<3, BORDER, NROWS>(fetch, store, x, y0, w, h, tab_lo, tab_hi, m);
+    if (cls == 0) edge_rows<0, BORDER, NROWS, G4>(fetch, store, x, y0, w, h, tab_lo, tab_hi, m);
+    else if (cls == 1) edge_rows<1, BORDER, NROWS, G4>(fetch, store, x, y0, w, h, tab_lo, tab_hi, m);
+    else if (cls == 2) edge_rows<2, BORDER, NROWS, G4>(fetch, store, x, y0, w, h, tab_lo, tab_hi, m);
+    else edge_rows<3, BORDER, NROWS, G4>(fetch, store, x, y0, w, h, tab_lo, tab_hi, m);
 }
 
 } /* namespace sao8 */
@@ -298,7 +306,7 @@ __device__ __forceinline__ uint32_t apply(uint32_t rec, uint32_t idx /* + sao8::
 }
 using sao8::edge_idx;
 
-template <int CLS, int BORDER, int NROWS, typename Fetch, typename Store>
+template <int CLS, int BORDER, int NROWS, bool G4 = false, typename Fetch, typename Store>
 __device__ __forceinline__ void edge_rows(const Fetch &fetch, const Store &store, int x, int y0, int w, int h, const Tab &t, uint32_t m = 0u)
 {
     constexpr bool horizontal = CLS != 1, vertical = CLS != 0;
@@ -330,7 +338,7 @@ __device__ __forceinline__ void edge_rows(const Fetch &fetch, const Store &store
             i2 = edge_idx(mid.P2, up.L3, dn.L2);
             i3 = edge_idx(mid.P3, up.R3, dn.L3);
         }
-        if constexpr (BORDER == 2) saonox::mask_row<CLS, NROWS>(m, r, i0, i1, i2, i3);
+        if constexpr (BORDER == 2) saonox::mask_row<CLS, NROWS, G4>(m, r, i0, i1, i2, i3);
         if constexpr (BORDER == 1) { /* a neighbour outside the picture: edgeIdx 0 (8.7.3.2) */
             if (vertical && (y == 0 || y == h - 1)) i0 = i1 = i2 = i3 = 0x00020002u | sao8::kSel;
             if (horizontal && x == 0) i0 = (i0 & 0xffff0000u) | 0x0c02u;              /* sample 0: low half of P0 */
@@ -344,7 +352,7 @@ __device__ __forceinline__ void edge_rows(const Fetch &fetch, const Store &store
 
 /* one block of 8 x NROWS 16-bit samples (NROWS = 8, or 2 for 32-sample CTBs: see sao8::block); fetch(i) = raw row i = image
  * row y0 - 1 + i; store(r, four dwords) */
-template <int BORDER, int NROWS = 8, typename Fetch, typename Store>
+template <int BORDER, int NROWS = 8, bool G4 = false, typename Fetch, typename Store>
 __device__ __forceinline__ void block(const Fetch &fetch, const Store &store, int x, int y0, int w, int h, const DbkSaoCtb &c, bool kept,
                                       int max_v, int band_shift, uint32_t m = 0u)
 {
@@ -378,10 +386,10 @@ __device__ __forceinline__ void block(const Fetch &fetch, const Store &store, in
     t.lo = b(c.offset[0]) | (b(c.offset[1]) << 8) | (0x80u << 16) | (b(c.offset[2]) << 24);
     t.hi = b(c.offset[3]);
     const int cls = c.cls & 3;
-    if (cls == 0) edge_rows<0, BORDER, NROWS>(fetch, store, x, y0, w, h, t, m);
-    else if (cls == 1) edge_rows<1, BORDER, NROWS>(fetch, store, x, y0, w, h, t, m);
-    else if (cls == 2) edge_rows<2, BORDER, NROWS>(fetch, store, x, y0, w, h, t, m);
-    else edge_rows<3, BORDER, NROWS>(fetch, store, x, y0, w, h, t, m);
+    if (cls == 0) edge_rows<0, BORDER, NROWS, G4>(fetch, store, x, y0, w, h, t, m);
+    else if (cls == 1) edge_rows<1, BORDER, NROWS, G4>(fetch, store, x, y0, w, h, t, m);
+    else if (cls == 2) edge_rows<2, BORDER, NROWS, G4>(fetch, store, x, y0, w, h, t, m);
+    else edge_rows<3, BORDER, NROWS, G4>(fetch, store, x, y0, w, h, t, m);
 }
 
 } /* namespace sao16 */

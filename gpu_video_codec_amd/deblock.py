@@ -344,13 +344,17 @@ class Context:
         return {"exec_s": tm.exec_s, "total_s": tm.total_s, "copy_s": tm.copy_s, "pipelined_s": tm.pipelined_s}
 
     def filter_device_h265(self, planes, qp, *, c_idx=0, tc_offset_div2=0, beta_offset_div2=0, cb_qp_offset=0, cr_qp_offset=0,
-                           variant=KERNEL_AUTO, chroma_format="420", slice_offsets=None):
+                           variant=KERNEL_AUTO, chroma_format="420", slice_offsets=None, g4=False):
         """hevc_deblocking_filter_h265_device[_cf]: a plane of a picture in chroma_format '400' / '420' / '422' / '444'.
         slice_offsets: a _lib.SliceOffsets (per-CTB slice_beta_offset_div2 / slice_tc_offset_div2, hevcdbk_h265_filter_device_sl);
-        with it tc_offset_div2 / beta_offset_div2 are not used."""
+        with it tc_offset_div2 / beta_offset_div2 are not used.  g4=True: hevcdbk_h265_filter_device_g4, which also takes a chroma
+        plane sized in multiples of 4 (960x540 of a 1920x1080 picture); without it such a plane is refused as ever."""
         cf = _lib.chroma_format_idc(chroma_format)
         prm = _lib.H265Params(tc_offset_div2, beta_offset_div2, cb_qp_offset, cr_qp_offset)
-        if slice_offsets is not None:
+        if g4:
+            rc = _lib.lib().hevcdbk_h265_filter_device_g4(self.handle, C.byref(planes), c_idx, cf, int(qp), C.byref(prm), variant,
+                                                          None if slice_offsets is None else C.byref(slice_offsets), None)
+        elif slice_offsets is not None:
             rc = _lib.lib().hevcdbk_h265_filter_device_sl(self.handle, C.byref(planes), c_idx, cf, int(qp), C.byref(prm), variant,
                                                           C.byref(slice_offsets), None)
         elif cf == _lib.CHROMA_420:
@@ -360,9 +364,10 @@ class Context:
                                                                   variant, None)
         _chk(rc, self.handle)
 
-    def derive_bs_h265(self, units, w, h, *, chroma=True, chroma_format="420"):
+    def derive_bs_h265(self, units, w, h, *, chroma=True, chroma_format="420", g4=False):
         """8.7.2.4 on the GPU from host arrays; returns (vert, hor[, chroma_vert, chroma_hor]) as host arrays; the chroma
-        arrays in the geometry of chroma_format's chroma plane (none for '400')."""
+        arrays in the geometry of chroma_format's chroma plane (none for '400').  g4=True: hevcdbk_h265_derive_bs_device_g4, whose
+        chroma plane may be sized in multiples of 4 (w x h stay multiples of 8)."""
         cf = _lib.chroma_format_idc(chroma_format)
         chroma = chroma and cf != _lib.CHROMA_400
         arrs = [np.ascontiguousarray(a, dt) for a, dt in zip(units, (np.uint16, np.int16, np.int16, np.int32, np.int32))]
@@ -376,7 +381,10 @@ class Context:
             sizes += [L.hevcdbk_h265_num_vert_bs(w // sx, h // sy), L.hevcdbk_h265_num_hor_bs(w // sx, h // sy)]
         outs = [self.alloc(max(n, 1)) for n in sizes]
         un = _lib.H265Units(*[b.ptr for b in bufs])
-        if cf == _lib.CHROMA_420:
+        if g4:
+            rc = L.hevcdbk_h265_derive_bs_device_g4(self.handle, C.byref(un), w, h, cf, outs[0].ptr, outs[1].ptr,
+                                                    outs[2].ptr if chroma else None, outs[3].ptr if chroma else None, None)
+        elif cf == _lib.CHROMA_420:
             rc = L.hevcdbk_h265_derive_bs_device(self.handle, C.byref(un), w, h, outs[0].ptr, outs[1].ptr,
                                                  outs[2].ptr if chroma else None, outs[3].ptr if chroma else None, None)
         else:
@@ -442,12 +450,18 @@ class Context:
         return res
 
     def sao_device(self, planes, params_ptr, params_stride, ctb_log2, *, params_frame_stride=0, keep_ptr=None, keep_stride=0,
-                   keep_frame_stride=0, chroma_format="420", ctb_log2_h=None, borders=None):
+                   keep_frame_stride=0, chroma_format="420", ctb_log2_h=None, borders=None, g4=False):
         """hevc_sao_filter_device[_cf]: H.265 8.7.3 on planes in HBM, src -> dst.  ctb_log2 = log2 of this plane's CTB width;
         its height follows from chroma_format (a 4:2:2 chroma plane, planes.is_chroma: twice the width) unless ctb_log2_h says.
-        borders: a _lib.SaoBorders (slice / tile boundaries not to be looked across, 8.7.3.2: hevcdbk_sao_filter_device_nox)."""
+        borders: a _lib.SaoBorders (slice / tile boundaries not to be looked across, 8.7.3.2: hevcdbk_sao_filter_device_nox).
+        g4=True: hevcdbk_sao_filter_device_g4, which also takes a plane sized in multiples of 4 (keep map and CTB grid by ceiling)."""
         cf = _lib.chroma_format_idc(chroma_format)
         lh = _ctb_log2_h(ctb_log2, ctb_log2_h, cf, planes.is_chroma)
+        if g4:
+            _chk(_lib.lib().hevcdbk_sao_filter_device_g4(self.handle, C.byref(planes), params_ptr, params_stride, params_frame_stride,
+                                                         ctb_log2, lh, keep_ptr, keep_stride, keep_frame_stride,
+                                                         None if borders is None else C.byref(borders), None), self.handle)
+            return
         if borders is not None:
             _chk(_lib.lib().hevcdbk_sao_filter_device_nox(self.handle, C.byref(planes), params_ptr, params_stride, params_frame_stride,
                                                           ctb_log2, lh, keep_ptr, keep_stride, keep_frame_stride, C.byref(borders), None),
@@ -473,13 +487,21 @@ class Context:
     def deblock_sao_h265_device(self, planes, qp, params_ptr, params_stride, ctb_log2, *, c_idx=0, tc_offset_div2=0,
                                 beta_offset_div2=0, cb_qp_offset=0, cr_qp_offset=0, params_frame_stride=0, keep_ptr=None,
                                 keep_stride=0, keep_frame_stride=0, fused=_lib.FUSED_AUTO, chroma_format="420", ctb_log2_h=None,
-                                borders=None, slice_offsets=None):
+                                borders=None, slice_offsets=None, g4=False):
         """hevc_deblock_sao_h265_device[_cf]: spec-exact deblocking (8.7.2) followed by SAO (8.7.3), src -> dst; chroma_format,
         ctb_log2 / ctb_log2_h and borders (hevcdbk_h265_deblock_sao_device_nox) as for sao_device; slice_offsets as for
-        filter_device_h265 (hevcdbk_h265_deblock_sao_device_sl)."""
+        filter_device_h265 (hevcdbk_h265_deblock_sao_device_sl); g4=True: hevcdbk_h265_deblock_sao_device_g4 (a chroma plane
+        sized in multiples of 4)."""
         cf = _lib.chroma_format_idc(chroma_format)
         lh = _ctb_log2_h(ctb_log2, ctb_log2_h, cf, c_idx != 0)
         prm = _lib.H265Params(tc_offset_div2, beta_offset_div2, cb_qp_offset, cr_qp_offset)
+        if g4:
+            _chk(_lib.lib().hevcdbk_h265_deblock_sao_device_g4(self.handle, C.byref(planes), c_idx, cf, int(qp), C.byref(prm), params_ptr,
+                                                               params_stride, params_frame_stride, ctb_log2, lh, keep_ptr, keep_stride,
+                                                               keep_frame_stride, fused, None if borders is None else C.byref(borders),
+                                                               None if slice_offsets is None else C.byref(slice_offsets), None),
+                 self.handle)
+            return
         if slice_offsets is not None:
             _chk(_lib.lib().hevcdbk_h265_deblock_sao_device_sl(self.handle, C.byref(planes), c_idx, cf, int(qp), C.byref(prm), params_ptr,
                                                                params_stride, params_frame_stride, ctb_log2, lh, keep_ptr, keep_stride,
@@ -502,7 +524,7 @@ class Context:
         _chk(rc, self.handle)
 
     def deblock_sao_device_planes(self, planes_list, qp, sao_list, *, h265=None, fused=_lib.FUSED_AUTO, tc_table=None, beta_table=None,
-                                  chroma_format="420", borders=None, slice_offsets=None):
+                                  chroma_format="420", borders=None, slice_offsets=None, g4=False):
         """hevc_deblock_sao_device_planes / hevc_deblock_sao_h265_device_planes: deblocking + SAO of Y, U, V of a batch in one
         call (one launch where the fused kernel takes every plane).  sao_list[i] = (params_ptr, params_stride, ctb_log2) or a
         dict with the optional params_frame_stride / keep / keep_stride / keep_frame_stride; h265 = None (reference-exact
@@ -510,8 +532,11 @@ class Context:
         (spec-exact mode only): '400' / '420' / '422' / '444'; ctb_log2 = log2 of the plane's CTB width, its height follows
         from the format (or a ctb_log2_h entry of the dict).  borders (spec-exact mode only): ONE _lib.SaoBorders for the
         picture (hevcdbk_h265_deblock_sao_device_planes_nox).  slice_offsets (spec-exact mode only): ONE _lib.SliceOffsets for the
-        picture (hevcdbk_h265_deblock_sao_device_planes_sl)."""
+        picture (hevcdbk_h265_deblock_sao_device_planes_sl).  g4=True (spec-exact mode only): hevcdbk_h265_deblock_sao_device_planes_g4,
+        whose chroma planes may be sized in multiples of 4 (Y 1920x1080 with Cb, Cr 960x540)."""
         cf = _lib.chroma_format_idc(chroma_format)
+        if g4 and h265 is None:
+            raise ValueError("the reference-exact mode takes multiples of 8 only: g4 needs h265=")
         if cf != _lib.CHROMA_420 and h265 is None:
             raise ValueError("the reference-exact mode is 4:2:0 only: chroma_format needs h265=")
         if borders is not None and h265 is None:
@@ -519,7 +544,7 @@ class Context:
         if slice_offsets is not None and h265 is None:
             raise ValueError("the reference-exact mode has no slices: slice_offsets needs h265=")
         arr = (_lib.DevicePlanes * len(planes_list))(*planes_list)
-        if borders is not None or slice_offsets is not None or cf != _lib.CHROMA_420 or any(isinstance(so, dict) and "ctb_log2_h" in so for so in sao_list):
+        if g4 or borders is not None or slice_offsets is not None or cf != _lib.CHROMA_420 or any(isinstance(so, dict) and "ctb_log2_h" in so for so in sao_list):
             spc = (_lib.SaoPlaneCf * len(sao_list))()
             for i, so in enumerate(sao_list):
                 d = so if isinstance(so, dict) else {"params": so[0], "params_stride": so[1], "ctb_log2": so[2]}
@@ -529,6 +554,12 @@ class Context:
                 spc[i].keep, spc[i].keep_stride, spc[i].keep_frame_stride = d.get("keep"), d.get("keep_stride", 0), d.get("keep_frame_stride", 0)
             prm = _lib.H265Params(h265.get("tc_offset_div2", 0), h265.get("beta_offset_div2", 0), h265.get("cb_qp_offset", 0),
                                   h265.get("cr_qp_offset", 0))
+            if g4:
+                _chk(_lib.lib().hevcdbk_h265_deblock_sao_device_planes_g4(self.handle, arr, len(planes_list), cf, int(qp), C.byref(prm), spc,
+                                                                          fused, None if borders is None else C.byref(borders),
+                                                                          None if slice_offsets is None else C.byref(slice_offsets),
+                                                                          None), self.handle)
+                return
             if slice_offsets is not None:
                 _chk(_lib.lib().hevcdbk_h265_deblock_sao_device_planes_sl(self.handle, arr, len(planes_list), cf, int(qp), C.byref(prm), spc,
                                                                           fused, None if borders is None else C.byref(borders),
@@ -629,18 +660,37 @@ class DeviceBatch:
         else:
             self.src = ctx.alloc(self.frame_bytes * n_frames)
             self.dst = self.src if in_place else ctx.alloc(self.frame_bytes * n_frames)
-        self.nv, self.nh = num_vert_bs(plane_w, plane_h), num_hor_bs(plane_w, plane_h)
         self.per_frame_bs = per_frame_bs
         nb = n_frames if per_frame_bs else 1
+        if plane_w % 8 or plane_h % 8:
+            # a plane sized in multiples of 4 (the g4= calls of the spec-exact mode): the reference-exact mode and its default bS do
+            # not exist for it; the arrays are the spec-exact mode's 4-sample-granular ones, all zero until set_bs()
+            L = _lib.lib()
+            self.nv, self.nh = int(L.hevcdbk_h265_num_vert_bs(plane_w, plane_h)), int(L.hevcdbk_h265_num_hor_bs(plane_w, plane_h))
+            dv, dh = np.zeros(self.nv, np.uint8), np.zeros(self.nh, np.uint8)
+        else:
+            self.nv, self.nh = num_vert_bs(plane_w, plane_h), num_hor_bs(plane_w, plane_h)
+            dv, dh = default_bs(plane_w, plane_h)
         self.vert = ctx.alloc(self.nv * nb)
         self.hor = ctx.alloc(self.nh * nb)
-        dv, dh = default_bs(plane_w, plane_h)
         self.vert.upload(np.tile(dv, nb))
         self.hor.upload(np.tile(dh, nb))
         self.qp_map = None
         self.map_stride = 0
         self.map_frame_stride = 0
         self.ctu_log2 = 6
+
+    @property
+    def keep_shape(self):
+        """(rows, columns) of the plane's SAO keep map, one byte per 8 x 8 samples: by ceiling, so that the last byte of a row or
+        column of a plane sized in multiples of 4 (the g4= calls) speaks for 4 samples; plane / 8 for multiples of 8"""
+        return (self.h + 7) // 8, (self.w + 7) // 8
+
+    def ctb_shape(self, ctb_log2_w, ctb_log2_h=None):
+        """(rows, columns) of the plane's CTB grid for CTBs of (1 << ctb_log2_w) x (1 << ctb_log2_h) samples, by ceiling: the last
+        CTB of a row or column may be cut"""
+        lh = ctb_log2_w if ctb_log2_h is None else ctb_log2_h
+        return (self.h + (1 << lh) - 1) >> lh, (self.w + (1 << ctb_log2_w) - 1) >> ctb_log2_w
 
     def _pitched(self, a, fill=0):
         """(.., h, w) samples -> (.., h, pitch/sb) with `fill` in the row padding"""

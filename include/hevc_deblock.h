@@ -696,6 +696,65 @@ HEVCDBK_API int hevcdbk_h265_deblock_sao_device_planes_sl(hevcdbk_context *ctx, 
                                                           const hevcdbk_sao_plane_cf *sao, int fused, const hevcdbk_sao_borders *borders,
                                                           const hevcdbk_h265_slice_offsets *slice_offsets, void *hip_stream);
 
+/* ==================================================================================================================
+ * Planes sized in multiples of 4, not 8: the chroma planes of a 1920x1080 picture (the _g4 entries).
+ *
+ * An HEVC picture is a multiple of MinCbSizeY (>= 8) luma samples, so its 4:2:0 chroma planes are multiples of 4: 1920x1080 has
+ * chroma planes of 960x540, and 540 = 67 * 8 + 4.  Every entry above demands multiples of 8 (plane_w % 8 == 0 && plane_h % 8 == 0, the
+ * restriction stated for hevcdbk_device_planes) and keeps demanding them; the _g4 entries below have the SAME signatures as the
+ * entries they extend and differ only in the plane sizes they accept.  A "g4 plane" has plane_w and plane_h that are multiples of 4
+ * and at least 8.  Everything is stated in the plane's own sample coordinates:
+ *   - the vertical edge x = 8k is filtered iff 0 < 8k < plane_w, the horizontal edge y = 8k iff 0 < 8k < plane_h.  For plane_w = 8k + 4
+ *     the edge at x = 8k is an ordinary edge whose Q side is four samples wide: exactly the four samples 8.7.2.5 reads;
+ *   - hevcdbk_h265_num_vert_bs / _num_hor_bs and the entry positions do not change ((W/8+1) x (H/4) and (H/8+1) x (W/4) with floor
+ *     division): column plane_w/8 of the vertical array and row plane_h/8 of the horizontal array now hold a real edge.  Chroma
+ *     entries are still the luma entry at (8 bx SubWidthC, 4 y4 SubHeightC) and its counterpart; only bS 2 filters;
+ *   - QpY, QpC, KEEP_P / KEEP_Q, the offsets and slice_offsets (the CTB at the luma position of q0,0): as for every plane;
+ *   - SAO: the CTB grid is ceil(plane / CTB) and the last CTB may be cut to a multiple of 4; the keep map has ceil(plane_w/8) bytes
+ *     per row and ceil(plane_h/8) rows, the last byte of a row or column speaking for 4 samples; a sample whose edge-offset
+ *     neighbour lies outside plane_w x plane_h is copied (8.7.3.2) -- which is why a caller cannot pad the planes to a multiple of
+ *     8 instead: deblocking of the padded plane is right, SAO of its last row or column is not; band offset and `borders` as ever.
+ * Accepted: the deblocking entries take g4 CHROMA planes (c_idx 1, 2) of 4:2:0, 4:2:2 and 4:4:4 pictures; a luma plane must stay
+ * a multiple of 8 (HEVC produces nothing else) and returns HEVCDBK_ERR_DIMENSIONS.  The SAO entry takes any g4 plane.  A size that
+ * is not a multiple of 4, or is below 8, returns HEVCDBK_ERR_DIMENSIONS before anything is enqueued.  With multiples of 8 a _g4 entry
+ * IS the entry it extends: the same kernels, byte for byte.  A g4 plane runs the _g4 twins of the same kernel families -- the 32-bit
+ * kernel, the packed kernels (8-bit and 16-bit containers, both block-to-lane maps), SAO (8-bit and 16-bit), the fused deblocking +
+ * SAO kernels, single plane and Y + Cb + Cr in one launch -- under the same guards: kernel_variant and `fused` mean what they mean
+ * there and HEVCDBK_ERR_UNSUPPORTED comes back where the multiple-of-8 call returns it.  The twins are built on the most general
+ * forms (per-lane QP and per-slice offsets, boundary bytes), given neutral operands where the caller passes NULL.
+ * The host-frame operators (hevc_deblocking_filter_h265, hevcdbk_h265_filter_frame_cf), the reference-exact mode (the reference
+ * itself demands multiples of 8) and the file operators take no g4 planes.
+ * Parity: tests/rext_oracle.py applied to the g4 plane, and for 4:2:0 the C oracle on the plane padded to a multiple of 8 and
+ * cropped ("parity unpinned").
+ * ================================================================================================================== */
+/* like hevcdbk_h265_derive_bs_device_cf: width / height stay multiples of 8; the chroma arrays may be those of a g4 plane
+ * (width / SubWidthC x height / SubHeightC, each at least 8, else HEVCDBK_ERR_DIMENSIONS) */
+HEVCDBK_API int hevcdbk_h265_derive_bs_device_g4(hevcdbk_context *ctx, const hevcdbk_h265_units *units, unsigned width, unsigned height,
+                                                 int chroma_format_idc, uint8_t *vert_bs4, uint8_t *hor_bs4, uint8_t *chroma_vert_bs4,
+                                                 uint8_t *chroma_hor_bs4, void *hip_stream);
+/* like hevcdbk_h265_filter_device_sl; slice_offsets may be NULL */
+HEVCDBK_API int hevcdbk_h265_filter_device_g4(hevcdbk_context *ctx, const hevcdbk_device_planes *planes, int c_idx, int chroma_format_idc,
+                                              unsigned qp, const hevcdbk_h265_params *params, int kernel_variant,
+                                              const hevcdbk_h265_slice_offsets *slice_offsets, void *hip_stream);
+/* like hevcdbk_sao_filter_device_nox; borders may be NULL; keep_stride >= ceil(plane_w / 8) */
+HEVCDBK_API int hevcdbk_sao_filter_device_g4(hevcdbk_context *ctx, const hevcdbk_device_planes *planes, const hevcdbk_sao_ctb *params,
+                                             unsigned params_stride, size_t params_frame_stride, unsigned ctb_log2_w,
+                                             unsigned ctb_log2_h, const uint8_t *keep, unsigned keep_stride,
+                                             size_t keep_frame_stride, const hevcdbk_sao_borders *borders, void *hip_stream);
+/* like hevcdbk_h265_deblock_sao_device_sl; borders and slice_offsets may be NULL */
+HEVCDBK_API int hevcdbk_h265_deblock_sao_device_g4(hevcdbk_context *ctx, const hevcdbk_device_planes *planes, int c_idx,
+                                                   int chroma_format_idc, unsigned qp, const hevcdbk_h265_params *h265_params,
+                                                   const hevcdbk_sao_ctb *params, unsigned params_stride, size_t params_frame_stride,
+                                                   unsigned ctb_log2_w, unsigned ctb_log2_h, const uint8_t *keep, unsigned keep_stride,
+                                                   size_t keep_frame_stride, int fused, const hevcdbk_sao_borders *borders,
+                                                   const hevcdbk_h265_slice_offsets *slice_offsets, void *hip_stream);
+/* like hevcdbk_h265_deblock_sao_device_planes_sl; planes[0] (luma) is a multiple of 8 and the chroma planes are
+ * planes[0] / (SubWidthC, SubHeightC), else HEVCDBK_ERR_ARG */
+HEVCDBK_API int hevcdbk_h265_deblock_sao_device_planes_g4(hevcdbk_context *ctx, const hevcdbk_device_planes *planes, unsigned n_planes,
+                                                          int chroma_format_idc, unsigned qp, const hevcdbk_h265_params *h265_params,
+                                                          const hevcdbk_sao_plane_cf *sao, int fused, const hevcdbk_sao_borders *borders,
+                                                          const hevcdbk_h265_slice_offsets *slice_offsets, void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

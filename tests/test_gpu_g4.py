@@ -1,0 +1,585 @@
+"""Planes sized in multiples of 4, not 8 -- the 960x540 chroma planes of a 1920x1080 picture -- on the GPU through the five _g4
+entries of the C ABI, bit-exact against tests/g4_ref.py (tests/rext_oracle.py applied to the g4 plane; test_g4_cpu.py ties it to the C
+oracle by pad and crop).  Every destination is pre-filled, has row padding, a gap between frames and guard rows before and after, all
+of which must come back untouched.  PARITY UNPINNED, like the rest of the spec-exact mode.  The conditions that keep a case from
+passing vacuously -- the new last edge moves samples; the last row / column holds samples that SAO of a padded plane would change and
+SAO of the g4 plane copies -- are asserted on the expectation before anything is compared.  The kernel that ran is read from a stream
+capture."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import g4_ref as G
+import rext_oracle as rx
+import sao_borders_ref as B
+import slice_offsets_ref as R
+from conftest import ROOT
+from test_gpu_sao_borders import FILL, Surface, dev_planes, up
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    from gpu_video_codec_amd import deblock
+    c = deblock.Context(0)
+    yield c
+    c.close()
+
+
+@pytest.fixture(scope="module")
+def lib():
+    from gpu_video_codec_amd import _lib
+    return _lib
+
+
+def names(k):
+    from kernel_capture import parse_kernel
+    return [parse_kernel(x[0])[0] for x in k]
+
+
+def row_pad(w, sb, aligned=True):
+    """bytes of row padding: a pitch that is a multiple of 8 (the packed 8-bit SAO kernel's condition), or one that is not"""
+    p = 16 + (-(w * sb) % 8)
+    return p if aligned else p + 4 * sb   # 16-bit containers: rows stay 8-byte aligned (the entries' own condition), another pitch
+
+
+class Plane:
+    """a vector's plane in HBM with its operands: src / dst surfaces, per-frame bS, the shared QP map"""
+
+    def __init__(self, ctx, c, planes=None, in_place=False, aligned=True, chroma=True, bs=True):
+        planes = c["planes"] if planes is None else planes
+        n = len(planes)
+        pad = row_pad(c["w"], c["sb"], aligned)
+        self.src = Surface(ctx, n, c["h"], c["w"], c["sb"], pad, planes)
+        self.dst = self.src if in_place else Surface(ctx, n, c["h"], c["w"], c["sb"], pad)
+        self.bufs = []
+        dv = dh = dm = None
+        if bs:
+            dv, dh = up(ctx, np.stack([b[0] for b in c["bs"]])), up(ctx, np.stack([b[1] for b in c["bs"]]))
+            self.bufs += [dv, dh]
+        if c.get("qp_map") is not None:
+            dm = up(ctx, c["qp_map"])
+            self.bufs.append(dm)
+        self.p = dev_planes(self.src, self.dst, c["depth"], chroma, dv, dh, dm, 0 if dm is None else c["qp_map"].shape[1], G.UNIT_LOG2)
+        if bs:
+            self.p.vert_bs_stride, self.p.hor_bs_stride = c["bs"][0][0].size, c["bs"][0][1].size
+
+    def free(self):
+        for x in {self.src, self.dst} | set(self.bufs):
+            x.free()
+
+
+def sl_operand(ctx, lib, pairs, log2=G.SL_CTB_LOG2):
+    d = up(ctx, pairs)
+    return lib.SliceOffsets(d.ptr, pairs.shape[1], 0, log2), d
+
+
+def sao_operands(ctx, c, keep=True):
+    """(params buffer, keep buffer or None, the argument tuple between `planes` and `borders` of the SAO entries)"""
+    rows, cols = c["params"][0].shape
+    dp = up(ctx, np.stack(c["params"]))
+    dk = up(ctx, np.stack(c["keep"])) if keep else None
+    kr, kc = c["keep"][0].shape
+    return dp, dk, (dp.ptr, cols, rows * cols, c["lw"], c["lh"], dk.ptr if dk else None, kc if dk else 0, kr * kc if dk else 0)
+
+
+def borders_operand(ctx, lib, layouts):
+    nox = np.stack([B.expected_nox(l) for l in layouts])
+    d = up(ctx, nox)
+    return lib.SaoBorders(d.ptr, nox.shape[2], nox.shape[1] * nox.shape[2] if len(layouts) > 1 else 0), d
+
+
+def hp_of(lib):
+    return lib.H265Params(G.TC_DIV2, 0, G.CQP, G.CQP)
+
+
+def check(dst, want, what):
+    got, clean = dst.read()
+    assert clean, ("bytes outside the frames were written", what)
+    for f, w in enumerate(want):
+        assert np.array_equal(got[f], w), (what, f, int((got[f] != w).sum()), np.argwhere(got[f] != w)[:4].tolist())
+
+
+# ---- deblocking: the 32-bit kernel and the packed kernels, both block-to-lane maps -----------------------------------------------
+
+@pytest.mark.parametrize("spec", G.CASES, ids=lambda s: s[0])
+def test_filter_device(ctx, lib, spec):
+    from kernel_capture import kernels_enqueued
+    L = lib.lib()
+    c = G.dbk_case(spec, frames=2)
+    so, dso = sl_operand(ctx, lib, c["pairs"])
+    hp = hp_of(lib)
+    for sl in (False, True):
+        want = [G.dbk_expected(c, f, sl) for f in range(2)]
+        for f in range(2):
+            assert sum(G.new_edge_changes(c["planes"][f], want[f])) > 0, "the new last edge is not exercised"
+        variants = [lib.KERNEL_GENERIC, lib.KERNEL_PACKED | lib.MAP_ROWS, lib.KERNEL_PACKED | lib.MAP_LINEAR, lib.KERNEL_AUTO]
+        for i, variant in enumerate(variants):
+            pl = Plane(ctx, c, in_place=(i % 2 == 1), aligned=(i < 2))
+            call = lambda st: L.hevcdbk_h265_filter_device_g4(ctx.handle, C.byref(pl.p), 1, c["cf"], c["qp"], C.byref(hp), variant,
+                                                             C.byref(so) if sl else None, st)
+            rc, k = kernels_enqueued(call)
+            assert rc == 0 and len(k) == 1 and names(k)[0].endswith("_g4_kernel"), (rc, names(k))
+            if variant == lib.KERNEL_GENERIC:
+                assert names(k)[0] == "dbk_h265_g4_kernel"
+            else:
+                assert names(k)[0] in ("dbk_packed_h265_g4_kernel", "dbk_packed16_h265_g4_kernel"), names(k)
+            assert call(None) == 0
+            ctx.synchronize()
+            check(pl.dst, want, (spec[0], sl, variant))
+            pl.free()
+    dso.free()
+
+
+def test_packed_maps_really_differ_on_a_wide_plane(ctx, lib):
+    """the row-major map is taken where it can be: 8196 columns are 1025 blocks per row, over one workgroup"""
+    from kernel_capture import kernels_enqueued, parse_kernel
+    L = lib.lib()
+    c = G.dbk_case(G.WIDE[3], frames=1)
+    pl = Plane(ctx, c)
+    hp = hp_of(lib)
+    seen = set()
+    for m in (lib.MAP_ROWS, lib.MAP_LINEAR, lib.MAP_AUTO):
+        rc, k = kernels_enqueued(lambda st: L.hevcdbk_h265_filter_device_g4(ctx.handle, C.byref(pl.p), 1, 1, c["qp"], C.byref(hp),
+                                                                            lib.KERNEL_PACKED | m, None, st))
+        assert rc == 0
+        seen.add((m, parse_kernel(k[0][0])[1][0]))
+    assert (lib.MAP_ROWS, 0) in seen and (lib.MAP_LINEAR, 1) in seen and (lib.MAP_AUTO, 1) in seen, seen
+    pl.free()
+
+
+# ---- SAO ------------------------------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("spec", G.CASES, ids=lambda s: s[0])
+def test_sao(ctx, lib, spec):
+    from kernel_capture import kernels_enqueued
+    L = lib.lib()
+    c = G.sao_case(spec)
+    cen = G.sao_census(c["planes"], c["params"], c["lw"], c["lh"], c["depth"])
+    assert G.census_ok(cen, c["w"], c["h"]), cen
+    n = len(c["planes"])
+    lays = [G.sao_layout(c, f) for f in range(n)]
+    dp, dk, args = sao_operands(ctx, c)
+    dp0, _, args0 = sao_operands(ctx, c, keep=False)
+    bo, dbo = borders_operand(ctx, lib, lays)
+    for borders in (False, True):
+        for keep in (False, True):
+            want = [G.sao_direct(c["planes"][f], c["params"][f], c["lw"], c["lh"], bit_depth=c["depth"], keep=c["keep"][f] if keep else None,
+                                 layout=lays[f] if borders else None) for f in range(n)]
+            for aligned in (True, False):
+                pl = Plane(ctx, c, aligned=aligned, chroma=False, bs=False)
+                call = lambda st: L.hevcdbk_sao_filter_device_g4(ctx.handle, C.byref(pl.p), *(args if keep else args0),
+                                                                 C.byref(bo) if borders else None, st)
+                rc, k = kernels_enqueued(call)
+                assert rc == 0 and names(k)[-1] in ("sao8_g4_kernel", "sao_g4_kernel"), (rc, names(k))
+                if c["sb"] == 1:
+                    assert names(k)[-1] == ("sao8_g4_kernel" if aligned else "sao_g4_kernel")
+                assert call(None) == 0
+                ctx.synchronize()
+                check(pl.dst, want, (spec[0], borders, keep, aligned))
+                pl.free()
+    for x in (dp, dk, dp0, dbo):
+        x.free()
+
+
+# ---- deblocking + SAO of one plane: the fused kernel and the two launches ----------------------------------------------------------
+
+def both_case(spec, frames=G.FRAMES):
+    """a deblocking vector and SAO parameters fitted to its deblocked planes; the census on the deblocked planes"""
+    c = G.dbk_case(spec, frames=frames)
+    s = G.sao_case(spec, frames=frames)
+    out = {}
+    for sl in (False, True):
+        mid = [G.dbk_expected(c, f, sl) for f in range(frames)]
+        params = [p.copy() for p in s["params"]]
+        G.fit_bands(mid, params, s["lw"], s["lh"], c["depth"])
+        out[sl] = (mid, params)
+    return c, s, out
+
+
+@pytest.mark.parametrize("spec", G.SMALL + G.TILES8 + G.TILES16 + G.WIDE[:2] + G.P1080[1:3] + G.FORMATS, ids=lambda s: s[0])
+def test_deblock_sao_device(ctx, lib, spec):
+    from kernel_capture import kernels_enqueued
+    L = lib.lib()
+    c, s, exp = both_case(spec)
+    n = len(c["planes"])
+    lays = [G.sao_layout(s, f) for f in range(n)]
+    bo, dbo = borders_operand(ctx, lib, lays)
+    so, dso = sl_operand(ctx, lib, c["pairs"])
+    hp = hp_of(lib)
+    for extra in (False, True):   # borders and slice_offsets absent / present
+        mid, params = exp[extra]
+        for f in range(n):
+            assert sum(G.new_edge_changes(c["planes"][f], mid[f])) > 0, "the new last edge is not exercised"
+        cen = G.sao_census(mid, params, s["lw"], s["lh"], c["depth"])
+        assert G.census_ok(cen, c["w"], c["h"]), cen
+        sc = dict(s, params=params)
+        dp, dk, args = sao_operands(ctx, sc)
+        want = [G.sao_direct(mid[f], params[f], s["lw"], s["lh"], bit_depth=c["depth"], keep=s["keep"][f], layout=lays[f] if extra else None)
+                for f in range(n)]
+        for fused in (lib.FUSED_ON, lib.FUSED_OFF, lib.FUSED_AUTO):
+            pl = Plane(ctx, c)
+            call = lambda st: L.hevcdbk_h265_deblock_sao_device_g4(ctx.handle, C.byref(pl.p), 1, c["cf"], c["qp"], C.byref(hp), *args, fused,
+                                                                  C.byref(bo) if extra else None, C.byref(so) if extra else None, st)
+            rc, k = kernels_enqueued(call)
+            assert rc == 0, rc
+            g4 = [x for x in names(k) if x.endswith("_g4_kernel")]
+            if fused == lib.FUSED_OFF:
+                assert len(g4) == 2 and g4[0].startswith("dbk_packed") and g4[1].startswith("sao"), names(k)
+            else:
+                assert g4 == ["dbk_sao_fused_h265_g4_kernel" if c["sb"] == 1 else "dbk_sao_fused16_h265_g4_kernel"], names(k)
+            assert call(None) == 0
+            ctx.synchronize()
+            check(pl.dst, want, (spec[0], extra, fused))
+            pl.free()
+        dp.free()
+        dk.free()
+    dbo.free()
+    dso.free()
+
+
+# ---- Y + Cb + Cr in one launch ---------------------------------------------------------------------------------------------------
+
+def picture_case(W, H, depth, cf, frames, luma_log2, seed):
+    """a picture: luma W x H (multiples of 8) with its chroma planes (W / SubWidthC) x (H / SubHeightC), blocky, per-frame bS of every
+    plane, a QP map, SAO parameters per plane and frame, a keep map; ONE layout of slices and tiles and ONE array of pairs per frame"""
+    rng = np.random.default_rng(seed)
+    sx, sy = rx.SUB[cf]
+    sizes = [(W, H), (W // sx, H // sy), (W // sx, H // sy)]
+    logs = [(luma_log2, luma_log2), (luma_log2 - (sx == 2), luma_log2 - (sy == 2)), (luma_log2 - (sx == 2), luma_log2 - (sy == 2))]
+    rows, cols = -(-H >> luma_log2), -(-W >> luma_log2)
+    sidx = R.slices_raster(rows, cols, 7)
+    pic = {"depth": depth, "sb": 1 if depth == 8 else 2, "cf": cf, "qp": G.QP, "sizes": sizes, "logs": logs, "frames": frames,
+           "qp_map": rng.integers(22, 44, (-(-H >> 3), -(-W >> 3))).astype(np.uint8),
+           "pairs": R.ctb_pairs(sidx, R.table_for(int(sidx.max()) + 1)), "sl_log2": luma_log2,
+           "layouts": [B._layout_of("mixed", rows, cols, rng) for _ in range(frames)], "planes": []}
+    for i, (w, h) in enumerate(sizes):
+        lw, lh = logs[i]
+        pl = {"w": w, "h": h, "depth": depth, "sb": pic["sb"], "lw": lw, "lh": lh, "qp_map": pic["qp_map"],
+              "planes": [G.blocky_plane(w, h, depth, rng) for _ in range(frames)], "bs": [G.random_bs(w, h, rng, p2=0.4) for _ in range(frames)],
+              "params": G.border_params(w, h, lw, lh, depth, frames, rng), "keep": [G.keep_map(w, h, rng) for _ in range(frames)]}
+        pic["planes"].append(pl)
+    return pic
+
+
+def picture_expected(pic, extra):
+    """per plane: (deblocked frames, SAO parameters fitted to them, final frames); extra = borders and per-slice offsets present"""
+    from oracle import h265
+    out = []
+    for i, pl in enumerate(pic["planes"]):
+        kw = dict(qp=pic["qp"], qp_map=pic["qp_map"], unit_log2=G.UNIT_LOG2, bit_depth=pic["depth"])
+        mid = []
+        for f in range(pic["frames"]):
+            vb, hb = pl["bs"][f]
+            if i == 0 and extra:
+                m = R.expected(pl["planes"][f], vb, hb, pic["pairs"], pic["sl_log2"], c_idx=0, **kw)
+            elif i == 0:
+                m = h265.filter_plane(pl["planes"][f], pic["qp"], vb, hb, c_idx=0, bit_depth=pic["depth"], qp_map=pic["qp_map"],
+                                      unit_log2=G.UNIT_LOG2, tc_offset_div2=G.TC_DIV2, beta_offset_div2=-1)
+            elif extra:
+                m = G.deblock_sl(pl["planes"][f], vb, hb, pic["cf"], pic["pairs"], pic["sl_log2"], c_qp_offset=G.CQP, **kw)
+            else:
+                m = G.deblock_direct(pl["planes"][f], vb, hb, pic["cf"], c_qp_offset=G.CQP, tc_offset_div2=G.TC_DIV2, **kw)
+            mid.append(m)
+        params = [p.copy() for p in pl["params"]]
+        G.fit_bands(mid, params, pl["lw"], pl["lh"], pic["depth"])
+        fin = [G.sao_direct(mid[f], params[f], pl["lw"], pl["lh"], bit_depth=pic["depth"], keep=pl["keep"][f],
+                            layout=pic["layouts"][f] if extra else None) for f in range(pic["frames"])]
+        out.append((mid, params, fin))
+    return out
+
+
+def run_picture(ctx, lib, pic, what):
+    from kernel_capture import kernels_enqueued
+    L = lib.lib()
+    bo, dbo = borders_operand(ctx, lib, pic["layouts"])
+    so, dso = sl_operand(ctx, lib, pic["pairs"], pic["sl_log2"])
+    hp = lib.H265Params(G.TC_DIV2, -1, G.CQP, G.CQP)
+    for extra in (False, True):
+        exp = picture_expected(pic, extra)
+        for i in (1, 2):
+            pl = pic["planes"][i]
+            for f in range(pic["frames"]):
+                assert sum(G.new_edge_changes(pl["planes"][f], exp[i][0][f])) > 0, "the new last edge is not exercised"
+            if G.is_g4(pl["w"], pl["h"]):
+                cen = G.sao_census(exp[i][0], exp[i][1], pl["lw"], pl["lh"], pic["depth"])
+                assert G.census_ok(cen, pl["w"], pl["h"]), cen
+        for fused in (lib.FUSED_AUTO, lib.FUSED_OFF):
+            P = [Plane(ctx, pl, chroma=(i > 0)) for i, pl in enumerate(pic["planes"])]
+            arr = (lib.DevicePlanes * 3)(*[x.p for x in P])
+            sp = (lib.SaoPlaneCf * 3)()
+            held = []
+            for i, pl in enumerate(pic["planes"]):
+                dp, dk, a = sao_operands(ctx, dict(pl, params=exp[i][1]))
+                held += [dp, dk]
+                (sp[i].params, sp[i].params_stride, sp[i].params_frame_stride, sp[i].ctb_log2_w, sp[i].ctb_log2_h, sp[i].keep,
+                 sp[i].keep_stride, sp[i].keep_frame_stride) = a
+            call = lambda st: L.hevcdbk_h265_deblock_sao_device_planes_g4(ctx.handle, arr, 3, pic["cf"], pic["qp"], C.byref(hp), sp, fused,
+                                                                         C.byref(bo) if extra else None, C.byref(so) if extra else None, st)
+            rc, k = kernels_enqueued(call)
+            assert rc == 0, rc
+            big = [x for x in names(k) if x.startswith("dbk_") and "rows_x2" not in x]
+            if fused == lib.FUSED_AUTO:
+                assert big == ["dbk_sao_fused_multi_h265_g4_kernel"], names(k)
+            else:
+                assert len([x for x in names(k) if x.endswith("_g4_kernel")]) == 4, names(k)   # deblocking and SAO of Cb and Cr
+            assert call(None) == 0
+            ctx.synchronize()
+            for i in range(3):
+                check(P[i].dst, exp[i][2], (what, extra, fused, "plane", i))
+            for x in P + held:
+                x.free()
+    dbo.free()
+    dso.free()
+
+
+@pytest.mark.parametrize("depth", [8, 10])
+def test_1080p_planes_in_one_launch(ctx, lib, depth):
+    run_picture(ctx, lib, picture_case(1920, 1080, depth, 1, 2, 6, 1080 + depth), ("1080p", depth))
+
+
+@pytest.mark.parametrize("W,H,depth,cf,log2", [(1928, 24, 8, 2, 5), (1928, 24, 10, 2, 4), (72, 40, 8, 1, 4), (264, 248, 10, 1, 5)])
+def test_other_pictures_in_one_launch(ctx, lib, W, H, depth, cf, log2):
+    """4:2:2 chroma 964x24 of a 1928x24 picture (CTBs twice as tall as wide: the parameters and boundary bytes rewritten for square
+    CTBs), and small 4:2:0 pictures whose chroma planes are g4 in both directions"""
+    run_picture(ctx, lib, picture_case(W, H, depth, cf, G.FRAMES, log2, W + H + depth), (W, H, depth, cf))   # five frames: every border CTB has been every kind
+
+
+# ---- multiples of 8 through the _g4 entries: the entries they extend ------------------------------------------------------------------
+
+def test_multiples_of_8_take_the_kernels_they_took(ctx, lib):
+    from kernel_capture import kernels_enqueued
+    L = lib.lib()
+    spec = ("64x48", 64, 48, 8, 1, True, 4)
+    c, s, exp = both_case(spec, frames=2)
+    so, dso = sl_operand(ctx, lib, c["pairs"])
+    hp = hp_of(lib)
+    dp, dk, args = sao_operands(ctx, s)
+    bo, dbo = borders_operand(ctx, lib, [G.sao_layout(s, f) for f in range(2)])
+    for extra in (False, True):
+        sop, bop = (C.byref(so) if extra else None), (C.byref(bo) if extra else None)
+        pairs = [
+            (lambda p, st: L.hevcdbk_h265_filter_device_g4(ctx.handle, C.byref(p), 1, 1, c["qp"], C.byref(hp), 0, sop, st),
+             lambda p, st: L.hevcdbk_h265_filter_device_sl(ctx.handle, C.byref(p), 1, 1, c["qp"], C.byref(hp), 0, sop, st)),
+            (lambda p, st: L.hevcdbk_sao_filter_device_g4(ctx.handle, C.byref(p), *args, bop, st),
+             lambda p, st: L.hevcdbk_sao_filter_device_nox(ctx.handle, C.byref(p), *args, bop, st)),
+            (lambda p, st: L.hevcdbk_h265_deblock_sao_device_g4(ctx.handle, C.byref(p), 1, 1, c["qp"], C.byref(hp), *args, 0, bop, sop, st),
+             lambda p, st: L.hevcdbk_h265_deblock_sao_device_sl(ctx.handle, C.byref(p), 1, 1, c["qp"], C.byref(hp), *args, 0, bop, sop, st)),
+        ]
+        for new, old in pairs:
+            a, b = Plane(ctx, c), Plane(ctx, c)
+            rc0, k0 = kernels_enqueued(lambda st: old(a.p, st))
+            rc1, k1 = kernels_enqueued(lambda st: new(a.p, st))
+            assert rc0 == 0 and rc1 == 0 and k0 == k1 and not any(x.endswith("_g4_kernel") for x in names(k1)), (names(k0), names(k1))
+            assert old(a.p, None) == 0 and new(b.p, None) == 0
+            ctx.synchronize()
+            ga, ca = a.dst.read()
+            gb, cb = b.dst.read()
+            assert ca and cb and all(np.array_equal(x, y) for x, y in zip(ga, gb))
+            a.free()
+            b.free()
+    for x in (dso, dp, dk, dbo):
+        x.free()
+
+
+def test_a_g4_call_runs_a_g4_kernel_beside_the_call_it_extends(ctx, lib):
+    """960x544 through the existing entry launches what it launched; 960x540 through the _g4 entry the twin on the same grid"""
+    from kernel_capture import kernels_enqueued
+    L = lib.lib()
+    hp = hp_of(lib)
+    got = {}
+    for h in (544, 540):
+        c = G.dbk_case(("k", 960, h, 8, 1, True, 5))
+        pl = Plane(ctx, c)
+        for variant in (lib.KERNEL_GENERIC, lib.KERNEL_PACKED):
+            if h == 544:
+                rc, k = kernels_enqueued(lambda st: L.hevcdbk_h265_filter_device_sl(ctx.handle, C.byref(pl.p), 1, 1, c["qp"], C.byref(hp), variant, None, st))
+            else:
+                rc, k = kernels_enqueued(lambda st: L.hevcdbk_h265_filter_device_g4(ctx.handle, C.byref(pl.p), 1, 1, c["qp"], C.byref(hp), variant, None, st))
+            assert rc == 0 and len(k) == 1
+            got[(h, variant)] = k[0]
+        pl.free()
+    assert names([got[(544, lib.KERNEL_GENERIC)]]) == ["dbk_h265_kernel"] and names([got[(540, lib.KERNEL_GENERIC)]]) == ["dbk_h265_g4_kernel"]
+    assert names([got[(544, lib.KERNEL_PACKED)]]) == ["dbk_packed_h265_kernel"] and names([got[(540, lib.KERNEL_PACKED)]]) == ["dbk_packed_h265_g4_kernel"]
+    for v in (lib.KERNEL_GENERIC, lib.KERNEL_PACKED):   # the same workgroups; 544 rows are one more row of blocks than 540
+        assert got[(544, v)][2] == got[(540, v)][2]
+
+
+# ---- bS derivation -----------------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("w,h,fmt", [(1920, 1080, "420"), (40, 24, "420"), (40, 24, "422"), (40, 24, "444"), (1928, 24, "422")])
+def test_derive_bs(ctx, lib, w, h, fmt):
+    from gpu_video_codec_amd import deblock
+    from oracle import h265
+    units = h265.random_units(w, h, w + h)
+    cf = lib.chroma_format_idc(fmt)
+    sx, sy = lib.CHROMA_SUB[cf]
+    g4 = G.is_g4(w // sx, h // sy)
+    if g4:
+        with pytest.raises(deblock.DeblockError) as e:
+            ctx.derive_bs_h265(units, w, h, chroma_format=fmt)
+        assert e.value.code in (lib.ERR_DIMENSIONS, lib.ERR_ARG)
+    vb, hb, cv, ch = ctx.derive_bs_h265(units, w, h, chroma_format=fmt, g4=True)
+    ov, oh = h265.derive_bs(*units, w, h)
+    assert np.array_equal(vb, ov) and np.array_equal(hb, oh)
+    wv, wh = rx.chroma_bs(ov, oh, w, h, cf)
+    assert cv.size == G.num_vert_bs(w // sx, h // sy) and ch.size == G.num_hor_bs(w // sx, h // sy)
+    assert np.array_equal(cv, wv) and np.array_equal(ch, wh)
+    if g4 and (w // sx) % 8:
+        assert (wv.reshape(-1, (w // sx) // 8 + 1)[:, -1] != 0).any(), "the new last column of the vertical array holds no edge"
+    if not g4:
+        old = ctx.derive_bs_h265(units, w, h, chroma_format=fmt)
+        assert all(np.array_equal(a, b) for a, b in zip(old, (vb, hb, cv, ch)))
+
+
+# ---- refusals: the documented code, nothing written -----------------------------------------------------------------------------------
+
+def test_refusals_write_nothing(ctx, lib):
+    L = lib.lib()
+    hp = hp_of(lib)
+    D, A = lib.ERR_DIMENSIONS, lib.ERR_ARG
+
+    def attempt(w, h, chroma, code):
+        # the operands of a plane that is a little larger, so that nothing could fault if the call were taken
+        W, H = max((w + 7) // 8 * 8, 16), max((h + 7) // 8 * 8, 16)
+        c = G.dbk_case(("r", W + 4, H + 4, 8, 1, False, 3))
+        s = G.sao_case(("r", W + 4, H + 4, 8, 1, False, 3), frames=1)
+        pl = Plane(ctx, c)
+        pl.p.plane_w, pl.p.plane_h, pl.p.is_chroma = w, h, int(chroma)
+        dp, dk, args = sao_operands(ctx, s)
+        c_idx = 1 if chroma else 0
+        assert L.hevcdbk_h265_filter_device_g4(ctx.handle, C.byref(pl.p), c_idx, 1, 30, C.byref(hp), 0, None, None) == code
+        assert L.hevcdbk_h265_deblock_sao_device_g4(ctx.handle, C.byref(pl.p), c_idx, 1, 30, C.byref(hp), *args, 0, None, None, None) == code
+        if chroma:
+            assert L.hevcdbk_sao_filter_device_g4(ctx.handle, C.byref(pl.p), *args, None, None) == code
+        ctx.synchronize()
+        host = pl.dst.buf.download(pl.dst.total)
+        assert (host == FILL).all(), "a refused call wrote"
+        pl.free()
+        dp.free()
+        dk.free()
+
+    attempt(20, 28, False, D)      # a g4 luma plane
+    attempt(4, 16, True, D)        # size 4
+    attempt(16, 4, True, D)
+    attempt(10, 16, True, D)       # size 10
+    attempt(16, 10, True, D)
+    # chroma planes that are not planes[0] / (SubWidthC, SubHeightC)
+    pic = picture_case(72, 40, 8, 1, 1, 4, 5)
+    P = [Plane(ctx, pl, chroma=(i > 0)) for i, pl in enumerate(pic["planes"])]
+    sp = (lib.SaoPlaneCf * 3)()
+    held = []
+    for i, pl in enumerate(pic["planes"]):
+        dp, dk, a = sao_operands(ctx, pl)
+        held += [dp, dk]
+        (sp[i].params, sp[i].params_stride, sp[i].params_frame_stride, sp[i].ctb_log2_w, sp[i].ctb_log2_h, sp[i].keep, sp[i].keep_stride,
+         sp[i].keep_frame_stride) = a
+    for (i, w, h, code) in [(2, 36, 16, A), (1, 32, 20, A), (0, 72, 36, D)]:
+        arr = (lib.DevicePlanes * 3)(*[x.p for x in P])
+        arr[i].plane_w, arr[i].plane_h = w, h
+        assert L.hevcdbk_h265_deblock_sao_device_planes_g4(ctx.handle, arr, 3, 1, 30, C.byref(hp), sp, 0, None, None, None) == code, (i, w, h)
+    ctx.synchronize()
+    for x in P:
+        assert (x.dst.buf.download(x.dst.total) == FILL).all(), "a refused call wrote"
+    for x in P + held:
+        x.free()
+
+
+# ---- the Python keyword ---------------------------------------------------------------------------------------------------------------
+
+def test_python_keyword(ctx, lib):
+    """g4=True reaches the _g4 entries; without it a g4 plane is refused as ever"""
+    from gpu_video_codec_amd import deblock
+    spec = G.SMALL[1]
+    c, s, exp = both_case(spec, frames=2)
+    mid, params = exp[False]
+    b = deblock.DeviceBatch(ctx, c["w"], c["h"], 2, bit_depth=c["depth"], is_chroma=True, pitch=c["w"] * c["sb"] + 12)
+    assert b.keep_shape == s["keep"][0].shape and b.ctb_shape(s["lw"], s["lh"]) == params[0].shape
+    for f in range(2):
+        b.upload_frame(f, c["planes"][f])
+    dv, dh = up(ctx, np.stack([x[0] for x in c["bs"]])), up(ctx, np.stack([x[1] for x in c["bs"]]))
+    dm = up(ctx, c["qp_map"])
+    p = b.planes()
+    p.vert_bs, p.hor_bs, p.vert_bs_stride, p.hor_bs_stride = dv.ptr, dh.ptr, c["bs"][0][0].size, c["bs"][0][1].size
+    p.qp_map, p.qp_map_stride, p.ctu_log2 = dm.ptr, c["qp_map"].shape[1], G.UNIT_LOG2
+    kw = dict(c_idx=1, tc_offset_div2=G.TC_DIV2, cb_qp_offset=G.CQP, cr_qp_offset=G.CQP)
+    with pytest.raises(deblock.DeblockError) as e:
+        ctx.filter_device_h265(p, c["qp"], **kw)
+    assert e.value.code == lib.ERR_DIMENSIONS
+    ctx.filter_device_h265(p, c["qp"], g4=True, **kw)
+    ctx.synchronize()
+    for f in range(2):
+        assert np.array_equal(b.download_frame(f), mid[f])
+    dp, dk, args = sao_operands(ctx, dict(s, params=params))
+    rows, cols = params[0].shape
+    skw = dict(params_frame_stride=rows * cols, keep_ptr=dk.ptr, keep_stride=args[6], keep_frame_stride=args[7])
+    with pytest.raises(deblock.DeblockError):
+        ctx.deblock_sao_h265_device(p, c["qp"], dp.ptr, cols, s["lw"], **kw, **skw)
+    ctx.deblock_sao_h265_device(p, c["qp"], dp.ptr, cols, s["lw"], g4=True, **kw, **skw)
+    ctx.synchronize()
+    want = [G.sao_direct(mid[f], params[f], s["lw"], s["lh"], bit_depth=c["depth"], keep=s["keep"][f]) for f in range(2)]
+    for f in range(2):
+        assert np.array_equal(b.download_frame(f), want[f])
+    # SAO alone: dst of the deblocking call above is not its input, so run it src -> dst on the uploaded planes
+    with pytest.raises(deblock.DeblockError):
+        ctx.sao_device(p, dp.ptr, cols, s["lw"], **skw)
+    ctx.sao_device(p, dp.ptr, cols, s["lw"], g4=True, **skw)
+    ctx.synchronize()
+    for f in range(2):
+        assert np.array_equal(b.download_frame(f), G.sao_direct(c["planes"][f], params[f], s["lw"], s["lh"], bit_depth=c["depth"], keep=s["keep"][f]))
+    for x in (dv, dh, dm, dp, dk):
+        x.free()
+    b.free()
+
+
+# ---- examples/decoder_loop.c: a 1920x1080 picture from plain C --------------------------------------------------------------------
+
+def test_decoder_loop_example_filters_1080p(tmp_path):
+    """the example's second picture is 1920x1080 4:2:0 through the _g4 entries; it writes what went in and what came out, and what
+    came out is what the CPU statements make of what went in"""
+    from gpu_video_codec_amd import _lib
+    from oracle import h265
+    exe, dump = str(tmp_path / "decoder_loop"), str(tmp_path / "dump.bin")
+    libdir = os.path.dirname(_lib.LIB_PATH)
+    subprocess.check_call(["gcc", "-std=c99", "-pedantic", "-Wall", "-Wextra", "-Werror", "-I", os.path.join(ROOT, "include"),
+                           os.path.join(ROOT, "examples", "decoder_loop.c"), "-L", libdir, "-lhevcdbk", "-Wl,-rpath," + libdir,
+                           "-Wl,-rpath,/opt/rocm/lib", "-o", exe])
+    r = subprocess.run([exe, dump], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "one 1920x1080 picture through bS derivation, deblocking and SAO on the GPU" in r.stdout, (r.stdout, r.stderr)
+    raw = np.fromfile(dump, np.uint8)
+    W, H, cx, cy, qx, qy = raw[:24].view(np.uint32).tolist()
+    assert (W, H, cx, cy, qx, qy) == (1920, 1080, 30, 17, 120, 68)
+    pos = [24]
+
+    def take(n, dtype=np.uint8):
+        a = raw[pos[0]: pos[0] + n * np.dtype(dtype).itemsize].view(dtype)
+        pos[0] += n * np.dtype(dtype).itemsize
+        return a
+    sizes = [(W, H), (W // 2, H // 2), (W // 2, H // 2)]
+    src = [take(w * h).reshape(h, w) for (w, h) in sizes]
+    flags = take((W // 4) * (H // 4), np.uint16).reshape(H // 4, W // 4)
+    qmap = take(qx * qy).reshape(qy, qx)
+    sao = [take(cx * cy, rx.SAO_CTB_DTYPE).reshape(cy, cx) for _ in range(3)]
+    out = [take(w * h).reshape(h, w) for (w, h) in sizes]
+    assert pos[0] == raw.size
+    z2, z1 = np.zeros((H // 4, W // 4, 2), np.int16), np.zeros((H // 4, W // 4), np.int32)
+    vb, hb = h265.derive_bs(flags, z2, z2, z1, z1, W, H)
+    cvb, chb = rx.chroma_bs(vb, hb, W, H, 1)
+    assert (np.asarray(vb) & 3).max() == 2
+    for i in range(3):
+        if i == 0:
+            mid = h265.filter_plane(src[0], 0, vb, hb, c_idx=0, qp_map=qmap, unit_log2=4)
+        else:
+            mid = G.deblock_direct(src[i], cvb, chb, 1, qp=0, qp_map=qmap, unit_log2=4)
+            assert np.array_equal(mid, G.deblock_padcrop(src[i], cvb, chb, qp=0, qp_map=qmap, unit_log2=4))
+            assert G.new_edge_changes(src[i], mid)[1] > 0, "the edge y = 536 of the chroma plane moves nothing"
+        log2 = 5 if i else 6
+        want = G.sao_direct(mid, sao[i], log2, log2)
+        assert (want != mid).any() and (mid != src[i]).any()
+        if i:
+            assert (G.padded_sao(mid, sao[i], log2, log2)[-1] != want[-1]).any(), "row 539 would be the same in a padded plane"
+        assert np.array_equal(out[i], want), (i, int((out[i] != want).sum()))

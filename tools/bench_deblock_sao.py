@@ -31,7 +31,12 @@ def main():
                          "everywhere, with a slice every 8 CTB rows with differing pairs, and without it again take turns in this one process; "
                          "with --borders every one of the four carries that layout (the _nox kernels are then the yardstick)")
     ap.add_argument("--rounds", type=int, default=3, help="--borders / --slice-offsets: rounds of turns; the median of each variant is reported")
+    ap.add_argument("--g4", action="store_true",
+                    help="--mode h265 --chroma-format F: the _g4 entry (hevcdbk_h265_deblock_sao_device_planes_g4), which takes chroma planes "
+                         "sized in multiples of 4: --width 1920 --height 1080 --chroma-format 420 is Y 1920x1080 with Cb, Cr 960x540")
     a = ap.parse_args()
+    if a.g4 and not a.chroma_format:
+        ap.error("--g4 needs --mode h265 --chroma-format (a luma plane is a multiple of 8)")
     if a.borders is not None and a.mode != "h265":
         ap.error("--borders needs --mode h265 (the reference-exact mode has no slices or tiles)")
     if a.slice_offsets and a.mode != "h265":
@@ -68,13 +73,13 @@ def main():
     if a.chroma_format:  # the planes of tools/bench_rext.py: bS 2 everywhere, seeded SAO parameters per plane
         sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
         import bench_rext
-        yuv, sao, nbytes, _keep = bench_rext.setup(ctx, a.chroma_format, w, h, n, 8, np.random.RandomState(5))
+        yuv, sao, nbytes, _keep = bench_rext.setup(ctx, a.chroma_format, w, h, n, a.bit_depth, np.random.RandomState(5))
         h265 = {"tc_offset_div2": 0, "beta_offset_div2": 0, "cb_qp_offset": 0, "cr_qp_offset": 0}
 
     def call(fused, borders=None, slice_offsets=None):
         if a.chroma_format:
             ctx.deblock_sao_device_planes(yuv, a.qp, sao, h265=h265, fused=fused, chroma_format=a.chroma_format, borders=borders,
-                                          slice_offsets=slice_offsets)
+                                          slice_offsets=slice_offsets, g4=a.g4)
         elif a.mode == "ref":
             ctx.deblock_sao_device(p, a.qp, dp.ptr, cols, 6, fused=fused)
         else:

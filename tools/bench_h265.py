@@ -45,6 +45,9 @@ def main():
                          "pair everywhere, with a slice every 8 CTB rows with differing pairs, and without it again take turns in this one "
                          "process on the same buffers; the median of --rounds rounds each")
     ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--g4", action="store_true",
+                    help="the _g4 entry (hevcdbk_h265_filter_device_g4): with --chroma-format it takes chroma planes sized in multiples of 4, "
+                         "e.g. --width 1920 --height 1080 --chroma-format 420 for the 960x540 Cb plane")
     a = ap.parse_args()
     n = a.frames
     fmt = a.chroma_format
@@ -53,17 +56,20 @@ def main():
     ctx = deblock.Context(0)
     b = deblock.DeviceBatch(ctx, w, h, n, bit_depth=a.bit_depth, per_frame_bs=False, is_chroma=fmt is not None)
     kw = {} if fmt is None else {"c_idx": 1, "chroma_format": fmt}
+    if a.g4:
+        kw["g4"] = True
     distinct = min(n, 8)
     src = np.stack([synth.blocky_plane(w, h, seed=7, frame=i, bit_depth=a.bit_depth) for i in range(distinct)])
     b.upload_all(np.concatenate([src] * (n // distinct + 1))[:n])
     vb = np.zeros((h // 4, w // 8 + 1), np.uint8)
-    vb[:, 1:w // 8] = 2
+    ex, ey = (w - 1) // 8, (h - 1) // 8   # the last interior edge: x = 8 ex < w (w / 8 - 1 for a multiple of 8, w / 8 for 8k + 4)
+    vb[:, 1:ex + 1] = 2
     hb = np.zeros((h // 8 + 1, w // 4), np.uint8)
-    hb[1:h // 8, :] = 2
+    hb[1:ey + 1, :] = 2
     if a.bs == "mixed":
         rng = np.random.RandomState(3)
-        vb[:, 1:w // 8] = rng.randint(0, 3, (h // 4, w // 8 - 1))
-        hb[1:h // 8, :] = rng.randint(0, 3, (h // 8 - 1, w // 4))
+        vb[:, 1:ex + 1] = rng.randint(0, 3, (h // 4, ex))
+        hb[1:ey + 1, :] = rng.randint(0, 3, (ey, w // 4))
     dv, dh = ctx.alloc(vb.size), ctx.alloc(hb.size)
     dv.upload(vb)
     dh.upload(hb)
