@@ -3,6 +3,8 @@
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
 
+#include "sao_types.h"
+
 struct DbkArgs {
     const uint8_t *src;
     uint8_t *dst;
@@ -134,11 +136,7 @@ hipError_t dbk_launch_h265_chroma_bs_cf(const uint8_t *vert, const uint8_t *hor,
 hipError_t dbk_launch_packed_h265_cf(const DbkH265Args &h, int sample_bytes, bool chroma, int chroma_format, hipStream_t stream);
 
 /* ---- sample adaptive offset (H.265 clause 8.7.3), sao.hip ---- */
-struct DbkSaoCtb {
-    uint8_t type;     /* 0 off, 1 band, 2 edge */
-    uint8_t cls;      /* band position / edge class */
-    int8_t offset[4]; /* SaoOffsetVal[1..4] */
-};
+/* DbkSaoCtb (one CTB's parameters) and DbkSaoNox (the boundary bytes): sao_types.h */
 struct DbkSaoArgs {
     const uint8_t *src;
     uint8_t *dst;
@@ -152,14 +150,6 @@ struct DbkSaoArgs {
     const uint8_t *keep;           /* per 8x8 samples of this plane, may be NULL */
     int keep_stride;
     long long keep_frame_stride;
-};
-/* slice / tile boundaries SAO must not look across (H.265 8.7.3.2; hevcdbk_sao_borders of the C ABI): one byte per CTB of the
- * plane's own CTB grid, HEVCDBK_SAO_NOX_* bits.  A kernel argument of its own, taken by the _nox kernels only: the kernels
- * without the operand keep their argument layout, i.e. their machine code */
-struct DbkSaoNox {
-    const uint8_t *nox;
-    int stride;
-    long long frame_stride; /* bytes, 0 = shared */
 };
 /* nx == NULL: the kernels without the operand; else their _nox twins, which honour the bytes */
 hipError_t dbk_launch_sao(const DbkSaoArgs &a, int sample_bytes, hipStream_t stream, const DbkSaoNox *nx = nullptr);

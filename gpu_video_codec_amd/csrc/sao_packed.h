@@ -2,14 +2,20 @@
  * sao_packed.h -- sample adaptive offset (H.265 8.7.3) of one 8x8 block of 8-bit samples held in registers, packed-int16
  * arithmetic (see sao.hip for the scheme).  Shared by the SAO pass (sao.hip) and the fused deblocking + SAO kernel
  * (deblock_sao_fused.inc): the block's ten rows y0-1 .. y0+8 arrive as SaoRaw (samples x-4 .. x+11 each) through a fetch functor
- * -- from the workgroup's LDS tile, row by row as they are needed -- and the eight output rows leave through a store functor.  Device code only.
+ * -- from the workgroup's LDS tile, row by row as they are needed -- and the eight output rows leave through a store functor.
+ *
+ * tests/sao_sim compiles this header for the CPU (the idiom of deblock_packed.h: DBK_HD, and under DBK_DEV == 0 the device
+ * primitives -- v_perm_b32, v_alignbit_b32, the saturating packed subtract, the packed minimum and the two instructions written
+ * out as inline assembly -- in plain C++), so that the arithmetic below and the mask rule of saonox are checked against H.265
+ * 8.7.3 without a GPU.
  */
 #pragma once
 #include <stdint.h>
 
 #include <type_traits>
 
-#include "deblock_kernels.h"
+#include "deblock_packed.h" /* DBK_HD, DBK_DEV, dbk::perm */
+#include "sao_types.h"
 
 /*
  * Slice and tile boundaries that SAO must not look across (H.265 8.7.3.2; DbkSaoNox): a lane's block of 8 x NROWS samples gets
@@ -26,13 +32,13 @@ constexpr uint32_t W4 = 0x100u;
 
 /* the byte of the CTB holding sample (x, y0) of frame f.  Asked for next to the CTB's SAO parameters -- ahead of them -- so that
  * the two requests are in flight together: the wave's ballot over the masks waits for the byte */
-__device__ __forceinline__ uint32_t ctb_byte(const DbkSaoNox &n, int f, int x, int y0, int ctb_log2)
+DBK_HD uint32_t ctb_byte(const DbkSaoNox &n, int f, int x, int y0, int ctb_log2)
 {
     return n.nox[(long long)f * n.frame_stride + (long long)(y0 >> ctb_log2) * n.stride + (x >> ctb_log2)];
 }
 
 template <int NROWS> /* b = ctb_byte of the block's CTB */
-__device__ __forceinline__ uint32_t block_mask(uint32_t b, int x, int y0, int w, int h, int ctb_log2)
+DBK_HD uint32_t block_mask(uint32_t b, int x, int y0, int w, int h, int ctb_log2)
 {
     const int cm = (1 << ctb_log2) - 1;
     const bool pl = x == 0, pr = x + 8 >= w, pt = y0 == 0, pb = y0 + NROWS >= h;                               /* the picture's border */
@@ -55,7 +61,7 @@ __device__ __forceinline__ uint32_t block_mask(uint32_t b, int x, int y0, int w,
  * layouts keep sample 0 in the low half of i0 and sample 7 in the high half of i3; samples 1..6 -- the rest -- share their fate:
  * their neighbours lie in the row above / below only */
 template <int CLS, int NROWS, bool G4 = false>
-__device__ __forceinline__ void mask_row(uint32_t m, int r, uint32_t &i0, uint32_t &i1, uint32_t &i2, uint32_t &i3)
+DBK_HD void mask_row(uint32_t m, int r, uint32_t &i0, uint32_t &i1, uint32_t &i2, uint32_t &i3)
 {
     constexpr uint32_t none = 0x0c020c02u; /* index 2 in both halves + the selector constant (sao8::kSel) */
     const bool top = r == 0, bot = r == NROWS - 1;
@@ -100,18 +106,18 @@ struct SaoRaw {
 };
 
 template <bool HALO>
-__device__ __forceinline__ SaoRow unpack(const SaoRaw &q)
+DBK_HD SaoRow unpack(const SaoRaw &q)
 {
     SaoRow r;
-    r.E0 = __builtin_amdgcn_perm(q.cx, q.cx, 0x0c020c00u);
-    r.O0 = __builtin_amdgcn_perm(q.cx, q.cx, 0x0c030c01u);
-    r.E1 = __builtin_amdgcn_perm(q.cy, q.cy, 0x0c020c00u);
-    r.O1 = __builtin_amdgcn_perm(q.cy, q.cy, 0x0c030c01u);
+    r.E0 = dbk::perm(q.cx, q.cx, 0x0c020c00u);
+    r.O0 = dbk::perm(q.cx, q.cx, 0x0c030c01u);
+    r.E1 = dbk::perm(q.cy, q.cy, 0x0c020c00u);
+    r.O1 = dbk::perm(q.cy, q.cy, 0x0c030c01u);
     if constexpr (HALO) {
-        r.lE0 = __builtin_amdgcn_perm(q.cx, q.lh, 0x0c050c03u); /* (lh.b3, cx.b1) */
-        r.lE1 = __builtin_amdgcn_perm(q.cy, q.cx, 0x0c050c03u); /* (cx.b3, cy.b1) */
-        r.rO0 = __builtin_amdgcn_perm(q.cy, q.cx, 0x0c040c02u); /* (cx.b2, cy.b0) */
-        r.rO1 = __builtin_amdgcn_perm(q.rh, q.cy, 0x0c040c02u); /* (cy.b2, rh.b0) */
+        r.lE0 = dbk::perm(q.cx, q.lh, 0x0c050c03u); /* (lh.b3, cx.b1) */
+        r.lE1 = dbk::perm(q.cy, q.cx, 0x0c050c03u); /* (cx.b3, cy.b1) */
+        r.rO0 = dbk::perm(q.cy, q.cx, 0x0c040c02u); /* (cx.b2, cy.b0) */
+        r.rO1 = dbk::perm(q.rh, q.cy, 0x0c040c02u); /* (cy.b2, rh.b0) */
     } else {
         r.lE0 = r.lE1 = r.rO0 = r.rO1 = 0u;
     }
@@ -120,44 +126,76 @@ __device__ __forceinline__ SaoRow unpack(const SaoRaw &q)
 
 typedef short spk __attribute__((vector_size(4)));
 typedef unsigned short supk __attribute__((vector_size(4)));
-__device__ __forceinline__ spk s_pk(uint32_t v) { return __builtin_bit_cast(spk, v); }
-__device__ __forceinline__ spk s_splat(int v) { return spk{(short)v, (short)v}; }
-__device__ __forceinline__ supk s_upk(uint32_t v) { return __builtin_bit_cast(supk, v); }
+DBK_HD spk s_pk(uint32_t v) { return __builtin_bit_cast(spk, v); }
+DBK_HD spk s_splat(int v) { return spk{(short)v, (short)v}; }
+DBK_HD supk s_upk(uint32_t v) { return __builtin_bit_cast(supk, v); }
+DBK_HD uint32_t s_bits(supk v) { return __builtin_bit_cast(uint32_t, v); }
 /* max(a - b, 0) in both halves: ONE v_pk_sub_u16 with the clamp bit (unsigned saturation) */
-__device__ __forceinline__ supk s_sub_sat(supk a, supk b) { return __builtin_elementwise_sub_sat(a, b); }
+DBK_HD supk s_sub_sat(supk a, supk b)
+{
+#if DBK_DEV
+    return __builtin_elementwise_sub_sat(a, b);
+#else
+    return supk{(unsigned short)(a[0] > b[0] ? a[0] - b[0] : 0), (unsigned short)(a[1] > b[1] ? a[1] - b[1] : 0)};
+#endif
+}
+DBK_HD supk s_min(supk a, supk b) /* v_pk_min_u16 */
+{
+#if DBK_DEV
+    return __builtin_elementwise_min(a, b);
+#else
+    return supk{a[0] < b[0] ? a[0] : b[0], a[1] < b[1] ? a[1] : b[1]};
+#endif
+}
+/* both halves shifted right arithmetically by one count */
+DBK_HD spk s_shr(spk a, int shift)
+{
+#if DBK_DEV
+    return a >> shift;
+#else
+    return spk{(short)(a[0] >> shift), (short)(a[1] >> shift)};
+#endif
+}
 
 /* a table index (0..4) in each half as a v_perm_b32 selector: byte 0 / 2 = the index, byte 1 / 3 = 0x0c (constant zero) */
 constexpr uint32_t kSel = 0x0c000c00u;
 
 /* rec + offset[index], clipped to 8 bit: tab_lo / tab_hi hold the five offset bytes + 128, `sel` = the indices of both
  * halves + kSel.  rec + t is non-negative, so the lower clip is the saturation of the unsigned subtraction of the bias */
-__device__ __forceinline__ uint32_t apply(uint32_t rec, uint32_t sel, uint32_t tab_lo, uint32_t tab_hi)
+DBK_HD uint32_t apply(uint32_t rec, uint32_t sel, uint32_t tab_lo, uint32_t tab_hi)
 {
-    const uint32_t t = __builtin_amdgcn_perm(tab_hi, tab_lo, sel);
+    const uint32_t t = dbk::perm(tab_hi, tab_lo, sel);
     const supk v = s_sub_sat(s_upk(rec) + s_upk(t), supk{128, 128});
-    return __builtin_bit_cast(uint32_t, __builtin_elementwise_min(v, supk{255, 255}));
+    return s_bits(s_min(v, supk{255, 255}));
 }
 /* edge index of both samples of `rec` against the neighbour pairs a and b, as a selector (+ kSel): 0..4, 2 = neither minimum nor maximum;
  * clamp(rec + 1 - a, 0, 2) = min(saturating (rec + 1) - a, 2) */
-__device__ __forceinline__ uint32_t edge_idx(uint32_t rec, uint32_t a, uint32_t b)
+DBK_HD uint32_t edge_idx(uint32_t rec, uint32_t a, uint32_t b)
 {
     const supk r1 = s_upk(rec) + supk{1, 1}, two = supk{2, 2};
     /* the halves hold 0..2 each: the sum and the selector constant are ONE 32-bit three-operand add (written out: hipcc sees
      * that no bits overlap, turns the second add into an OR with a literal and then cannot merge the two) */
+    const uint32_t da = s_bits(s_min(s_sub_sat(r1, s_upk(a)), two)), db = s_bits(s_min(s_sub_sat(r1, s_upk(b)), two));
+#if DBK_DEV
     uint32_t r;
-    asm("v_add3_u32 %0, %1, %2, %3"
-        : "=v"(r)
-        : "v"(__builtin_bit_cast(uint32_t, __builtin_elementwise_min(s_sub_sat(r1, s_upk(a)), two))),
-          "v"(__builtin_bit_cast(uint32_t, __builtin_elementwise_min(s_sub_sat(r1, s_upk(b)), two))), "s"(kSel));
+    asm("v_add3_u32 %0, %1, %2, %3" : "=v"(r) : "v"(da), "v"(db), "s"(kSel));
     return r;
+#else
+    return da + db + kSel; /* the instruction: one 32-bit sum, a carry out of the low half would reach the high one */
+#endif
 }
 /* band index of both samples of `rec` as a selector: min(((rec >> shift) - pos) & 31, 4) + kSel, the constant OR-ed in by
  * the mask instruction (v_and_or_b32, written out for the same reason) and carried through the minimum */
-__device__ __forceinline__ uint32_t band_sel(uint32_t rec, int shift, spk pos)
+DBK_HD uint32_t band_sel(uint32_t rec, int shift, spk pos)
 {
+    const uint32_t d = __builtin_bit_cast(uint32_t, s_shr(s_pk(rec), shift) - pos);
+#if DBK_DEV
     uint32_t k;
-    asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(k) : "v"(__builtin_bit_cast(uint32_t, (s_pk(rec) >> shift) - pos)), "s"(0x001f001fu), "v"(kSel));
-    return __builtin_bit_cast(uint32_t, __builtin_elementwise_min(s_upk(k), s_upk(kSel | 0x00040004u)));
+    asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(k) : "v"(d), "s"(0x001f001fu), "v"(kSel));
+#else
+    const uint32_t k = (d & 0x001f001fu) | kSel;
+#endif
+    return s_bits(s_min(s_upk(k), s_upk(kSel | 0x00040004u)));
 }
 
 /* the NROWS (8) output rows of an edge-offset block from its NROWS + 2 (ten) raw rows, class CLS of Table 8-13: 0 (-1,0)/(1,0); 1 (0,-1)/(0,1);
@@ -166,7 +204,7 @@ __device__ __forceinline__ uint32_t band_sel(uint32_t rec, int shift, spk pos)
  * for every direction of the block's mask m (saonox::block_mask: picture border, slice and tile boundaries).
  * store(r, lo, hi) takes output row r as its two dwords. */
 template <int CLS, int BORDER, int NROWS, bool G4 = false, typename Fetch, typename Store>
-__device__ __forceinline__ void edge_rows(const Fetch &fetch, const Store &store, int x, int y0, int w, int h, uint32_t tab_lo,
+DBK_HD void edge_rows(const Fetch &fetch, const Store &store, int x, int y0, int w, int h, uint32_t tab_lo,
                                           uint32_t tab_hi, uint32_t m = 0u)
 {
     constexpr bool horizontal = CLS != 1, vertical = CLS != 0;
@@ -220,7 +258,7 @@ __device__ __forceinline__ void edge_rows(const Fetch &fetch, const Store &store
  * of a 4:2:0 picture with 64-sample luma CTBs) -- the same, where 8-row lanes would spread a wave over four CTBs and run every
  * path that occurs among them with a quarter of its lanes. */
 template <int BORDER, int NROWS = 8, bool G4 = false /* the _g4 kernels: m may carry saonox::W4 */, typename Fetch, typename Store>
-__device__ __forceinline__ void block(const Fetch &fetch, const Store &store, int x, int y0, int w, int h, const DbkSaoCtb &c, bool kept, uint32_t m = 0u)
+DBK_HD void block(const Fetch &fetch, const Store &store, int x, int y0, int w, int h, const DbkSaoCtb &c, bool kept, uint32_t m = 0u)
 {
     if (kept || c.type == 0 || c.type > 2) {
 #pragma unroll
@@ -268,6 +306,18 @@ using sao8::spk;
 using sao8::s_upk;
 using sao8::s_pk;
 using sao8::s_sub_sat;
+using sao8::s_min;
+using sao8::s_bits;
+
+/* v_alignbit_b32: the low 32 bits of {hi:lo} >> shift */
+DBK_HD uint32_t alignbit(uint32_t hi, uint32_t lo, uint32_t shift)
+{
+#if DBK_DEV
+    return __builtin_amdgcn_alignbit(hi, lo, shift);
+#else
+    return (uint32_t)((((uint64_t)hi << 32) | lo) >> (shift & 31u));
+#endif
+}
 
 struct Raw {
     uint32_t d[8];
@@ -278,16 +328,16 @@ struct Row {
     uint32_t R3;
 };
 template <bool HALO>
-__device__ __forceinline__ Row unpack(const Raw &q)
+DBK_HD Row unpack(const Raw &q)
 {
     Row r;
     r.P0 = q.d[2]; r.P1 = q.d[3]; r.P2 = q.d[4]; r.P3 = q.d[5];
     if constexpr (HALO) {
-        r.L0 = __builtin_amdgcn_alignbit(q.d[2], q.d[1], 16); /* (d1.hi, d2.lo) = (s[-1], s0) */
-        r.L1 = __builtin_amdgcn_alignbit(q.d[3], q.d[2], 16);
-        r.L2 = __builtin_amdgcn_alignbit(q.d[4], q.d[3], 16);
-        r.L3 = __builtin_amdgcn_alignbit(q.d[5], q.d[4], 16);
-        r.R3 = __builtin_amdgcn_alignbit(q.d[6], q.d[5], 16); /* (s7, s8) */
+        r.L0 = alignbit(q.d[2], q.d[1], 16); /* (d1.hi, d2.lo) = (s[-1], s0) */
+        r.L1 = alignbit(q.d[3], q.d[2], 16);
+        r.L2 = alignbit(q.d[4], q.d[3], 16);
+        r.L3 = alignbit(q.d[5], q.d[4], 16);
+        r.R3 = alignbit(q.d[6], q.d[5], 16); /* (s7, s8) */
     } else {
         r.L0 = r.L1 = r.L2 = r.L3 = r.R3 = 0u;
     }
@@ -298,16 +348,16 @@ struct Tab {
     uint32_t lo, hi; /* the five offset bytes + 128 */
     uint32_t maxv;   /* max_v in both halves */
 };
-__device__ __forceinline__ uint32_t apply(uint32_t rec, uint32_t idx /* + sao8::kSel */, const Tab &t)
+DBK_HD uint32_t apply(uint32_t rec, uint32_t idx /* + sao8::kSel */, const Tab &t)
 {
-    const uint32_t o = __builtin_amdgcn_perm(t.hi, t.lo, idx);
+    const uint32_t o = dbk::perm(t.hi, t.lo, idx);
     const supk v = s_sub_sat(s_upk(rec) + s_upk(o), supk{128, 128});
-    return __builtin_bit_cast(uint32_t, __builtin_elementwise_min(v, s_upk(t.maxv)));
+    return s_bits(s_min(v, s_upk(t.maxv)));
 }
 using sao8::edge_idx;
 
 template <int CLS, int BORDER, int NROWS, bool G4 = false, typename Fetch, typename Store>
-__device__ __forceinline__ void edge_rows(const Fetch &fetch, const Store &store, int x, int y0, int w, int h, const Tab &t, uint32_t m = 0u)
+DBK_HD void edge_rows(const Fetch &fetch, const Store &store, int x, int y0, int w, int h, const Tab &t, uint32_t m = 0u)
 {
     constexpr bool horizontal = CLS != 1, vertical = CLS != 0;
     constexpr std::bool_constant<horizontal> halo{};
@@ -353,7 +403,7 @@ __device__ __forceinline__ void edge_rows(const Fetch &fetch, const Store &store
 /* one block of 8 x NROWS 16-bit samples (NROWS = 8, or 2 for 32-sample CTBs: see sao8::block); fetch(i) = raw row i = image
  * row y0 - 1 + i; store(r, four dwords) */
 template <int BORDER, int NROWS = 8, bool G4 = false, typename Fetch, typename Store>
-__device__ __forceinline__ void block(const Fetch &fetch, const Store &store, int x, int y0, int w, int h, const DbkSaoCtb &c, bool kept,
+DBK_HD void block(const Fetch &fetch, const Store &store, int x, int y0, int w, int h, const DbkSaoCtb &c, bool kept,
                                       int max_v, int band_shift, uint32_t m = 0u)
 {
     if (kept || c.type == 0 || c.type > 2) {

@@ -592,7 +592,9 @@ HEVCDBK_API int hevcdbk_h265_deblock_sao_device_planes_cf(hevcdbk_context *ctx, 
  * keep map and the picture-border rule are as in the entries above.  One CTB grid -- the luma one -- serves every plane of
  * a picture: the chroma CTBs are the luma CTBs sub-sampled.  Deblocking takes its share of the same syntax elements
  * through the units' HEVCDBK_U_NOX_LEFT / _TOP flags.  The reference has no SAO at all (main.cu:41-43 ends at
- * DeblockingFilter); parity against the per-sample restatement in tests/ only ("parity unpinned").
+ * DeblockingFilter); parity against the per-sample restatement in tests/ only ("parity unpinned").  The meaning of the
+ * bytes is tested on its own, independently of any slice / tile layout -- every byte value under every edge class, bytes
+ * that contradict their neighbours' -- against tests/sao_borders_ref.py: sao_plane_by_bytes.
  * ================================================================================================================== */
 #define HEVCDBK_SAO_NOX_L  0x01u /* the CTB left of this one must not be read by this CTB's samples */
 #define HEVCDBK_SAO_NOX_R  0x02u

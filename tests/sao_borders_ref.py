@@ -93,6 +93,64 @@ def per_ctb(layout):
     return s, a, np.ascontiguousarray(layout["tile_idx"], np.uint16)
 
 
+# ---- the rule stated from the bytes themselves ------------------------------------------------------------------------------
+
+def look_bits(params, lw, lh, h, w):
+    """per sample of an h x w plane: the bits of its CTB's byte that speak for its two neighbours (Table 8-13, by the CTB's
+    class) -- the bit of direction (sign(cx' - cx), sign(cy' - cy)) for a neighbour inside the picture in another CTB
+    (cx', cy'), nothing for a neighbour in the same CTB or outside the picture; 0 in CTBs without edge offset"""
+    yy, xx = np.mgrid[0:h, 0:w]
+    cy, cx = yy >> lh, xx >> lw
+    P = np.asarray(params, ro.SAO_CTB_DTYPE)
+    edge = (P["type"] == 2)[cy, cx]
+    cls = (P["cls"] & 3)[cy, cx]
+    table = np.zeros((3, 3), np.uint8)              # [sign dy + 1, sign dx + 1] -> bit; (0, 0) = the same CTB -> 0
+    for (dy, dx), bit in NOX_BITS.items():
+        table[dy + 1, dx + 1] = bit
+    out = np.zeros((h, w), np.uint8)
+    for c, nbs in HV.items():
+        bits = np.zeros((h, w), np.uint8)
+        for dy, dx in nbs:
+            ny, nx = yy + dy, xx + dx
+            ins = (ny >= 0) & (ny < h) & (nx >= 0) & (nx < w)
+            sy = np.sign((np.clip(ny, 0, h - 1) >> lh) - cy) + 1
+            sx = np.sign((np.clip(nx, 0, w - 1) >> lw) - cx) + 1
+            bits |= np.where(ins, table[sy, sx], 0).astype(np.uint8)
+        out = np.where(edge & (cls == c), bits, out)
+    return out
+
+
+def sao_plane_by_bytes(plane, params, lw, lh, nox, *, bit_depth=8, keep=None, _free=None, _look=None):
+    """8.7.3 on one plane with the boundaries given as hevcdbk_sao_borders bytes -- any bytes, not those of a layout: nox[cy, cx]
+    is the byte of CTB (cx, cy) (columns beyond the grid are not looked at).  Per sample of an edge-offset CTB (cx, cy) and each
+    of its two neighbours: the sample is copied if the neighbour is outside the plane; copied if the neighbour lies in a CTB
+    (cx', cy') != (cx, cy) and THIS CTB's byte has the bit of direction (sign(cx' - cx), sign(cy' - cy)); else the edge offset
+    applies.  No byte of another CTB is looked at.  CTBs of any (1 << lw) x (1 << lh), the last row / column cut by the plane or
+    not.  Band offset and keep as in rext_oracle.sao_plane.  (_free, _look: the border-less result and look_bits of the same
+    operands, for callers that go through many byte arrays.)"""
+    src = np.asarray(plane)
+    h, w = src.shape
+    free = ro.sao_plane(src, params, lw, lh, bit_depth=bit_depth, keep=keep) if _free is None else _free
+    look = look_bits(params, lw, lh, h, w) if _look is None else _look
+    yy, xx = np.mgrid[0:h, 0:w]
+    byte = np.asarray(nox, np.uint8)[yy >> lh, xx >> lw]
+    return np.where((byte & look) != 0, src, free).astype(src.dtype)
+
+
+def reconciled(nox):
+    """what a library that "reconciled" the bytes would use: a CTB's bit also set when the neighbouring CTB in that direction
+    has the bit that points back (the operand's definition says this never happens)"""
+    b = np.asarray(nox, np.uint8)
+    rows, cols = b.shape
+    out = b.copy()
+    for (dy, dx), bit in NOX_BITS.items():
+        back = NOX_BITS[(-dy, -dx)]
+        ys, xs = slice(max(0, -dy), rows - max(0, dy)), slice(max(0, -dx), cols - max(0, dx))
+        yn, xn = slice(max(0, dy), rows - max(0, -dy)), slice(max(0, dx), cols - max(0, -dx))
+        out[ys, xs] |= np.where(b[yn, xn] & back, bit, 0).astype(np.uint8)
+    return out
+
+
 # ---- layouts ------------------------------------------------------------------------------------------------------------
 
 def one_slice(rows, cols):
