@@ -1186,4 +1186,43 @@ int hevcdbk_h265_deblock_sao_device_planes_g4(hevcdbk_context *ctx, const hevcdb
     return rc;
 }
 
+/* ---- semi-planar chroma: one plane of interleaved Cb / Cr pairs (the _sp entry) ---------------------------------------------- */
+
+namespace {
+
+/* what the _sp entry asks of the plane beyond what the planar entries ask of a g4 plane of plane_w x plane_h: a chroma plane whose
+ * rows hold the pairs */
+int sp_plane_ok(const hevcdbk_device_planes *p)
+{
+    if (!p->is_chroma) return HEVCDBK_ERR_ARG;
+    if (g4_kind(p->plane_w, p->plane_h) < 0) return HEVCDBK_ERR_DIMENSIONS;
+    if (!bad_depth(p->bit_depth, p->sample_bytes) && p->pitch < 2 * (size_t)p->plane_w * p->sample_bytes) return HEVCDBK_ERR_ARG;
+    return HEVCDBK_OK;
+}
+
+} /* namespace */
+
+int hevcdbk_h265_filter_device_sp(hevcdbk_context *ctx, const hevcdbk_device_planes *planes, unsigned qp, const hevcdbk_h265_params *params,
+                                  int kernel_variant, const hevcdbk_h265_slice_offsets *slice_offsets, void *hip_stream)
+{
+    if (!ctx || !planes) return HEVCDBK_ERR_ARG;
+    if (int rc = sp_plane_ok(planes)) return rc;
+    DbkH265Args h;
+    if (int rc = h265_args(planes, 1, qp, params, h, true)) return rc; /* h.c_qp_offset = cb_qp_offset: the even samples */
+    const int cr_qp_offset = params ? params->cr_qp_offset : 0;
+    DbkSlOffs sl;
+    if (int rc = sl_args_g4(slice_offsets, planes, 1, HEVCDBK_CHROMA_420, h, sl)) return rc;
+    const int map = kernel_variant & HEVCDBK_MAP_MASK, variant = kernel_variant & ~HEVCDBK_MAP_MASK;
+    if (map != HEVCDBK_MAP_AUTO && map != HEVCDBK_MAP_ROWS && map != HEVCDBK_MAP_LINEAR) return HEVCDBK_ERR_ARG;
+    if (variant != HEVCDBK_KERNEL_PACKED && variant != HEVCDBK_KERNEL_GENERIC && variant != HEVCDBK_KERNEL_AUTO) return HEVCDBK_ERR_ARG;
+    if (map == HEVCDBK_MAP_LINEAR) return HEVCDBK_ERR_UNSUPPORTED; /* the packed kernels have the row map only */
+    const bool pack = dbk_packed_h265_sp_supports(h, (int)planes->sample_bytes);
+    if (variant == HEVCDBK_KERNEL_PACKED && !pack) return HEVCDBK_ERR_UNSUPPORTED;
+    if (int rc = bind(ctx)) return rc;
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->compute;
+    const hipError_t e = (variant != HEVCDBK_KERNEL_GENERIC && pack) ? dbk_launch_packed_h265_sp(h, sl, cr_qp_offset, (int)planes->sample_bytes, s)
+                                                                    : dbk_launch_h265_sp(h, sl, cr_qp_offset, (int)planes->sample_bytes, s);
+    return hip_ok(ctx, e, "kernel launch") ? HEVCDBK_OK : HEVCDBK_ERR_HIP;
+}
+
 } /* extern "C" */

@@ -250,3 +250,13 @@ hipError_t dbk_launch_deblock_sao_h265_g4(const DbkH265Args &h, const DbkSaoArgs
 /* plane 0 = the luma plane (multiples of 8), the others its chroma planes */
 hipError_t dbk_launch_deblock_sao_multi_h265_g4(const DbkH265Args *h, const DbkSaoArgs *s, const DbkSlOffs &sl, int n, int sample_bytes,
                                                 int chroma_format, hipStream_t stream, const DbkSaoNox *nx);
+
+/* ---- semi-planar chroma (the _sp entry of the C ABI; deblock_sp.h): ONE plane of interleaved Cb / Cr pairs of a 4:2:0 picture, both
+ * components in one launch.  plane_w x plane_h, nbx / nby, the bS layouts, the QP map, the per-slice pairs are those of one component; a row holds 2 * plane_w samples.  Built on the forms the _g4 kernels are
+ * built on: sizes that are multiples of 4, sl.n_bytes == 0 = no per-slice offsets with h.tc_off / h.beta_off added.  h.c_qp_offset belongs to the even samples, cr_qp_offset to the odd ones ---- */
+hipError_t dbk_launch_h265_sp(const DbkH265Args &h, const DbkSlOffs &sl, int cr_qp_offset, int sample_bytes, hipStream_t stream);
+/* the packed kernels (deblock_sp.hip): 8-bit samples and 16-bit containers up to 12 bit; pitch, frame stride and both plane addresses
+ * multiples of 8 bytes (8-bit) / 16 bytes (16-bit), i.e. of one half of a block's row; at most 1024 blocks per row (plane_w < 8192);
+ * pitch * plane_h < 2^31 */
+bool dbk_packed_h265_sp_supports(const DbkH265Args &h, int sample_bytes);
+hipError_t dbk_launch_packed_h265_sp(const DbkH265Args &h, const DbkSlOffs &sl, int cr_qp_offset, int sample_bytes, hipStream_t stream);

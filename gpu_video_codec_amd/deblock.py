@@ -344,14 +344,22 @@ class Context:
         return {"exec_s": tm.exec_s, "total_s": tm.total_s, "copy_s": tm.copy_s, "pipelined_s": tm.pipelined_s}
 
     def filter_device_h265(self, planes, qp, *, c_idx=0, tc_offset_div2=0, beta_offset_div2=0, cb_qp_offset=0, cr_qp_offset=0,
-                           variant=KERNEL_AUTO, chroma_format="420", slice_offsets=None, g4=False):
+                           variant=KERNEL_AUTO, chroma_format="420", slice_offsets=None, g4=False, semi_planar=False):
         """hevc_deblocking_filter_h265_device[_cf]: a plane of a picture in chroma_format '400' / '420' / '422' / '444'.
+        semi_planar=True: hevcdbk_h265_filter_device_sp -- `planes` is one plane of interleaved Cb / Cr pairs of a 4:2:0 picture
+        (plane_w x plane_h per component, multiples of 4), both components in one launch: c_idx is not used, cb_qp_offset applies
+        to the even samples and cr_qp_offset to the odd ones.
         slice_offsets: a _lib.SliceOffsets (per-CTB slice_beta_offset_div2 / slice_tc_offset_div2, hevcdbk_h265_filter_device_sl);
         with it tc_offset_div2 / beta_offset_div2 are not used.  g4=True: hevcdbk_h265_filter_device_g4, which also takes a chroma
         plane sized in multiples of 4 (960x540 of a 1920x1080 picture); without it such a plane is refused as ever."""
         cf = _lib.chroma_format_idc(chroma_format)
         prm = _lib.H265Params(tc_offset_div2, beta_offset_div2, cb_qp_offset, cr_qp_offset)
-        if g4:
+        if semi_planar:
+            if cf != _lib.CHROMA_420:
+                raise ValueError("semi_planar is 4:2:0 only")
+            rc = _lib.lib().hevcdbk_h265_filter_device_sp(self.handle, C.byref(planes), int(qp), C.byref(prm), variant,
+                                                          None if slice_offsets is None else C.byref(slice_offsets), None)
+        elif g4:
             rc = _lib.lib().hevcdbk_h265_filter_device_g4(self.handle, C.byref(planes), c_idx, cf, int(qp), C.byref(prm), variant,
                                                           None if slice_offsets is None else C.byref(slice_offsets), None)
         elif slice_offsets is not None:
@@ -641,17 +649,21 @@ class DeviceBatch:
     This is the layout bench.py times: frame f at base + f*frame_stride, tight pitch."""
 
     def __init__(self, ctx, plane_w, plane_h, n_frames, *, bit_depth=8, sample_bytes=None, is_chroma=False,
-                 in_place=False, per_frame_bs=True, pitch=None, storage=None):
+                 in_place=False, per_frame_bs=True, pitch=None, storage=None, semi_planar=False):
         """storage = (src_buffer, dst_buffer) of another batch: lay this batch out in that device memory instead of
-        allocating (a decoder's frame pool serving another geometry); free() then leaves those buffers alone."""
+        allocating (a decoder's frame pool serving another geometry); free() then leaves those buffers alone.
+        semi_planar=True: a plane of interleaved Cb / Cr pairs (semi_planar= on filter_device_h265): plane_w x plane_h are
+        the samples per component, a row holds 2 * plane_w samples, and frames are uploaded and downloaded as (plane_h, plane_w, 2)."""
         self.ctx = ctx
         self.w, self.h, self.n = plane_w, plane_h, n_frames
         self.bit_depth = bit_depth
         self.sb = sample_bytes or (1 if bit_depth == 8 else 2)
         self.dtype = np.uint8 if self.sb == 1 else np.uint16
-        self.is_chroma = is_chroma
-        self.pitch = plane_w * self.sb if pitch is None else int(pitch)  # bytes; > width*sb leaves row padding
-        assert self.pitch >= plane_w * self.sb and self.pitch % self.sb == 0
+        self.semi_planar = bool(semi_planar)
+        self.is_chroma = is_chroma or self.semi_planar
+        self.row_w = plane_w * (2 if self.semi_planar else 1)            # samples a row holds
+        self.pitch = self.row_w * self.sb if pitch is None else int(pitch)  # bytes; > width*sb leaves row padding
+        assert self.pitch >= self.row_w * self.sb and self.pitch % self.sb == 0
         self.frame_bytes = self.pitch * plane_h
         self._borrowed = storage is not None
         if storage is not None:
@@ -662,7 +674,7 @@ class DeviceBatch:
             self.dst = self.src if in_place else ctx.alloc(self.frame_bytes * n_frames)
         self.per_frame_bs = per_frame_bs
         nb = n_frames if per_frame_bs else 1
-        if plane_w % 8 or plane_h % 8:
+        if plane_w % 8 or plane_h % 8 or self.semi_planar:
             # a plane sized in multiples of 4 (the g4= calls of the spec-exact mode): the reference-exact mode and its default bS do
             # not exist for it; the arrays are the spec-exact mode's 4-sample-granular ones, all zero until set_bs()
             L = _lib.lib()
@@ -695,21 +707,24 @@ class DeviceBatch:
     def _pitched(self, a, fill=0):
         """(.., h, w) samples -> (.., h, pitch/sb) with `fill` in the row padding"""
         ps = self.pitch // self.sb
-        if ps == self.w:
+        if ps == self.row_w:
             return np.ascontiguousarray(a, self.dtype)
         out = np.full(a.shape[:-1] + (ps,), fill, self.dtype)
-        out[..., : self.w] = a
+        out[..., : self.row_w] = a
         return out
 
+    def _rows(self, a, lead):
+        """frames as rows of samples: (.., h, w), or (.., h, w, 2) pairs of a semi-planar batch -> (.., h, row_w)"""
+        a = np.asarray(a, self.dtype)
+        want = lead + ((self.h, self.w, 2) if self.semi_planar else (self.h, self.w))
+        assert a.shape == want, (a.shape, want)
+        return a.reshape(lead + (self.h, self.row_w))
+
     def upload_frame(self, f, plane, fill=0):
-        a = np.asarray(plane, self.dtype)
-        assert a.shape == (self.h, self.w)
-        self.src.upload(self._pitched(a, fill), f * self.frame_bytes)
+        self.src.upload(self._pitched(self._rows(plane, ()), fill), f * self.frame_bytes)
 
     def upload_all(self, frames, fill=0):
-        a = np.asarray(frames, self.dtype)
-        assert a.shape == (self.n, self.h, self.w)
-        self.src.upload(self._pitched(a, fill))
+        self.src.upload(self._pitched(self._rows(frames, (self.n,)), fill))
 
     def set_bs(self, f, vert, hor):
         assert self.per_frame_bs or f == 0
@@ -755,7 +770,10 @@ class DeviceBatch:
     def download_frame(self, f, which="dst", with_padding=False):
         buf = self.dst if which == "dst" else self.src
         a = buf.download(self.frame_bytes, f * self.frame_bytes, self.dtype).reshape(self.h, self.pitch // self.sb)
-        return a if with_padding else a[:, : self.w]
+        if with_padding:
+            return a
+        a = a[:, : self.row_w]
+        return a.reshape(self.h, self.w, 2) if self.semi_planar else a
 
     def free(self):
         own = (self.vert, self.hor, self.qp_map) if self._borrowed else (self.src, self.dst, self.vert, self.hor, self.qp_map)

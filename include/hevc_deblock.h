@@ -757,6 +757,39 @@ HEVCDBK_API int hevcdbk_h265_deblock_sao_device_planes_g4(hevcdbk_context *ctx, 
                                                           const hevcdbk_sao_plane_cf *sao, int fused, const hevcdbk_sao_borders *borders,
                                                           const hevcdbk_h265_slice_offsets *slice_offsets, void *hip_stream);
 
+/* ==================================================================================================================
+ * Semi-planar chroma: one plane of interleaved Cb / Cr pairs (the _sp entry).
+ *
+ * Decoder surfaces are semi-planar: one Y plane and one plane whose rows hold Cb0 Cr0 Cb1 Cr1 ... (the NV12 layout, and its sibling
+ * with 16-bit containers).  hevcdbk_h265_filter_device_sp deblocks such a chroma plane as it is, both components in one launch; a
+ * caller need not split the pairs into two planes and merge them again for this stage.  4:2:0 only.  SAO has no _sp entry yet (it
+ * takes the split planes: hevcdbk_sao_filter_device_g4).
+ *
+ * The plane is described by a hevcdbk_device_planes with is_chroma = 1 (is_chroma = 0: HEVCDBK_ERR_ARG):
+ *   - plane_w x plane_h are the samples PER COMPONENT (W/2 x H/2 of the picture); a row holds 2 * plane_w samples, the first
+ *     component at the even positions, the second at the odd ones; pitch >= 2 * plane_w * sample_bytes, else HEVCDBK_ERR_ARG;
+ *   - samples are LSB-aligned in their containers, like every plane here (P010 proper keeps its samples in the high bits: not taken);
+ *   - plane_w and plane_h are multiples of 4 and at least 8 -- the rule of the _g4 entries, so the 960x540 pair plane of a 1920x1080
+ *     picture is taken as it is -- else HEVCDBK_ERR_DIMENSIONS;
+ *   - the bS arrays, the QP map and slice_offsets are those of the plane_w x plane_h chroma plane, exactly what the planar entries
+ *     take, and both components use them (8.7.2 gives Cb and Cr of a 4:2:0 picture the same edges, the same QpY, the same slices and
+ *     the same pcm / bypass flags).  What differs per component is cQpPicOffset.
+ * NV21 order (Cr first) needs no flag: the caller swaps cb_qp_offset and cr_qp_offset.
+ * The result is, per component, what hevcdbk_h265_filter_device_g4 gives for the split planes.
+ * Alignment: pitch, frame_stride and both addresses are multiples of 4 * sample_bytes (else HEVCDBK_ERR_UNSUPPORTED), as for every
+ * plane.  The packed kernels (HEVCDBK_KERNEL_PACKED, and HEVCDBK_KERNEL_AUTO where they apply) further need: samples of at most 12
+ * bit; pitch, frame_stride and both addresses multiples of 8 bytes (8-bit samples) / 16 bytes (16-bit containers); plane_w < 8192
+ * (one workgroup per block row); pitch * plane_h < 2^31.  Otherwise HEVCDBK_KERNEL_AUTO runs the 32-bit kernel and
+ * HEVCDBK_KERNEL_PACKED returns HEVCDBK_ERR_UNSUPPORTED.  The packed kernels have the row map only: HEVCDBK_MAP_LINEAR returns
+ * HEVCDBK_ERR_UNSUPPORTED.
+ * Parity: tests/sp_ref.py -- the planar statement applied per component ("parity unpinned").
+ * ================================================================================================================== */
+/* like hevcdbk_h265_filter_device_g4, both components at once: no c_idx; params->cb_qp_offset applies to the even samples,
+ * params->cr_qp_offset to the odd ones; slice_offsets may be NULL; src may equal dst */
+HEVCDBK_API int hevcdbk_h265_filter_device_sp(hevcdbk_context *ctx, const hevcdbk_device_planes *planes, unsigned qp,
+                                              const hevcdbk_h265_params *params, int kernel_variant,
+                                              const hevcdbk_h265_slice_offsets *slice_offsets, void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif
