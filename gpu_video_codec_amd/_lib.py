@@ -49,7 +49,7 @@ EXPORTS = [
     "hevcdbk_h265_deblock_sao_device_planes_sl",
     "hevcdbk_h265_derive_bs_device_g4", "hevcdbk_h265_filter_device_g4", "hevcdbk_sao_filter_device_g4",
     "hevcdbk_h265_deblock_sao_device_g4", "hevcdbk_h265_deblock_sao_device_planes_g4",
-    "hevcdbk_h265_filter_device_sp",
+    "hevcdbk_h265_filter_device_sp", "hevcdbk_sao_filter_device_sp", "hevcdbk_h265_deblock_sao_device_sp",
 ]
 
 # chroma_format_idc of the spec-exact mode and SAO (HEVCDBK_CHROMA_*): 4:0:0, 4:2:0, 4:2:2, 4:4:4
@@ -303,6 +303,11 @@ def lib():
         # the _sp entry (a semi-planar chroma plane: interleaved Cb / Cr pairs)
         L.hevcdbk_h265_filter_device_sp.argtypes = [C.c_void_p, C.POINTER(DevicePlanes), C.c_uint, C.POINTER(H265Params), C.c_int,
                                                     C.POINTER(SliceOffsets), C.c_void_p]
+        L.hevcdbk_sao_filter_device_sp.argtypes = [C.c_void_p, C.POINTER(DevicePlanes), C.c_void_p, C.c_void_p, C.c_uint, C.c_size_t,
+                                                   C.c_uint, C.c_void_p, C.c_uint, C.c_size_t, C.POINTER(SaoBorders), C.c_void_p]
+        L.hevcdbk_h265_deblock_sao_device_sp.argtypes = [C.c_void_p, C.POINTER(DevicePlanes), C.c_uint, C.POINTER(H265Params), C.c_void_p,
+                                                         C.c_void_p, C.c_uint, C.c_size_t, C.c_uint, C.c_void_p, C.c_uint, C.c_size_t,
+                                                         C.c_int, C.POINTER(SaoBorders), C.POINTER(SliceOffsets), C.c_void_p]
         L.hevc_deblock_sao_h265_device_planes.argtypes = [C.c_void_p, C.POINTER(DevicePlanes), C.c_uint, C.c_uint, C.POINTER(H265Params),
                                                           C.POINTER(SaoPlane), C.c_int, C.c_void_p]
         L.hevcdbk_set_host_threads.argtypes = [C.c_void_p, C.c_uint]

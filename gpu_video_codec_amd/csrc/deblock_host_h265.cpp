@@ -1225,4 +1225,76 @@ int hevcdbk_h265_filter_device_sp(hevcdbk_context *ctx, const hevcdbk_device_pla
     return hip_ok(ctx, e, "kernel launch") ? HEVCDBK_OK : HEVCDBK_ERR_HIP;
 }
 
+namespace {
+
+/* the SAO operands of a pair plane: what sp_plane_ok and, for one component of it, the _g4 SAO entry ask; square CTBs of 8..32 */
+int sp_sao_args(const hevcdbk_device_planes *p, const hevcdbk_sao_ctb *params_cb, const hevcdbk_sao_ctb *params_cr, unsigned params_stride,
+                size_t params_frame_stride, unsigned ctb_log2, const uint8_t *keep, unsigned keep_stride, size_t keep_frame_stride,
+                const hevcdbk_sao_borders *borders, DbkSaoArgs &a, DbkSaoNox &nx)
+{
+    if (int rc = sp_plane_ok(p)) return rc;
+    if (!params_cb || !params_cr || ctb_log2 < 3 || ctb_log2 > 5) return HEVCDBK_ERR_ARG;
+    if (int rc = sao_args(p, params_cb, params_stride, params_frame_stride, ctb_log2, keep, keep_stride, keep_frame_stride, a, true)) return rc;
+    if (borders)
+        if (int rc = nox_args(borders, a, nx)) return rc;
+    return HEVCDBK_OK;
+}
+
+} /* namespace */
+
+int hevcdbk_sao_filter_device_sp(hevcdbk_context *ctx, const hevcdbk_device_planes *planes, const hevcdbk_sao_ctb *params_cb,
+                                 const hevcdbk_sao_ctb *params_cr, unsigned params_stride, size_t params_frame_stride, unsigned ctb_log2,
+                                 const uint8_t *keep, unsigned keep_stride, size_t keep_frame_stride, const hevcdbk_sao_borders *borders,
+                                 void *hip_stream)
+{
+    if (!ctx || !planes) return HEVCDBK_ERR_ARG;
+    DbkSaoArgs a;
+    DbkSaoNox nx;
+    if (int rc = sp_sao_args(planes, params_cb, params_cr, params_stride, params_frame_stride, ctb_log2, keep, keep_stride, keep_frame_stride,
+                             borders, a, nx))
+        return rc;
+    if (int rc = bind(ctx)) return rc;
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->compute;
+    const hipError_t e = dbk_launch_sao_sp(a, reinterpret_cast<const DbkSaoCtb *>(params_cr), (int)planes->sample_bytes, s, borders ? &nx : nullptr);
+    return hip_ok(ctx, e, "SAO launch") ? HEVCDBK_OK : HEVCDBK_ERR_HIP;
+}
+
+int hevcdbk_h265_deblock_sao_device_sp(hevcdbk_context *ctx, const hevcdbk_device_planes *planes, unsigned qp, const hevcdbk_h265_params *prm,
+                                       const hevcdbk_sao_ctb *params_cb, const hevcdbk_sao_ctb *params_cr, unsigned params_stride,
+                                       size_t params_frame_stride, unsigned ctb_log2, const uint8_t *keep, unsigned keep_stride,
+                                       size_t keep_frame_stride, int fused, const hevcdbk_sao_borders *borders,
+                                       const hevcdbk_h265_slice_offsets *slice_offsets, void *hip_stream)
+{
+    if (!ctx || !planes || (fused != HEVCDBK_FUSED_AUTO && fused != HEVCDBK_FUSED_OFF && fused != HEVCDBK_FUSED_ON)) return HEVCDBK_ERR_ARG;
+    DbkSaoArgs sa;
+    DbkSaoNox nx;
+    if (int rc = sp_sao_args(planes, params_cb, params_cr, params_stride, params_frame_stride, ctb_log2, keep, keep_stride, keep_frame_stride,
+                             borders, sa, nx))
+        return rc;
+    DbkH265Args h;
+    if (int rc = h265_args(planes, 1, qp, prm, h, true)) return rc;
+    DbkSlOffs sl;
+    if (int rc = sl_args_g4(slice_offsets, planes, 1, HEVCDBK_CHROMA_420, h, sl)) return rc;
+    if (fused == HEVCDBK_FUSED_ON) return HEVCDBK_ERR_UNSUPPORTED; /* no fused kernel for this layout: before any launch */
+    if (int rc = bind(ctx)) return rc;
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->compute;
+    /* the two launches through the context's scratch plane, as deblock_sao_plane_h265_g4 runs them */
+    hevcdbk_device_planes first, second;
+    if (int rc = tmp_planes(ctx, planes, s, first, second)) return rc;
+    const int tc_off = h.tc_off, beta_off = h.beta_off; /* zero with per-slice offsets (sl_args_g4) */
+    if (int rc = h265_args(&first, 1, qp, prm, h, true)) return rc;
+    h.tc_off = tc_off;
+    h.beta_off = beta_off;
+    const int cr_qp_offset = prm ? prm->cr_qp_offset : 0;
+    const hipError_t e = dbk_packed_h265_sp_supports(h, (int)planes->sample_bytes)
+                             ? dbk_launch_packed_h265_sp(h, sl, cr_qp_offset, (int)planes->sample_bytes, s)
+                             : dbk_launch_h265_sp(h, sl, cr_qp_offset, (int)planes->sample_bytes, s);
+    if (!hip_ok(ctx, e, "kernel launch")) return HEVCDBK_ERR_HIP;
+    sa.src = (const uint8_t *)second.src;
+    if (!hip_ok(ctx, dbk_launch_sao_sp(sa, reinterpret_cast<const DbkSaoCtb *>(params_cr), (int)planes->sample_bytes, s, borders ? &nx : nullptr),
+                "SAO launch"))
+        return HEVCDBK_ERR_HIP;
+    return tmp_done(ctx, s);
+}
+
 } /* extern "C" */

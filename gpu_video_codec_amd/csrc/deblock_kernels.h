@@ -260,3 +260,10 @@ hipError_t dbk_launch_h265_sp(const DbkH265Args &h, const DbkSlOffs &sl, int cr_
  * pitch * plane_h < 2^31 */
 bool dbk_packed_h265_sp_supports(const DbkH265Args &h, int sample_bytes);
 hipError_t dbk_launch_packed_h265_sp(const DbkH265Args &h, const DbkSlOffs &sl, int cr_qp_offset, int sample_bytes, hipStream_t stream);
+/* SAO of the same plane (sao_sp.hip): a.params = the even samples' CTB entries, params_cr the odd samples' (one stride, one frame stride);
+ * a.plane_w x a.plane_h, the CTB grid, the keep map and the boundary bytes are one component's; sizes multiples of 4; nx == NULL or
+ * nx->nox == NULL: no boundary bytes.  The packed kernels (sao8_sp_kernel, sao16_sp_kernel) where dbk_sao_sp_packed_supports says so:
+ * pitch, frame stride and both addresses multiples of a lane's row piece (16 bytes for 8-bit samples, 32 for 16-bit containers),
+ * pitch * plane_h < 2^31, max_v / band_shift those of 8 bit, or of 8..12 bit in 16-bit containers; else the per-sample kernel */
+bool dbk_sao_sp_packed_supports(const DbkSaoArgs &a, int sample_bytes);
+hipError_t dbk_launch_sao_sp(const DbkSaoArgs &a, const DbkSaoCtb *params_cr, int sample_bytes, hipStream_t stream, const DbkSaoNox *nx);

@@ -458,12 +458,27 @@ class Context:
         return res
 
     def sao_device(self, planes, params_ptr, params_stride, ctb_log2, *, params_frame_stride=0, keep_ptr=None, keep_stride=0,
-                   keep_frame_stride=0, chroma_format="420", ctb_log2_h=None, borders=None, g4=False):
+                   keep_frame_stride=0, chroma_format="420", ctb_log2_h=None, borders=None, g4=False, semi_planar=False,
+                   params_cr_ptr=None):
         """hevc_sao_filter_device[_cf]: H.265 8.7.3 on planes in HBM, src -> dst.  ctb_log2 = log2 of this plane's CTB width;
         its height follows from chroma_format (a 4:2:2 chroma plane, planes.is_chroma: twice the width) unless ctb_log2_h says.
         borders: a _lib.SaoBorders (slice / tile boundaries not to be looked across, 8.7.3.2: hevcdbk_sao_filter_device_nox).
-        g4=True: hevcdbk_sao_filter_device_g4, which also takes a plane sized in multiples of 4 (keep map and CTB grid by ceiling)."""
+        g4=True: hevcdbk_sao_filter_device_g4, which also takes a plane sized in multiples of 4 (keep map and CTB grid by ceiling).
+        semi_planar=True: hevcdbk_sao_filter_device_sp -- `planes` is one plane of interleaved Cb / Cr pairs of a 4:2:0 picture
+        (plane_w x plane_h per component, multiples of 4); params_ptr speaks for the even samples, params_cr_ptr (needed) for the odd
+        ones, with one stride and one frame stride; the keep map and borders serve both components; square CTBs of ctb_log2 3..5."""
         cf = _lib.chroma_format_idc(chroma_format)
+        if semi_planar:
+            if cf != _lib.CHROMA_420:
+                raise ValueError("semi_planar is 4:2:0 only")
+            if params_cr_ptr is None:
+                raise ValueError("semi_planar needs params_cr_ptr: the parameters of the odd samples")
+            _chk(_lib.lib().hevcdbk_sao_filter_device_sp(self.handle, C.byref(planes), params_ptr, params_cr_ptr, params_stride,
+                                                         params_frame_stride, ctb_log2, keep_ptr, keep_stride, keep_frame_stride,
+                                                         None if borders is None else C.byref(borders), None), self.handle)
+            return
+        if params_cr_ptr is not None:
+            raise ValueError("params_cr_ptr belongs to semi_planar=True")
         lh = _ctb_log2_h(ctb_log2, ctb_log2_h, cf, planes.is_chroma)
         if g4:
             _chk(_lib.lib().hevcdbk_sao_filter_device_g4(self.handle, C.byref(planes), params_ptr, params_stride, params_frame_stride,
@@ -495,14 +510,28 @@ class Context:
     def deblock_sao_h265_device(self, planes, qp, params_ptr, params_stride, ctb_log2, *, c_idx=0, tc_offset_div2=0,
                                 beta_offset_div2=0, cb_qp_offset=0, cr_qp_offset=0, params_frame_stride=0, keep_ptr=None,
                                 keep_stride=0, keep_frame_stride=0, fused=_lib.FUSED_AUTO, chroma_format="420", ctb_log2_h=None,
-                                borders=None, slice_offsets=None, g4=False):
+                                borders=None, slice_offsets=None, g4=False, semi_planar=False, params_cr_ptr=None):
         """hevc_deblock_sao_h265_device[_cf]: spec-exact deblocking (8.7.2) followed by SAO (8.7.3), src -> dst; chroma_format,
         ctb_log2 / ctb_log2_h and borders (hevcdbk_h265_deblock_sao_device_nox) as for sao_device; slice_offsets as for
         filter_device_h265 (hevcdbk_h265_deblock_sao_device_sl); g4=True: hevcdbk_h265_deblock_sao_device_g4 (a chroma plane
-        sized in multiples of 4)."""
+        sized in multiples of 4).  semi_planar=True: hevcdbk_h265_deblock_sao_device_sp -- a plane of interleaved Cb / Cr pairs as
+        for filter_device_h265 and sao_device (c_idx is not used; params_cr_ptr is needed); fused=FUSED_ON is refused."""
         cf = _lib.chroma_format_idc(chroma_format)
-        lh = _ctb_log2_h(ctb_log2, ctb_log2_h, cf, c_idx != 0)
         prm = _lib.H265Params(tc_offset_div2, beta_offset_div2, cb_qp_offset, cr_qp_offset)
+        if semi_planar:
+            if cf != _lib.CHROMA_420:
+                raise ValueError("semi_planar is 4:2:0 only")
+            if params_cr_ptr is None:
+                raise ValueError("semi_planar needs params_cr_ptr: the parameters of the odd samples")
+            _chk(_lib.lib().hevcdbk_h265_deblock_sao_device_sp(self.handle, C.byref(planes), int(qp), C.byref(prm), params_ptr, params_cr_ptr,
+                                                               params_stride, params_frame_stride, ctb_log2, keep_ptr, keep_stride,
+                                                               keep_frame_stride, fused, None if borders is None else C.byref(borders),
+                                                               None if slice_offsets is None else C.byref(slice_offsets), None),
+                 self.handle)
+            return
+        if params_cr_ptr is not None:
+            raise ValueError("params_cr_ptr belongs to semi_planar=True")
+        lh = _ctb_log2_h(ctb_log2, ctb_log2_h, cf, c_idx != 0)
         if g4:
             _chk(_lib.lib().hevcdbk_h265_deblock_sao_device_g4(self.handle, C.byref(planes), c_idx, cf, int(qp), C.byref(prm), params_ptr,
                                                                params_stride, params_frame_stride, ctb_log2, lh, keep_ptr, keep_stride,

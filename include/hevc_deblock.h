@@ -758,12 +758,13 @@ HEVCDBK_API int hevcdbk_h265_deblock_sao_device_planes_g4(hevcdbk_context *ctx, 
                                                           const hevcdbk_h265_slice_offsets *slice_offsets, void *hip_stream);
 
 /* ==================================================================================================================
- * Semi-planar chroma: one plane of interleaved Cb / Cr pairs (the _sp entry).
+ * Semi-planar chroma: one plane of interleaved Cb / Cr pairs (the _sp entries).
  *
  * Decoder surfaces are semi-planar: one Y plane and one plane whose rows hold Cb0 Cr0 Cb1 Cr1 ... (the NV12 layout, and its sibling
  * with 16-bit containers).  hevcdbk_h265_filter_device_sp deblocks such a chroma plane as it is, both components in one launch; a
- * caller need not split the pairs into two planes and merge them again for this stage.  4:2:0 only.  SAO has no _sp entry yet (it
- * takes the split planes: hevcdbk_sao_filter_device_g4).
+ * caller need not split the pairs into two planes and merge them again.  hevcdbk_sao_filter_device_sp runs SAO on the same plane and
+ * hevcdbk_h265_deblock_sao_device_sp the in-loop chain, deblocking then SAO: a decoder's chroma surface goes in and comes out as it
+ * is.  4:2:0 only.
  *
  * The plane is described by a hevcdbk_device_planes with is_chroma = 1 (is_chroma = 0: HEVCDBK_ERR_ARG):
  *   - plane_w x plane_h are the samples PER COMPONENT (W/2 x H/2 of the picture); a row holds 2 * plane_w samples, the first
@@ -789,6 +790,34 @@ HEVCDBK_API int hevcdbk_h265_deblock_sao_device_planes_g4(hevcdbk_context *ctx, 
 HEVCDBK_API int hevcdbk_h265_filter_device_sp(hevcdbk_context *ctx, const hevcdbk_device_planes *planes, unsigned qp,
                                               const hevcdbk_h265_params *params, int kernel_variant,
                                               const hevcdbk_h265_slice_offsets *slice_offsets, void *hip_stream);
+
+/* SAO (8.7.3) of the pair plane described above, src -> dst (src == dst: HEVCDBK_ERR_ARG, as hevcdbk_sao_filter_device_g4 answers it).
+ *   - params_cb speaks for the even samples of a row, params_cr for the odd ones (NV21: the caller swaps them; either NULL:
+ *     HEVCDBK_ERR_ARG): two arrays with one stride and one frame stride, one entry per CTB of the plane_w x plane_h grid, taken by
+ *     ceiling; the CTBs are square, ctb_log2 = 3..5 (else HEVCDBK_ERR_ARG);
+ *   - keep is ONE map for both components, ceil(plane_w / 8) bytes per row (the flags behind it -- pcm with the loop filter disabled,
+ *     transquant bypass -- belong to the coding unit); borders is ONE operand on the picture's CTB grid; either may be NULL.
+ * The result is, per component, what hevcdbk_sao_filter_device_g4 gives for the split plane with that component's parameters -- for
+ * ANY two entries of a CTB.  H.265 7.3.8.3 gives Cb and Cr of a CTB one SaoTypeIdx and one SaoEoClass with their own offsets and band
+ * position; the kernels take a shorter path where the two agree, and are right where they do not.
+ * The packed kernels run for samples of at most 12 bit when pitch, frame_stride and both addresses are multiples of a lane's row
+ * piece -- 16 bytes (8-bit samples) / 32 bytes (16-bit containers) -- and pitch * plane_h < 2^31; every other plane takes the
+ * per-sample kernel.  There is no kernel_variant.  Parity: tests/sao_sp_ref.py ("parity unpinned"). */
+HEVCDBK_API int hevcdbk_sao_filter_device_sp(hevcdbk_context *ctx, const hevcdbk_device_planes *planes, const hevcdbk_sao_ctb *params_cb,
+                                             const hevcdbk_sao_ctb *params_cr, unsigned params_stride, size_t params_frame_stride,
+                                             unsigned ctb_log2, const uint8_t *keep, unsigned keep_stride, size_t keep_frame_stride,
+                                             const hevcdbk_sao_borders *borders, void *hip_stream);
+
+/* the in-loop chain on the pair plane: hevcdbk_h265_filter_device_sp (HEVCDBK_KERNEL_AUTO) into the context's scratch plane, then
+ * hevcdbk_sao_filter_device_sp from there into dst -- two launches, a host composition.  fused: HEVCDBK_FUSED_AUTO and
+ * HEVCDBK_FUSED_OFF run the two launches; HEVCDBK_FUSED_ON returns HEVCDBK_ERR_UNSUPPORTED before anything is enqueued (there is no
+ * fused kernel for this layout yet; the argument is there so that one needs no new signature); any other value HEVCDBK_ERR_ARG */
+HEVCDBK_API int hevcdbk_h265_deblock_sao_device_sp(hevcdbk_context *ctx, const hevcdbk_device_planes *planes, unsigned qp,
+                                                   const hevcdbk_h265_params *h265_params, const hevcdbk_sao_ctb *params_cb,
+                                                   const hevcdbk_sao_ctb *params_cr, unsigned params_stride, size_t params_frame_stride,
+                                                   unsigned ctb_log2, const uint8_t *keep, unsigned keep_stride, size_t keep_frame_stride,
+                                                   int fused, const hevcdbk_sao_borders *borders,
+                                                   const hevcdbk_h265_slice_offsets *slice_offsets, void *hip_stream);
 
 #ifdef __cplusplus
 }
