@@ -19,43 +19,6 @@ extern "C" {
 size_t hevcdbk_h265_num_vert_bs(unsigned w, unsigned h) { return (size_t)(w / 8 + 1) * (h / 4); }
 size_t hevcdbk_h265_num_hor_bs(unsigned w, unsigned h) { return (size_t)(h / 8 + 1) * (w / 4); }
 
-int hevcdbk_h265_derive_bs_device(hevcdbk_context *ctx, const hevcdbk_h265_units *u, unsigned width, unsigned height,
-                                  uint8_t *vert_bs4, uint8_t *hor_bs4, uint8_t *chroma_vert_bs4, uint8_t *chroma_hor_bs4,
-                                  void *hip_stream)
-{
-    if (!ctx || !u || !u->flags || !u->mv0 || !u->mv1 || !u->ref0 || !u->ref1 || !vert_bs4 || !hor_bs4) return HEVCDBK_ERR_ARG;
-    if ((chroma_vert_bs4 != nullptr) != (chroma_hor_bs4 != nullptr)) return HEVCDBK_ERR_ARG;
-    if (width == 0 || height == 0 || width % 8 != 0 || height % 8 != 0) return HEVCDBK_ERR_DIMENSIONS;
-    if (chroma_vert_bs4 && ((width / 2) % 8 != 0 || (height / 2) % 8 != 0)) return HEVCDBK_ERR_DIMENSIONS;
-    if (int rc = bind(ctx)) return rc;
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->compute;
-    const hipError_t e = dbk_launch_h265_bs(u->flags, u->mv0, u->mv1, u->ref0, u->ref1, (int)width, (int)height, vert_bs4,
-                                            hor_bs4, chroma_vert_bs4, chroma_hor_bs4, s);
-    return hip_ok(ctx, e, "bS derivation launch") ? HEVCDBK_OK : HEVCDBK_ERR_HIP;
-}
-
-int hevcdbk_h265_derive_bs_device_cf(hevcdbk_context *ctx, const hevcdbk_h265_units *u, unsigned width, unsigned height,
-                                     int chroma_format_idc, uint8_t *vert_bs4, uint8_t *hor_bs4, uint8_t *chroma_vert_bs4,
-                                     uint8_t *chroma_hor_bs4, void *hip_stream)
-{
-    const int cf = chroma_format_idc;
-    if (cf == HEVCDBK_CHROMA_420)
-        return hevcdbk_h265_derive_bs_device(ctx, u, width, height, vert_bs4, hor_bs4, chroma_vert_bs4, chroma_hor_bs4, hip_stream);
-    if (!ctx || !u || !u->flags || !u->mv0 || !u->mv1 || !u->ref0 || !u->ref1 || !vert_bs4 || !hor_bs4) return HEVCDBK_ERR_ARG;
-    if (cf < HEVCDBK_CHROMA_400 || cf > HEVCDBK_CHROMA_444) return HEVCDBK_ERR_ARG;
-    if ((chroma_vert_bs4 != nullptr) != (chroma_hor_bs4 != nullptr)) return HEVCDBK_ERR_ARG;
-    if (cf == HEVCDBK_CHROMA_400 && chroma_vert_bs4) return HEVCDBK_ERR_ARG;
-    if (width == 0 || height == 0 || width % 8 != 0 || height % 8 != 0) return HEVCDBK_ERR_DIMENSIONS;
-    if (chroma_vert_bs4 && cf == HEVCDBK_CHROMA_422 && width % 16 != 0) return HEVCDBK_ERR_ARG; /* chroma plane W/2: 8-sample grid */
-    if (int rc = bind(ctx)) return rc;
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->compute;
-    hipError_t e = dbk_launch_h265_bs(u->flags, u->mv0, u->mv1, u->ref0, u->ref1, (int)width, (int)height, vert_bs4, hor_bs4,
-                                      nullptr, nullptr, s);
-    if (e == hipSuccess && chroma_vert_bs4)
-        e = dbk_launch_h265_chroma_bs_cf(vert_bs4, hor_bs4, (int)width, (int)height, cf, chroma_vert_bs4, chroma_hor_bs4, s);
-    return hip_ok(ctx, e, "bS derivation launch") ? HEVCDBK_OK : HEVCDBK_ERR_HIP;
-}
-
 namespace {
 
 /* SubWidthC / SubHeightC of chroma_format_idc 1..3 (H.265 Table 6-1) */
@@ -118,65 +81,189 @@ int h265_args_cf(const hevcdbk_device_planes *planes, int c_idx, int cf, unsigne
     return h265_args(planes, c_idx, qp, prm, h, g4);
 }
 
-/* cf = chroma_format_idc of a chroma plane (1 for luma: the format does not enter luma) */
-int launch_h265(hevcdbk_context *ctx, const DbkH265Args &h0, int sample_bytes, bool chroma, int variant, hipStream_t s, int cf = 1)
+/* "no per-slice offsets" for the _g4 / _sp kernels: an array of no bytes, every pair of which reads (0, 0) */
+const DbkSlOffs kNoSlOffs = {nullptr, 0, 0, 4, 0u};
+
+/* validates the operand against the LUMA picture of plane p (c_idx 0: the plane itself; else scaled by the format) and fills sl */
+int sl_args(const hevcdbk_h265_slice_offsets *so, const hevcdbk_device_planes *p, int c_idx, int cf, DbkSlOffs &sl)
+{
+    if (!so->offs || (uintptr_t)so->offs % 2 != 0 || so->frame_stride % 2 != 0 || so->ctb_log2 < 4 || so->ctb_log2 > 6) return HEVCDBK_ERR_ARG;
+    const unsigned long long lw = (unsigned long long)p->plane_w * (c_idx ? sub_w(cf) : 1u), lh = (unsigned long long)p->plane_h * (c_idx ? sub_h(cf) : 1u);
+    const unsigned long long cols = (lw + (1u << so->ctb_log2) - 1) >> so->ctb_log2, rows = (lh + (1u << so->ctb_log2) - 1) >> so->ctb_log2;
+    if (so->stride < cols || so->stride >= (1u << 23)) return HEVCDBK_ERR_ARG; /* 2 * stride is a 24-bit multiplicand of the kernels */
+    const unsigned long long bytes = 2ull * so->stride * rows;
+    if (bytes > 0x7fffffffull || rows >= (1u << 24)) return HEVCDBK_ERR_ARG;
+    sl.offs = so->offs;
+    sl.stride = (int)so->stride;
+    sl.frame_stride = (long long)so->frame_stride;
+    sl.ctb_log2 = (int)so->ctb_log2;
+    sl.n_bytes = (uint32_t)bytes;
+    return HEVCDBK_OK;
+}
+
+/* the operand of a _g4 launch: the caller's array -- then the call's own pair, which the kernels add, is zero (8.7.2.5.3: the pair is
+ * the slice's) -- or none */
+int sl_args_g4(const hevcdbk_h265_slice_offsets *so, const hevcdbk_device_planes *p, int c_idx, int cf, DbkH265Args &h, DbkSlOffs &sl)
+{
+    if (!so) {
+        sl = kNoSlOffs;
+        return HEVCDBK_OK;
+    }
+    if (int rc = sl_args(so, p, c_idx, cf, sl)) return rc;
+    h.tc_off = h.beta_off = 0;
+    return HEVCDBK_OK;
+}
+
+/* the operand of a plane's launches.  g4 (the call holds a g4 plane): as sl_args_g4 for every plane of the call; else the caller's
+ * array, the call's own pair staying in h (the _sl kernels do not read it) */
+int slice_args(const hevcdbk_h265_slice_offsets *so, const hevcdbk_device_planes *p, int c_idx, int cf, bool g4, DbkH265Args &h, DbkSlOffs &sl)
+{
+    return g4 || !so ? sl_args_g4(so, p, c_idx, cf, h, sl) : sl_args(so, p, c_idx, cf, sl);
+}
+
+/* the kernel generation a plane runs: a g4 plane (where the entry takes one) the _g4 kernels, with kNoSlOffs when there is no
+ * per-slice operand; any other plane the _sl kernels with the operand and the _cf / _nox kernels without it -- never _sl kernels on
+ * an empty array */
+enum class Gen { CF, SL, G4 };
+Gen plane_gen(const hevcdbk_device_planes *p, const hevcdbk_h265_slice_offsets *so, bool g4)
+{
+    if (g4 && g4_kind(p->plane_w, p->plane_h) == 1) return Gen::G4;
+    return so ? Gen::SL : Gen::CF;
+}
+
+/* kernel_variant split into the kernel (HEVCDBK_KERNEL_*) and DbkArgs::map_override; HEVCDBK_ERR_ARG for a selector that does not
+ * exist.  diag_maps: the diagnostic build's maps as well (_cf generation only: the _sl / _g4 / _sp kernels have the product's maps) */
+int check_variant(int &variant, int &map_override, bool diag_maps)
 {
     const int map = variant & HEVCDBK_MAP_MASK; /* as in dbkh::launch */
     variant &= ~HEVCDBK_MAP_MASK;
-    #ifdef HEVCDBK_DIAG
-    if (map != HEVCDBK_MAP_AUTO && map != HEVCDBK_MAP_ROWS && map != HEVCDBK_MAP_LINEAR && map != HEVCDBK_DIAG_MAP_TILES && map != HEVCDBK_DIAG_MAP_STRIPE && map != HEVCDBK_DIAG_MAP_PIPE && map != HEVCDBK_DIAG_MAP_GROUP) return HEVCDBK_ERR_ARG;
-#else
-    if (map != HEVCDBK_MAP_AUTO && map != HEVCDBK_MAP_ROWS && map != HEVCDBK_MAP_LINEAR) return HEVCDBK_ERR_ARG;
+    bool known = map == HEVCDBK_MAP_AUTO || map == HEVCDBK_MAP_ROWS || map == HEVCDBK_MAP_LINEAR;
+#ifdef HEVCDBK_DIAG
+    known = known || (diag_maps && (map == HEVCDBK_DIAG_MAP_TILES || map == HEVCDBK_DIAG_MAP_STRIPE || map == HEVCDBK_DIAG_MAP_PIPE || map == HEVCDBK_DIAG_MAP_GROUP));
 #endif
+    if (!known || (variant != HEVCDBK_KERNEL_PACKED && variant != HEVCDBK_KERNEL_GENERIC && variant != HEVCDBK_KERNEL_AUTO)) return HEVCDBK_ERR_ARG;
+    map_override = map >> 8; /* ROWS 1, LINEAR 2, the diagnostic maps 3..6 */
+    return HEVCDBK_OK;
+}
+
+/* the deblocking launch of plane c_idx of a picture in chroma format cf: the packed kernel where it applies (and is not ruled out),
+ * else the 32-bit one, of generation gen (sl: its per-slice operand, not read by Gen::CF) */
+int launch_h265(hevcdbk_context *ctx, const DbkH265Args &h0, const DbkSlOffs &sl, Gen gen, int sample_bytes, int c_idx, int cf, int variant,
+                hipStream_t s)
+{
+    int map_override;
+    if (int rc = check_variant(variant, map_override, gen == Gen::CF)) return rc;
     DbkH265Args h = h0;
-    h.base.map_override = map == HEVCDBK_MAP_ROWS ? 1 : (map == HEVCDBK_MAP_LINEAR ? 2 : (map == 0x300 ? 3 : (map == 0x400 ? 4 : (map == 0x500 ? 5 : (map == 0x600 ? 6 : 0)))));
+    h.base.map_override = map_override;
+    const bool chroma = c_idx != 0;
+    const bool pack = dbk_packed_h265_supports(h, sample_bytes, chroma);
+    if (variant == HEVCDBK_KERNEL_PACKED && !pack) return HEVCDBK_ERR_UNSUPPORTED;
+    const bool packed = pack && variant != HEVCDBK_KERNEL_GENERIC;
     hipError_t e;
-    if (chroma && cf != HEVCDBK_CHROMA_420) {
+    if (gen == Gen::G4) /* chroma planes only */
+        e = packed ? dbk_launch_packed_h265_g4(h, sl, sample_bytes, cf, s) : dbk_launch_h265_g4(h, sl, sample_bytes, cf, s);
+    else if (gen == Gen::SL) /* luma is format 0 to the 32-bit kernel, format 1 (which does not enter luma) to the packed ones */
+        e = packed ? dbk_launch_packed_h265_sl(h, sl, sample_bytes, chroma, chroma ? cf : 1, s) : dbk_launch_h265_sl(h, sl, sample_bytes, chroma ? cf : 0, s);
+    else if (chroma && cf != HEVCDBK_CHROMA_420)
         /* 4:2:2 / 4:4:4 chroma: the packed kernels (one QP: the 4:2:0 kernels with QpC folded into their scalar tc; a QP map: the
          * format's own instantiations), the 32-bit kernel for every operand kind */
-        const bool pack = dbk_packed_h265_supports(h, sample_bytes, true);
-        if (variant == HEVCDBK_KERNEL_PACKED && !pack) return HEVCDBK_ERR_UNSUPPORTED;
-        if (variant != HEVCDBK_KERNEL_PACKED && variant != HEVCDBK_KERNEL_GENERIC && variant != HEVCDBK_KERNEL_AUTO) return HEVCDBK_ERR_ARG;
-        if (variant != HEVCDBK_KERNEL_GENERIC && pack) e = dbk_launch_packed_h265_cf(h, sample_bytes, true, cf, s);
-        else e = dbk_launch_h265_cf(h, sample_bytes, cf, s);
-        return hip_ok(ctx, e, "kernel launch") ? HEVCDBK_OK : HEVCDBK_ERR_HIP;
-    }
-    const bool can_pack = dbk_packed_h265_supports(h, sample_bytes, chroma);
-    if (variant == HEVCDBK_KERNEL_PACKED) {
-        if (!can_pack) return HEVCDBK_ERR_UNSUPPORTED;
-        e = dbk_launch_packed_h265(h, sample_bytes, chroma, s);
-    } else if (variant == HEVCDBK_KERNEL_GENERIC) {
-        e = dbk_launch_h265(h, sample_bytes, chroma, s);
-    } else if (variant == HEVCDBK_KERNEL_AUTO) {
-        e = can_pack ? dbk_launch_packed_h265(h, sample_bytes, chroma, s) : dbk_launch_h265(h, sample_bytes, chroma, s);
-    } else {
-        return HEVCDBK_ERR_ARG;
-    }
+        e = packed ? dbk_launch_packed_h265_cf(h, sample_bytes, true, cf, s) : dbk_launch_h265_cf(h, sample_bytes, cf, s);
+    else
+        e = packed ? dbk_launch_packed_h265(h, sample_bytes, chroma, s) : dbk_launch_h265(h, sample_bytes, chroma, s);
     return hip_ok(ctx, e, "kernel launch") ? HEVCDBK_OK : HEVCDBK_ERR_HIP;
+}
+
+/* the bS derivation entries.  g4: chroma planes of multiples of 4 (the _g4 entry) */
+int derive_bs(hevcdbk_context *ctx, const hevcdbk_h265_units *u, unsigned width, unsigned height, int cf, bool g4, uint8_t *vert_bs4,
+              uint8_t *hor_bs4, uint8_t *chroma_vert_bs4, uint8_t *chroma_hor_bs4, void *hip_stream)
+{
+    if (!ctx || !u || !u->flags || !u->mv0 || !u->mv1 || !u->ref0 || !u->ref1 || !vert_bs4 || !hor_bs4) return HEVCDBK_ERR_ARG;
+    if (cf < HEVCDBK_CHROMA_400 || cf > HEVCDBK_CHROMA_444) return HEVCDBK_ERR_ARG;
+    if ((chroma_vert_bs4 != nullptr) != (chroma_hor_bs4 != nullptr)) return HEVCDBK_ERR_ARG;
+    if (cf == HEVCDBK_CHROMA_400 && chroma_vert_bs4) return HEVCDBK_ERR_ARG;
+    if (width == 0 || height == 0 || width % 8 != 0 || height % 8 != 0) return HEVCDBK_ERR_DIMENSIONS;
+    if (chroma_vert_bs4) {
+        const unsigned cw = width / sub_w(cf), ch = height / sub_h(cf);
+        /* _g4: multiples of 4 in every format, what is left to ask is "at least 8".  The others: the chroma planes' 8-sample grid;
+         * the codes are the generations' own (4:2:0 entry: a dimension error; _cf: 4:2:2 with width % 16 != 0 an argument error) */
+        if (g4 ? g4_kind(cw, ch) < 0 : (cw % 8 != 0 || ch % 8 != 0)) return g4 || cf == HEVCDBK_CHROMA_420 ? HEVCDBK_ERR_DIMENSIONS : HEVCDBK_ERR_ARG;
+    }
+    if (int rc = bind(ctx)) return rc;
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->compute;
+    const bool gather = cf == HEVCDBK_CHROMA_420; /* 4:2:0 chroma arrays come out of the luma launch (its gathers divide with floor) */
+    hipError_t e = dbk_launch_h265_bs(u->flags, u->mv0, u->mv1, u->ref0, u->ref1, (int)width, (int)height, vert_bs4, hor_bs4,
+                                      gather ? chroma_vert_bs4 : nullptr, gather ? chroma_hor_bs4 : nullptr, s);
+    if (e == hipSuccess && chroma_vert_bs4 && !gather)
+        e = dbk_launch_h265_chroma_bs_cf(vert_bs4, hor_bs4, (int)width, (int)height, cf, chroma_vert_bs4, chroma_hor_bs4, s);
+    return hip_ok(ctx, e, "bS derivation launch") ? HEVCDBK_OK : HEVCDBK_ERR_HIP;
+}
+
+/* the block filter entries.  g4: the entry takes a g4 plane */
+int filter_plane(hevcdbk_context *ctx, const hevcdbk_device_planes *planes, int c_idx, int cf, unsigned qp, const hevcdbk_h265_params *params,
+                 int kernel_variant, const hevcdbk_h265_slice_offsets *so, bool g4, void *hip_stream)
+{
+    if (!ctx) return HEVCDBK_ERR_ARG;
+    DbkH265Args h;
+    if (int rc = h265_args_cf(planes, c_idx, cf, qp, params, h, g4)) return rc;
+    const Gen gen = plane_gen(planes, so, g4);
+    DbkSlOffs sl;
+    if (int rc = slice_args(so, planes, c_idx, cf, gen == Gen::G4, h, sl)) return rc;
+    if (gen != Gen::CF) { /* the _sl and _g4 generations check kernel_variant before they bind the device, the _cf one after (in launch_h265) */
+        int variant = kernel_variant, map_override;
+        if (int rc = check_variant(variant, map_override, false)) return rc;
+        if (variant == HEVCDBK_KERNEL_PACKED && !dbk_packed_h265_supports(h, (int)planes->sample_bytes, c_idx != 0)) return HEVCDBK_ERR_UNSUPPORTED;
+    }
+    if (int rc = bind(ctx)) return rc;
+    return launch_h265(ctx, h, sl, gen, (int)planes->sample_bytes, c_idx, cf, kernel_variant, hip_stream ? (hipStream_t)hip_stream : ctx->compute);
 }
 
 } /* namespace */
 
+int hevcdbk_h265_derive_bs_device(hevcdbk_context *ctx, const hevcdbk_h265_units *u, unsigned width, unsigned height,
+                                  uint8_t *vert_bs4, uint8_t *hor_bs4, uint8_t *chroma_vert_bs4, uint8_t *chroma_hor_bs4,
+                                  void *hip_stream)
+{
+    return derive_bs(ctx, u, width, height, HEVCDBK_CHROMA_420, false, vert_bs4, hor_bs4, chroma_vert_bs4, chroma_hor_bs4, hip_stream);
+}
+
+int hevcdbk_h265_derive_bs_device_cf(hevcdbk_context *ctx, const hevcdbk_h265_units *u, unsigned width, unsigned height,
+                                     int chroma_format_idc, uint8_t *vert_bs4, uint8_t *hor_bs4, uint8_t *chroma_vert_bs4,
+                                     uint8_t *chroma_hor_bs4, void *hip_stream)
+{
+    return derive_bs(ctx, u, width, height, chroma_format_idc, false, vert_bs4, hor_bs4, chroma_vert_bs4, chroma_hor_bs4, hip_stream);
+}
+
+int hevcdbk_h265_derive_bs_device_g4(hevcdbk_context *ctx, const hevcdbk_h265_units *u, unsigned width, unsigned height,
+                                     int chroma_format_idc, uint8_t *vert_bs4, uint8_t *hor_bs4, uint8_t *chroma_vert_bs4,
+                                     uint8_t *chroma_hor_bs4, void *hip_stream)
+{
+    return derive_bs(ctx, u, width, height, chroma_format_idc, true, vert_bs4, hor_bs4, chroma_vert_bs4, chroma_hor_bs4, hip_stream);
+}
+
 int hevc_deblocking_filter_h265_device(hevcdbk_context *ctx, const hevcdbk_device_planes *planes, int c_idx, unsigned qp,
                                        const hevcdbk_h265_params *params, int kernel_variant, void *hip_stream)
 {
-    if (!ctx) return HEVCDBK_ERR_ARG;
-    DbkH265Args h;
-    if (int rc = h265_args(planes, c_idx, qp, params, h)) return rc;
-    if (int rc = bind(ctx)) return rc;
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->compute;
-    return launch_h265(ctx, h, (int)planes->sample_bytes, c_idx != 0, kernel_variant, s);
+    return filter_plane(ctx, planes, c_idx, HEVCDBK_CHROMA_420, qp, params, kernel_variant, nullptr, false, hip_stream);
 }
 
 int hevcdbk_h265_filter_device_cf(hevcdbk_context *ctx, const hevcdbk_device_planes *planes, int c_idx, int chroma_format_idc,
                                           unsigned qp, const hevcdbk_h265_params *params, int kernel_variant, void *hip_stream)
 {
-    if (!ctx) return HEVCDBK_ERR_ARG;
-    DbkH265Args h;
-    if (int rc = h265_args_cf(planes, c_idx, chroma_format_idc, qp, params, h)) return rc;
-    if (int rc = bind(ctx)) return rc;
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->compute;
-    return launch_h265(ctx, h, (int)planes->sample_bytes, c_idx != 0, kernel_variant, s, c_idx != 0 ? chroma_format_idc : 1);
+    return filter_plane(ctx, planes, c_idx, chroma_format_idc, qp, params, kernel_variant, nullptr, false, hip_stream);
+}
+
+int hevcdbk_h265_filter_device_sl(hevcdbk_context *ctx, const hevcdbk_device_planes *planes, int c_idx, int chroma_format_idc, unsigned qp,
+                                  const hevcdbk_h265_params *params, int kernel_variant, const hevcdbk_h265_slice_offsets *slice_offsets,
+                                  void *hip_stream)
+{
+    return filter_plane(ctx, planes, c_idx, chroma_format_idc, qp, params, kernel_variant, slice_offsets, false, hip_stream);
+}
+
+int hevcdbk_h265_filter_device_g4(hevcdbk_context *ctx, const hevcdbk_device_planes *planes, int c_idx, int chroma_format_idc, unsigned qp,
+                                  const hevcdbk_h265_params *params, int kernel_variant, const hevcdbk_h265_slice_offsets *slice_offsets,
+                                  void *hip_stream)
+{
+    return filter_plane(ctx, planes, c_idx, chroma_format_idc, qp, params, kernel_variant, slice_offsets, true, hip_stream);
 }
 
 int hevc_deblocking_filter_h265(hevcdbk_context *ctx, hevcdbk_frame *frame, const hevcdbk_h265_units *units,
@@ -291,7 +378,7 @@ int hevcdbk_h265_filter_frame_cf(hevcdbk_context *ctx, hevcdbk_frame *frame, int
         p.qp_map = dmap; p.qp_map_stride = qp->map_stride; p.ctu_log2 = qp->ctu_log2;
         DbkH265Args h;
         if (int rc = h265_args(&p, i, qp->qp, params, h)) return rc;
-        if (int rc = launch_h265(ctx, h, (int)sb, i != 0, HEVCDBK_KERNEL_AUTO, s, i != 0 ? cf : 1)) return rc;
+        if (int rc = launch_h265(ctx, h, kNoSlOffs, Gen::CF, (int)sb, i, cf, HEVCDBK_KERNEL_AUTO, s)) return rc;
     }
     HIP_TRY(ctx, hipEventRecord(ev[2], s));
     if (!dpush) HIP_TRY(ctx, hipMemcpyAsync(ring, ctx->dev[0].p, frame_bytes, hipMemcpyDeviceToHost, s));
@@ -384,37 +471,35 @@ int tmp_done(hevcdbk_context *ctx, hipStream_t s)
     return HEVCDBK_OK;
 }
 
+/* the two-launch form itself: deblock(first) filters the plane into the scratch plane, sao() -- its source now the scratch plane --
+ * reads it from there; fenced for the next user */
+extern "C++" template <class Deblock, class Sao>
+int through_scratch(hevcdbk_context *ctx, const hevcdbk_device_planes *p, hipStream_t s, DbkSaoArgs &sa, Deblock deblock, Sao sao)
+{
+    hevcdbk_device_planes first, second;
+    if (int rc = tmp_planes(ctx, p, s, first, second)) return rc;
+    if (int rc = deblock(first)) return rc;
+    sa.src = (const uint8_t *)second.src;
+    if (int rc = sao()) return rc;
+    return tmp_done(ctx, s);
+}
+
 /* one plane: the fused kernel where it applies (and is not switched off), else the two launches */
 int deblock_sao_plane(hevcdbk_context *ctx, const hevcdbk_device_planes *p, unsigned qp, const hevcdbk_tables *tables, DbkArgs &da,
                       DbkSaoArgs &sa, int fused, hipStream_t s)
 {
-    const bool can = dbk_deblock_sao_supports(da, sa, (int)p->sample_bytes, p->is_chroma != 0);
+    const int sb = (int)p->sample_bytes;
+    const bool chroma = p->is_chroma != 0, can = dbk_deblock_sao_supports(da, sa, sb, chroma);
     if (fused == HEVCDBK_FUSED_ON && !can) return HEVCDBK_ERR_UNSUPPORTED;
     if (can && fused != HEVCDBK_FUSED_OFF)
-        return hip_ok(ctx, dbk_launch_deblock_sao(da, sa, (int)p->sample_bytes, p->is_chroma != 0, s), "fused deblocking + SAO launch") ? HEVCDBK_OK : HEVCDBK_ERR_HIP;
-    hevcdbk_device_planes first, second;
-    if (int rc = tmp_planes(ctx, p, s, first, second)) return rc;
-    if (int rc = planes_to_args(&first, qp, tables, da)) return rc;
-    if (int rc = launch(ctx, da, (int)p->sample_bytes, p->is_chroma != 0, HEVCDBK_KERNEL_AUTO, s)) return rc;
-    sa.src = (const uint8_t *)second.src;
-    if (!hip_ok(ctx, dbk_launch_sao(sa, (int)p->sample_bytes, s), "SAO launch")) return HEVCDBK_ERR_HIP;
-    return tmp_done(ctx, s);
-}
-int deblock_sao_plane_h265(hevcdbk_context *ctx, const hevcdbk_device_planes *p, int c_idx, unsigned qp, const hevcdbk_h265_params *prm,
-                           DbkH265Args &h, DbkSaoArgs &sa, int fused, hipStream_t s, const DbkSaoNox *nx = nullptr)
-{
-    const bool can = dbk_packed_h265_supports(h, (int)p->sample_bytes, c_idx != 0) &&
-                     dbk_deblock_sao_supports(h.base, sa, (int)p->sample_bytes, c_idx != 0);
-    if (fused == HEVCDBK_FUSED_ON && !can) return HEVCDBK_ERR_UNSUPPORTED;
-    if (can && fused != HEVCDBK_FUSED_OFF)
-        return hip_ok(ctx, dbk_launch_deblock_sao_h265_cf(h, sa, (int)p->sample_bytes, c_idx != 0, 1, s, nx), "fused deblocking + SAO launch") ? HEVCDBK_OK : HEVCDBK_ERR_HIP;
-    hevcdbk_device_planes first, second;
-    if (int rc = tmp_planes(ctx, p, s, first, second)) return rc;
-    if (int rc = h265_args(&first, c_idx, qp, prm, h)) return rc;
-    if (int rc = launch_h265(ctx, h, (int)p->sample_bytes, c_idx != 0, HEVCDBK_KERNEL_AUTO, s)) return rc;
-    sa.src = (const uint8_t *)second.src;
-    if (!hip_ok(ctx, dbk_launch_sao(sa, (int)p->sample_bytes, s, nx), "SAO launch")) return HEVCDBK_ERR_HIP;
-    return tmp_done(ctx, s);
+        return hip_ok(ctx, dbk_launch_deblock_sao(da, sa, sb, chroma, s), "fused deblocking + SAO launch") ? HEVCDBK_OK : HEVCDBK_ERR_HIP;
+    return through_scratch(
+        ctx, p, s, sa,
+        [&](const hevcdbk_device_planes &first) {
+            if (int rc = planes_to_args(&first, qp, tables, da)) return rc;
+            return launch(ctx, da, sb, chroma, HEVCDBK_KERNEL_AUTO, s);
+        },
+        [&] { return hip_ok(ctx, dbk_launch_sao(sa, sb, s), "SAO launch") ? HEVCDBK_OK : HEVCDBK_ERR_HIP; });
 }
 
 /* 4:2:2 chroma planes (ctb_log2_h[i] = sa[i].ctb_log2 + 1): their SAO parameters rewritten as those of square CTBs into the
@@ -473,26 +558,6 @@ bool fused_can(const DbkH265Args &h, const DbkSaoArgs &sa, const hevcdbk_device_
     return dbk_packed_h265_supports(h, (int)p->sample_bytes, c_idx != 0) && dbk_deblock_sao_supports(h.base, sa, (int)p->sample_bytes, c_idx != 0);
 }
 
-/* deblock_sao_plane_h265 for a plane of a picture in chroma format cf (luma: cf 1), square CTBs (after sao_square_params) */
-int deblock_sao_plane_h265_cf(hevcdbk_context *ctx, const hevcdbk_device_planes *p, int c_idx, int cf, unsigned qp,
-                              const hevcdbk_h265_params *prm, DbkH265Args &h, DbkSaoArgs &sa, int fused, hipStream_t s,
-                              const DbkSaoNox *nx = nullptr)
-{
-    if (cf == HEVCDBK_CHROMA_420 || c_idx == 0) return deblock_sao_plane_h265(ctx, p, c_idx, qp, prm, h, sa, fused, s, nx);
-    const bool can = fused_can(h, sa, p, c_idx);
-    if (fused == HEVCDBK_FUSED_ON && !can) return HEVCDBK_ERR_UNSUPPORTED;
-    if (can && fused != HEVCDBK_FUSED_OFF)
-        return hip_ok(ctx, dbk_launch_deblock_sao_h265_cf(h, sa, (int)p->sample_bytes, true, cf, s, nx), "fused deblocking + SAO launch")
-                   ? HEVCDBK_OK : HEVCDBK_ERR_HIP;
-    hevcdbk_device_planes first, second;
-    if (int rc = tmp_planes(ctx, p, s, first, second)) return rc;
-    if (int rc = h265_args(&first, c_idx, qp, prm, h)) return rc;
-    if (int rc = launch_h265(ctx, h, (int)p->sample_bytes, true, HEVCDBK_KERNEL_AUTO, s, cf)) return rc;
-    sa.src = (const uint8_t *)second.src;
-    if (!hip_ok(ctx, dbk_launch_sao(sa, (int)p->sample_bytes, s, nx), "SAO launch")) return HEVCDBK_ERR_HIP;
-    return tmp_done(ctx, s);
-}
-
 /* validates the slice / tile boundary operand of a plane whose SAO operands are `a` (before sao_square_params) and fills nx */
 int nox_args(const hevcdbk_sao_borders *b, const DbkSaoArgs &a, DbkSaoNox &nx)
 {
@@ -503,16 +568,86 @@ int nox_args(const hevcdbk_sao_borders *b, const DbkSaoArgs &a, DbkSaoNox &nx)
     return HEVCDBK_OK;
 }
 
-} /* namespace */
+/* what a deblocking + SAO call says about its picture, whichever generation of the C ABI it came through */
+struct Picture {
+    int cf;                                   /* chroma_format_idc (4:2:0 for the original entries) */
+    unsigned qp;
+    const hevcdbk_h265_params *prm;
+    int fused;
+    const hevcdbk_sao_borders *borders;       /* may be NULL: the kernels without the operand */
+    const hevcdbk_h265_slice_offsets *so;     /* may be NULL: likewise */
+    bool first_gen;                           /* the original 4:2:0 entries: square CTBs, and HEVCDBK_FUSED_ON is looked at after the bind */
+    bool g4;                                  /* a _g4 entry that was given a g4 plane */
+};
 
-int hevcdbk_sao_filter_device_nox(hevcdbk_context *ctx, const hevcdbk_device_planes *p, const hevcdbk_sao_ctb *params,
-                                  unsigned params_stride, size_t params_frame_stride, unsigned ctb_log2_w, unsigned ctb_log2_h,
-                                  const uint8_t *keep, unsigned keep_stride, size_t keep_frame_stride,
-                                  const hevcdbk_sao_borders *borders, void *hip_stream)
+bool bad_fused(int fused) { return fused != HEVCDBK_FUSED_AUTO && fused != HEVCDBK_FUSED_OFF && fused != HEVCDBK_FUSED_ON; }
+
+/* validates the operands of plane c_idx and fills what its launches take */
+int plane_operands(const Picture &pic, const hevcdbk_device_planes *p, int c_idx, const hevcdbk_sao_plane_cf &sao, DbkH265Args &h, DbkSaoArgs &sa,
+                   DbkSaoNox &nx, DbkSlOffs &sl)
+{
+    if (int rc = pic.first_gen ? sao_args(p, sao.params, sao.params_stride, sao.params_frame_stride, sao.ctb_log2_w, sao.keep, sao.keep_stride,
+                                          sao.keep_frame_stride, sa)
+                               : sao_args_cf(p, sao.params, sao.params_stride, sao.params_frame_stride, sao.ctb_log2_w, sao.ctb_log2_h, sao.keep,
+                                             sao.keep_stride, sao.keep_frame_stride, sa, pic.g4))
+        return rc;
+    if (int rc = h265_args_cf(p, c_idx, pic.cf, pic.qp, pic.prm, h, pic.g4)) return rc;
+    if (pic.borders)
+        if (int rc = nox_args(pic.borders, sa, nx)) return rc;
+    return slice_args(pic.so, p, c_idx, pic.cf, pic.g4, h, sl);
+}
+
+/* deblocking + SAO of one plane (square CTBs: after sao_square_params): the fused kernel where it applies (and is not switched
+ * off), else the two launches through the context's scratch plane; the kernels of the plane's generation */
+int deblock_sao_plane_h265(hevcdbk_context *ctx, const Picture &pic, const hevcdbk_device_planes *p, int c_idx, DbkH265Args &h, DbkSaoArgs &sa,
+                           const DbkSlOffs &sl, const DbkSaoNox *nx, hipStream_t s)
+{
+    const Gen gen = plane_gen(p, pic.so, pic.g4);
+    const int sb = (int)p->sample_bytes, cf = c_idx != 0 ? pic.cf : 1; /* the format does not enter luma */
+    const bool can = fused_can(h, sa, p, c_idx);
+    if (pic.fused == HEVCDBK_FUSED_ON && !can) return HEVCDBK_ERR_UNSUPPORTED;
+    if (can && pic.fused != HEVCDBK_FUSED_OFF) {
+        const hipError_t e = gen == Gen::G4   ? dbk_launch_deblock_sao_h265_g4(h, sa, sl, sb, pic.cf, s, nx)
+                             : gen == Gen::SL ? dbk_launch_deblock_sao_h265_sl(h, sa, sl, sb, c_idx != 0, cf, s, nx)
+                                              : dbk_launch_deblock_sao_h265_cf(h, sa, sb, c_idx != 0, cf, s, nx);
+        return hip_ok(ctx, e, "fused deblocking + SAO launch") ? HEVCDBK_OK : HEVCDBK_ERR_HIP;
+    }
+    const int tc_off = h.tc_off, beta_off = h.beta_off;
+    return through_scratch(
+        ctx, p, s, sa,
+        [&](const hevcdbk_device_planes &first) {
+            if (int rc = h265_args(&first, c_idx, pic.qp, pic.prm, h, gen == Gen::G4)) return rc;
+            if (gen == Gen::G4) { /* zero with per-slice offsets (sl_args_g4); _g4 generation only: the _sl kernels do not read the pair */
+                h.tc_off = tc_off;
+                h.beta_off = beta_off;
+            }
+            return launch_h265(ctx, h, sl, gen, sb, c_idx, pic.cf, HEVCDBK_KERNEL_AUTO, s);
+        },
+        [&] {
+            return hip_ok(ctx, gen == Gen::G4 ? dbk_launch_sao_g4(sa, sb, s, nx) : dbk_launch_sao(sa, sb, s, nx), "SAO launch") ? HEVCDBK_OK : HEVCDBK_ERR_HIP;
+        });
+}
+
+/* HEVCDBK_FUSED_ON where the fused kernel does not apply is refused before the device is bound -- by the original entries after
+ * (first generation: they looked inside deblock_sao_plane_h265) */
+int bind_or_refuse(hevcdbk_context *ctx, const Picture &pic, bool refuse)
+{
+    if (refuse && !pic.first_gen) return HEVCDBK_ERR_UNSUPPORTED;
+    if (int rc = bind(ctx)) return rc;
+    return refuse ? HEVCDBK_ERR_UNSUPPORTED : HEVCDBK_OK;
+}
+
+/* the SAO pass entries.  first_gen: hevc_sao_filter_device (one ctb_log2); g4_entry: the entry takes a g4 plane */
+int sao_pass(hevcdbk_context *ctx, const hevcdbk_device_planes *p, const hevcdbk_sao_plane_cf &sao, const hevcdbk_sao_borders *borders,
+             bool first_gen, bool g4_entry, void *hip_stream)
 {
     if (!ctx) return HEVCDBK_ERR_ARG;
+    const bool g4 = g4_entry && p && g4_kind(p->plane_w, p->plane_h) == 1;
     DbkSaoArgs a;
-    if (int rc = sao_args_cf(p, params, params_stride, params_frame_stride, ctb_log2_w, ctb_log2_h, keep, keep_stride, keep_frame_stride, a))
+    if (int rc = first_gen ? sao_args(p, sao.params, sao.params_stride, sao.params_frame_stride, sao.ctb_log2_w, sao.keep, sao.keep_stride,
+                                      sao.keep_frame_stride, a)
+                           : sao_args_cf(p, sao.params, sao.params_stride, sao.params_frame_stride, sao.ctb_log2_w, sao.ctb_log2_h, sao.keep,
+                                         sao.keep_stride, sao.keep_frame_stride, a, g4))
         return rc;
     DbkSaoNox nx, *nxp = nullptr; /* no operand: the kernels without it */
     if (borders) {
@@ -521,17 +656,126 @@ int hevcdbk_sao_filter_device_nox(hevcdbk_context *ctx, const hevcdbk_device_pla
     }
     if (int rc = bind(ctx)) return rc;
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->compute;
-    if (int rc = sao_square_params(ctx, &a, &ctb_log2_h, 1, s, nxp)) return rc;
-    if (!hip_ok(ctx, dbk_launch_sao(a, (int)p->sample_bytes, s, nxp), "SAO launch")) return HEVCDBK_ERR_HIP;
-    return ctb_log2_h != ctb_log2_w ? sao_done(ctx, s) : HEVCDBK_OK;
+    if (int rc = sao_square_params(ctx, &a, &sao.ctb_log2_h, 1, s, nxp)) return rc;
+    /* (a failed launch leaves the parameter launch unfenced: as the _cf generation wrote it, before the deblocking + SAO entries fenced "whatever followed") */
+    if (!hip_ok(ctx, g4 ? dbk_launch_sao_g4(a, (int)p->sample_bytes, s, nxp) : dbk_launch_sao(a, (int)p->sample_bytes, s, nxp), "SAO launch")) return HEVCDBK_ERR_HIP;
+    return sao.ctb_log2_h != sao.ctb_log2_w ? sao_done(ctx, s) : HEVCDBK_OK;
+}
+
+/* the one-plane deblocking + SAO entries (pic.g4: the entry takes a g4 plane) */
+int deblock_sao_one(hevcdbk_context *ctx, Picture pic, const hevcdbk_device_planes *p, int c_idx, const hevcdbk_sao_plane_cf &sao, void *hip_stream)
+{
+    if (!ctx || bad_fused(pic.fused)) return HEVCDBK_ERR_ARG;
+    pic.g4 = pic.g4 && p && g4_kind(p->plane_w, p->plane_h) == 1;
+    DbkH265Args h;
+    DbkSaoArgs sa;
+    DbkSaoNox nx, *nxp = pic.borders ? &nx : nullptr;
+    DbkSlOffs sl;
+    if (int rc = plane_operands(pic, p, c_idx, sao, h, sa, nx, sl)) return rc;
+    if (int rc = bind_or_refuse(ctx, pic, pic.fused == HEVCDBK_FUSED_ON && !fused_can(h, sa, p, c_idx))) return rc;
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->compute;
+    if (int rc = sao_square_params(ctx, &sa, &sao.ctb_log2_h, 1, s, nxp)) return rc;
+    const int rc = deblock_sao_plane_h265(ctx, pic, p, c_idx, h, sa, sl, nxp, s);
+    if (sao.ctb_log2_h != sao.ctb_log2_w)
+        if (int rc2 = sao_done(ctx, s)) return rc ? rc : rc2; /* the parameter launch is fenced whatever followed it */
+    return rc;
+}
+
+/* the Y + Cb + Cr entries: deblocking + SAO of all planes in ONE launch where the fused kernel takes every plane, else plane by plane;
+ * every plane is checked before the first launch (pic.g4: the entry takes g4 planes) */
+int deblock_sao_planes(hevcdbk_context *ctx, Picture pic, const hevcdbk_device_planes *planes, unsigned n_planes, const hevcdbk_sao_plane_cf *sao,
+                       void *hip_stream)
+{
+    const int cf = pic.cf;
+    if (!ctx || !planes || !sao || n_planes == 0 || n_planes > 3 || cf < HEVCDBK_CHROMA_400 || cf > HEVCDBK_CHROMA_444 || bad_fused(pic.fused))
+        return HEVCDBK_ERR_ARG;
+    if (cf == HEVCDBK_CHROMA_400 && n_planes > 1) return HEVCDBK_ERR_ARG;
+    bool any_g4 = false, square = true;
+    for (unsigned i = 0; i < n_planes; i++) {
+        any_g4 = any_g4 || g4_kind(planes[i].plane_w, planes[i].plane_h) == 1;
+        square = square && sao[i].ctb_log2_w == sao[i].ctb_log2_h;
+    }
+    pic.g4 = pic.g4 && any_g4;
+    /* 4:2:0 with square CTBs and no operand of a later generation: exactly the original entry, its order of checks included */
+    pic.first_gen = pic.first_gen || (cf == HEVCDBK_CHROMA_420 && square && !pic.borders && !pic.so && !pic.g4);
+    DbkH265Args h[3];
+    DbkSaoArgs sa[3];
+    DbkSaoNox nx[3], *nxp = pic.borders ? nx : nullptr; /* ONE operand for the picture: every plane's CTB grid is the luma grid sub-sampled */
+    DbkSlOffs sl[3];                                      /* likewise: every plane looks its CTBs up on the luma grid */
+    bool can[3] = {false, false, false}, rect = false, all_can = true;
+    unsigned log2_h[3] = {0, 0, 0};
+    bool one = n_planes >= 2 && pic.fused != HEVCDBK_FUSED_OFF && !planes[0].is_chroma;
+    for (unsigned i = 0; i < n_planes; i++) {
+        if (int rc = plane_operands(pic, &planes[i], (int)i, sao[i], h[i], sa[i], nx[i], sl[i])) return rc; /* c_idx = plane index: 0 Y, 1 Cb, 2 Cr */
+        if (planes[i].n_frames != planes[0].n_frames) return HEVCDBK_ERR_ARG;
+        /* chroma planes in the format's geometry of the luma plane: with a g4 plane always; else when planes[0] is the luma plane
+         * and the format is not 4:2:0 (as the _nox generation wrote it, 4:2:0 being the original entry's) */
+        if (i > 0 && (pic.g4 || (!planes[0].is_chroma && cf != HEVCDBK_CHROMA_420)) &&
+            (planes[i].plane_w * sub_w(cf) != planes[0].plane_w || planes[i].plane_h * sub_h(cf) != planes[0].plane_h))
+            return HEVCDBK_ERR_ARG;
+        log2_h[i] = sao[i].ctb_log2_h;
+        rect = rect || sao[i].ctb_log2_h != sao[i].ctb_log2_w;
+        can[i] = fused_can(h[i], sa[i], &planes[i], (int)i);
+        all_can = all_can && can[i];
+        /* one launch: one sample width and depth, one kind of QP, and one luma picture behind all planes (the kernel takes ONE
+         * per-slice operand; without it every n_bytes is 0) */
+        one = one && (i == 0 || planes[i].is_chroma) && planes[i].sample_bytes == planes[0].sample_bytes &&
+              planes[i].bit_depth == planes[0].bit_depth && (h[i].base.qp_map != nullptr) == (h[0].base.qp_map != nullptr) && can[i] &&
+              sl[i].n_bytes == sl[0].n_bytes;
+    }
+    if (int rc = bind_or_refuse(ctx, pic, !one && pic.fused == HEVCDBK_FUSED_ON && !all_can)) return rc;
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->compute;
+    if (int rc = sao_square_params(ctx, sa, log2_h, n_planes, s, nxp)) return rc;
+    int rc = HEVCDBK_OK;
+    if (one) {
+        const int n = (int)n_planes, sb = (int)planes[0].sample_bytes;
+        const hipError_t e = pic.first_gen ? dbk_launch_deblock_sao_multi_h265(h, sa, n, sb, s)
+                             : pic.g4     ? dbk_launch_deblock_sao_multi_h265_g4(h, sa, sl[0], n, sb, cf, s, nxp)
+                             : pic.so     ? dbk_launch_deblock_sao_multi_h265_sl(h, sa, sl[0], n, sb, cf, s, nxp)
+                                          : dbk_launch_deblock_sao_multi_h265_cf(h, sa, n, sb, cf, s, nxp);
+        if (!hip_ok(ctx, e, "fused deblocking + SAO launch")) rc = HEVCDBK_ERR_HIP;
+    }
+    for (unsigned i = 0; !one && i < n_planes && rc == HEVCDBK_OK; i++) /* each plane the kernels of its own generation */
+        rc = deblock_sao_plane_h265(ctx, pic, &planes[i], (int)i, h[i], sa[i], sl[i], nxp ? &nxp[i] : nullptr, s);
+    if (rect)
+        if (int rc2 = sao_done(ctx, s)) return rc ? rc : rc2; /* the parameter launch is fenced whatever followed it */
+    return rc;
+}
+
+} /* namespace */
+
+int hevc_sao_filter_device(hevcdbk_context *ctx, const hevcdbk_device_planes *p, const hevcdbk_sao_ctb *params,
+                           unsigned params_stride, size_t params_frame_stride, unsigned ctb_log2, const uint8_t *keep,
+                           unsigned keep_stride, size_t keep_frame_stride, void *hip_stream)
+{
+    return sao_pass(ctx, p, {params, params_stride, params_frame_stride, ctb_log2, ctb_log2, keep, keep_stride, keep_frame_stride}, nullptr, true,
+                    false, hip_stream);
 }
 
 int hevcdbk_sao_filter_device_cf(hevcdbk_context *ctx, const hevcdbk_device_planes *p, const hevcdbk_sao_ctb *params,
                               unsigned params_stride, size_t params_frame_stride, unsigned ctb_log2_w, unsigned ctb_log2_h,
                               const uint8_t *keep, unsigned keep_stride, size_t keep_frame_stride, void *hip_stream)
 {
-    return hevcdbk_sao_filter_device_nox(ctx, p, params, params_stride, params_frame_stride, ctb_log2_w, ctb_log2_h, keep, keep_stride,
-                                         keep_frame_stride, nullptr, hip_stream);
+    return sao_pass(ctx, p, {params, params_stride, params_frame_stride, ctb_log2_w, ctb_log2_h, keep, keep_stride, keep_frame_stride}, nullptr,
+                    false, false, hip_stream);
+}
+
+int hevcdbk_sao_filter_device_nox(hevcdbk_context *ctx, const hevcdbk_device_planes *p, const hevcdbk_sao_ctb *params,
+                                  unsigned params_stride, size_t params_frame_stride, unsigned ctb_log2_w, unsigned ctb_log2_h,
+                                  const uint8_t *keep, unsigned keep_stride, size_t keep_frame_stride,
+                                  const hevcdbk_sao_borders *borders, void *hip_stream)
+{
+    return sao_pass(ctx, p, {params, params_stride, params_frame_stride, ctb_log2_w, ctb_log2_h, keep, keep_stride, keep_frame_stride}, borders,
+                    false, false, hip_stream);
+}
+
+int hevcdbk_sao_filter_device_g4(hevcdbk_context *ctx, const hevcdbk_device_planes *p, const hevcdbk_sao_ctb *params,
+                                 unsigned params_stride, size_t params_frame_stride, unsigned ctb_log2_w, unsigned ctb_log2_h,
+                                 const uint8_t *keep, unsigned keep_stride, size_t keep_frame_stride,
+                                 const hevcdbk_sao_borders *borders, void *hip_stream)
+{
+    return sao_pass(ctx, p, {params, params_stride, params_frame_stride, ctb_log2_w, ctb_log2_h, keep, keep_stride, keep_frame_stride}, borders,
+                    false, true, hip_stream);
 }
 
 int hevcdbk_h265_sao_borders_device(hevcdbk_context *ctx, const uint16_t *slice_idx, const uint8_t *slice_across, const uint16_t *tile_idx,
@@ -545,18 +789,6 @@ int hevcdbk_h265_sao_borders_device(hevcdbk_context *ctx, const uint16_t *slice_
     const hipError_t e = dbk_launch_sao_borders(slice_idx, slice_across, tile_idx, loop_filter_across_tiles_enabled_flag != 0, (int)ctbs_x,
                                                 (int)ctbs_y, (int)in_stride, nox, (int)nox_stride, s);
     return hip_ok(ctx, e, "SAO border derivation launch") ? HEVCDBK_OK : HEVCDBK_ERR_HIP;
-}
-
-int hevc_sao_filter_device(hevcdbk_context *ctx, const hevcdbk_device_planes *p, const hevcdbk_sao_ctb *params,
-                           unsigned params_stride, size_t params_frame_stride, unsigned ctb_log2, const uint8_t *keep,
-                           unsigned keep_stride, size_t keep_frame_stride, void *hip_stream)
-{
-    if (!ctx) return HEVCDBK_ERR_ARG;
-    DbkSaoArgs a;
-    if (int rc = sao_args(p, params, params_stride, params_frame_stride, ctb_log2, keep, keep_stride, keep_frame_stride, a)) return rc;
-    if (int rc = bind(ctx)) return rc;
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->compute;
-    return hip_ok(ctx, dbk_launch_sao(a, (int)p->sample_bytes, s), "SAO launch") ? HEVCDBK_OK : HEVCDBK_ERR_HIP;
 }
 
 /* ---- deblocking followed by SAO in one call ---------------------------------------------- */
@@ -574,18 +806,55 @@ int hevc_deblock_sao_device(hevcdbk_context *ctx, const hevcdbk_device_planes *p
     return deblock_sao_plane(ctx, p, qp, tables, da, sa, fused, hip_stream ? (hipStream_t)hip_stream : ctx->compute);
 }
 
+/* ---- spec-exact deblocking + SAO of one plane: the original 4:2:0 entry, chroma formats (_cf), SAO borders (_nox), per-slice
+ * offsets (_sl), planes sized in multiples of 4 (_g4: the chroma planes of 1920x1080 are 960x540) -- one body, deblock_sao_one ---- */
+
 int hevc_deblock_sao_h265_device(hevcdbk_context *ctx, const hevcdbk_device_planes *p, int c_idx, unsigned qp,
                                  const hevcdbk_h265_params *prm, const hevcdbk_sao_ctb *params, unsigned params_stride,
                                  size_t params_frame_stride, unsigned ctb_log2, const uint8_t *keep, unsigned keep_stride,
                                  size_t keep_frame_stride, int fused, void *hip_stream)
 {
-    if (!ctx || (fused != HEVCDBK_FUSED_AUTO && fused != HEVCDBK_FUSED_OFF && fused != HEVCDBK_FUSED_ON)) return HEVCDBK_ERR_ARG;
-    DbkSaoArgs sa;
-    if (int rc = sao_args(p, params, params_stride, params_frame_stride, ctb_log2, keep, keep_stride, keep_frame_stride, sa)) return rc;
-    DbkH265Args h;
-    if (int rc = h265_args(p, c_idx, qp, prm, h)) return rc;
-    if (int rc = bind(ctx)) return rc;
-    return deblock_sao_plane_h265(ctx, p, c_idx, qp, prm, h, sa, fused, hip_stream ? (hipStream_t)hip_stream : ctx->compute);
+    return deblock_sao_one(ctx, {HEVCDBK_CHROMA_420, qp, prm, fused, nullptr, nullptr, true, false}, p, c_idx,
+                           {params, params_stride, params_frame_stride, ctb_log2, ctb_log2, keep, keep_stride, keep_frame_stride}, hip_stream);
+}
+
+int hevcdbk_h265_deblock_sao_device_cf(hevcdbk_context *ctx, const hevcdbk_device_planes *p, int c_idx, int chroma_format_idc, unsigned qp,
+                                    const hevcdbk_h265_params *prm, const hevcdbk_sao_ctb *params, unsigned params_stride,
+                                    size_t params_frame_stride, unsigned ctb_log2_w, unsigned ctb_log2_h, const uint8_t *keep,
+                                    unsigned keep_stride, size_t keep_frame_stride, int fused, void *hip_stream)
+{
+    return deblock_sao_one(ctx, {chroma_format_idc, qp, prm, fused, nullptr, nullptr, false, false}, p, c_idx,
+                           {params, params_stride, params_frame_stride, ctb_log2_w, ctb_log2_h, keep, keep_stride, keep_frame_stride}, hip_stream);
+}
+
+int hevcdbk_h265_deblock_sao_device_nox(hevcdbk_context *ctx, const hevcdbk_device_planes *p, int c_idx, int chroma_format_idc, unsigned qp,
+                                        const hevcdbk_h265_params *prm, const hevcdbk_sao_ctb *params, unsigned params_stride,
+                                        size_t params_frame_stride, unsigned ctb_log2_w, unsigned ctb_log2_h, const uint8_t *keep,
+                                        unsigned keep_stride, size_t keep_frame_stride, int fused, const hevcdbk_sao_borders *borders,
+                                        void *hip_stream)
+{
+    return deblock_sao_one(ctx, {chroma_format_idc, qp, prm, fused, borders, nullptr, false, false}, p, c_idx,
+                           {params, params_stride, params_frame_stride, ctb_log2_w, ctb_log2_h, keep, keep_stride, keep_frame_stride}, hip_stream);
+}
+
+int hevcdbk_h265_deblock_sao_device_sl(hevcdbk_context *ctx, const hevcdbk_device_planes *p, int c_idx, int chroma_format_idc, unsigned qp,
+                                       const hevcdbk_h265_params *prm, const hevcdbk_sao_ctb *params, unsigned params_stride,
+                                       size_t params_frame_stride, unsigned ctb_log2_w, unsigned ctb_log2_h, const uint8_t *keep,
+                                       unsigned keep_stride, size_t keep_frame_stride, int fused, const hevcdbk_sao_borders *borders,
+                                       const hevcdbk_h265_slice_offsets *slice_offsets, void *hip_stream)
+{
+    return deblock_sao_one(ctx, {chroma_format_idc, qp, prm, fused, borders, slice_offsets, false, false}, p, c_idx,
+                           {params, params_stride, params_frame_stride, ctb_log2_w, ctb_log2_h, keep, keep_stride, keep_frame_stride}, hip_stream);
+}
+
+int hevcdbk_h265_deblock_sao_device_g4(hevcdbk_context *ctx, const hevcdbk_device_planes *p, int c_idx, int chroma_format_idc, unsigned qp,
+                                       const hevcdbk_h265_params *prm, const hevcdbk_sao_ctb *params, unsigned params_stride,
+                                       size_t params_frame_stride, unsigned ctb_log2_w, unsigned ctb_log2_h, const uint8_t *keep,
+                                       unsigned keep_stride, size_t keep_frame_stride, int fused, const hevcdbk_sao_borders *borders,
+                                       const hevcdbk_h265_slice_offsets *slice_offsets, void *hip_stream)
+{
+    return deblock_sao_one(ctx, {chroma_format_idc, qp, prm, fused, borders, slice_offsets, false, true}, p, c_idx,
+                           {params, params_stride, params_frame_stride, ctb_log2_w, ctb_log2_h, keep, keep_stride, keep_frame_stride}, hip_stream);
 }
 
 /* ---- Y, U, V of a batch: deblocking + SAO of all planes in ONE launch where the fused kernel takes every plane ---- */
@@ -623,83 +892,22 @@ int hevc_deblock_sao_device_planes(hevcdbk_context *ctx, const hevcdbk_device_pl
     return HEVCDBK_OK;
 }
 
+/* the spec-exact generations of the same: one body, deblock_sao_planes */
 int hevc_deblock_sao_h265_device_planes(hevcdbk_context *ctx, const hevcdbk_device_planes *planes, unsigned n_planes, unsigned qp,
                                         const hevcdbk_h265_params *prm, const hevcdbk_sao_plane *sao, int fused, void *hip_stream)
 {
-    if (!ctx || !planes || !sao || n_planes == 0 || n_planes > 3 ||
-        (fused != HEVCDBK_FUSED_AUTO && fused != HEVCDBK_FUSED_OFF && fused != HEVCDBK_FUSED_ON))
-        return HEVCDBK_ERR_ARG;
-    DbkH265Args h[3];
-    DbkSaoArgs sa[3];
-    bool can[3] = {false, false, false};
-    bool one = n_planes >= 2 && fused != HEVCDBK_FUSED_OFF && !planes[0].is_chroma;
-    for (unsigned i = 0; i < n_planes; i++) {
-        if (int rc = sao_args(&planes[i], sao[i].params, sao[i].params_stride, sao[i].params_frame_stride, sao[i].ctb_log2, sao[i].keep,
-                              sao[i].keep_stride, sao[i].keep_frame_stride, sa[i]))
-            return rc;
-        if (int rc = h265_args(&planes[i], (int)i, qp, prm, h[i])) return rc; /* c_idx = plane index: 0 Y, 1 Cb, 2 Cr */
-        if (planes[i].n_frames != planes[0].n_frames) return HEVCDBK_ERR_ARG;
-        can[i] = dbk_packed_h265_supports(h[i], (int)planes[i].sample_bytes, i != 0) &&
-                 dbk_deblock_sao_supports(h[i].base, sa[i], (int)planes[i].sample_bytes, i != 0);
-        one = one && (i == 0 || planes[i].is_chroma) && planes[i].sample_bytes == planes[0].sample_bytes &&
-              planes[i].bit_depth == planes[0].bit_depth && (h[i].base.qp_map != nullptr) == (h[0].base.qp_map != nullptr) && can[i];
-    }
-    if (int rc = bind(ctx)) return rc;
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->compute;
-    if (one)
-        return hip_ok(ctx, dbk_launch_deblock_sao_multi_h265(h, sa, (int)n_planes, (int)planes[0].sample_bytes, s), "fused deblocking + SAO launch")
-                   ? HEVCDBK_OK : HEVCDBK_ERR_HIP;
-    if (fused == HEVCDBK_FUSED_ON)
-        for (unsigned i = 0; i < n_planes; i++)
-            if (!can[i]) return HEVCDBK_ERR_UNSUPPORTED;
-    for (unsigned i = 0; i < n_planes; i++)
-        if (int rc = deblock_sao_plane_h265(ctx, &planes[i], (int)i, qp, prm, h[i], sa[i], fused, s)) return rc;
-    return HEVCDBK_OK;
-}
-
-/* ---- chroma formats other than 4:2:0 (chroma_format_idc operand) ---------------------------------------------- */
-
-int hevcdbk_h265_deblock_sao_device_cf(hevcdbk_context *ctx, const hevcdbk_device_planes *p, int c_idx, int chroma_format_idc, unsigned qp,
-                                    const hevcdbk_h265_params *prm, const hevcdbk_sao_ctb *params, unsigned params_stride,
-                                    size_t params_frame_stride, unsigned ctb_log2_w, unsigned ctb_log2_h, const uint8_t *keep,
-                                    unsigned keep_stride, size_t keep_frame_stride, int fused, void *hip_stream)
-{
-    return hevcdbk_h265_deblock_sao_device_nox(ctx, p, c_idx, chroma_format_idc, qp, prm, params, params_stride, params_frame_stride,
-                                               ctb_log2_w, ctb_log2_h, keep, keep_stride, keep_frame_stride, fused, nullptr, hip_stream);
-}
-
-int hevcdbk_h265_deblock_sao_device_nox(hevcdbk_context *ctx, const hevcdbk_device_planes *p, int c_idx, int chroma_format_idc, unsigned qp,
-                                        const hevcdbk_h265_params *prm, const hevcdbk_sao_ctb *params, unsigned params_stride,
-                                        size_t params_frame_stride, unsigned ctb_log2_w, unsigned ctb_log2_h, const uint8_t *keep,
-                                        unsigned keep_stride, size_t keep_frame_stride, int fused, const hevcdbk_sao_borders *borders,
-                                        void *hip_stream)
-{
-    if (!ctx || (fused != HEVCDBK_FUSED_AUTO && fused != HEVCDBK_FUSED_OFF && fused != HEVCDBK_FUSED_ON)) return HEVCDBK_ERR_ARG;
-    DbkSaoArgs sa;
-    if (int rc = sao_args_cf(p, params, params_stride, params_frame_stride, ctb_log2_w, ctb_log2_h, keep, keep_stride, keep_frame_stride, sa))
-        return rc;
-    DbkH265Args h;
-    if (int rc = h265_args_cf(p, c_idx, chroma_format_idc, qp, prm, h)) return rc;
-    DbkSaoNox nx, *nxp = nullptr; /* no operand: the kernels without it */
-    if (borders) {
-        if (int rc = nox_args(borders, sa, nx)) return rc;
-        nxp = &nx;
-    }
-    if (fused == HEVCDBK_FUSED_ON && !fused_can(h, sa, p, c_idx)) return HEVCDBK_ERR_UNSUPPORTED; /* before any launch */
-    if (int rc = bind(ctx)) return rc;
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->compute;
-    if (int rc = sao_square_params(ctx, &sa, &ctb_log2_h, 1, s, nxp)) return rc;
-    const int rc = deblock_sao_plane_h265_cf(ctx, p, c_idx, c_idx != 0 ? chroma_format_idc : 1, qp, prm, h, sa, fused, s, nxp);
-    if (ctb_log2_h != ctb_log2_w)
-        if (int rc2 = sao_done(ctx, s)) return rc ? rc : rc2; /* the parameter launch is fenced whatever followed it */
-    return rc;
+    hevcdbk_sao_plane_cf cf[3];
+    for (unsigned i = 0; sao && i < n_planes && i < 3; i++)
+        cf[i] = {sao[i].params, sao[i].params_stride, sao[i].params_frame_stride, sao[i].ctb_log2, sao[i].ctb_log2, sao[i].keep, sao[i].keep_stride,
+                 sao[i].keep_frame_stride};
+    return deblock_sao_planes(ctx, {HEVCDBK_CHROMA_420, qp, prm, fused, nullptr, nullptr, true, false}, planes, n_planes, sao ? cf : nullptr, hip_stream);
 }
 
 int hevcdbk_h265_deblock_sao_device_planes_cf(hevcdbk_context *ctx, const hevcdbk_device_planes *planes, unsigned n_planes,
                                            int chroma_format_idc, unsigned qp, const hevcdbk_h265_params *prm,
                                            const hevcdbk_sao_plane_cf *sao, int fused, void *hip_stream)
 {
-    return hevcdbk_h265_deblock_sao_device_planes_nox(ctx, planes, n_planes, chroma_format_idc, qp, prm, sao, fused, nullptr, hip_stream);
+    return deblock_sao_planes(ctx, {chroma_format_idc, qp, prm, fused, nullptr, nullptr, false, false}, planes, n_planes, sao, hip_stream);
 }
 
 int hevcdbk_h265_deblock_sao_device_planes_nox(hevcdbk_context *ctx, const hevcdbk_device_planes *planes, unsigned n_planes,
@@ -707,136 +915,26 @@ int hevcdbk_h265_deblock_sao_device_planes_nox(hevcdbk_context *ctx, const hevcd
                                                const hevcdbk_sao_plane_cf *sao, int fused, const hevcdbk_sao_borders *borders,
                                                void *hip_stream)
 {
-    const int cf = chroma_format_idc;
-    if (!ctx || !planes || !sao || n_planes == 0 || n_planes > 3 || cf < HEVCDBK_CHROMA_400 || cf > HEVCDBK_CHROMA_444 ||
-        (fused != HEVCDBK_FUSED_AUTO && fused != HEVCDBK_FUSED_OFF && fused != HEVCDBK_FUSED_ON))
-        return HEVCDBK_ERR_ARG;
-    if (cf == HEVCDBK_CHROMA_400 && n_planes > 1) return HEVCDBK_ERR_ARG;
-    if (cf == HEVCDBK_CHROMA_420 && !borders) { /* square CTBs: exactly the 4:2:0 entry, checks included */
-        bool square = true;
-        hevcdbk_sao_plane sq[3];
-        for (unsigned i = 0; i < n_planes; i++) {
-            square = square && sao[i].ctb_log2_w == sao[i].ctb_log2_h;
-            sq[i] = {sao[i].params, sao[i].params_stride, sao[i].params_frame_stride, sao[i].ctb_log2_w, sao[i].keep, sao[i].keep_stride,
-                     sao[i].keep_frame_stride};
-        }
-        if (square) return hevc_deblock_sao_h265_device_planes(ctx, planes, n_planes, qp, prm, sq, fused, hip_stream);
-    }
-    DbkH265Args h[3];
-    DbkSaoArgs sa[3];
-    DbkSaoNox nx[3], *nxp = borders ? nx : nullptr; /* ONE operand for the picture: every plane's CTB grid is the luma grid sub-sampled */
-    bool can[3] = {false, false, false}, rect = false;
-    unsigned log2_h[3] = {0, 0, 0};
-    bool one = n_planes >= 2 && fused != HEVCDBK_FUSED_OFF && !planes[0].is_chroma;
-    for (unsigned i = 0; i < n_planes; i++) {
-        if (int rc = sao_args_cf(&planes[i], sao[i].params, sao[i].params_stride, sao[i].params_frame_stride, sao[i].ctb_log2_w,
-                                 sao[i].ctb_log2_h, sao[i].keep, sao[i].keep_stride, sao[i].keep_frame_stride, sa[i]))
-            return rc;
-        if (int rc = h265_args_cf(&planes[i], (int)i, cf, qp, prm, h[i])) return rc; /* c_idx = plane index: 0 Y, 1 Cb, 2 Cr */
-        if (borders)
-            if (int rc = nox_args(borders, sa[i], nx[i])) return rc;
-        if (planes[i].n_frames != planes[0].n_frames) return HEVCDBK_ERR_ARG;
-        /* chroma planes in the format's geometry of the luma plane (when planes[0] is the luma plane; 4:2:0 as its own entry) */
-        if (i > 0 && !planes[0].is_chroma && cf != HEVCDBK_CHROMA_420 &&
-            (planes[i].plane_w * sub_w(cf) != planes[0].plane_w || planes[i].plane_h * sub_h(cf) != planes[0].plane_h))
-            return HEVCDBK_ERR_ARG;
-        log2_h[i] = sao[i].ctb_log2_h;
-        rect = rect || sao[i].ctb_log2_h != sao[i].ctb_log2_w;
-        can[i] = fused_can(h[i], sa[i], &planes[i], (int)i);
-        one = one && (i == 0 || planes[i].is_chroma) && planes[i].sample_bytes == planes[0].sample_bytes &&
-              planes[i].bit_depth == planes[0].bit_depth && (h[i].base.qp_map != nullptr) == (h[0].base.qp_map != nullptr) && can[i];
-    }
-    if (!one && fused == HEVCDBK_FUSED_ON)
-        for (unsigned i = 0; i < n_planes; i++)
-            if (!can[i]) return HEVCDBK_ERR_UNSUPPORTED;
-    if (int rc = bind(ctx)) return rc;
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->compute;
-    if (int rc = sao_square_params(ctx, sa, log2_h, n_planes, s, nxp)) return rc;
-    int rc = HEVCDBK_OK;
-    if (one) {
-        if (!hip_ok(ctx, dbk_launch_deblock_sao_multi_h265_cf(h, sa, (int)n_planes, (int)planes[0].sample_bytes, cf, s, nxp),
-                    "fused deblocking + SAO launch"))
-            rc = HEVCDBK_ERR_HIP;
-    } else {
-        for (unsigned i = 0; i < n_planes && rc == HEVCDBK_OK; i++)
-            rc = deblock_sao_plane_h265_cf(ctx, &planes[i], (int)i, i != 0 ? cf : 1, qp, prm, h[i], sa[i], fused, s, nxp ? &nxp[i] : nullptr);
-    }
-    if (rect)
-        if (int rc2 = sao_done(ctx, s)) return rc ? rc : rc2; /* the parameter launch is fenced whatever followed it */
-    return rc;
+    return deblock_sao_planes(ctx, {chroma_format_idc, qp, prm, fused, borders, nullptr, false, false}, planes, n_planes, sao, hip_stream);
 }
 
-/* ---- per-slice deblocking offsets (H.265 8.7.2.5.3 / 8.7.2.5.5: the pair of the slice that holds q0,0) -------------------- */
-
-namespace {
-
-/* validates the operand against the LUMA picture of plane p (c_idx 0: the plane itself; else scaled by the format) and fills sl */
-int sl_args(const hevcdbk_h265_slice_offsets *so, const hevcdbk_device_planes *p, int c_idx, int cf, DbkSlOffs &sl)
+int hevcdbk_h265_deblock_sao_device_planes_sl(hevcdbk_context *ctx, const hevcdbk_device_planes *planes, unsigned n_planes,
+                                              int chroma_format_idc, unsigned qp, const hevcdbk_h265_params *prm,
+                                              const hevcdbk_sao_plane_cf *sao, int fused, const hevcdbk_sao_borders *borders,
+                                              const hevcdbk_h265_slice_offsets *slice_offsets, void *hip_stream)
 {
-    if (!so->offs || (uintptr_t)so->offs % 2 != 0 || so->frame_stride % 2 != 0 || so->ctb_log2 < 4 || so->ctb_log2 > 6) return HEVCDBK_ERR_ARG;
-    const unsigned long long lw = (unsigned long long)p->plane_w * (c_idx ? sub_w(cf) : 1u), lh = (unsigned long long)p->plane_h * (c_idx ? sub_h(cf) : 1u);
-    const unsigned long long cols = (lw + (1u << so->ctb_log2) - 1) >> so->ctb_log2, rows = (lh + (1u << so->ctb_log2) - 1) >> so->ctb_log2;
-    if (so->stride < cols || so->stride >= (1u << 23)) return HEVCDBK_ERR_ARG; /* 2 * stride is a 24-bit multiplicand of the kernels */
-    const unsigned long long bytes = 2ull * so->stride * rows;
-    if (bytes > 0x7fffffffull || rows >= (1u << 24)) return HEVCDBK_ERR_ARG;
-    sl.offs = so->offs;
-    sl.stride = (int)so->stride;
-    sl.frame_stride = (long long)so->frame_stride;
-    sl.ctb_log2 = (int)so->ctb_log2;
-    sl.n_bytes = (uint32_t)bytes;
-    return HEVCDBK_OK;
+    return deblock_sao_planes(ctx, {chroma_format_idc, qp, prm, fused, borders, slice_offsets, false, false}, planes, n_planes, sao, hip_stream);
 }
 
-/* the deblocking launch of a plane with the operand: the kernel families of launch_h265, each one's _sl twin */
-int launch_h265_sl(hevcdbk_context *ctx, const DbkH265Args &h0, const DbkSlOffs &sl, int sample_bytes, int c_idx, int cf, int variant,
-                   hipStream_t s)
+int hevcdbk_h265_deblock_sao_device_planes_g4(hevcdbk_context *ctx, const hevcdbk_device_planes *planes, unsigned n_planes,
+                                              int chroma_format_idc, unsigned qp, const hevcdbk_h265_params *prm,
+                                              const hevcdbk_sao_plane_cf *sao, int fused, const hevcdbk_sao_borders *borders,
+                                              const hevcdbk_h265_slice_offsets *slice_offsets, void *hip_stream)
 {
-    const int map = variant & HEVCDBK_MAP_MASK; /* as in launch_h265 */
-    variant &= ~HEVCDBK_MAP_MASK;
-    if (map != HEVCDBK_MAP_AUTO && map != HEVCDBK_MAP_ROWS && map != HEVCDBK_MAP_LINEAR) return HEVCDBK_ERR_ARG;
-    if (variant != HEVCDBK_KERNEL_PACKED && variant != HEVCDBK_KERNEL_GENERIC && variant != HEVCDBK_KERNEL_AUTO) return HEVCDBK_ERR_ARG;
-    DbkH265Args h = h0;
-    h.base.map_override = map == HEVCDBK_MAP_ROWS ? 1 : (map == HEVCDBK_MAP_LINEAR ? 2 : 0);
-    const bool pack = dbk_packed_h265_supports(h, sample_bytes, c_idx != 0);
-    if (variant == HEVCDBK_KERNEL_PACKED && !pack) return HEVCDBK_ERR_UNSUPPORTED;
-    hipError_t e;
-    if (variant != HEVCDBK_KERNEL_GENERIC && pack) e = dbk_launch_packed_h265_sl(h, sl, sample_bytes, c_idx != 0, c_idx ? cf : 1, s);
-    else e = dbk_launch_h265_sl(h, sl, sample_bytes, c_idx ? cf : 0, s);
-    return hip_ok(ctx, e, "kernel launch") ? HEVCDBK_OK : HEVCDBK_ERR_HIP;
+    return deblock_sao_planes(ctx, {chroma_format_idc, qp, prm, fused, borders, slice_offsets, false, true}, planes, n_planes, sao, hip_stream);
 }
 
-/* launch_h265_sl's argument errors, for the entries that check everything before they bind the device */
-int check_variant_sl(const DbkH265Args &h, int sample_bytes, int c_idx, int variant)
-{
-    const int map = variant & HEVCDBK_MAP_MASK;
-    variant &= ~HEVCDBK_MAP_MASK;
-    if (map != HEVCDBK_MAP_AUTO && map != HEVCDBK_MAP_ROWS && map != HEVCDBK_MAP_LINEAR) return HEVCDBK_ERR_ARG;
-    if (variant != HEVCDBK_KERNEL_PACKED && variant != HEVCDBK_KERNEL_GENERIC && variant != HEVCDBK_KERNEL_AUTO) return HEVCDBK_ERR_ARG;
-    if (variant == HEVCDBK_KERNEL_PACKED && !dbk_packed_h265_supports(h, sample_bytes, c_idx != 0)) return HEVCDBK_ERR_UNSUPPORTED;
-    return HEVCDBK_OK;
-}
-
-/* deblocking + SAO of one plane with the operand: the fused kernel where it applies (and is not switched off), else the two
- * launches through the context's scratch plane (square CTBs: after sao_square_params) */
-int deblock_sao_plane_h265_sl(hevcdbk_context *ctx, const hevcdbk_device_planes *p, int c_idx, int cf, unsigned qp,
-                              const hevcdbk_h265_params *prm, DbkH265Args &h, DbkSaoArgs &sa, const DbkSlOffs &sl, int fused, hipStream_t s,
-                              const DbkSaoNox *nx)
-{
-    const bool can = fused_can(h, sa, p, c_idx);
-    if (fused == HEVCDBK_FUSED_ON && !can) return HEVCDBK_ERR_UNSUPPORTED;
-    if (can && fused != HEVCDBK_FUSED_OFF)
-        return hip_ok(ctx, dbk_launch_deblock_sao_h265_sl(h, sa, sl, (int)p->sample_bytes, c_idx != 0, c_idx ? cf : 1, s, nx),
-                      "fused deblocking + SAO launch") ? HEVCDBK_OK : HEVCDBK_ERR_HIP;
-    hevcdbk_device_planes first, second;
-    if (int rc = tmp_planes(ctx, p, s, first, second)) return rc;
-    if (int rc = h265_args(&first, c_idx, qp, prm, h)) return rc;
-    if (int rc = launch_h265_sl(ctx, h, sl, (int)p->sample_bytes, c_idx, cf, HEVCDBK_KERNEL_AUTO, s)) return rc;
-    sa.src = (const uint8_t *)second.src;
-    if (!hip_ok(ctx, dbk_launch_sao(sa, (int)p->sample_bytes, s, nx), "SAO launch")) return HEVCDBK_ERR_HIP;
-    return tmp_done(ctx, s);
-}
-
-} /* namespace */
+/* ---- per-slice deblocking offsets (H.265 8.7.2.5.3 / 8.7.2.5.5: the pair of the slice that holds q0,0): the operand from the decoder's arrays ---- */
 
 int hevcdbk_h265_slice_offsets_device(hevcdbk_context *ctx, const uint16_t *slice_idx, unsigned in_stride, const int8_t *slice_table,
                                       unsigned n_slices, unsigned ctbs_x, unsigned ctbs_y, int8_t *offs, unsigned offs_stride,
@@ -851,339 +949,6 @@ int hevcdbk_h265_slice_offsets_device(hevcdbk_context *ctx, const uint16_t *slic
     const hipError_t e = dbk_launch_h265_slice_offsets(slice_idx, (int)in_stride, slice_table, n_slices, (int)ctbs_x, (int)ctbs_y, offs,
                                                        (int)offs_stride, s);
     return hip_ok(ctx, e, "slice offset derivation launch") ? HEVCDBK_OK : HEVCDBK_ERR_HIP;
-}
-
-int hevcdbk_h265_filter_device_sl(hevcdbk_context *ctx, const hevcdbk_device_planes *planes, int c_idx, int chroma_format_idc, unsigned qp,
-                                  const hevcdbk_h265_params *params, int kernel_variant, const hevcdbk_h265_slice_offsets *slice_offsets,
-                                  void *hip_stream)
-{
-    if (!slice_offsets) /* no operand: the kernels without it */
-        return hevcdbk_h265_filter_device_cf(ctx, planes, c_idx, chroma_format_idc, qp, params, kernel_variant, hip_stream);
-    if (!ctx) return HEVCDBK_ERR_ARG;
-    DbkH265Args h;
-    if (int rc = h265_args_cf(planes, c_idx, chroma_format_idc, qp, params, h)) return rc;
-    DbkSlOffs sl;
-    if (int rc = sl_args(slice_offsets, planes, c_idx, chroma_format_idc, sl)) return rc;
-    if (int rc = check_variant_sl(h, (int)planes->sample_bytes, c_idx, kernel_variant)) return rc;
-    if (int rc = bind(ctx)) return rc;
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->compute;
-    return launch_h265_sl(ctx, h, sl, (int)planes->sample_bytes, c_idx, chroma_format_idc, kernel_variant, s);
-}
-
-int hevcdbk_h265_deblock_sao_device_sl(hevcdbk_context *ctx, const hevcdbk_device_planes *p, int c_idx, int chroma_format_idc, unsigned qp,
-                                       const hevcdbk_h265_params *prm, const hevcdbk_sao_ctb *params, unsigned params_stride,
-                                       size_t params_frame_stride, unsigned ctb_log2_w, unsigned ctb_log2_h, const uint8_t *keep,
-                                       unsigned keep_stride, size_t keep_frame_stride, int fused, const hevcdbk_sao_borders *borders,
-                                       const hevcdbk_h265_slice_offsets *slice_offsets, void *hip_stream)
-{
-    if (!slice_offsets)
-        return hevcdbk_h265_deblock_sao_device_nox(ctx, p, c_idx, chroma_format_idc, qp, prm, params, params_stride, params_frame_stride,
-                                                   ctb_log2_w, ctb_log2_h, keep, keep_stride, keep_frame_stride, fused, borders, hip_stream);
-    if (!ctx || (fused != HEVCDBK_FUSED_AUTO && fused != HEVCDBK_FUSED_OFF && fused != HEVCDBK_FUSED_ON)) return HEVCDBK_ERR_ARG;
-    DbkSaoArgs sa;
-    if (int rc = sao_args_cf(p, params, params_stride, params_frame_stride, ctb_log2_w, ctb_log2_h, keep, keep_stride, keep_frame_stride, sa))
-        return rc;
-    DbkH265Args h;
-    if (int rc = h265_args_cf(p, c_idx, chroma_format_idc, qp, prm, h)) return rc;
-    DbkSaoNox nx, *nxp = nullptr;
-    if (borders) {
-        if (int rc = nox_args(borders, sa, nx)) return rc;
-        nxp = &nx;
-    }
-    DbkSlOffs sl;
-    if (int rc = sl_args(slice_offsets, p, c_idx, chroma_format_idc, sl)) return rc;
-    if (fused == HEVCDBK_FUSED_ON && !fused_can(h, sa, p, c_idx)) return HEVCDBK_ERR_UNSUPPORTED; /* before any launch */
-    if (int rc = bind(ctx)) return rc;
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->compute;
-    if (int rc = sao_square_params(ctx, &sa, &ctb_log2_h, 1, s, nxp)) return rc;
-    const int rc = deblock_sao_plane_h265_sl(ctx, p, c_idx, chroma_format_idc, qp, prm, h, sa, sl, fused, s, nxp);
-    if (ctb_log2_h != ctb_log2_w)
-        if (int rc2 = sao_done(ctx, s)) return rc ? rc : rc2; /* the parameter launch is fenced whatever followed it */
-    return rc;
-}
-
-int hevcdbk_h265_deblock_sao_device_planes_sl(hevcdbk_context *ctx, const hevcdbk_device_planes *planes, unsigned n_planes,
-                                              int chroma_format_idc, unsigned qp, const hevcdbk_h265_params *prm,
-                                              const hevcdbk_sao_plane_cf *sao, int fused, const hevcdbk_sao_borders *borders,
-                                              const hevcdbk_h265_slice_offsets *slice_offsets, void *hip_stream)
-{
-    if (!slice_offsets)
-        return hevcdbk_h265_deblock_sao_device_planes_nox(ctx, planes, n_planes, chroma_format_idc, qp, prm, sao, fused, borders, hip_stream);
-    const int cf = chroma_format_idc;
-    if (!ctx || !planes || !sao || n_planes == 0 || n_planes > 3 || cf < HEVCDBK_CHROMA_400 || cf > HEVCDBK_CHROMA_444 ||
-        (fused != HEVCDBK_FUSED_AUTO && fused != HEVCDBK_FUSED_OFF && fused != HEVCDBK_FUSED_ON))
-        return HEVCDBK_ERR_ARG;
-    if (cf == HEVCDBK_CHROMA_400 && n_planes > 1) return HEVCDBK_ERR_ARG;
-    DbkH265Args h[3];
-    DbkSaoArgs sa[3];
-    DbkSaoNox nx[3], *nxp = borders ? nx : nullptr;
-    DbkSlOffs sl[3]; /* ONE operand for the picture: every plane looks its CTBs up on the luma grid */
-    bool can[3] = {false, false, false}, rect = false;
-    unsigned log2_h[3] = {0, 0, 0};
-    bool one = n_planes >= 2 && fused != HEVCDBK_FUSED_OFF && !planes[0].is_chroma;
-    for (unsigned i = 0; i < n_planes; i++) {
-        if (int rc = sao_args_cf(&planes[i], sao[i].params, sao[i].params_stride, sao[i].params_frame_stride, sao[i].ctb_log2_w,
-                                 sao[i].ctb_log2_h, sao[i].keep, sao[i].keep_stride, sao[i].keep_frame_stride, sa[i]))
-            return rc;
-        if (int rc = h265_args_cf(&planes[i], (int)i, cf, qp, prm, h[i])) return rc; /* c_idx = plane index: 0 Y, 1 Cb, 2 Cr */
-        if (borders)
-            if (int rc = nox_args(borders, sa[i], nx[i])) return rc;
-        if (int rc = sl_args(slice_offsets, &planes[i], (int)i, cf, sl[i])) return rc;
-        if (planes[i].n_frames != planes[0].n_frames) return HEVCDBK_ERR_ARG;
-        if (i > 0 && !planes[0].is_chroma && cf != HEVCDBK_CHROMA_420 &&
-            (planes[i].plane_w * sub_w(cf) != planes[0].plane_w || planes[i].plane_h * sub_h(cf) != planes[0].plane_h))
-            return HEVCDBK_ERR_ARG;
-        log2_h[i] = sao[i].ctb_log2_h;
-        rect = rect || sao[i].ctb_log2_h != sao[i].ctb_log2_w;
-        can[i] = fused_can(h[i], sa[i], &planes[i], (int)i);
-        /* one launch: as in the _nox entry, and one luma picture behind all planes (the kernel takes ONE operand) */
-        one = one && (i == 0 || planes[i].is_chroma) && planes[i].sample_bytes == planes[0].sample_bytes &&
-              planes[i].bit_depth == planes[0].bit_depth && (h[i].base.qp_map != nullptr) == (h[0].base.qp_map != nullptr) && can[i] &&
-              sl[i].n_bytes == sl[0].n_bytes;
-    }
-    if (!one && fused == HEVCDBK_FUSED_ON)
-        for (unsigned i = 0; i < n_planes; i++)
-            if (!can[i]) return HEVCDBK_ERR_UNSUPPORTED;
-    if (int rc = bind(ctx)) return rc;
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->compute;
-    if (int rc = sao_square_params(ctx, sa, log2_h, n_planes, s, nxp)) return rc;
-    int rc = HEVCDBK_OK;
-    if (one) {
-        if (!hip_ok(ctx, dbk_launch_deblock_sao_multi_h265_sl(h, sa, sl[0], (int)n_planes, (int)planes[0].sample_bytes, cf, s, nxp),
-                    "fused deblocking + SAO launch"))
-            rc = HEVCDBK_ERR_HIP;
-    }
-    for (unsigned i = 0; !one && i < n_planes && rc == HEVCDBK_OK; i++)
-        rc = deblock_sao_plane_h265_sl(ctx, &planes[i], (int)i, cf, qp, prm, h[i], sa[i], sl[i], fused, s, nxp ? &nxp[i] : nullptr);
-    if (rect)
-        if (int rc2 = sao_done(ctx, s)) return rc ? rc : rc2;
-    return rc;
-}
-
-/* ---- planes whose sizes are multiples of 4, not 8: the chroma planes of 1920x1080 (960x540), 640x360, ... (the _g4 entries) ------- */
-
-namespace {
-
-/* "no per-slice offsets" for the _g4 kernels: an array of no bytes, every pair of which reads (0, 0) */
-const DbkSlOffs kNoSlOffs = {nullptr, 0, 0, 4, 0u};
-
-/* the operand of a _g4 launch: the caller's array -- then the call's own pair, which the kernels add, is zero (8.7.2.5.3: the pair is
- * the slice's) -- or none */
-int sl_args_g4(const hevcdbk_h265_slice_offsets *so, const hevcdbk_device_planes *p, int c_idx, int cf, DbkH265Args &h, DbkSlOffs &sl)
-{
-    if (!so) {
-        sl = kNoSlOffs;
-        return HEVCDBK_OK;
-    }
-    if (int rc = sl_args(so, p, c_idx, cf, sl)) return rc;
-    h.tc_off = h.beta_off = 0;
-    return HEVCDBK_OK;
-}
-
-/* the deblocking launch of a g4 chroma plane: the families of launch_h265_sl, each one's _g4 twin */
-int launch_h265_g4(hevcdbk_context *ctx, const DbkH265Args &h0, const DbkSlOffs &sl, int sample_bytes, int cf, int variant, hipStream_t s)
-{
-    const int map = variant & HEVCDBK_MAP_MASK;
-    variant &= ~HEVCDBK_MAP_MASK;
-    DbkH265Args h = h0;
-    h.base.map_override = map == HEVCDBK_MAP_ROWS ? 1 : (map == HEVCDBK_MAP_LINEAR ? 2 : 0);
-    const bool pack = dbk_packed_h265_supports(h, sample_bytes, true);
-    if (variant == HEVCDBK_KERNEL_PACKED && !pack) return HEVCDBK_ERR_UNSUPPORTED;
-    hipError_t e;
-    if (variant != HEVCDBK_KERNEL_GENERIC && pack) e = dbk_launch_packed_h265_g4(h, sl, sample_bytes, cf, s);
-    else e = dbk_launch_h265_g4(h, sl, sample_bytes, cf, s);
-    return hip_ok(ctx, e, "kernel launch") ? HEVCDBK_OK : HEVCDBK_ERR_HIP;
-}
-
-/* deblocking + SAO of one g4 chroma plane: deblock_sao_plane_h265_sl with the _g4 kernels (square CTBs: after sao_square_params) */
-int deblock_sao_plane_h265_g4(hevcdbk_context *ctx, const hevcdbk_device_planes *p, int c_idx, int cf, unsigned qp,
-                              const hevcdbk_h265_params *prm, DbkH265Args &h, DbkSaoArgs &sa, const DbkSlOffs &sl, int fused, hipStream_t s,
-                              const DbkSaoNox *nx)
-{
-    const bool can = fused_can(h, sa, p, c_idx);
-    if (fused == HEVCDBK_FUSED_ON && !can) return HEVCDBK_ERR_UNSUPPORTED;
-    if (can && fused != HEVCDBK_FUSED_OFF)
-        return hip_ok(ctx, dbk_launch_deblock_sao_h265_g4(h, sa, sl, (int)p->sample_bytes, cf, s, nx), "fused deblocking + SAO launch")
-                   ? HEVCDBK_OK : HEVCDBK_ERR_HIP;
-    hevcdbk_device_planes first, second;
-    if (int rc = tmp_planes(ctx, p, s, first, second)) return rc;
-    const int tc_off = h.tc_off, beta_off = h.beta_off; /* zero with per-slice offsets (sl_args_g4) */
-    if (int rc = h265_args(&first, c_idx, qp, prm, h, true)) return rc;
-    h.tc_off = tc_off;
-    h.beta_off = beta_off;
-    if (int rc = launch_h265_g4(ctx, h, sl, (int)p->sample_bytes, cf, HEVCDBK_KERNEL_AUTO, s)) return rc;
-    sa.src = (const uint8_t *)second.src;
-    if (!hip_ok(ctx, dbk_launch_sao_g4(sa, (int)p->sample_bytes, s, nx), "SAO launch")) return HEVCDBK_ERR_HIP;
-    return tmp_done(ctx, s);
-}
-
-} /* namespace */
-
-int hevcdbk_h265_derive_bs_device_g4(hevcdbk_context *ctx, const hevcdbk_h265_units *u, unsigned width, unsigned height,
-                                     int chroma_format_idc, uint8_t *vert_bs4, uint8_t *hor_bs4, uint8_t *chroma_vert_bs4,
-                                     uint8_t *chroma_hor_bs4, void *hip_stream)
-{
-    const int cf = chroma_format_idc;
-    if (!ctx || !u || !u->flags || !u->mv0 || !u->mv1 || !u->ref0 || !u->ref1 || !vert_bs4 || !hor_bs4) return HEVCDBK_ERR_ARG;
-    if (cf < HEVCDBK_CHROMA_400 || cf > HEVCDBK_CHROMA_444) return HEVCDBK_ERR_ARG;
-    if ((chroma_vert_bs4 != nullptr) != (chroma_hor_bs4 != nullptr)) return HEVCDBK_ERR_ARG;
-    if (cf == HEVCDBK_CHROMA_400 && chroma_vert_bs4) return HEVCDBK_ERR_ARG;
-    if (width == 0 || height == 0 || width % 8 != 0 || height % 8 != 0) return HEVCDBK_ERR_DIMENSIONS;
-    /* the chroma planes of a picture of multiples of 8 are multiples of 4 in every format: what is left to ask is "at least 8" */
-    if (chroma_vert_bs4 && g4_kind(width / sub_w(cf), height / sub_h(cf)) < 0) return HEVCDBK_ERR_DIMENSIONS;
-    if (int rc = bind(ctx)) return rc;
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->compute;
-    hipError_t e;
-    if (cf == HEVCDBK_CHROMA_420) { /* the launches of hevcdbk_h265_derive_bs_device: the gathers divide with floor */
-        e = dbk_launch_h265_bs(u->flags, u->mv0, u->mv1, u->ref0, u->ref1, (int)width, (int)height, vert_bs4, hor_bs4, chroma_vert_bs4,
-                               chroma_hor_bs4, s);
-    } else {
-        e = dbk_launch_h265_bs(u->flags, u->mv0, u->mv1, u->ref0, u->ref1, (int)width, (int)height, vert_bs4, hor_bs4, nullptr, nullptr, s);
-        if (e == hipSuccess && chroma_vert_bs4)
-            e = dbk_launch_h265_chroma_bs_cf(vert_bs4, hor_bs4, (int)width, (int)height, cf, chroma_vert_bs4, chroma_hor_bs4, s);
-    }
-    return hip_ok(ctx, e, "bS derivation launch") ? HEVCDBK_OK : HEVCDBK_ERR_HIP;
-}
-
-int hevcdbk_h265_filter_device_g4(hevcdbk_context *ctx, const hevcdbk_device_planes *planes, int c_idx, int chroma_format_idc, unsigned qp,
-                                  const hevcdbk_h265_params *params, int kernel_variant, const hevcdbk_h265_slice_offsets *slice_offsets,
-                                  void *hip_stream)
-{
-    if (!planes || g4_kind(planes->plane_w, planes->plane_h) != 1) /* multiples of 8, or no plane at all: the entry this one extends */
-        return hevcdbk_h265_filter_device_sl(ctx, planes, c_idx, chroma_format_idc, qp, params, kernel_variant, slice_offsets, hip_stream);
-    if (!ctx) return HEVCDBK_ERR_ARG;
-    DbkH265Args h;
-    if (int rc = h265_args_cf(planes, c_idx, chroma_format_idc, qp, params, h, true)) return rc;
-    DbkSlOffs sl;
-    if (int rc = sl_args_g4(slice_offsets, planes, c_idx, chroma_format_idc, h, sl)) return rc;
-    if (int rc = check_variant_sl(h, (int)planes->sample_bytes, c_idx, kernel_variant)) return rc;
-    if (int rc = bind(ctx)) return rc;
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->compute;
-    return launch_h265_g4(ctx, h, sl, (int)planes->sample_bytes, chroma_format_idc, kernel_variant, s);
-}
-
-int hevcdbk_sao_filter_device_g4(hevcdbk_context *ctx, const hevcdbk_device_planes *p, const hevcdbk_sao_ctb *params,
-                                 unsigned params_stride, size_t params_frame_stride, unsigned ctb_log2_w, unsigned ctb_log2_h,
-                                 const uint8_t *keep, unsigned keep_stride, size_t keep_frame_stride,
-                                 const hevcdbk_sao_borders *borders, void *hip_stream)
-{
-    if (!p || g4_kind(p->plane_w, p->plane_h) != 1)
-        return hevcdbk_sao_filter_device_nox(ctx, p, params, params_stride, params_frame_stride, ctb_log2_w, ctb_log2_h, keep, keep_stride,
-                                             keep_frame_stride, borders, hip_stream);
-    if (!ctx) return HEVCDBK_ERR_ARG;
-    DbkSaoArgs a;
-    if (int rc = sao_args_cf(p, params, params_stride, params_frame_stride, ctb_log2_w, ctb_log2_h, keep, keep_stride, keep_frame_stride, a, true))
-        return rc;
-    DbkSaoNox nx, *nxp = nullptr;
-    if (borders) {
-        if (int rc = nox_args(borders, a, nx)) return rc;
-        nxp = &nx;
-    }
-    if (int rc = bind(ctx)) return rc;
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->compute;
-    if (int rc = sao_square_params(ctx, &a, &ctb_log2_h, 1, s, nxp)) return rc;
-    if (!hip_ok(ctx, dbk_launch_sao_g4(a, (int)p->sample_bytes, s, nxp), "SAO launch")) return HEVCDBK_ERR_HIP;
-    return ctb_log2_h != ctb_log2_w ? sao_done(ctx, s) : HEVCDBK_OK;
-}
-
-int hevcdbk_h265_deblock_sao_device_g4(hevcdbk_context *ctx, const hevcdbk_device_planes *p, int c_idx, int chroma_format_idc, unsigned qp,
-                                       const hevcdbk_h265_params *prm, const hevcdbk_sao_ctb *params, unsigned params_stride,
-                                       size_t params_frame_stride, unsigned ctb_log2_w, unsigned ctb_log2_h, const uint8_t *keep,
-                                       unsigned keep_stride, size_t keep_frame_stride, int fused, const hevcdbk_sao_borders *borders,
-                                       const hevcdbk_h265_slice_offsets *slice_offsets, void *hip_stream)
-{
-    if (!p || g4_kind(p->plane_w, p->plane_h) != 1)
-        return hevcdbk_h265_deblock_sao_device_sl(ctx, p, c_idx, chroma_format_idc, qp, prm, params, params_stride, params_frame_stride,
-                                                  ctb_log2_w, ctb_log2_h, keep, keep_stride, keep_frame_stride, fused, borders, slice_offsets,
-                                                  hip_stream);
-    if (!ctx || (fused != HEVCDBK_FUSED_AUTO && fused != HEVCDBK_FUSED_OFF && fused != HEVCDBK_FUSED_ON)) return HEVCDBK_ERR_ARG;
-    DbkSaoArgs sa;
-    if (int rc = sao_args_cf(p, params, params_stride, params_frame_stride, ctb_log2_w, ctb_log2_h, keep, keep_stride, keep_frame_stride, sa, true))
-        return rc;
-    DbkH265Args h;
-    if (int rc = h265_args_cf(p, c_idx, chroma_format_idc, qp, prm, h, true)) return rc;
-    DbkSaoNox nx, *nxp = nullptr;
-    if (borders) {
-        if (int rc = nox_args(borders, sa, nx)) return rc;
-        nxp = &nx;
-    }
-    DbkSlOffs sl;
-    if (int rc = sl_args_g4(slice_offsets, p, c_idx, chroma_format_idc, h, sl)) return rc;
-    if (fused == HEVCDBK_FUSED_ON && !fused_can(h, sa, p, c_idx)) return HEVCDBK_ERR_UNSUPPORTED; /* before any launch */
-    if (int rc = bind(ctx)) return rc;
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->compute;
-    if (int rc = sao_square_params(ctx, &sa, &ctb_log2_h, 1, s, nxp)) return rc;
-    const int rc = deblock_sao_plane_h265_g4(ctx, p, c_idx, chroma_format_idc, qp, prm, h, sa, sl, fused, s, nxp);
-    if (ctb_log2_h != ctb_log2_w)
-        if (int rc2 = sao_done(ctx, s)) return rc ? rc : rc2; /* the parameter launch is fenced whatever followed it */
-    return rc;
-}
-
-int hevcdbk_h265_deblock_sao_device_planes_g4(hevcdbk_context *ctx, const hevcdbk_device_planes *planes, unsigned n_planes,
-                                              int chroma_format_idc, unsigned qp, const hevcdbk_h265_params *prm,
-                                              const hevcdbk_sao_plane_cf *sao, int fused, const hevcdbk_sao_borders *borders,
-                                              const hevcdbk_h265_slice_offsets *slice_offsets, void *hip_stream)
-{
-    const int cf = chroma_format_idc;
-    bool any_g4 = false;
-    if (planes && n_planes >= 1 && n_planes <= 3)
-        for (unsigned i = 0; i < n_planes; i++) any_g4 = any_g4 || g4_kind(planes[i].plane_w, planes[i].plane_h) == 1;
-    if (!any_g4) /* multiples of 8 (or operands no entry takes): the entry this one extends */
-        return hevcdbk_h265_deblock_sao_device_planes_sl(ctx, planes, n_planes, cf, qp, prm, sao, fused, borders, slice_offsets, hip_stream);
-    if (!ctx || !sao || cf < HEVCDBK_CHROMA_400 || cf > HEVCDBK_CHROMA_444 ||
-        (fused != HEVCDBK_FUSED_AUTO && fused != HEVCDBK_FUSED_OFF && fused != HEVCDBK_FUSED_ON))
-        return HEVCDBK_ERR_ARG;
-    if (cf == HEVCDBK_CHROMA_400 && n_planes > 1) return HEVCDBK_ERR_ARG;
-    DbkH265Args h[3];
-    DbkSaoArgs sa[3];
-    DbkSaoNox nx[3], *nxp = borders ? nx : nullptr;
-    DbkSlOffs sl[3];
-    bool can[3] = {false, false, false}, rect = false;
-    unsigned log2_h[3] = {0, 0, 0};
-    bool one = n_planes >= 2 && fused != HEVCDBK_FUSED_OFF && !planes[0].is_chroma;
-    for (unsigned i = 0; i < n_planes; i++) {
-        if (int rc = sao_args_cf(&planes[i], sao[i].params, sao[i].params_stride, sao[i].params_frame_stride, sao[i].ctb_log2_w,
-                                 sao[i].ctb_log2_h, sao[i].keep, sao[i].keep_stride, sao[i].keep_frame_stride, sa[i], true))
-            return rc;
-        if (int rc = h265_args_cf(&planes[i], (int)i, cf, qp, prm, h[i], true)) return rc; /* c_idx = plane index; a g4 luma plane is refused here */
-        if (borders)
-            if (int rc = nox_args(borders, sa[i], nx[i])) return rc;
-        if (int rc = sl_args_g4(slice_offsets, &planes[i], (int)i, cf, h[i], sl[i])) return rc;
-        if (planes[i].n_frames != planes[0].n_frames) return HEVCDBK_ERR_ARG;
-        /* the chroma planes in the format's geometry of the luma plane */
-        if (i > 0 && (planes[i].plane_w * sub_w(cf) != planes[0].plane_w || planes[i].plane_h * sub_h(cf) != planes[0].plane_h))
-            return HEVCDBK_ERR_ARG;
-        log2_h[i] = sao[i].ctb_log2_h;
-        rect = rect || sao[i].ctb_log2_h != sao[i].ctb_log2_w;
-        can[i] = fused_can(h[i], sa[i], &planes[i], (int)i);
-        one = one && (i == 0 || planes[i].is_chroma) && planes[i].sample_bytes == planes[0].sample_bytes &&
-              planes[i].bit_depth == planes[0].bit_depth && (h[i].base.qp_map != nullptr) == (h[0].base.qp_map != nullptr) && can[i] &&
-              sl[i].n_bytes == sl[0].n_bytes;
-    }
-    if (!one && fused == HEVCDBK_FUSED_ON)
-        for (unsigned i = 0; i < n_planes; i++)
-            if (!can[i]) return HEVCDBK_ERR_UNSUPPORTED;
-    if (int rc = bind(ctx)) return rc;
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->compute;
-    if (int rc = sao_square_params(ctx, sa, log2_h, n_planes, s, nxp)) return rc;
-    int rc = HEVCDBK_OK;
-    if (one) {
-        if (!hip_ok(ctx, dbk_launch_deblock_sao_multi_h265_g4(h, sa, sl[0], (int)n_planes, (int)planes[0].sample_bytes, cf, s, nxp),
-                    "fused deblocking + SAO launch"))
-            rc = HEVCDBK_ERR_HIP;
-    }
-    for (unsigned i = 0; !one && i < n_planes && rc == HEVCDBK_OK; i++) {
-        const DbkSaoNox *nxi = nxp ? &nxp[i] : nullptr;
-        if (g4_kind(planes[i].plane_w, planes[i].plane_h) == 1)
-            rc = deblock_sao_plane_h265_g4(ctx, &planes[i], (int)i, cf, qp, prm, h[i], sa[i], sl[i], fused, s, nxi);
-        else if (slice_offsets) /* the luma plane: what the entry this one extends runs for it */
-            rc = deblock_sao_plane_h265_sl(ctx, &planes[i], (int)i, cf, qp, prm, h[i], sa[i], sl[i], fused, s, nxi);
-        else
-            rc = deblock_sao_plane_h265_cf(ctx, &planes[i], (int)i, i != 0 ? cf : 1, qp, prm, h[i], sa[i], fused, s, nxi);
-    }
-    if (rect)
-        if (int rc2 = sao_done(ctx, s)) return rc ? rc : rc2;
-    return rc;
 }
 
 /* ---- semi-planar chroma: one plane of interleaved Cb / Cr pairs (the _sp entry) ---------------------------------------------- */
@@ -1212,10 +977,9 @@ int hevcdbk_h265_filter_device_sp(hevcdbk_context *ctx, const hevcdbk_device_pla
     const int cr_qp_offset = params ? params->cr_qp_offset : 0;
     DbkSlOffs sl;
     if (int rc = sl_args_g4(slice_offsets, planes, 1, HEVCDBK_CHROMA_420, h, sl)) return rc;
-    const int map = kernel_variant & HEVCDBK_MAP_MASK, variant = kernel_variant & ~HEVCDBK_MAP_MASK;
-    if (map != HEVCDBK_MAP_AUTO && map != HEVCDBK_MAP_ROWS && map != HEVCDBK_MAP_LINEAR) return HEVCDBK_ERR_ARG;
-    if (variant != HEVCDBK_KERNEL_PACKED && variant != HEVCDBK_KERNEL_GENERIC && variant != HEVCDBK_KERNEL_AUTO) return HEVCDBK_ERR_ARG;
-    if (map == HEVCDBK_MAP_LINEAR) return HEVCDBK_ERR_UNSUPPORTED; /* the packed kernels have the row map only */
+    int variant = kernel_variant, map_override;
+    if (int rc = check_variant(variant, map_override, false)) return rc;
+    if (map_override == 2) return HEVCDBK_ERR_UNSUPPORTED; /* HEVCDBK_MAP_LINEAR: the packed kernels have the row map only */
     const bool pack = dbk_packed_h265_sp_supports(h, (int)planes->sample_bytes);
     if (variant == HEVCDBK_KERNEL_PACKED && !pack) return HEVCDBK_ERR_UNSUPPORTED;
     if (int rc = bind(ctx)) return rc;
@@ -1265,7 +1029,7 @@ int hevcdbk_h265_deblock_sao_device_sp(hevcdbk_context *ctx, const hevcdbk_devic
                                        size_t keep_frame_stride, int fused, const hevcdbk_sao_borders *borders,
                                        const hevcdbk_h265_slice_offsets *slice_offsets, void *hip_stream)
 {
-    if (!ctx || !planes || (fused != HEVCDBK_FUSED_AUTO && fused != HEVCDBK_FUSED_OFF && fused != HEVCDBK_FUSED_ON)) return HEVCDBK_ERR_ARG;
+    if (!ctx || !planes || bad_fused(fused)) return HEVCDBK_ERR_ARG;
     DbkSaoArgs sa;
     DbkSaoNox nx;
     if (int rc = sp_sao_args(planes, params_cb, params_cr, params_stride, params_frame_stride, ctb_log2, keep, keep_stride, keep_frame_stride,
@@ -1278,23 +1042,23 @@ int hevcdbk_h265_deblock_sao_device_sp(hevcdbk_context *ctx, const hevcdbk_devic
     if (fused == HEVCDBK_FUSED_ON) return HEVCDBK_ERR_UNSUPPORTED; /* no fused kernel for this layout: before any launch */
     if (int rc = bind(ctx)) return rc;
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->compute;
-    /* the two launches through the context's scratch plane, as deblock_sao_plane_h265_g4 runs them */
-    hevcdbk_device_planes first, second;
-    if (int rc = tmp_planes(ctx, planes, s, first, second)) return rc;
+    const int sb = (int)planes->sample_bytes, cr_qp_offset = prm ? prm->cr_qp_offset : 0;
     const int tc_off = h.tc_off, beta_off = h.beta_off; /* zero with per-slice offsets (sl_args_g4) */
-    if (int rc = h265_args(&first, 1, qp, prm, h, true)) return rc;
-    h.tc_off = tc_off;
-    h.beta_off = beta_off;
-    const int cr_qp_offset = prm ? prm->cr_qp_offset : 0;
-    const hipError_t e = dbk_packed_h265_sp_supports(h, (int)planes->sample_bytes)
-                             ? dbk_launch_packed_h265_sp(h, sl, cr_qp_offset, (int)planes->sample_bytes, s)
-                             : dbk_launch_h265_sp(h, sl, cr_qp_offset, (int)planes->sample_bytes, s);
-    if (!hip_ok(ctx, e, "kernel launch")) return HEVCDBK_ERR_HIP;
-    sa.src = (const uint8_t *)second.src;
-    if (!hip_ok(ctx, dbk_launch_sao_sp(sa, reinterpret_cast<const DbkSaoCtb *>(params_cr), (int)planes->sample_bytes, s, borders ? &nx : nullptr),
-                "SAO launch"))
-        return HEVCDBK_ERR_HIP;
-    return tmp_done(ctx, s);
+    /* the two launches through the context's scratch plane, as deblock_sao_plane_h265 runs them for a g4 plane */
+    return through_scratch(
+        ctx, planes, s, sa,
+        [&](const hevcdbk_device_planes &first) {
+            if (int rc = h265_args(&first, 1, qp, prm, h, true)) return rc;
+            h.tc_off = tc_off;
+            h.beta_off = beta_off;
+            const hipError_t e = dbk_packed_h265_sp_supports(h, sb) ? dbk_launch_packed_h265_sp(h, sl, cr_qp_offset, sb, s)
+                                                                    : dbk_launch_h265_sp(h, sl, cr_qp_offset, sb, s);
+            return hip_ok(ctx, e, "kernel launch") ? HEVCDBK_OK : HEVCDBK_ERR_HIP;
+        },
+        [&] {
+            const hipError_t e = dbk_launch_sao_sp(sa, reinterpret_cast<const DbkSaoCtb *>(params_cr), sb, s, borders ? &nx : nullptr);
+            return hip_ok(ctx, e, "SAO launch") ? HEVCDBK_OK : HEVCDBK_ERR_HIP;
+        });
 }
 
 } /* extern "C" */

@@ -62,17 +62,33 @@ def _tables(tc, beta):
     return t, keep
 
 
+def _bs(keep, **arrays):
+    """an _lib.Bs of the given uint8 arrays (vert=, hor=, chroma_vert=, chroma_hor=); `keep` holds them alive for the call"""
+    bs = _lib.Bs()
+    for nm, arr in arrays.items():
+        a = np.ascontiguousarray(arr, np.uint8)
+        keep.append(a)
+        setattr(bs, nm, a.ctypes.data)
+        setattr(bs, "n_" + nm, a.size)
+    return bs
+
+
+def _frame(fr, planes, bit_depth):
+    """fills the _lib.Frame `fr` from writable 2-D numpy planes (y,) or (y, u, v) with contiguous rows"""
+    fr.height, fr.width = planes[0].shape
+    fr.bit_depth, fr.sample_bytes = bit_depth, planes[0].dtype.itemsize
+    for i, p in enumerate(planes):
+        assert p.flags.writeable and p.strides[1] == p.itemsize
+        fr.plane[i] = p.ctypes.data
+        fr.pitch[i] = p.strides[0]
+    return fr
+
+
 def filter_yuv_file_multi(devices, in_name, out_name, width, height, qp, *, vert_bs=None, hor_bs=None):
     """hevcdbk_filter_yuv_file_multi: the file operator sharded frame-parallel over `devices` (one worker thread and one
     context per entry; no collective).  Returns (n_frames, wall seconds)."""
-    bs, keep = None, []
-    if vert_bs is not None:
-        bs = _lib.Bs()
-        for nm, arr in (("vert", vert_bs), ("hor", hor_bs)):
-            a = np.ascontiguousarray(arr, np.uint8)
-            keep.append(a)
-            setattr(bs, nm, a.ctypes.data)
-            setattr(bs, "n_" + nm, a.size)
+    keep = []
+    bs = _bs(keep, vert=vert_bs, hor=hor_bs) if vert_bs is not None else None
     dev = (C.c_int * len(devices))(*devices)
     n, tm = C.c_uint(0), _lib.Timing()
     rc = _lib.lib().hevcdbk_filter_yuv_file_multi(dev, len(devices), os.fsencode(in_name), os.fsencode(out_name), width, height,
@@ -150,25 +166,12 @@ class Context:
                      tc_table=None, beta_table=None, check_sizes=True, want_timing=True):
         """Filters the given 2-D numpy planes IN PLACE (they must be writable, C-contiguous rows).
         Returns the reference's timing triple as a dict."""
-        sample_bytes = y.dtype.itemsize
-        fr = _lib.Frame()
-        fr.height, fr.width = y.shape
-        fr.bit_depth, fr.sample_bytes = bit_depth, sample_bytes
-        planes = [y] + ([u, v] if u is not None else [])
-        for i, p in enumerate(planes):
-            assert p.flags.writeable and p.strides[1] == p.itemsize
-            fr.plane[i] = p.ctypes.data
-            fr.pitch[i] = p.strides[0]
+        fr = _frame(_lib.Frame(), [y] + ([u, v] if u is not None else []), bit_depth)
         bs = None
         keep = []
         if vert_bs is not None or chroma_vert_bs is not None:
-            bs = _lib.Bs()
-            for nm, arr in (("vert", vert_bs), ("hor", hor_bs), ("chroma_vert", chroma_vert_bs), ("chroma_hor", chroma_hor_bs)):
-                if arr is not None:
-                    a = np.ascontiguousarray(arr, np.uint8)
-                    keep.append(a)
-                    setattr(bs, nm, a.ctypes.data)
-                    setattr(bs, "n_" + nm, a.size)
+            given = {"vert": vert_bs, "hor": hor_bs, "chroma_vert": chroma_vert_bs, "chroma_hor": chroma_hor_bs}
+            bs = _bs(keep, **{nm: arr for nm, arr in given.items() if arr is not None})
         q = _lib.Qp()
         q.qp, q.ctu_log2 = int(qp), ctu_log2
         if qp_map is not None:
@@ -243,22 +246,9 @@ class Context:
         place through the 3-deep H2D || kernel || D2H pipeline.  Returns the wall time of the sequence (s)."""
         arr = (_lib.Frame * len(frames))()
         for i, pl in enumerate(frames):
-            y = pl[0]
-            arr[i].height, arr[i].width = y.shape
-            arr[i].bit_depth, arr[i].sample_bytes = bit_depth, y.dtype.itemsize
-            for k, p in enumerate(pl):
-                assert p.flags.writeable and p.strides[1] == p.itemsize
-                arr[i].plane[k] = p.ctypes.data
-                arr[i].pitch[k] = p.strides[0]
-        bs = None
+            _frame(arr[i], pl, bit_depth)
         keep = []
-        if vert_bs is not None:
-            bs = _lib.Bs()
-            for nm, a in (("vert", vert_bs), ("hor", hor_bs)):
-                a = np.ascontiguousarray(a, np.uint8)
-                keep.append(a)
-                setattr(bs, nm, a.ctypes.data)
-                setattr(bs, "n_" + nm, a.size)
+        bs = _bs(keep, vert=vert_bs, hor=hor_bs) if vert_bs is not None else None
         q = _lib.Qp()
         q.qp, q.ctu_log2 = int(qp), 6
         tm = _lib.Timing()
@@ -272,15 +262,8 @@ class Context:
         """Multi-frame planar 8-bit 4:2:0 file -> file (hevcdbk_filter_yuv_file): every frame gets what the
         reference's ReadYuvFrame -> [SetBoundaryStrenght] -> DeblockingFilter -> Save gives a one-frame file
         (cpu.h:35-132, 995-1018).  Returns (n_frames, wall seconds including file I/O)."""
-        bs = None
         keep = []
-        if vert_bs is not None:
-            bs = _lib.Bs()
-            for nm, arr in (("vert", vert_bs), ("hor", hor_bs)):
-                a = np.ascontiguousarray(arr, np.uint8)
-                keep.append(a)
-                setattr(bs, nm, a.ctypes.data)
-                setattr(bs, "n_" + nm, a.size)
+        bs = _bs(keep, vert=vert_bs, hor=hor_bs) if vert_bs is not None else None
         t, k2 = _tables(tc_table, beta_table)
         tm = _lib.Timing()
         n = C.c_uint(0)
@@ -305,13 +288,7 @@ class Context:
         luma unit (bS derived on the GPU, 8.7.2.4) or the 4-sample-granular luma bS arrays.  chroma_format '400' / '420' /
         '422' / '444': u, v are (H / SubHeightC) x (W / SubWidthC) planes (none for '400'; '420' = the 4:2:0 entry)."""
         cf = _lib.chroma_format_idc(chroma_format)
-        fr = _lib.Frame()
-        fr.height, fr.width = y.shape
-        fr.bit_depth, fr.sample_bytes = bit_depth, y.dtype.itemsize
-        for i, p in enumerate([y] + ([u, v] if u is not None else [])):
-            assert p.flags.writeable and p.strides[1] == p.itemsize
-            fr.plane[i] = p.ctypes.data
-            fr.pitch[i] = p.strides[0]
+        fr = _frame(_lib.Frame(), [y] + ([u, v] if u is not None else []), bit_depth)
         keep, un, bs = [], None, None
         if units is not None:
             un = _lib.H265Units()
@@ -320,12 +297,7 @@ class Context:
                 keep.append(a)
                 setattr(un, nm, a.ctypes.data)
         if vert_bs4 is not None:
-            bs = _lib.Bs()
-            for nm, arr in (("vert", vert_bs4), ("hor", hor_bs4)):
-                a = np.ascontiguousarray(arr, np.uint8)
-                keep.append(a)
-                setattr(bs, nm, a.ctypes.data)
-                setattr(bs, "n_" + nm, a.size)
+            bs = _bs(keep, vert=vert_bs4, hor=hor_bs4)
         q = _lib.Qp()
         q.qp, q.ctu_log2 = int(qp), unit_log2
         if qp_map is not None:

@@ -1,0 +1,451 @@
+/*
+ * entry_sim.cpp -- the C-ABI entries of csrc/deblock_host_h265.cpp on the CPU: the two real host sources linked against stubs.cpp.
+ *
+ * A case is a set of operands (planes, SAO operands, borders, per-slice offsets, selectors, what the predicates answer, whether the
+ * device binds, which launch fails) made from a seed: a valid call with zero, one or two things wrong with it.  Every entry is
+ * called with every case on a context of its own; what an entry did is its return code, the context's error text and the trace
+ * the stubs wrote.
+ *
+ *   entry_sim dump SEED CASES    one line per call: for comparing two builds of the host source
+ *   entry_sim check SEED CASES   the identities include/hevc_deblock.h promises between the generations of an entry, and two
+ *                                properties of every call; prints what it compared and "N violations"
+ */
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <map>
+#include <string>
+
+#include "../../gpu_video_codec_amd/csrc/deblock_ctx.h"
+#include "entry_sim.h"
+
+namespace {
+
+struct Rng {
+    uint64_t s;
+    uint64_t next() { uint64_t z = (s += 0x9e3779b97f4a7c15ull); z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull; z = (z ^ (z >> 27)) * 0x94d049bb133111ebull; return z ^ (z >> 31); }
+    unsigned below(unsigned n) { return (unsigned)(next() % n); }
+    bool pct(unsigned p) { return below(100) < p; }
+    int range(int lo, int hi) { return lo + (int)below((unsigned)(hi - lo + 1)); }
+};
+
+struct Ops {
+    bool ctx_null, bind_fail, stream, planes_null, sao_null, prm_null, units_null, tables_bad;
+    int fail_at, repeat;
+    unsigned packed_mask, fused_mask, sp_mask;
+    unsigned n_planes, qp;
+    hevcdbk_device_planes pl[4];
+    hevcdbk_sao_plane_cf sao[4];
+    int cf, c_idx, variant, fused;
+    hevcdbk_h265_params prm;
+    bool has_borders, has_sl;
+    hevcdbk_sao_borders borders;
+    hevcdbk_h265_slice_offsets sl;
+    const hevcdbk_sao_ctb *params_cr;
+    /* bS derivation */
+    hevcdbk_h265_units units;
+    unsigned bs_w, bs_h;
+    uint8_t *bs_out[4];
+    /* the two derivations of per-CTB operands */
+    const uint16_t *slice_idx, *tile_idx;
+    const uint8_t *across;
+    const int8_t *table;
+    uint8_t *derived;
+    unsigned ctbs_x, ctbs_y, in_stride, out_stride, n_slices;
+    int tiles_flag;
+};
+
+template <class T> T *fake(unsigned long long a) { return reinterpret_cast<T *>((uintptr_t)a); }
+unsigned sub_w(int cf) { return cf == 3 ? 1u : 2u; }
+unsigned sub_h(int cf) { return cf == 1 ? 2u : 1u; }
+unsigned ceil_shift(unsigned v, unsigned s) { return (v + (1u << s) - 1) >> s; }
+
+const unsigned kSizes[][2] = {{0, 0}, {4, 8}, {6, 8}, {8, 8}, {12, 8}, {8, 12}, {16, 16}, {36, 20}, {64, 64}, {70000, 8}};
+const unsigned kLuma[][2] = {{16, 16}, {64, 64}, {32, 16}, {72, 40}, {24, 16}, {16, 24}, {128, 64}, {48, 48}};
+const unsigned kCtb[][2] = {{2, 2}, {3, 3}, {4, 5}, {5, 4}, {6, 6}, {6, 7}};
+
+void size_plane(Ops &o, int i, unsigned w, unsigned h, bool wide_rows)
+{
+    hevcdbk_device_planes &p = o.pl[i];
+    p.plane_w = w;
+    p.plane_h = h;
+    p.pitch = ((size_t)w * p.sample_bytes * (wide_rows ? 2 : 1) + 31) & ~(size_t)31;
+    p.frame_stride = p.pitch * h;
+}
+void sao_strides(Ops &o, int i)
+{
+    hevcdbk_sao_plane_cf &s = o.sao[i];
+    const unsigned lw = s.ctb_log2_w < 16 ? s.ctb_log2_w : 16, lh = s.ctb_log2_h < 16 ? s.ctb_log2_h : 16;
+    s.params_stride = ceil_shift(o.pl[i].plane_w, lw);
+    if (s.params_frame_stride) s.params_frame_stride = (size_t)s.params_stride * ceil_shift(o.pl[i].plane_h, lh);
+    s.keep_stride = (o.pl[i].plane_w + 7) / 8;
+    if (s.keep_frame_stride) s.keep_frame_stride = (size_t)s.keep_stride * ((o.pl[i].plane_h + 7) / 8);
+}
+
+void mutate(Ops &o, Rng &r)
+{
+    const int i = (int)r.below(3);
+    hevcdbk_device_planes &p = o.pl[i];
+    switch (r.below(40)) {
+    case 0: case 1: case 2: { const unsigned k = r.below(10); size_plane(o, i, kSizes[k][0], kSizes[k][1], i != 0); sao_strides(o, i); break; }
+    case 3: for (int k = 0; k < 3; k++) { const unsigned q = r.below(10); size_plane(o, k, kSizes[q][0], kSizes[q][1], k != 0); sao_strides(o, k); } break;
+    case 4: p.is_chroma = !p.is_chroma; break;
+    case 5: o.c_idx = r.pct(50) ? -1 : 3; break;
+    case 6: o.cf = r.pct(50) ? -1 : 4; break;
+    case 7: o.n_planes = r.pct(50) ? 0 : 4; break;
+    case 8: p.n_frames += 1; break;
+    case 9: p.n_frames = 65536; break;
+    case 10: o.has_borders = true; o.borders.nox = nullptr; break;
+    case 11: o.has_borders = true; o.borders.stride = r.pct(50) ? 0 : o.borders.stride - 1; break;
+    case 12: o.has_sl = true; o.sl.offs = fake<int8_t>(0xa0000001ull); break;
+    case 13: o.has_sl = true; o.sl.frame_stride = 4097; break;
+    case 14: o.has_sl = true; o.sl.ctb_log2 = r.pct(50) ? 3 : 7; break;
+    case 15: o.has_sl = true; o.sl.stride = r.pct(50) ? 0 : o.sl.stride - 1; break;
+    case 16: o.has_sl = true; o.sl.stride = 1u << 23; break;
+    case 17: o.fused = 9; break;
+    case 18: o.variant = (o.variant & 0x700) | 77; break;
+    case 19: o.variant = (o.variant & 0xff) | (r.pct(50) ? 0x300 : 0x700); break;
+    case 20: case 21: { const unsigned k = r.below(6); o.sao[i].ctb_log2_w = kCtb[k][0]; o.sao[i].ctb_log2_h = kCtb[k][1]; if (r.pct(70)) sao_strides(o, i); break; }
+    case 22: o.sao[i].params = nullptr; break;
+    case 23: o.sao[i].params_stride = o.sao[i].params_stride ? o.sao[i].params_stride - 1 : 0; break;
+    case 24: o.sao[i].keep = fake<uint8_t>(0x90000000ull); o.sao[i].keep_stride = 0; break;
+    case 25: for (int k = 0; k < 3; k++) { o.pl[k].qp_map = fake<uint8_t>(0xb0000000ull); o.pl[k].qp_map_stride = 4096; o.pl[k].ctu_log2 = (unsigned[]){2, 3, 8, 9}[r.below(4)]; } break;
+    case 26: o.prm_null = false; (r.pct(50) ? o.prm.tc_offset_div2 : o.prm.beta_offset_div2) = (int[]){-7, -6, 6, 7}[r.below(4)]; break;
+    case 27: o.prm_null = false; (r.pct(50) ? o.prm.cb_qp_offset : o.prm.cr_qp_offset) = (int[]){-13, -12, 12, 13}[r.below(4)]; break;
+    case 28: p.src = (const char *)p.src + 1; break;
+    case 29: p.dst = const_cast<void *>(p.src); break;
+    case 30: (r.pct(50) ? o.planes_null : o.sao_null) = true; break;
+    case 31: p.bit_depth = 9; p.sample_bytes = 1; break;
+    case 32: p.pitch = p.pitch >= 64 ? p.pitch / 2 : 0; break;
+    case 33: p.pitch += 2; break;
+    case 34: for (int k = 0; k < 3; k++) { o.pl[k].qp_map = fake<uint8_t>(0xb0000000ull); o.pl[k].qp_map_stride = 1u << 24; o.pl[k].ctu_log2 = 4; } break;
+    case 35: if (r.pct(50)) p.src = nullptr; else p.vert_bs = nullptr; break;
+    case 36: o.params_cr = nullptr; break;
+    case 37: o.tables_bad = true; break;
+    case 38: p.frame_stride += 2; break;
+    case 39: p.plane_h = 65536 + 8; p.frame_stride = p.pitch * p.plane_h; sao_strides(o, i); break;
+    }
+}
+
+Ops make_case(Rng &r)
+{
+    Ops o;
+    std::memset(&o, 0, sizeof(o));
+    o.ctx_null = r.pct(2);
+    o.bind_fail = r.pct(5);
+    o.stream = r.pct(50);
+    o.fail_at = r.pct(70) ? 0 : r.range(1, 4);
+    o.repeat = r.pct(70) ? 0 : (r.pct(66) ? 1 : 2);
+    unsigned *masks[3] = {&o.packed_mask, &o.fused_mask, &o.sp_mask};
+    for (unsigned *m : masks) *m = r.pct(40) ? 0xffu : (r.pct(33) ? 0u : r.below(256));
+    const unsigned cfw = r.below(100);
+    o.cf = cfw < 40 ? 1 : (cfw < 62 ? 2 : (cfw < 84 ? 3 : 0));
+    const int cfe = o.cf ? o.cf : 1;
+    const unsigned li = r.below(8), lw = kLuma[li][0], lh = kLuma[li][1];
+    const unsigned depth = r.pct(50) ? 8 : (r.pct(60) ? 10 : (r.pct(50) ? 12 : 16));
+    const unsigned n_frames = (unsigned)r.range(1, 3);
+    const bool map = r.pct(20), bs_strided = r.pct(50);
+    const unsigned L = (unsigned)r.range(4, 6);
+    for (int i = 0; i < 4; i++) {
+        hevcdbk_device_planes &p = o.pl[i];
+        p.src = fake<void>(sim_plane_base(i));
+        p.dst = fake<void>(sim_plane_base(i) + 0x8000000ull);
+        p.n_frames = n_frames;
+        p.bit_depth = depth;
+        p.sample_bytes = depth == 8 ? 1 : 2;
+        p.is_chroma = i != 0;
+        size_plane(o, i, i ? lw / sub_w(cfe) : lw, i ? lh / sub_h(cfe) : lh, i != 0);
+        p.vert_bs = fake<uint8_t>(0x70000000ull + 0x100000ull * i);
+        p.hor_bs = fake<uint8_t>(0x78000000ull + 0x100000ull * i);
+        p.vert_bs_stride = bs_strided ? 4096 : 0;
+        p.hor_bs_stride = bs_strided ? 8192 : 0;
+        if (map) {
+            p.qp_map = fake<uint8_t>(0xb0000000ull);
+            p.ctu_log2 = L;
+            p.qp_map_stride = ceil_shift(lw, L);
+            p.qp_map_frame_stride = r.pct(50) ? 0 : 512;
+        }
+        hevcdbk_sao_plane_cf &s = o.sao[i];
+        s.params = fake<hevcdbk_sao_ctb>(0x80000000ull + 0x1000000ull * i);
+        s.ctb_log2_w = i ? L - (sub_w(cfe) == 2) : L;
+        s.ctb_log2_h = i ? L - (sub_h(cfe) == 2) : L;
+        s.params_frame_stride = r.pct(50);
+        if (r.pct(50)) s.keep = fake<uint8_t>(0x90000000ull + 0x1000000ull * i);
+        s.keep_frame_stride = r.pct(50);
+        sao_strides(o, i);
+    }
+    o.params_cr = fake<hevcdbk_sao_ctb>(0x88000000ull);
+    const unsigned nw = r.below(100);
+    o.n_planes = o.cf == 0 ? 1 : (nw < 60 ? 3 : (nw < 80 ? 2 : 1));
+    o.c_idx = o.cf == 0 && r.pct(80) ? 0 : (int)r.below(3);
+    o.qp = r.below(61);
+    o.prm_null = r.pct(30);
+    o.prm = {r.range(-6, 6), r.range(-6, 6), r.range(-12, 12), r.range(-12, 12)};
+    o.variant = (int)r.below(3) | (int)(r.below(3) << 8);
+    o.fused = (int)r.below(3);
+    o.has_borders = r.pct(50);
+    o.borders = {fake<uint8_t>(0xc0000000ull), ceil_shift(lw, 3), r.pct(50) ? (size_t)0 : (size_t)4096};
+    o.has_sl = r.pct(50);
+    const unsigned slog = (unsigned)r.range(4, 6);
+    o.sl = {fake<int8_t>(0xa0000000ull), ceil_shift(lw, slog), r.pct(50) ? (size_t)0 : (size_t)4096, slog};
+    /* bS derivation */
+    o.units = {fake<uint16_t>(0xd0000000ull), fake<int16_t>(0xd1000000ull), fake<int16_t>(0xd2000000ull), fake<int32_t>(0xd3000000ull), fake<int32_t>(0xd4000000ull)};
+    const unsigned bi = r.below(100);
+    if (bi < 60) { o.bs_w = lw; o.bs_h = lh; }
+    else { const unsigned k = r.below(10), q = r.below(10); o.bs_w = kSizes[k][0] * (bi < 80 ? 2 : 1); o.bs_h = kSizes[q][1] * (bi < 80 ? 2 : 1); }
+    for (int k = 0; k < 4; k++) o.bs_out[k] = fake<uint8_t>(0xe0000000ull + 0x1000000ull * k);
+    if (r.pct(25)) o.bs_out[2] = o.bs_out[3] = nullptr;
+    if (r.pct(6)) o.bs_out[r.below(4)] = nullptr;
+    if (r.pct(4)) o.units_null = true;
+    if (r.pct(6)) { const void **f[5] = {(const void **)&o.units.flags, (const void **)&o.units.mv0, (const void **)&o.units.mv1, (const void **)&o.units.ref0, (const void **)&o.units.ref1}; *f[r.below(5)] = nullptr; }
+    /* per-CTB derivations */
+    o.slice_idx = fake<uint16_t>(0xf0000000ull);
+    o.tile_idx = r.pct(50) ? fake<uint16_t>(0xf1000000ull) : nullptr;
+    o.across = fake<uint8_t>(0xf2000000ull);
+    o.table = fake<int8_t>(0xf3000000ull);
+    o.derived = fake<uint8_t>(0xf4000000ull);
+    const unsigned kCtbs[] = {1, 5, 30, 65535, 0, 65536, 40000};
+    o.ctbs_x = kCtbs[r.below(r.pct(70) ? 3 : 7)];
+    o.ctbs_y = kCtbs[r.below(r.pct(70) ? 3 : 7)];
+    o.in_stride = o.ctbs_x + r.below(3);
+    o.out_stride = o.ctbs_x + r.below(3);
+    o.n_slices = r.below(4);
+    o.tiles_flag = (int)r.below(2);
+    if (r.pct(30)) switch (r.below(8)) {
+        case 0: o.slice_idx = nullptr; break;
+        case 1: o.across = nullptr; break;
+        case 2: o.table = nullptr; break;
+        case 3: o.derived = nullptr; break;
+        case 4: o.derived += 1; break;
+        case 5: o.in_stride = o.ctbs_x ? o.ctbs_x - 1 : 0; break;
+        case 6: o.out_stride = o.ctbs_x ? o.ctbs_x - 1 : 0; break;
+        case 7: o.n_slices = 0; o.table = nullptr; break;
+    }
+    const unsigned m = r.below(100);
+    for (unsigned k = 0; k < (m < 45 ? 1u : (m < 60 ? 2u : 0u)); k++) mutate(o, r);
+    return o;
+}
+
+/* ---- the entries ---------------------------------------------------------------------------------------------------------------- */
+
+struct Call {
+    const Ops &o;
+    hevcdbk_context *ctx;
+    unsigned frames; /* 0: the case's own n_frames; else every plane's */
+    hevcdbk_device_planes pl[4];
+    hevcdbk_sao_plane sq[4];
+    unsigned tab[52];
+    hevcdbk_tables tables;
+    Call(const Ops &ops, hevcdbk_context *c, unsigned f) : o(ops), ctx(c), frames(f)
+    {
+        for (int i = 0; i < 4; i++) {
+            pl[i] = o.pl[i];
+            if (frames) pl[i].n_frames = frames;
+            sq[i] = {o.sao[i].params, o.sao[i].params_stride, o.sao[i].params_frame_stride, o.sao[i].ctb_log2_w, o.sao[i].keep, o.sao[i].keep_stride,
+                     o.sao[i].keep_frame_stride};
+        }
+        for (int i = 0; i < 52; i++) tab[i] = (unsigned)i;
+        if (o.tables_bad) tab[17] = 256;
+        tables = {tab, nullptr};
+    }
+    int k() const { return o.c_idx < 0 ? 0 : (o.c_idx > 2 ? 2 : o.c_idx); }      /* the plane of a one-plane entry */
+    const hevcdbk_device_planes *one() const { return o.planes_null ? nullptr : &pl[k()]; }
+    const hevcdbk_device_planes *pair() const { return o.planes_null ? nullptr : &pl[k() ? k() : 1]; } /* the _sp entries' */
+    const hevcdbk_device_planes *all() const { return o.planes_null ? nullptr : pl; }
+    const hevcdbk_sao_plane_cf &s1() const { return o.sao[k()]; }
+    const hevcdbk_sao_plane_cf &sp() const { return o.sao[k() ? k() : 1]; }
+    const hevcdbk_h265_params *prm() const { return o.prm_null ? nullptr : &o.prm; }
+    const hevcdbk_sao_borders *nox() const { return o.has_borders ? &o.borders : nullptr; }
+    const hevcdbk_h265_slice_offsets *sl() const { return o.has_sl ? &o.sl : nullptr; }
+    const hevcdbk_h265_units *units() const { return o.units_null ? nullptr : &o.units; }
+    void *stream() const { return o.stream ? fake<void>(0x7770) : nullptr; }
+};
+
+/* how an entry is called: the operands it has no parameter for are left out, `b` / `sl` are the borders / offsets it is given */
+typedef int (*EntryFn)(const Call &c, const hevcdbk_sao_borders *b, const hevcdbk_h265_slice_offsets *sl);
+struct Entry { const char *name; EntryFn fn; };
+
+#define SAO1(s) (s).params, (s).params_stride, (s).params_frame_stride
+#define KEEP1(s) (s).keep, (s).keep_stride, (s).keep_frame_stride
+#define E(name, expr) {#name, [](const Call &c, const hevcdbk_sao_borders *b, const hevcdbk_h265_slice_offsets *sl) -> int { (void)b; (void)sl; return expr; }}
+
+const Entry kEntries[] = {
+    E(hevcdbk_h265_num_bs, (int)(hevcdbk_h265_num_vert_bs(c.o.bs_w, c.o.bs_h) * 31 + hevcdbk_h265_num_hor_bs(c.o.bs_w, c.o.bs_h)) & 0x7fffffff),
+    E(hevcdbk_h265_derive_bs_device, hevcdbk_h265_derive_bs_device(c.ctx, c.units(), c.o.bs_w, c.o.bs_h, c.o.bs_out[0], c.o.bs_out[1], c.o.bs_out[2], c.o.bs_out[3], c.stream())),
+    E(hevcdbk_h265_derive_bs_device_cf, hevcdbk_h265_derive_bs_device_cf(c.ctx, c.units(), c.o.bs_w, c.o.bs_h, c.o.cf, c.o.bs_out[0], c.o.bs_out[1], c.o.bs_out[2], c.o.bs_out[3], c.stream())),
+    E(hevcdbk_h265_derive_bs_device_g4, hevcdbk_h265_derive_bs_device_g4(c.ctx, c.units(), c.o.bs_w, c.o.bs_h, c.o.cf, c.o.bs_out[0], c.o.bs_out[1], c.o.bs_out[2], c.o.bs_out[3], c.stream())),
+    E(hevc_deblocking_filter_h265_device, hevc_deblocking_filter_h265_device(c.ctx, c.one(), c.o.c_idx, c.o.qp, c.prm(), c.o.variant, c.stream())),
+    E(hevcdbk_h265_filter_device_cf, hevcdbk_h265_filter_device_cf(c.ctx, c.one(), c.o.c_idx, c.o.cf, c.o.qp, c.prm(), c.o.variant, c.stream())),
+    E(hevcdbk_h265_filter_device_sl, hevcdbk_h265_filter_device_sl(c.ctx, c.one(), c.o.c_idx, c.o.cf, c.o.qp, c.prm(), c.o.variant, sl, c.stream())),
+    E(hevcdbk_h265_filter_device_g4, hevcdbk_h265_filter_device_g4(c.ctx, c.one(), c.o.c_idx, c.o.cf, c.o.qp, c.prm(), c.o.variant, sl, c.stream())),
+    E(hevcdbk_h265_filter_device_sp, hevcdbk_h265_filter_device_sp(c.ctx, c.pair(), c.o.qp, c.prm(), c.o.variant, sl, c.stream())),
+    E(hevc_sao_filter_device, hevc_sao_filter_device(c.ctx, c.one(), SAO1(c.s1()), c.s1().ctb_log2_w, KEEP1(c.s1()), c.stream())),
+    E(hevcdbk_sao_filter_device_cf, hevcdbk_sao_filter_device_cf(c.ctx, c.one(), SAO1(c.s1()), c.s1().ctb_log2_w, c.s1().ctb_log2_h, KEEP1(c.s1()), c.stream())),
+    E(hevcdbk_sao_filter_device_nox, hevcdbk_sao_filter_device_nox(c.ctx, c.one(), SAO1(c.s1()), c.s1().ctb_log2_w, c.s1().ctb_log2_h, KEEP1(c.s1()), b, c.stream())),
+    E(hevcdbk_sao_filter_device_g4, hevcdbk_sao_filter_device_g4(c.ctx, c.one(), SAO1(c.s1()), c.s1().ctb_log2_w, c.s1().ctb_log2_h, KEEP1(c.s1()), b, c.stream())),
+    E(hevcdbk_sao_filter_device_sp, hevcdbk_sao_filter_device_sp(c.ctx, c.pair(), c.sp().params, c.o.params_cr, c.sp().params_stride, c.sp().params_frame_stride, c.sp().ctb_log2_w, KEEP1(c.sp()), b, c.stream())),
+    E(hevcdbk_h265_sao_borders_device, hevcdbk_h265_sao_borders_device(c.ctx, c.o.slice_idx, c.o.across, c.o.tile_idx, c.o.tiles_flag, c.o.ctbs_x, c.o.ctbs_y, c.o.in_stride, c.o.derived, c.o.out_stride, c.stream())),
+    E(hevcdbk_h265_slice_offsets_device, hevcdbk_h265_slice_offsets_device(c.ctx, c.o.slice_idx, c.o.in_stride, c.o.table, c.o.n_slices, c.o.ctbs_x, c.o.ctbs_y, (int8_t *)c.o.derived, c.o.out_stride, c.stream())),
+    E(hevc_deblock_sao_device, hevc_deblock_sao_device(c.ctx, c.one(), c.o.qp, &c.tables, SAO1(c.s1()), c.s1().ctb_log2_w, KEEP1(c.s1()), c.o.fused, c.stream())),
+    E(hevc_deblock_sao_device_planes, hevc_deblock_sao_device_planes(c.ctx, c.all(), c.o.n_planes, c.o.qp, &c.tables, c.o.sao_null ? nullptr : c.sq, c.o.fused, c.stream())),
+    E(hevc_deblock_sao_h265_device, hevc_deblock_sao_h265_device(c.ctx, c.one(), c.o.c_idx, c.o.qp, c.prm(), SAO1(c.s1()), c.s1().ctb_log2_w, KEEP1(c.s1()), c.o.fused, c.stream())),
+    E(hevc_deblock_sao_h265_device_planes, hevc_deblock_sao_h265_device_planes(c.ctx, c.all(), c.o.n_planes, c.o.qp, c.prm(), c.o.sao_null ? nullptr : c.sq, c.o.fused, c.stream())),
+    E(hevcdbk_h265_deblock_sao_device_cf, hevcdbk_h265_deblock_sao_device_cf(c.ctx, c.one(), c.o.c_idx, c.o.cf, c.o.qp, c.prm(), SAO1(c.s1()), c.s1().ctb_log2_w, c.s1().ctb_log2_h, KEEP1(c.s1()), c.o.fused, c.stream())),
+    E(hevcdbk_h265_deblock_sao_device_nox, hevcdbk_h265_deblock_sao_device_nox(c.ctx, c.one(), c.o.c_idx, c.o.cf, c.o.qp, c.prm(), SAO1(c.s1()), c.s1().ctb_log2_w, c.s1().ctb_log2_h, KEEP1(c.s1()), c.o.fused, b, c.stream())),
+    E(hevcdbk_h265_deblock_sao_device_sl, hevcdbk_h265_deblock_sao_device_sl(c.ctx, c.one(), c.o.c_idx, c.o.cf, c.o.qp, c.prm(), SAO1(c.s1()), c.s1().ctb_log2_w, c.s1().ctb_log2_h, KEEP1(c.s1()), c.o.fused, b, sl, c.stream())),
+    E(hevcdbk_h265_deblock_sao_device_g4, hevcdbk_h265_deblock_sao_device_g4(c.ctx, c.one(), c.o.c_idx, c.o.cf, c.o.qp, c.prm(), SAO1(c.s1()), c.s1().ctb_log2_w, c.s1().ctb_log2_h, KEEP1(c.s1()), c.o.fused, b, sl, c.stream())),
+    E(hevcdbk_h265_deblock_sao_device_sp, hevcdbk_h265_deblock_sao_device_sp(c.ctx, c.pair(), c.o.qp, c.prm(), c.sp().params, c.o.params_cr, c.sp().params_stride, c.sp().params_frame_stride, c.sp().ctb_log2_w, KEEP1(c.sp()), c.o.fused, b, sl, c.stream())),
+    E(hevcdbk_h265_deblock_sao_device_planes_cf, hevcdbk_h265_deblock_sao_device_planes_cf(c.ctx, c.all(), c.o.n_planes, c.o.cf, c.o.qp, c.prm(), c.o.sao_null ? nullptr : c.o.sao, c.o.fused, c.stream())),
+    E(hevcdbk_h265_deblock_sao_device_planes_nox, hevcdbk_h265_deblock_sao_device_planes_nox(c.ctx, c.all(), c.o.n_planes, c.o.cf, c.o.qp, c.prm(), c.o.sao_null ? nullptr : c.o.sao, c.o.fused, b, c.stream())),
+    E(hevcdbk_h265_deblock_sao_device_planes_sl, hevcdbk_h265_deblock_sao_device_planes_sl(c.ctx, c.all(), c.o.n_planes, c.o.cf, c.o.qp, c.prm(), c.o.sao_null ? nullptr : c.o.sao, c.o.fused, b, sl, c.stream())),
+    E(hevcdbk_h265_deblock_sao_device_planes_g4, hevcdbk_h265_deblock_sao_device_planes_g4(c.ctx, c.all(), c.o.n_planes, c.o.cf, c.o.qp, c.prm(), c.o.sao_null ? nullptr : c.o.sao, c.o.fused, b, sl, c.stream())),
+};
+const int kNumEntries = (int)(sizeof(kEntries) / sizeof(kEntries[0]));
+
+const Entry &entry(const char *name)
+{
+    for (const Entry &e : kEntries)
+        if (!std::strcmp(e.name, name)) return e;
+    std::fprintf(stderr, "no entry %s\n", name);
+    std::abort();
+}
+
+/* ---- one call, and the two properties every call has ------------------------------------------------------------------------------ */
+
+int g_violations = 0;
+void violation(const char *what, const char *name, long id, const std::string &a, const std::string &b = "")
+{
+    if (++g_violations <= 20) std::printf("VIOLATION %s: case %ld %s\n  %s\n  %s\n", what, id, name, a.c_str(), b.c_str());
+}
+
+bool refusal(int rc) { return rc == HEVCDBK_ERR_ARG || rc == HEVCDBK_ERR_DIMENSIONS || rc == HEVCDBK_ERR_UNSUPPORTED || rc == HEVCDBK_ERR_BS_SIZE; }
+
+struct Result {
+    std::string text;  /* everything the call did */
+    bool launched;     /* it got as far as a launch */
+};
+
+/* the entry on a context of its own, with the borders / offsets operands given; the case's `repeat` calls it twice (1: the same
+ * call, which meets the scratch buffers' fences; 2: one frame first, so that the scratch buffers grow) */
+Result run(const Entry &e, const Ops &o, long id, bool borders, bool offsets, bool check)
+{
+    sim_new_case();
+    hevcdbk_context *ctx = nullptr;
+    if (hevcdbk_create(0, &ctx) != HEVCDBK_OK) std::abort();
+    g_sim.trace.clear();
+    g_sim.set_device_fails = o.bind_fail;
+    g_sim.fail_at = o.fail_at;
+    g_sim.packed_mask = o.packed_mask;
+    g_sim.fused_mask = o.fused_mask;
+    g_sim.sp_mask = o.sp_mask;
+    Result res = {"", false};
+    const bool is_h265_num = e.fn == kEntries[0].fn;
+    for (int round = 0; round < (o.repeat ? 2 : 1); round++) {
+        const Call c(o, o.ctx_null ? nullptr : ctx, o.repeat == 2 && round == 0 ? 1 : 0);
+        g_sim.trace.clear();
+        const int rc = e.fn(c, borders && o.has_borders ? &o.borders : nullptr, offsets && o.has_sl ? &o.sl : nullptr);
+        std::string t = g_sim.trace;
+        const std::string sao_ev = sim_event_name(ctx->sao_ev);
+        if (check && !is_h265_num) {
+            if (refusal(rc))
+                for (size_t at = 0; at < t.size(); at = t.find('\n', at) + 1)
+                    if (t.compare(at, 13, "hipSetDevice\n") != 0) { violation("work after a refusal", e.name, id, t); break; }
+            const size_t x2 = t.rfind("sao_rows_x2:");
+            /* the SAO pass entries return at once when their own launch fails, as they did before the deblocking + SAO entries
+             * learnt to fence "whatever followed": asked of them only when the call succeeded */
+            if (x2 != std::string::npos && (rc == HEVCDBK_OK || !std::strstr(e.name, "sao_filter"))) {
+                bool failed = false;
+                for (size_t at = t.find("rows_x2:"); at != std::string::npos; at = t.find("rows_x2:", at + 1))
+                    failed = failed || t.compare(t.find('\n', at) - 8, 8, " -> FAIL") == 0;
+                if (!failed && t.find("hipEventRecord " + sao_ev + " ", x2) == std::string::npos)
+                    violation("no fence after the parameter launch", e.name, id, t);
+            }
+        }
+        res.launched = res.launched || t.find(": src=") != std::string::npos || t.find(": s.src=") != std::string::npos || t.find("h265_bs:") != std::string::npos;
+        for (char &ch : t)
+            if (ch == '\n') ch = ';';
+        char head[512];
+        std::snprintf(head, sizeof(head), "%src=%d err=[%s] tmp=%s/%s sao=%s/%s | ", round ? " || " : "", rc, hevcdbk_last_error(ctx),
+                      sim_dev_name(ctx->dev_tmp.p).c_str(), sim_event_name(ctx->tmp_ev).c_str(), sim_dev_name(ctx->dev_sao.p).c_str(), sao_ev.c_str());
+        res.text += head + t;
+    }
+    hevcdbk_destroy(ctx);
+    return res;
+}
+
+bool all_mult8(const Ops &o)
+{
+    for (int i = 0; i < 4; i++)
+        if (o.pl[i].plane_w % 8 != 0 || o.pl[i].plane_h % 8 != 0) return false;
+    return true;
+}
+
+} /* namespace */
+
+int main(int argc, char **argv)
+{
+    if (argc != 4 || (std::strcmp(argv[1], "dump") && std::strcmp(argv[1], "check"))) {
+        std::fprintf(stderr, "usage: %s dump|check SEED CASES\n", argv[0]);
+        return 2;
+    }
+    const bool check = !std::strcmp(argv[1], "check");
+    Rng r = {std::strtoull(argv[2], nullptr, 0)};
+    const long n = std::strtol(argv[3], nullptr, 0);
+    std::map<std::string, long> counts, compared;
+    for (long id = 0; id < n; id++) {
+        const Ops o = make_case(r);
+        if (!check) {
+            for (const Entry &e : kEntries) {
+                std::printf("%ld %s %s\n", id, e.name, run(e, o, id, true, true, false).text.c_str());
+                counts[e.name]++;
+            }
+            continue;
+        }
+        for (const Entry &e : kEntries) {
+            run(e, o, id, true, true, true);
+            counts[e.name]++;
+        }
+        /* {the later generation, the earlier one, borders given to both, offsets given to both, the condition, both must have launched} */
+        struct Pair { const char *a, *b; bool borders, offsets, when, launched; };
+        const bool m8 = all_mult8(o);
+        bool square = true;
+        for (unsigned i = 0; i < 3; i++) square = square && o.sao[i].ctb_log2_w == o.sao[i].ctb_log2_h;
+        const bool sq1 = o.sao[o.c_idx < 0 ? 0 : (o.c_idx > 2 ? 2 : o.c_idx)].ctb_log2_w == o.sao[o.c_idx < 0 ? 0 : (o.c_idx > 2 ? 2 : o.c_idx)].ctb_log2_h;
+        const bool c420 = o.cf == HEVCDBK_CHROMA_420;
+        const Pair pairs[] = {
+            /* an _sl entry without the operand is the _nox (_cf) entry */
+            {"hevcdbk_h265_filter_device_sl", "hevcdbk_h265_filter_device_cf", true, false, true, false},
+            {"hevcdbk_h265_deblock_sao_device_sl", "hevcdbk_h265_deblock_sao_device_nox", true, false, true, false},
+            {"hevcdbk_h265_deblock_sao_device_planes_sl", "hevcdbk_h265_deblock_sao_device_planes_nox", true, false, true, false},
+            /* a _g4 entry on planes sized in multiples of 8 is the _sl (_nox) entry */
+            {"hevcdbk_h265_filter_device_g4", "hevcdbk_h265_filter_device_sl", true, true, m8, false},
+            {"hevcdbk_sao_filter_device_g4", "hevcdbk_sao_filter_device_nox", true, true, m8, false},
+            {"hevcdbk_h265_deblock_sao_device_g4", "hevcdbk_h265_deblock_sao_device_sl", true, true, m8, false},
+            {"hevcdbk_h265_deblock_sao_device_planes_g4", "hevcdbk_h265_deblock_sao_device_planes_sl", true, true, m8, false},
+            /* a _nox entry without borders is the _cf entry */
+            {"hevcdbk_sao_filter_device_nox", "hevcdbk_sao_filter_device_cf", false, false, true, false},
+            {"hevcdbk_h265_deblock_sao_device_nox", "hevcdbk_h265_deblock_sao_device_cf", false, false, true, false},
+            {"hevcdbk_h265_deblock_sao_device_planes_nox", "hevcdbk_h265_deblock_sao_device_planes_cf", false, false, true, false},
+            /* a _cf entry with 4:2:0 and square CTBs is the original entry, where neither was refused before the launch */
+            {"hevcdbk_h265_filter_device_cf", "hevc_deblocking_filter_h265_device", false, false, c420, true},
+            {"hevcdbk_h265_deblock_sao_device_cf", "hevc_deblock_sao_h265_device", false, false, c420 && sq1, true},
+            {"hevcdbk_h265_deblock_sao_device_planes_cf", "hevc_deblock_sao_h265_device_planes", false, false, c420 && square, true},
+            {"hevcdbk_sao_filter_device_cf", "hevc_sao_filter_device", false, false, sq1, true},
+            {"hevcdbk_h265_derive_bs_device_cf", "hevcdbk_h265_derive_bs_device", false, false, c420, true},
+            {"hevcdbk_h265_derive_bs_device_g4", "hevcdbk_h265_derive_bs_device", false, false, c420, true},
+        };
+        for (const Pair &p : pairs) {
+            if (!p.when) continue;
+            const Result a = run(entry(p.a), o, id, p.borders, p.offsets, false), b = run(entry(p.b), o, id, p.borders, p.offsets, false);
+            if (p.launched && !(a.launched && b.launched)) continue;
+            compared[std::string(p.a) + " == " + p.b]++;
+            if (a.text != b.text) violation("identity", (std::string(p.a) + " vs " + p.b).c_str(), id, a.text, b.text);
+        }
+    }
+    for (const auto &kv : counts) std::fprintf(check ? stdout : stderr, "cases %s %ld\n", kv.first.c_str(), kv.second);
+    for (const auto &kv : compared) std::printf("compared %s %ld\n", kv.first.c_str(), kv.second);
+    if (check) std::printf("%d violations\n", g_violations);
+    std::fprintf(stderr, "%d entries, %ld cases each\n", kNumEntries, n);
+    return g_violations ? 1 : 0;
+}
