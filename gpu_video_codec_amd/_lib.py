@@ -50,6 +50,7 @@ EXPORTS = [
     "hevcdbk_h265_derive_bs_device_g4", "hevcdbk_h265_filter_device_g4", "hevcdbk_sao_filter_device_g4",
     "hevcdbk_h265_deblock_sao_device_g4", "hevcdbk_h265_deblock_sao_device_planes_g4",
     "hevcdbk_h265_filter_device_sp", "hevcdbk_sao_filter_device_sp", "hevcdbk_h265_deblock_sao_device_sp",
+    "hevcdbk_h265_deblock_sao_device_sp_fused", "hevcdbk_h265_deblock_sao_device_nv12",
 ]
 
 # chroma_format_idc of the spec-exact mode and SAO (HEVCDBK_CHROMA_*): 4:0:0, 4:2:0, 4:2:2, 4:4:4
@@ -105,6 +106,12 @@ class SaoPlaneCf(C.Structure):
     """hevcdbk_sao_plane_cf: SaoPlane with CTBs of (1 << ctb_log2_w) x (1 << ctb_log2_h) samples"""
     _fields_ = [("params", C.c_void_p), ("params_stride", C.c_uint), ("params_frame_stride", C.c_size_t), ("ctb_log2_w", C.c_uint),
                 ("ctb_log2_h", C.c_uint), ("keep", C.c_void_p), ("keep_stride", C.c_uint), ("keep_frame_stride", C.c_size_t)]
+
+
+class SaoPlaneSp(C.Structure):
+    """hevcdbk_sao_plane_sp: the SAO operands of a plane of interleaved Cb / Cr pairs (square CTBs of 1 << ctb_log2 samples)"""
+    _fields_ = [("params_cb", C.c_void_p), ("params_cr", C.c_void_p), ("params_stride", C.c_uint), ("params_frame_stride", C.c_size_t),
+                ("ctb_log2", C.c_uint), ("keep", C.c_void_p), ("keep_stride", C.c_uint), ("keep_frame_stride", C.c_size_t)]
 
 
 class SaoBorders(C.Structure):
@@ -308,6 +315,11 @@ def lib():
         L.hevcdbk_h265_deblock_sao_device_sp.argtypes = [C.c_void_p, C.POINTER(DevicePlanes), C.c_uint, C.POINTER(H265Params), C.c_void_p,
                                                          C.c_void_p, C.c_uint, C.c_size_t, C.c_uint, C.c_void_p, C.c_uint, C.c_size_t,
                                                          C.c_int, C.POINTER(SaoBorders), C.POINTER(SliceOffsets), C.c_void_p]
+        # deblocking + SAO of the pair plane in one kernel, and of a whole semi-planar picture in one launch
+        L.hevcdbk_h265_deblock_sao_device_sp_fused.argtypes = L.hevcdbk_h265_deblock_sao_device_sp.argtypes
+        L.hevcdbk_h265_deblock_sao_device_nv12.argtypes = [C.c_void_p, C.POINTER(DevicePlanes), C.POINTER(DevicePlanes), C.c_uint,
+                                                           C.POINTER(H265Params), C.POINTER(SaoPlaneCf), C.POINTER(SaoPlaneSp), C.c_int,
+                                                           C.POINTER(SaoBorders), C.POINTER(SliceOffsets), C.c_void_p]
         L.hevc_deblock_sao_h265_device_planes.argtypes = [C.c_void_p, C.POINTER(DevicePlanes), C.c_uint, C.c_uint, C.POINTER(H265Params),
                                                           C.POINTER(SaoPlane), C.c_int, C.c_void_p]
         L.hevcdbk_set_host_threads.argtypes = [C.c_void_p, C.c_uint]

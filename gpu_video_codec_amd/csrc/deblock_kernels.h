@@ -267,3 +267,19 @@ hipError_t dbk_launch_packed_h265_sp(const DbkH265Args &h, const DbkSlOffs &sl, 
  * pitch * plane_h < 2^31, max_v / band_shift those of 8 bit, or of 8..12 bit in 16-bit containers; else the per-sample kernel */
 bool dbk_sao_sp_packed_supports(const DbkSaoArgs &a, int sample_bytes);
 hipError_t dbk_launch_sao_sp(const DbkSaoArgs &a, const DbkSaoCtb *params_cr, int sample_bytes, hipStream_t stream, const DbkSaoNox *nx);
+
+/* ---- deblocking + SAO of the same plane in ONE kernel (deblock_sao_sp_fused.h, deblock_sao_sp.hip): h.base.src -> s.dst through an LDS
+ * tile of pairs; operands as dbk_launch_packed_h265_sp and dbk_launch_sao_sp take them.  dbk_deblock_sao_sp_supports is where the
+ * kernels' guards are stated: 8-bit samples or 16-bit containers up to 12 bit; one pitch and one frame stride for source and
+ * destination; pitch, frame stride, the source and the destination address multiples of a lane's row piece (16 bytes of 8-bit pairs,
+ * 32 of 16-bit ones); pitch * plane_h < 2^31; at most 65535 frames; tile counts that keep the kernels' reciprocal divisions exact ---- */
+bool dbk_deblock_sao_sp_supports(const DbkH265Args &h, const DbkSaoArgs &s, int sample_bytes);
+/* the pair plane's part of a grid: its tiles (96 x 128 pairs of 8-bit samples, 64 x 128 of 16-bit ones), a multiple of 8 workgroups */
+unsigned dbk_deblock_sao_sp_grid(int plane_w, int plane_h, int n_frames, int sample_bytes, DbkFusedGrid &g);
+hipError_t dbk_launch_deblock_sao_h265_sp(const DbkH265Args &h, const DbkSaoArgs &s, const DbkSaoCtb *params_cr, const DbkSlOffs &sl,
+                                          int cr_qp_offset, int sample_bytes, hipStream_t stream, const DbkSaoNox *nx);
+/* a whole semi-planar 4:2:0 picture in one launch (deblock_kernels.hip): h[0] / s[0] = the luma plane, accepted by
+ * dbk_deblock_sao_supports and run by the luma body of the _g4 multi-plane kernel; h[1] / s[1] = the plane of pairs, accepted by
+ * dbk_deblock_sao_sp_supports; one sample width, bit depth and frame count; ONE DbkSlOffs on the luma CTB grid; nx NULL or one per plane */
+hipError_t dbk_launch_deblock_sao_h265_nv12(const DbkH265Args *h, const DbkSaoArgs *s, const DbkSaoCtb *params_cr, const DbkSlOffs &sl,
+                                            int cr_qp_offset, int sample_bytes, hipStream_t stream, const DbkSaoNox *nx);

@@ -26,6 +26,7 @@
 #include "deblock_sl_packed.h"
 #include "deblock_packed16.h"
 #include "sao_packed.h"
+#include "deblock_sao_sp_fused.h"
 
 /*
  * Every launch goes through hipExtLaunchKernelGGL so that a caller can ask for the NEXT launch to stamp its own start and
@@ -1089,6 +1090,32 @@ __global__ __launch_bounds__(1024) void dbk_packed16_multi_kernel(const DbkMulti
 
 #include "deblock_sao_fused.inc"
 
+/* ---- a whole semi-planar 4:2:0 picture in ONE launch (hevcdbk_h265_deblock_sao_device_nv12): the Y plane's tiles run the luma body
+ * with the template arguments of the _g4 multi-plane kernel, the pair plane's tiles follow and run the pair body
+ * (deblock_sao_sp_fused.h), each part of the grid a multiple of 8 workgroups.  The two bodies share the block size and the tile's
+ * bytes: the pair tile is two component tiles in the rows of one luma tile ---- */
+static_assert(spf::Geo<1>::kLds == kFusedLds && spf::Geo<1>::kLanes <= kFusedThreads, "the 8-bit pair tile is the luma tile");
+static_assert(spf::Geo<2>::kLds == kFused16Lds && spf::Geo<2>::kLanes <= kFused16Threads, "the 16-bit pair tile is the luma tile");
+struct DbkSaoNox2 {
+    DbkSaoNox pl[2];
+};
+/* (a second launch bound asking for four workgroups per CU -- 7 / 5 waves per SIMD, what the planar multi-plane kernels have -- makes
+ * the pair body spill 16 / 152 bytes per lane: not taken) */
+template <int SB, bool WIDE>
+__global__ __launch_bounds__(SB == 1 ? kFusedThreads : kFused16Threads) void dbk_sao_fused_multi_h265_sp_kernel(
+    const DbkFusedH265Args y, const DbkFusedH265Args c, const uint32_t y_wgs, const DbkSaoNox2 nx, const DbkSlOffs sl, const DbkSaoCtb *params_cr,
+    const int cr_qp_offset)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t fused_tile[];
+    const uint32_t b = blockIdx.x;
+    if (b < y_wgs) { /* scalar */
+        if constexpr (SB == 1) fused_body<false, 2, true, 1, true, true, true>(y.d.base, &y.d, y.s, y.g, fused_tile, b, &nx.pl[0], &sl);
+        else fused_body16<false, 2, WIDE, true, 1, true, true, true>(y.d.base, &y.d, y.s, y.g, fused_tile, b, &nx.pl[0], &sl);
+    } else {
+        spf::body<SB, SB == 1 ? kFusedThreads : kFused16Threads>(c.d, c.s, c.g, params_cr, cr_qp_offset, nx.pl[1], sl, fused_tile, b - y_wgs);
+    }
+}
+
 #ifdef HEVCDBK_DIAG
 /* the measured-and-rejected kernels (LDS queue, stripe map, tile map): diagnostic build only, DESIGN.md 4.1 */
 #include "deblock_diag_kernels.inc"
@@ -1948,4 +1975,37 @@ hipError_t dbk_launch_deblock_sao_multi_h265_g4(const DbkH265Args *h, const DbkS
                                                 int chroma_format, hipStream_t stream, const DbkSaoNox *nxp)
 {
     return launch_deblock_sao_multi_h265_sl(h, s, sl, n, sample_bytes, chroma_format, stream, nxp, true);
+}
+
+/* a semi-planar 4:2:0 picture: h[0] / s[0] the luma plane, h[1] / s[1] the plane of pairs (deblock_sao_sp.hip) */
+hipError_t dbk_launch_deblock_sao_h265_nv12(const DbkH265Args *h, const DbkSaoArgs *s, const DbkSaoCtb *params_cr, const DbkSlOffs &sl,
+                                            int cr_qp_offset, int sample_bytes, hipStream_t stream, const DbkSaoNox *nxp)
+{
+    if (h[0].base.n_frames <= 0) return hipSuccess;
+    if (h[1].base.n_frames != h[0].base.n_frames || !dbk_deblock_sao_supports(h[0].base, s[0], sample_bytes, false) ||
+        !dbk_deblock_sao_sp_supports(h[1], s[1], sample_bytes))
+        return hipErrorInvalidValue;
+    DbkFusedH265Args y, c;
+    y.d = h[0];
+    y.s = s[0];
+    c.d = h[1];
+    c.s = s[1];
+    const unsigned y_wgs = fused_grid(h[0].base.plane_w, h[0].base.plane_h, h[0].base.n_frames, sample_bytes, y.g);
+    const unsigned c_wgs = dbk_deblock_sao_sp_grid(h[1].base.plane_w, h[1].base.plane_h, h[1].base.n_frames, sample_bytes, c.g);
+    const dim3 grid(y_wgs + c_wgs, 1, 1);
+    DbkSaoNox2 nx = {};
+    if (nxp) {
+        nx.pl[0] = nxp[0];
+        nx.pl[1] = nxp[1];
+    }
+    if (sample_bytes == 1)
+        DBK_LAUNCH_LDS((dbk_sao_fused_multi_h265_sp_kernel<1, false>), grid, dim3(kFusedThreads), kFusedLds, stream, y, c, y_wgs, nx, sl, params_cr,
+                       cr_qp_offset);
+    else if (h[0].base.max_v > 2047)
+        DBK_LAUNCH_LDS((dbk_sao_fused_multi_h265_sp_kernel<2, true>), grid, dim3(kFused16Threads), kFused16Lds, stream, y, c, y_wgs, nx, sl, params_cr,
+                       cr_qp_offset);
+    else
+        DBK_LAUNCH_LDS((dbk_sao_fused_multi_h265_sp_kernel<2, false>), grid, dim3(kFused16Threads), kFused16Lds, stream, y, c, y_wgs, nx, sl,
+                       params_cr, cr_qp_offset);
+    return hipGetLastError();
 }

@@ -19,41 +19,15 @@
 #include <hip/hip_runtime.h>
 
 #include "deblock_h265_quad4.h"
-#include "deblock_sl_dev.h"
-#include "deblock_sl_packed.h"
 #include "deblock_packed16.h"
 #include "deblock_sp.h"
+#include "deblock_sp_dev.h"
 
 namespace {
 
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 constexpr uint32_t kOob = 0xfffffff0u; /* voffset >= num_records: load returns 0, store is dropped */
-
-/* what the two components of a lane's block share: the four bS bytes, the four segment QPs and the four offset pairs (the launch's
- * own pair added).  Every load is issued before anything waits. */
-__device__ __forceinline__ void sp_block_operands(const DbkH265Args &h, const DbkSlOffs &sl, int f, int bx, int by, int (&entry)[4],
-                                                  int (&qpl)[4], int (&tc_off)[4], int (&beta_off)[4])
-{
-    const DbkArgs &a = h.base;
-    unsigned ar, bl, br;
-    dbk_sl_load_pairs<2, 2>(sl, f, bx, by, a.plane_w * 2, a.plane_h * 2, ar, bl, br);
-    dbk::load_block_bs_h265_g4(a.vert_bs + (long long)f * a.vert_bs_stride, a.hor_bs + (long long)f * a.hor_bs_stride, bx, by,
-                               a.plane_w, a.plane_h, a.vstride, a.hstride, entry);
-    if (a.qp_map) { /* wave-uniform */
-        dbk::h265_block_qpl4(a.qp_map + (long long)f * a.map_frame_stride, a.map_stride, a.ctu_log2, 2, a.plane_w * 2, a.plane_h * 2,
-                             bx * 8 - 4, by * 8 - 4, qpl);
-    } else {
-#pragma unroll
-        for (int i = 0; i < 4; i++) qpl[i] = h.qp;
-    }
-    dbk::h265_sl_seg_offs(ar, bl, br, tc_off, beta_off);
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        tc_off[i] += h.tc_off;
-        beta_off[i] += h.beta_off;
-    }
-}
 
 /* ---- 32-bit arithmetic, every operand kind: samples of any depth, planes aligned to one 4-sample word ---- */
 template <typename T>
@@ -68,7 +42,7 @@ __global__ __launch_bounds__(256) void dbk_h265_sp_kernel(const DbkH265Args h, c
     if (bx >= a.nbx || by >= a.nby) return;
 
     int entry[4], qpl[4], tc_off[4], beta_off[4];
-    sp_block_operands(h, sl, f, bx, by, entry, qpl, tc_off, beta_off);
+    dbk::sp_block_operands(h, sl, f, bx, by, entry, qpl, tc_off, beta_off);
     /* chroma ignores bS 1 (8.7.2.5): blocks with nothing to filter move no samples at all when filtering in place */
     bool any = false;
 #pragma unroll
@@ -116,17 +90,6 @@ __global__ __launch_bounds__(256) void dbk_h265_sp_kernel(const DbkH265Args h, c
 
 /* ---- packed-int16 arithmetic ---- */
 
-/* the two components' per-segment operands from what they share */
-__device__ __forceinline__ void sp_seg_params(const DbkH265Args &h, const DbkSlOffs &sl, int cr_qp_offset, int f, int bx, int by, int shift,
-                                              int max_v, dbk::H265Seg &cb, dbk::H265Seg &cr)
-{
-    int entry[4], qpl[4], tc_off[4], beta_off[4];
-    sp_block_operands(h, sl, f, bx, by, entry, qpl, tc_off, beta_off);
-    const dbk::H265Prm pb = {0, 0, h.c_qp_offset, shift, max_v}, pr = {0, 0, cr_qp_offset, shift, max_v};
-    dbk::h265_seg_params_sl<true, 1>(entry, qpl, pb, tc_off, beta_off, cb);
-    dbk::h265_seg_params_sl<true, 1>(entry, qpl, pr, tc_off, beta_off, cr);
-}
-
 /* a 16-byte store with a scalar row offset is followed by two wait states before anything may write its data registers
  * (profiles/r04/store_hazard.md; the 16-bit fused kernel's stores do the same) */
 __device__ __forceinline__ void sp_store128(const u32x4 w, __amdgpu_buffer_rsrc_t rd, uint32_t voff, int soff)
@@ -169,7 +132,7 @@ __device__ __forceinline__ void sp8_body(const DbkH265Args &h, const DbkSlOffs &
     }
 
     dbk::H265Seg sb, sr;
-    sp_seg_params(h, sl, cr_qp_offset, f, bx, by, 0, 255, sb, sr);
+    dbk::sp_seg_params(h, sl, cr_qp_offset, f, bx, by, 0, 255, sb, sr);
 
     uint32_t Lb[8], Rb[8], Lr[8], Rr[8];
 #pragma unroll
@@ -240,7 +203,7 @@ __device__ __forceinline__ void sp16_body(const DbkH265Args &h, const DbkSlOffs 
     }
 
     dbk::H265Seg sb, sr;
-    sp_seg_params(h, sl, cr_qp_offset, f, bx, by, a.shift, a.max_v, sb, sr);
+    dbk::sp_seg_params(h, sl, cr_qp_offset, f, bx, by, a.shift, a.max_v, sb, sr);
 
     uint32_t Wb[8][4], Wr[8][4];
 #pragma unroll

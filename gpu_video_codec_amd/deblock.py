@@ -482,12 +482,16 @@ class Context:
     def deblock_sao_h265_device(self, planes, qp, params_ptr, params_stride, ctb_log2, *, c_idx=0, tc_offset_div2=0,
                                 beta_offset_div2=0, cb_qp_offset=0, cr_qp_offset=0, params_frame_stride=0, keep_ptr=None,
                                 keep_stride=0, keep_frame_stride=0, fused=_lib.FUSED_AUTO, chroma_format="420", ctb_log2_h=None,
-                                borders=None, slice_offsets=None, g4=False, semi_planar=False, params_cr_ptr=None):
+                                borders=None, slice_offsets=None, g4=False, semi_planar=False, params_cr_ptr=None, one_kernel=False):
         """hevc_deblock_sao_h265_device[_cf]: spec-exact deblocking (8.7.2) followed by SAO (8.7.3), src -> dst; chroma_format,
         ctb_log2 / ctb_log2_h and borders (hevcdbk_h265_deblock_sao_device_nox) as for sao_device; slice_offsets as for
         filter_device_h265 (hevcdbk_h265_deblock_sao_device_sl); g4=True: hevcdbk_h265_deblock_sao_device_g4 (a chroma plane
         sized in multiples of 4).  semi_planar=True: hevcdbk_h265_deblock_sao_device_sp -- a plane of interleaved Cb / Cr pairs as
-        for filter_device_h265 and sao_device (c_idx is not used; params_cr_ptr is needed); fused=FUSED_ON is refused."""
+        for filter_device_h265 and sao_device (c_idx is not used; params_cr_ptr is needed); fused=FUSED_ON is refused.  one_kernel=True
+        (with semi_planar=True only): hevcdbk_h265_deblock_sao_device_sp_fused -- the same result from ONE kernel where its guards allow
+        (fused=FUSED_AUTO), or nothing else (FUSED_ON); FUSED_OFF is the two launches."""
+        if one_kernel and not semi_planar:
+            raise ValueError("one_kernel belongs to semi_planar=True")
         cf = _lib.chroma_format_idc(chroma_format)
         prm = _lib.H265Params(tc_offset_div2, beta_offset_div2, cb_qp_offset, cr_qp_offset)
         if semi_planar:
@@ -495,11 +499,10 @@ class Context:
                 raise ValueError("semi_planar is 4:2:0 only")
             if params_cr_ptr is None:
                 raise ValueError("semi_planar needs params_cr_ptr: the parameters of the odd samples")
-            _chk(_lib.lib().hevcdbk_h265_deblock_sao_device_sp(self.handle, C.byref(planes), int(qp), C.byref(prm), params_ptr, params_cr_ptr,
-                                                               params_stride, params_frame_stride, ctb_log2, keep_ptr, keep_stride,
-                                                               keep_frame_stride, fused, None if borders is None else C.byref(borders),
-                                                               None if slice_offsets is None else C.byref(slice_offsets), None),
-                 self.handle)
+            entry = _lib.lib().hevcdbk_h265_deblock_sao_device_sp_fused if one_kernel else _lib.lib().hevcdbk_h265_deblock_sao_device_sp
+            _chk(entry(self.handle, C.byref(planes), int(qp), C.byref(prm), params_ptr, params_cr_ptr, params_stride, params_frame_stride,
+                       ctb_log2, keep_ptr, keep_stride, keep_frame_stride, fused, None if borders is None else C.byref(borders),
+                       None if slice_offsets is None else C.byref(slice_offsets), None), self.handle)
             return
         if params_cr_ptr is not None:
             raise ValueError("params_cr_ptr belongs to semi_planar=True")
@@ -596,6 +599,31 @@ class Context:
                                   h265.get("cr_qp_offset", 0))
             rc = _lib.lib().hevc_deblock_sao_h265_device_planes(self.handle, arr, len(planes_list), int(qp), C.byref(prm), sp, fused, None)
         _chk(rc, self.handle)
+
+    def deblock_sao_nv12(self, luma_planes, pair_planes, qp, sao_luma, sao_pairs, *, h265, fused=_lib.FUSED_AUTO, borders=None,
+                         slice_offsets=None):
+        """hevcdbk_h265_deblock_sao_device_nv12: spec-exact deblocking + SAO of a whole semi-planar 4:2:0 picture -- the Y plane
+        (DeviceBatch(...).planes()) and the plane of interleaved Cb / Cr pairs (DeviceBatch(..., semi_planar=True).planes()) -- in ONE
+        launch where both fused kernels apply, else plane by plane.  sao_luma: a dict as deblock_sao_device_planes takes (params,
+        params_stride, ctb_log2, optional params_frame_stride / keep / keep_stride / keep_frame_stride); sao_pairs: a dict with
+        params_cb, params_cr, params_stride, ctb_log2 (= the luma ctb_log2 - 1) and the same optional entries.  h265: a dict of
+        tc_offset_div2, beta_offset_div2, cb_qp_offset, cr_qp_offset.  borders / slice_offsets: ONE operand each on the luma CTB grid."""
+        if h265 is None:
+            raise ValueError("a semi-planar picture is filtered in the spec-exact mode: h265= is needed")
+        for d, keys in ((sao_luma, ("params", "params_stride", "ctb_log2")), (sao_pairs, ("params_cb", "params_cr", "params_stride", "ctb_log2"))):
+            missing = [k for k in keys if not isinstance(d, dict) or d.get(k) is None]
+            if missing:
+                raise ValueError("SAO operands missing: %s" % ", ".join(missing))
+        sl = _lib.SaoPlaneCf(sao_luma["params"], sao_luma["params_stride"], sao_luma.get("params_frame_stride", 0), sao_luma["ctb_log2"],
+                             sao_luma.get("ctb_log2_h", sao_luma["ctb_log2"]), sao_luma.get("keep"), sao_luma.get("keep_stride", 0),
+                             sao_luma.get("keep_frame_stride", 0))
+        sp = _lib.SaoPlaneSp(sao_pairs["params_cb"], sao_pairs["params_cr"], sao_pairs["params_stride"], sao_pairs.get("params_frame_stride", 0),
+                             sao_pairs["ctb_log2"], sao_pairs.get("keep"), sao_pairs.get("keep_stride", 0), sao_pairs.get("keep_frame_stride", 0))
+        prm = _lib.H265Params(h265.get("tc_offset_div2", 0), h265.get("beta_offset_div2", 0), h265.get("cb_qp_offset", 0),
+                              h265.get("cr_qp_offset", 0))
+        _chk(_lib.lib().hevcdbk_h265_deblock_sao_device_nv12(self.handle, C.byref(luma_planes), C.byref(pair_planes), int(qp), C.byref(prm),
+                                                             C.byref(sl), C.byref(sp), fused, None if borders is None else C.byref(borders),
+                                                             None if slice_offsets is None else C.byref(slice_offsets), None), self.handle)
 
     def filter_device_planes(self, planes_list, qp, *, tc_table=None, beta_table=None, variant=KERNEL_AUTO):
         """hevc_deblocking_filter_device_planes: Y, U, V of a batch in one call (one fused launch where that applies)."""

@@ -810,14 +810,58 @@ HEVCDBK_API int hevcdbk_sao_filter_device_sp(hevcdbk_context *ctx, const hevcdbk
 
 /* the in-loop chain on the pair plane: hevcdbk_h265_filter_device_sp (HEVCDBK_KERNEL_AUTO) into the context's scratch plane, then
  * hevcdbk_sao_filter_device_sp from there into dst -- two launches, a host composition.  fused: HEVCDBK_FUSED_AUTO and
- * HEVCDBK_FUSED_OFF run the two launches; HEVCDBK_FUSED_ON returns HEVCDBK_ERR_UNSUPPORTED before anything is enqueued (there is no
- * fused kernel for this layout yet; the argument is there so that one needs no new signature); any other value HEVCDBK_ERR_ARG */
+ * HEVCDBK_FUSED_OFF run the two launches; HEVCDBK_FUSED_ON returns HEVCDBK_ERR_UNSUPPORTED before anything is enqueued (this entry
+ * stays the host composition: the one-kernel form is hevcdbk_h265_deblock_sao_device_sp_fused below); any other value HEVCDBK_ERR_ARG */
 HEVCDBK_API int hevcdbk_h265_deblock_sao_device_sp(hevcdbk_context *ctx, const hevcdbk_device_planes *planes, unsigned qp,
                                                    const hevcdbk_h265_params *h265_params, const hevcdbk_sao_ctb *params_cb,
                                                    const hevcdbk_sao_ctb *params_cr, unsigned params_stride, size_t params_frame_stride,
                                                    unsigned ctb_log2, const uint8_t *keep, unsigned keep_stride, size_t keep_frame_stride,
                                                    int fused, const hevcdbk_sao_borders *borders,
                                                    const hevcdbk_h265_slice_offsets *slice_offsets, void *hip_stream);
+
+/* The same chain in ONE kernel: a workgroup deblocks a tile of pairs into its LDS, the two components de-interleaved, and applies SAO
+ * from there; the deblocked plane never exists in memory and the context's scratch plane is not touched.  Same operands as
+ * hevcdbk_h265_deblock_sao_device_sp, same checks in the same order, and the result is byte for byte that entry's.
+ * fused: HEVCDBK_FUSED_AUTO = the one-kernel form where the kernel's guards allow, else the two launches;
+ *        HEVCDBK_FUSED_ON   = the one-kernel form, or HEVCDBK_ERR_UNSUPPORTED before anything is enqueued;
+ *        HEVCDBK_FUSED_OFF  = the two launches; any other value HEVCDBK_ERR_ARG.
+ * The guards: samples of at most 12 bit; pitch, frame_stride and both addresses multiples of a lane's row piece -- 16 bytes (8-bit
+ * samples) / 32 bytes (16-bit containers); pitch * plane_h < 2^31; at most 65535 frames. */
+HEVCDBK_API int hevcdbk_h265_deblock_sao_device_sp_fused(hevcdbk_context *ctx, const hevcdbk_device_planes *planes, unsigned qp,
+                                                         const hevcdbk_h265_params *h265_params, const hevcdbk_sao_ctb *params_cb,
+                                                         const hevcdbk_sao_ctb *params_cr, unsigned params_stride,
+                                                         size_t params_frame_stride, unsigned ctb_log2, const uint8_t *keep,
+                                                         unsigned keep_stride, size_t keep_frame_stride, int fused,
+                                                         const hevcdbk_sao_borders *borders,
+                                                         const hevcdbk_h265_slice_offsets *slice_offsets, void *hip_stream);
+
+/* SAO operands of a pair plane, as hevcdbk_sao_filter_device_sp takes them */
+typedef struct hevcdbk_sao_plane_sp {
+    const hevcdbk_sao_ctb *params_cb, *params_cr;
+    unsigned params_stride;
+    size_t params_frame_stride;
+    unsigned ctb_log2; /* 3..5, square */
+    const uint8_t *keep; /* may be NULL */
+    unsigned keep_stride;
+    size_t keep_frame_stride;
+} hevcdbk_sao_plane_sp;
+
+/* A whole semi-planar 4:2:0 picture -- the surface a decoder holds -- deblocked and SAO-filtered: luma (is_chroma = 0, sizes multiples
+ * of 8) and pairs (is_chroma = 1, plane_w x plane_h per component = luma / 2, multiples of 4 and at least 8), the same n_frames,
+ * sample_bytes and bit_depth (anything else: HEVCDBK_ERR_ARG).
+ *   - Y is what hevcdbk_h265_deblock_sao_device_planes_g4 gives for the luma plane alone, the pair plane what
+ *     hevcdbk_h265_deblock_sao_device_sp gives;
+ *   - borders and slice_offsets are ONE operand each on the luma CTB grid, as for the _planes_g4 entry; either may be NULL;
+ *   - sao_luma has square CTBs and sao_pairs->ctb_log2 == sao_luma->ctb_log2_w - 1, else HEVCDBK_ERR_ARG;
+ *   - every operand of both planes is checked before the device is bound or anything is enqueued.
+ * ONE launch when fused is not HEVCDBK_FUSED_OFF, both planes pass the guards of their fused kernels and both have the same kind of
+ * QP (one value, or a map); otherwise plane by plane, each in its best available form.  HEVCDBK_FUSED_ON is refused with
+ * HEVCDBK_ERR_UNSUPPORTED, before anything is enqueued, when a plane cannot be fused. */
+HEVCDBK_API int hevcdbk_h265_deblock_sao_device_nv12(hevcdbk_context *ctx, const hevcdbk_device_planes *luma,
+                                                     const hevcdbk_device_planes *pairs, unsigned qp,
+                                                     const hevcdbk_h265_params *h265_params, const hevcdbk_sao_plane_cf *sao_luma,
+                                                     const hevcdbk_sao_plane_sp *sao_pairs, int fused, const hevcdbk_sao_borders *borders,
+                                                     const hevcdbk_h265_slice_offsets *slice_offsets, void *hip_stream);
 
 #ifdef __cplusplus
 }
