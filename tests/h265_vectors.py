@@ -578,13 +578,17 @@ def sao_offset_limits(bit_depth):
 FUSED_COLS, FUSED_ROWS = (63, 64, 191, 192), (127, 128)   # tile and quadrant borders of the fused kernels
 
 
-def sao_full_range(bit_depth, ctb_log2, rng, *, w=320, h=256, keep_every=6):
+def sao_full_range(bit_depth, ctb_log2, rng, *, w=320, h=256, keep_every=6, stripe_cols=FUSED_COLS,
+                   stripe_rows=FUSED_ROWS, walk_start=0):
     """Full-range SAO content and parameters for a w x h plane with square CTBs of 1 << ctb_log2:
     8x8 blocks of ramps through all 32 bands, runs of 0 and max_v, plateaus with single-sample spikes (edge categories with
     sgn = 0 next to extremes), full-range noise and 0 / max_v checkers; 0 and max_v side by side across columns 63/64,
-    191/192 and rows 127/128.  Parameters: band CTBs walk every band position 0..31, edge CTBs every class; offsets take the
-    spec-legal scaled magnitudes and the int8 ends -128 / 127 (edge offsets signed as 7.4.9.3.2).  Returns plane, params
-    (oracle/h265 SAO_CTB_DTYPE), keep (one byte per 8x8 block)."""
+    191/192 and rows 127/128 (stripe_cols / stripe_rows: the borders of other kernels; no draw depends on them).  Parameters:
+    band CTBs walk every band position 0..31, edge CTBs every class; offsets take the spec-legal scaled magnitudes and the
+    int8 ends -128 / 127 (edge offsets signed as 7.4.9.3.2); walk_start: where the walk through the band positions and the
+    offset magnitudes begins, for the frames of a plane of few CTBs (the first band CTB takes position 13 * walk_start % 32,
+    CTB i the magnitudes of turn i // 5 + walk_start).  Returns plane, params (oracle/h265 SAO_CTB_DTYPE), keep (one byte per
+    8x8 block)."""
     max_v = (1 << bit_depth) - 1
     p = np.zeros((h, w), np.int64)
     yy, xx = np.mgrid[0:8, 0:8]
@@ -608,10 +612,10 @@ def sao_full_range(bit_depth, ctb_log2, rng, *, w=320, h=256, keep_every=6):
             else:
                 blk = np.where((xx + yy) % 2 == 0, 0, max_v)
             p[8 * by:8 * by + 8, 8 * bx:8 * bx + 8] = blk
-    for c in FUSED_COLS:
+    for c in stripe_cols:
         if c < w:
             p[:, c] = np.where((np.arange(h) + c) % 3 == 0, p[:, c], max_v if c % 2 else 0)
-    for r in FUSED_ROWS:
+    for r in stripe_rows:
         if r < h:
             p[r] = np.where((np.arange(w) + r) % 3 == 0, p[r], max_v if r % 2 else 0)
     p = np.clip(p, 0, max_v)
@@ -619,7 +623,7 @@ def sao_full_range(bit_depth, ctb_log2, rng, *, w=320, h=256, keep_every=6):
     from oracle import h265
     prm = np.zeros((rows, cols), h265.SAO_CTB_DTYPE)
     lims = sao_offset_limits(bit_depth)
-    n_band = n_edge = 0
+    n_band, n_edge = walk_start, 0
     for i in range(rows * cols):
         r_, c_ = divmod(i, cols)
         t = (0, 1, 2, 1, 2)[i % 5]
@@ -630,7 +634,7 @@ def sao_full_range(bit_depth, ctb_log2, rng, *, w=320, h=256, keep_every=6):
         elif t == 2:
             prm["cls"][r_, c_] = n_edge % 4
             n_edge += 1
-        j = i // 5
+        j = i // 5 + walk_start
         if j % 4 == 3:
             mags = [127, 128, 127, 128]
         else:

@@ -179,9 +179,10 @@ def sim(tmp_path_factory):
 PAD_ROWS, PAD_BYTES = 3, 32
 
 
-def run_sim(sim, c, f, qmap, sl, layout, lds_poison, poison):
+def run_sim(sim, c, f, qmap, sl, layout, lds_poison, poison, nox=None):
     """frame f of chain case c through the program: the plane inside a larger array of `poison` (rows above and below, bytes behind
-    every row), the "LDS" array filled with `lds_poison`"""
+    every row), the "LDS" array filled with `lds_poison`; the QP offsets and the tC offset are sp_ref's unless c has its own ("cb", "cr",
+    "tc_div2"); nox: boundary bytes of the caller's own (rows x stride) in place of a layout's"""
     h, w, sb = c["h"], c["w"], c["sb"]
     row = 2 * w * sb
     pitch = row + PAD_BYTES
@@ -192,13 +193,16 @@ def run_sim(sim, c, f, qmap, sl, layout, lds_poison, poison):
     pr = np.ascontiguousarray(c["pairs"], np.int8)
     pcb, pcr = np.ascontiguousarray(c["pcb"][f]), np.ascontiguousarray(c["pcr"][f])
     keep = np.ascontiguousarray(c["keep"][f], np.uint8)
-    nox = np.ascontiguousarray(B.expected_nox(layout), np.uint8) if layout is not None else None
-    head = [w, h, pitch, sb, c["depth"], c["qp"], int(qmap), qm.shape[-1], S.UNIT_LOG2, S.CB_OFF, S.CR_OFF, 0 if sl else 2 * S.TC_DIV2, 0,
+    if nox is None and layout is not None:
+        nox = B.expected_nox(layout)
+    nox = None if nox is None else np.ascontiguousarray(nox, np.uint8)
+    head = [w, h, pitch, sb, c["depth"], c["qp"], int(qmap), qm.shape[-1], S.UNIT_LOG2, c.get("cb", S.CB_OFF), c.get("cr", S.CR_OFF),
+            0 if sl else 2 * c.get("tc_div2", S.TC_DIV2), 0,
             int(sl), pr.shape[1], S.SL_CTB_LOG2, pcb.shape[1], c["lg"], keep.shape[1], 0 if nox is None else nox.shape[1], PAD_ROWS,
             lds_poison, 0, 0]
     blobs = [src, np.ascontiguousarray(vb, np.uint8), np.ascontiguousarray(hb, np.uint8), qm, pr, pcb, pcr, keep, nox]
     keepdir = os.environ.get("FUSED_SP_SIM_KEEP")
-    tag = "%s_f%d_q%d_s%d_l%d_%02x_%02x" % (c["name"], f, qmap, sl, layout is not None, lds_poison, poison)
+    tag = "%s_f%d_q%d_s%d_l%d_%02x_%02x" % (c["name"].replace("/", "_"), f, qmap, sl, nox is not None, lds_poison, poison)
     job, out = os.path.join(keepdir or sim, tag + ".job"), os.path.join(sim, tag + ".out")
     with open(job, "wb") as fh:
         fh.write(struct.pack("<24q", *head))

@@ -49,17 +49,19 @@ def pad_of(c, rest=0):
 
 
 class Operands:
-    """both components' parameters, the keep maps (per frame, tight strides) and the boundary bytes of ONE layout for every frame"""
+    """both components' parameters, the keep maps (per frame, tight strides) and the boundary bytes of ONE layout for every frame;
+    nox: bytes of the caller's own instead, (frames, rows, stride), one array per frame"""
 
-    def __init__(self, ctx, lib, c, frames=None):
+    def __init__(self, ctx, lib, c, frames=None, nox=None):
         frames = range(len(c["pcb"])) if frames is None else frames
         self.rows, self.cols = c["pcb"][0].shape
         self.kr, self.kc = c["keep"][0].shape
         self.pcb, self.pcr = up(ctx, np.stack([c["pcb"][f] for f in frames])), up(ctx, np.stack([c["pcr"][f] for f in frames]))
         self.keep = up(ctx, np.stack([c["keep"][f] for f in frames]))
-        nox = np.ascontiguousarray(B.expected_nox(c["layout"]), np.uint8)
+        per_frame = nox is not None
+        nox = np.ascontiguousarray(np.stack([nox[f] for f in frames]) if per_frame else B.expected_nox(c["layout"]), np.uint8)
         self.nox = up(ctx, nox)
-        self.borders = lib.SaoBorders(self.nox.ptr, nox.shape[1], 0)
+        self.borders = lib.SaoBorders(self.nox.ptr, nox.shape[-1], nox.shape[1] * nox.shape[2] if per_frame else 0)
         self.lg = c["lg"]
 
     def sao(self, L, ctx, p, keep, borders, stream=None, pcb=None, pcr=None):

@@ -147,8 +147,9 @@ def sim(tmp_path_factory):
 PAD_ROWS, PAD_BYTES = 3, 32
 
 
-def run_sim(sim, c, f, keep, layout, form, poison):
-    """the plane inside a larger array of `poison`: rows above and below, bytes behind every row"""
+def run_sim(sim, c, f, keep, layout, form, poison, nox=None):
+    """the plane inside a larger array of `poison`: rows above and below, bytes behind every row; nox: boundary bytes of the
+    caller's own (rows x stride) in place of a layout's"""
     h, w, sb = c["h"], c["w"], c["sb"]
     row = 2 * w * sb
     pitch = row + PAD_BYTES
@@ -157,7 +158,9 @@ def run_sim(sim, c, f, keep, layout, form, poison):
     dst = np.full_like(src, 0x5A)
     pcb, pcr = np.ascontiguousarray(c["pcb"][f]), np.ascontiguousarray(c["pcr"][f])
     k = np.ascontiguousarray(c["keep"][f]) if keep else None
-    nox = np.ascontiguousarray(B.expected_nox(layout), np.uint8) if layout is not None else None
+    if nox is None and layout is not None:
+        nox = B.expected_nox(layout)
+    nox = None if nox is None else np.ascontiguousarray(nox, np.uint8)
     vp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
     rc = sim.sao_sp_sim_plane(C.c_void_p(src.ctypes.data + PAD_ROWS * pitch), C.c_void_p(dst.ctypes.data + PAD_ROWS * pitch), w, h, C.c_long(pitch),
                               sb, c["depth"], vp(pcb), vp(pcr), pcb.shape[1], c["lg"], vp(k), 0 if k is None else k.shape[1], vp(nox),
