@@ -51,6 +51,7 @@ EXPORTS = [
     "hevcdbk_h265_deblock_sao_device_g4", "hevcdbk_h265_deblock_sao_device_planes_g4",
     "hevcdbk_h265_filter_device_sp", "hevcdbk_sao_filter_device_sp", "hevcdbk_h265_deblock_sao_device_sp",
     "hevcdbk_h265_deblock_sao_device_sp_fused", "hevcdbk_h265_deblock_sao_device_nv12",
+    "hevcdbk_sao_stats_device", "hevcdbk_sao_pick_device",
 ]
 
 # chroma_format_idc of the spec-exact mode and SAO (HEVCDBK_CHROMA_*): 4:0:0, 4:2:0, 4:2:2, 4:4:4
@@ -166,6 +167,13 @@ U_KEEP, U_DBK_OFF, U_PRED_L0, U_PRED_L1, U_NOX_LEFT, U_NOX_TOP = 64, 128, 256, 5
 
 
 SAO_CTB_DTYPE = [("type", "u1"), ("cls", "u1"), ("offset", "i1", (4,))]  # numpy dtype of hevcdbk_sao_ctb
+# numpy dtype of hevcdbk_sao_stats: per CTB, counts and sums of (org - rec) per edge bin [class][category - 1] and per band
+SAO_STATS_DTYPE = [("eo_count", "<i4", (4, 4)), ("eo_sum", "<i4", (4, 4)), ("bo_count", "<i4", (32,)), ("bo_sum", "<i4", (32,))]
+
+
+class SaoStats(C.Structure):
+    """hevcdbk_sao_stats: the statistics of one CTB (384 bytes)"""
+    _fields_ = [("eo_count", (C.c_int32 * 4) * 4), ("eo_sum", (C.c_int32 * 4) * 4), ("bo_count", C.c_int32 * 32), ("bo_sum", C.c_int32 * 32)]
 
 
 class DeviceInfo(C.Structure):
@@ -320,6 +328,12 @@ def lib():
         L.hevcdbk_h265_deblock_sao_device_nv12.argtypes = [C.c_void_p, C.POINTER(DevicePlanes), C.POINTER(DevicePlanes), C.c_uint,
                                                            C.POINTER(H265Params), C.POINTER(SaoPlaneCf), C.POINTER(SaoPlaneSp), C.c_int,
                                                            C.POINTER(SaoBorders), C.POINTER(SliceOffsets), C.c_void_p]
+        # SAO parameter estimation: per-CTB statistics, and the parameters picked from them
+        L.hevcdbk_sao_stats_device.argtypes = [C.c_void_p, C.POINTER(DevicePlanes), C.c_void_p, C.c_size_t, C.c_size_t, C.c_uint, C.c_uint,
+                                               C.c_void_p, C.c_uint, C.c_size_t, C.POINTER(SaoBorders), C.c_void_p, C.c_uint, C.c_size_t,
+                                               C.c_void_p]
+        L.hevcdbk_sao_pick_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint, C.c_size_t, C.c_uint, C.c_uint, C.c_uint, C.c_uint,
+                                              C.c_uint, C.c_void_p, C.c_void_p, C.c_uint, C.c_size_t, C.c_void_p, C.c_void_p]
         L.hevc_deblock_sao_h265_device_planes.argtypes = [C.c_void_p, C.POINTER(DevicePlanes), C.c_uint, C.c_uint, C.POINTER(H265Params),
                                                           C.POINTER(SaoPlane), C.c_int, C.c_void_p]
         L.hevcdbk_set_host_threads.argtypes = [C.c_void_p, C.c_uint]

@@ -470,6 +470,30 @@ class Context:
                                                       ctb_log2, lh, keep_ptr, keep_stride, keep_frame_stride, None)
         _chk(rc, self.handle)
 
+    def sao_stats_device(self, planes, org_ptr, ctb_log2, *, org_pitch=None, org_frame_stride=None, ctb_log2_h=None, chroma_format="420",
+                         keep_ptr=None, keep_stride=0, keep_frame_stride=0, borders=None, out_ptr, out_stride, out_frame_stride=0,
+                         stream=None):
+        """hevcdbk_sao_stats_device: per-CTB SAO statistics of the deblocked plane planes.src against the original at org_ptr (device
+        memory, the same geometry and container; pitch and frame stride default to the plane's).  out_ptr: device memory for one
+        _lib.SaoStats (numpy: _lib.SAO_STATS_DTYPE) per CTB, out_stride entries per CTB row, out_frame_stride entries between frames;
+        every entry of the grid is written, nothing needs clearing.  ctb_log2 = log2 of this plane's CTB width; the height follows
+        from chroma_format as for sao_device unless ctb_log2_h says.  keep_ptr, borders: as for sao_device(g4=True)."""
+        cf = _lib.chroma_format_idc(chroma_format)
+        lh = _ctb_log2_h(ctb_log2, ctb_log2_h, cf, planes.is_chroma)
+        _chk(_lib.lib().hevcdbk_sao_stats_device(self.handle, C.byref(planes), org_ptr, planes.pitch if org_pitch is None else org_pitch,
+                                                 planes.frame_stride if org_frame_stride is None else org_frame_stride, ctb_log2, lh,
+                                                 keep_ptr, keep_stride, keep_frame_stride, None if borders is None else C.byref(borders),
+                                                 out_ptr, out_stride, out_frame_stride, stream), self.handle)
+
+    def sao_pick_device(self, stats_ptr, stats_stride, ctbs_x, ctbs_y, bit_depth, lambda_q8, *, out_ptr, out_stride, n_frames=1,
+                        stats_frame_stride=0, out_frame_stride=0, stats_b_ptr=None, out_b_ptr=None, delta_d_ptr=None, stream=None):
+        """hevcdbk_sao_pick_device: one hevcdbk_sao_ctb per CTB (out_ptr, out_stride entries per row) from the statistics at stats_ptr,
+        by the rule of include/hevc_deblock.h with lambda_q8 = lambda * 256.  stats_b_ptr / out_b_ptr: Cr beside Cb -- one type and
+        one edge class for both.  delta_d_ptr: ctbs_x * ctbs_y * n_frames int64, the predicted change of the SSE per CTB."""
+        _chk(_lib.lib().hevcdbk_sao_pick_device(self.handle, stats_ptr, stats_b_ptr, stats_stride, stats_frame_stride, ctbs_x, ctbs_y,
+                                                n_frames, bit_depth, lambda_q8, out_ptr, out_b_ptr, out_stride, out_frame_stride,
+                                                delta_d_ptr, stream), self.handle)
+
     def deblock_sao_device(self, planes, qp, params_ptr, params_stride, ctb_log2, *, params_frame_stride=0, keep_ptr=None,
                            keep_stride=0, keep_frame_stride=0, tc_table=None, beta_table=None, fused=_lib.FUSED_AUTO, stream=None):
         """hevc_deblock_sao_device: reference-exact deblocking followed by SAO, src -> dst, one kernel where it applies.

@@ -863,6 +863,75 @@ HEVCDBK_API int hevcdbk_h265_deblock_sao_device_nv12(hevcdbk_context *ctx, const
                                                      const hevcdbk_sao_plane_sp *sao_pairs, int fused, const hevcdbk_sao_borders *borders,
                                                      const hevcdbk_h265_slice_offsets *slice_offsets, void *hip_stream);
 
+/* ==================================================================================================================
+ * SAO parameter estimation, the producing side of a codec: per-CTB statistics on the GPU and the choice of hevcdbk_sao_ctb from them.
+ *
+ * Every entry above APPLIES SAO parameters; these two PRODUCE them.  The chain is deblocking -> statistics -> pick -> SAO.
+ *
+ * Statistics, per sample of the deblocked plane `rec` against the original `org`:
+ *   - a sample in a kept 8x8 block counts nowhere;
+ *   - any other sample counts in its band bin, bo_*[rec >> (bitDepth - 5)];
+ *   - such a sample counts in eo_*[k][e - 1] iff both neighbours of class k (Table 8-13) are available and its remapped edgeIdx
+ *     (8.7.3.2: 0, 1, 2 -> 1, 2, 0) is e >= 1.  Available = inside the plane and, if in another CTB, not forbidden by the byte of the
+ *     sample's own CTB, exactly as the boundary operand above defines the byte;
+ *   - neighbour values are read whether or not the neighbour is kept, as SAO itself reads them.
+ * So a sample counts in bin (class k, category e) if and only if hevcdbk_sao_filter_device_nox would add offset[e - 1] to it, were its
+ * CTB an edge-offset CTB of class k under the same keep map and borders; likewise for the bands.  For any parameters, with n = count,
+ * s = sum and o = offset, on inputs where the final clip to [0, max] never acts:
+ *     SSE(org, SAO(rec)) - SSE(org, rec) = sum over the bins the parameters use of (n o^2 - 2 o s).
+ * Parity: tests/sao_stats_ref.py, a per-sample statement, and that identity against the SAO statements ("parity unpinned").
+ * ================================================================================================================== */
+typedef struct hevcdbk_sao_stats {   /* one per CTB of THIS plane, 384 bytes, DEVICE memory */
+    int32_t eo_count[4][4];          /* [SaoEoClass 0..3][edgeIdx - 1], edgeIdx 1..4 after the remap */
+    int32_t eo_sum[4][4];            /* sum of (org - rec) over the counted samples */
+    int32_t bo_count[32];            /* [rec >> (bitDepth - 5)] */
+    int32_t bo_sum[32];
+} hevcdbk_sao_stats;
+
+/*
+ * The statistics pass.  Of `rec` the members src (the deblocked plane: SAO's input), pitch, frame_stride, n_frames, plane_w, plane_h,
+ * bit_depth (8..16) and sample_bytes are used; dst and the deblocking operands are not looked at.  `org` (DEVICE): the same geometry
+ * and container with its own pitch and frame stride (bytes; a frame stride of 0 = one original for every frame, as for every operand).
+ * plane_w and plane_h are multiples of 4 and at least 8 (else HEVCDBK_ERR_DIMENSIONS); the CTB grid and the keep map are taken by
+ * ceiling as in the _g4 entries.  ctb_log2_w = 3..6, ctb_log2_h = ctb_log2_w or ctb_log2_w + 1 (4:2:2 chroma), at most 6.  keep and
+ * borders may be NULL.  stats: stats_stride entries per CTB row (at least the CTB columns), stats_frame_stride entries between frames
+ * (at least one grid when n_frames > 1: an output is never shared).  Every hevcdbk_sao_stats of the grid is written exactly once,
+ * zeros included, with plain stores -- the caller clears nothing; entries beyond the CTB columns are not touched.  No global atomics:
+ * the result is bit-reproducible.  All sums are exact in int32 (a 64x64 CTB at 16 bit reaches 4096 * 65535).  Rows that start at a
+ * multiple of four samples in both planes move four samples per load; any other pitch or address that is a multiple of the sample
+ * size runs sample by sample (a misaligned sample: HEVCDBK_ERR_UNSUPPORTED).  Any other bad operand: HEVCDBK_ERR_ARG.  Nothing is
+ * enqueued on refusal.  Asynchronous on hip_stream (NULL = the context's compute stream).
+ */
+HEVCDBK_API int hevcdbk_sao_stats_device(hevcdbk_context *ctx, const hevcdbk_device_planes *rec, const void *org, size_t org_pitch,
+                                         size_t org_frame_stride, unsigned ctb_log2_w, unsigned ctb_log2_h, const uint8_t *keep,
+                                         unsigned keep_stride, size_t keep_frame_stride, const hevcdbk_sao_borders *borders,
+                                         hevcdbk_sao_stats *stats, unsigned stats_stride, size_t stats_frame_stride, void *hip_stream);
+
+/*
+ * From statistics to parameters: the library's own rule, integers only, "parity unpinned" like the rest.
+ * cost = deltaD * 256 + lambda_q8 * bits in int64, lambda_q8 <= 2^24 (else HEVCDBK_ERR_ARG); M = (1 << (Min(bitDepth, 10) - 5)) - 1;
+ * log2OffsetScale is 0.
+ *   - The offset of a bin (n, s): 0 if n = 0; otherwise o0 = sign(s) * ((2|s| + n) / (2n)), clamped to [0, M] for edge categories 1
+ *     and 2, to [-M, 0] for categories 3 and 4 and to [-M, M] for bands; the search walks from o0 towards 0 one step at a time and
+ *     keeps the o with the least (n o^2 - 2 o s) * 256 + lambda * bits(o), on a tie the one nearer 0;
+ *     bits(o) = (|o| < M ? |o| + 1 : M), plus 1 sign bit for a non-zero band offset.
+ *   - The candidates of a CTB, in this order, the lowest cost wins and on a tie the earliest: "not applied" costs lambda * 1; edge class
+ *     0..3 costs lambda * 4 plus its four bins; band position 0..31 costs lambda * 7 plus the four bands (p + k) & 31.
+ *   - stats_b != NULL (Cr beside Cb; params_b is then needed, and refused without it): both components share one type and one edge
+ *     class and have their own offsets and band positions, as 7.3.8.3 demands.  "Not applied" costs lambda * 1; edge class c costs
+ *     lambda * 4 plus both components' bins; band costs lambda * 2 plus, per component, lambda * 5 and its best position (on a tie
+ *     the lowest).
+ *   - delta_d (may be NULL): one int64 per CTB, tight -- [(frame * ctbs_y + cy) * ctbs_x + cx] -- the predicted change of the SSE
+ *     under the choice, both components summed.
+ * Both statistics arrays have one stride and one frame stride (entries), both parameter arrays likewise; params_frame_stride is at
+ * least one grid when n_frames > 1.  ctbs_x, ctbs_y at least 1 (else HEVCDBK_ERR_DIMENSIONS).  One small launch, asynchronous.
+ */
+HEVCDBK_API int hevcdbk_sao_pick_device(hevcdbk_context *ctx, const hevcdbk_sao_stats *stats_a, const hevcdbk_sao_stats *stats_b,
+                                        unsigned stats_stride, size_t stats_frame_stride, unsigned ctbs_x, unsigned ctbs_y,
+                                        unsigned n_frames, unsigned bit_depth, unsigned lambda_q8, hevcdbk_sao_ctb *params_a,
+                                        hevcdbk_sao_ctb *params_b, unsigned params_stride, size_t params_frame_stride, int64_t *delta_d,
+                                        void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif
