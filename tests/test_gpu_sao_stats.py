@@ -31,14 +31,6 @@ def up(ctx, a):
     return d
 
 
-def pitched(frames, pitch):
-    """(n, h, w) samples -> (n, h, pitch) with 0x5A.. in the row padding"""
-    frames = np.asarray(frames)
-    out = np.full(frames.shape[:2] + (pitch,), 0x5A5A & (0xFF if frames.itemsize == 1 else 0xFFFF), frames.dtype)
-    out[:, :, : frames.shape[2]] = frames
-    return out
-
-
 def dev_planes(buf, n, w, h, depth, sb, pitch, dst=None):
     from gpu_video_codec_amd import _lib
     p = _lib.DevicePlanes()
@@ -47,18 +39,35 @@ def dev_planes(buf, n, w, h, depth, sb, pitch, dst=None):
     return p
 
 
-def gpu_stats(ctx, recs, orgs, bd, lw, lh, *, keeps=None, noxs=None, pitch=None, tight=False):
-    """recs (n, h, w); orgs, keeps, noxs: (n, ...) = per frame, (1, ...) = shared, None = absent.  Returns (n, rows, cols) statistics
-    after comparing every other int32 of the output buffer with the sentinel and the sources with what was uploaded"""
+def laid_out(frames, pitch, gap, off):
+    """(n, h, w) samples -> one run of memory in which row y of frame f starts at sample off + f * (h * pitch + gap) + y * pitch;
+    0x5A.. everywhere else, the row padding included"""
+    frames = np.asarray(frames)
+    n, h, w = frames.shape
+    out = np.full(off + (n - 1) * (h * pitch + gap) + h * pitch, 0x5A5A & (0xFF if frames.itemsize == 1 else 0xFFFF), frames.dtype)
+    for f in range(n):
+        at = off + f * (h * pitch + gap)
+        out[at: at + h * pitch].reshape(h, pitch)[:, :w] = frames[f]
+    return out
+
+
+def gpu_stats(ctx, recs, orgs, bd, lw, lh, *, keeps=None, noxs=None, pitch=None, tight=False, org_pitch=None, rec_off=0, org_off=0, rec_gap=0,
+              org_gap=0):
+    """recs (n, h, w); orgs, keeps, noxs: (n, ...) = per frame, (1, ...) = shared, None = absent; the stride of keeps and noxs is
+    their last dimension, their frame stride their last two (columns and rows beyond the map's or the grid's: padding the entry
+    must not read).  pitch, org_pitch (default: pitch), rec_off / org_off (how far the plane's first sample lies behind the start of
+    its allocation) and rec_gap / org_gap (what a frame stride has beyond the rows of a frame) are in samples.  Returns (n, rows,
+    cols) statistics after comparing every other int32 of the output buffer with the sentinel and the sources with what was uploaded"""
     from gpu_video_codec_amd import _lib
     recs = np.asarray(recs)
     n, h, w = recs.shape
     sb = recs.itemsize
     pitch = w if pitch is None else pitch
+    org_pitch = pitch if org_pitch is None else org_pitch
     rows, cols = S.grid(w, h, lw, lh)
     stride, guard = (cols, 0) if tight else (cols + PAD, GUARD)
     fstride = rows * stride + (0 if tight else GAP)
-    hrec, horg = pitched(recs, pitch), pitched(orgs, pitch)
+    hrec, horg = laid_out(recs, pitch, rec_gap, rec_off), laid_out(orgs, org_pitch, org_gap, org_off)
     drec, dorg = up(ctx, hrec), up(ctx, horg)
     bufs = [drec, dorg]
     total = 2 * guard + fstride * n
@@ -76,7 +85,9 @@ def gpu_stats(ctx, recs, orgs, bd, lw, lh, *, keeps=None, noxs=None, pitch=None,
         bufs.append(dn)
         kw.update(borders=_lib.SaoBorders(dn.ptr, noxs.shape[2], 0 if noxs.shape[0] == 1 else noxs.shape[1] * noxs.shape[2]))
     p = dev_planes(drec, n, w, h, bd, sb, pitch)
-    ctx.sao_stats_device(p, dorg.ptr, lw, ctb_log2_h=lh, org_pitch=pitch * sb, org_frame_stride=0 if horg.shape[0] == 1 else pitch * sb * h,
+    p.src, p.frame_stride = drec.ptr + rec_off * sb, (pitch * h + rec_gap) * sb
+    ctx.sao_stats_device(p, dorg.ptr + org_off * sb, lw, ctb_log2_h=lh, org_pitch=org_pitch * sb,
+                         org_frame_stride=0 if np.asarray(orgs).shape[0] == 1 else (org_pitch * h + org_gap) * sb,
                          out_ptr=dout.ptr + guard * 384, out_stride=stride, out_frame_stride=fstride, **kw)
     ctx.synchronize()
     raw = dout.download(total * 384).view(np.uint32).reshape(total, 96)
@@ -171,17 +182,29 @@ def test_batch_is_three_single_frame_calls(ctx, shared, tight):
     assert got[0].tobytes() != got[1].tobytes()
 
 
-def gpu_pick(ctx, st_a, st_b, bd, lam):
-    """(params_a, params_b, delta_d) of (n, rows, cols) statistics, the parameter rows padded and guarded"""
+def poisoned(st, pad, gap):
+    """(n, rows, cols) statistics -> the same read through a stride of cols + pad and a frame stride with gap entries more; every
+    int32 of the padding is the sentinel: statistics that would change any choice they entered"""
+    n, rows, cols = st.shape
+    out = np.full((n, rows * (cols + pad) + gap, 96), SENTINEL, np.uint32)
+    for f in range(n):
+        out[f, : rows * (cols + pad)].reshape(rows, cols + pad, 96)[:, :cols] = np.ascontiguousarray(st[f]).view(np.uint32).reshape(rows, cols, 96)
+    return out
+
+
+def gpu_pick(ctx, st_a, st_b, bd, lam, *, stats_pad=0, stats_gap=0):
+    """(params_a, params_b, delta_d) of (n, rows, cols) statistics, the parameter rows padded and guarded; stats_pad, stats_gap: the
+    statistics too lie behind a padded stride and frame stride (poisoned())"""
     n, rows, cols = st_a.shape
     stride = cols + PAD
     fstride = rows * stride + GAP
     total = 2 * GUARD + fstride * n
-    da = up(ctx, st_a)
-    db = None if st_b is None else up(ctx, st_b)
+    da = up(ctx, poisoned(st_a, stats_pad, stats_gap))
+    db = None if st_b is None else up(ctx, poisoned(st_b, stats_pad, stats_gap))
     outs = [up(ctx, np.full(total * 6, 0xA5, np.uint8)) for _ in range(1 if st_b is None else 2)]
     dd = up(ctx, np.full(n * rows * cols + 2, -7, np.int64))
-    ctx.sao_pick_device(da.ptr, cols, cols, rows, bd, lam, out_ptr=outs[0].ptr + GUARD * 6, out_stride=stride, n_frames=n, stats_frame_stride=rows * cols,
+    ctx.sao_pick_device(da.ptr, cols + stats_pad, cols, rows, bd, lam, out_ptr=outs[0].ptr + GUARD * 6, out_stride=stride, n_frames=n,
+                        stats_frame_stride=rows * (cols + stats_pad) + stats_gap,
                         out_frame_stride=fstride, stats_b_ptr=None if db is None else db.ptr,
                         out_b_ptr=None if db is None else outs[1].ptr + GUARD * 6, delta_d_ptr=dd.ptr + 8)
     ctx.synchronize()
