@@ -2,6 +2,7 @@
 every cell of every frame, the coverage of kernel families x operands x states (from the dispatch restatement, not by hand), the
 generator's own invariants, and a numpy restatement of the two 4:2:2 rewrites tied to tests/sao_borders_ref.py."""
 import collections
+import dataclasses
 import itertools
 
 import numpy as np
@@ -9,6 +10,7 @@ import pytest
 
 import batch_vectors as bv
 import dispatch_cases as dc
+import g4_ref as G
 import rext_oracle as rx
 import sao_borders_ref as R
 
@@ -23,9 +25,15 @@ def test_census(name):
     c = BY_NAME[name]
     bad, exp, wrong = bv.census(c, bv.make_operands(c, bv.seed_of(c)))
     assert not bad, (name, [(x, i, f, g, cells[:3]) for x, i, f, g, cells in bad][:6])
-    per_frame = [x for x in bv.OPERANDS if c.state(x) in bv.PER_FRAME]
-    want = c.n_planes * len(per_frame) * c.n * (c.n - 1) + c.n_planes * (c.n - 1) * sum(c.state(x) == "padded" for x in per_frame)
-    assert len(wrong) == want and len(exp) == c.n_planes * c.n, (name, len(wrong), want)
+    # every plane reads every operand in the state that plane has it in; a plane of pairs adds one reading per frame (Cb <-> Cr)
+    want = 0
+    for i in range(c.n_planes):
+        per_frame = [x for x in bv.OPERANDS if c.state(x, i) in bv.PER_FRAME]
+        want += len(per_frame) * c.n * (c.n - 1) + (c.n - 1) * sum(c.state(x, i) == "padded" for x in per_frame)
+        want += c.n * (c.pair(i) and c.has_sao())
+    assert len(wrong) == want == bv.census_readings(c) and len(exp) == c.n_planes * c.n, (name, len(wrong), want)
+    for i in range(c.n_planes):   # a plane of pairs is compared per component: cells of Cb and cells of Cr
+        assert exp[i, 0].shape == ((c.geom(i)[1], c.geom(i)[0], 2) if c.pair(i) else (c.geom(i)[1], c.geom(i)[0]))
 
 
 def _table():
@@ -146,14 +154,16 @@ def test_padded_gaps_hold_poison_and_odd_strides_occur():
     for c in CASES:
         ops = bv.make_operands(c, bv.seed_of(c))
         for x in bv.OPERANDS:
-            if c.state(x) != "padded":
-                continue
-            for i in range(1 if x in ("map", "borders") else c.n_planes):
-                for which in ((0, 1) if x == "bs" else (0,)):
+            for i in range(1 if x in ("borders", "sl") or (x == "map" and c.planes != "NV") else c.n_planes):
+                if c.state(x, i) != "padded":
+                    continue
+                for which in ((0, 1) if x == "bs" or (x == "params" and c.pair(i)) else (0,)):
                     arrs = bv.operand_arrays(c, ops, x, i, which)
                     buf, stride = bv.lay_out(arrs, "padded", bv.poison_entry(x, c.bd), bv.operand_dtype(x))
                     size = np.asarray(arrs[0]).size
                     assert stride > size and buf.size == stride * c.n
+                    if x == "sl":   # 16-bit words: the stride in bytes is even whatever the stride in words; the gap holds SL_POISON
+                        assert buf.dtype == np.uint16 and buf[size:stride].view(np.int8).reshape(-1, 2).tolist() == [list(bv.SL_POISON)] * (stride - size)
                     odd += (x == "map" and stride % 2 == 1)
                     for f in range(c.n):
                         assert np.array_equal(buf[f * stride:f * stride + size], np.ascontiguousarray(arrs[f], bv.operand_dtype(x)).ravel())
@@ -245,3 +255,172 @@ def test_giant_3d_family_and_census(name):
 
 def test_giant_3d_states():
     assert {g.state for g in bv.giants()} == {"tight", "padded"}
+
+
+# ---- the _sl, _g4, _sp and NV12 families ---------------------------------------------------------------------------------------------
+
+NEW = [c for c in CASES if c.fam]
+LISTED = {"sl": set(bv.K_SL.values()), "g4": set(bv.K_G4.values()), "sp": set(bv.K_SP.values())}
+TAKES = {"dbk": ("map", "bs", "sl"), "sao": ("params", "keep", "borders")}
+
+
+def _operands_of(kernel):
+    return (TAKES["dbk"] if kernel.startswith("dbk") else ()) + (TAKES["sao"] if "sao" in kernel else ())
+
+
+def test_new_families_see_every_operand_in_every_state():
+    """every kernel of the three lists is some case's, and reads each operand it takes shared, tight and padded (from the cases'
+    own kernel lists, which the GPU test holds against the stream capture)"""
+    t = collections.Counter(k for c in NEW for k in bv.attribution(c))
+    missing = [(k, x, s) for fam in LISTED.values() for k in sorted(fam) for x in _operands_of(k) for s in bv.THREE if not t[k, x, s]]
+    # the _sl deblocking kernels take sl tight here: sl alone, in every state, is test_gpu_slice_offsets.py's
+    missing = [m for m in missing if not (m[0] in (bv.K_SL["g"], bv.K_SL[8], bv.K_SL[16]) and m[1] == "sl" and m[2] != "tight")]
+    assert not missing, missing
+    for c in NEW:
+        assert set(c.kernels) <= set().union(*LISTED.values()), c.name
+        assert all(s in bv.THREE + ("far",) for s in bv.all_states(c)), c.name
+
+
+def test_new_families_shapes_frame_counts_and_combinations():
+    by = collections.defaultdict(list)
+    for c in NEW:
+        for k in c.kernels:
+            by[k].append(c)
+    assert {1, 2, 3, 5, 7} <= {c.n for c in NEW}
+    for k in (bv.K_SL["f8"], bv.K_SL["f16"], bv.K_SL["multi"], bv.K_G4["f8"], bv.K_G4["f16"], bv.K_G4["multi"], bv.K_SP["f8"], bv.K_SP["f16"],
+              bv.K_SP["multi"]):
+        assert any(c.n == 5 and any(s in bv.PER_FRAME for s in bv.all_states(c)) for c in by[k]), ("a five-frame case", k)
+    # the fused grids are whole multiples of 8 workgroups: the tiles of the three- and five-frame cases, counted from the plane and
+    # the kernels' tile sizes (pairs 96 / 64 x 128, luma 192 / 128 x 128; the NV12 kernel rounds its luma part and its pair part each)
+    def tiles(c, i):
+        pw, ph = c.geom(i)[:2]
+        tw = {1: 96, 2: 64}[c.sb] if c.pair(i) else dc.FUSED_TILE[c.sb][0]
+        return -(-pw // tw) * -(-ph // 128)
+    seen = collections.Counter()
+    for c in NEW:
+        if c.planes in ("P", "NV") and c.has_deblock() and c.has_sao() and any("fused" in k for k in c.kernels):
+            per_frame = [tiles(c, i) for i in range(c.n_planes)]
+            assert per_frame == ([6, 4] if c.planes == "NV" else [4]), (c.name, per_frame)
+            if c.n in (3, 5):
+                assert all((t * c.n) % 8 != 0 for t in per_frame), (c.name, per_frame)   # padding workgroups exist in every part
+                seen[c.kernels, c.n] += 1
+    for k in (bv.K_SP["f8"], bv.K_SP["f16"], bv.K_SP["multi"]):
+        assert seen[(k,), 3] and seen[(k,), 5], k
+    for k in (bv.K_SL["f8"], bv.K_G4["f8"], bv.K_SP["f8"], bv.K_SP["f16"]):   # five frames with keep map and borders padded
+        assert any(c.n == 5 and c.state("keep") == c.state("borders") == "padded" for c in by[k]), k
+    for k, entry, with_sl in ((bv.K_SL["f8"], "dbk_sao_sl", True), (bv.K_G4["sao8"], "sao_g4", False), (bv.K_SP["sao8"], "sao_sp", False)):
+        for combo in itertools.product(bv.THREE, repeat=3):
+            assert [c for c in by[k] if c.entry == entry and (c.state("params"), c.state("keep"), c.state("borders")) == combo and
+                    (not with_sl or c.state("sl") == "padded")], (k, combo)
+    # planes: pairs 100 x 132, NV12 luma 200 x 264, planar g4 chroma 100 x 132, _sl in multiples of 8; SAO CTBs of 8 on the pair plane
+    for c in NEW:
+        if c.fam in ("sp", "nv12"):
+            i = c.n_planes - 1
+            assert c.pair(i) and c.geom(i) == (100, 132, 3, 3) and c.pitch(i) >= 200 * c.sb and c.offs[2] != c.offs[3], c.name
+        if c.fam == "nv12":
+            assert c.geom(0) == (200, 264, 4, 4) and c.st1 is not None and not c.pair(0)
+        if c.fam == "g4":
+            assert G.is_g4(*c.geom(c.n_planes - 1)[:2]) and (c.linear or c.geom(c.n_planes - 1)[:2] == (100, 264 if c.cf == 2 else 132)), c.name
+        if c.fam == "sl":
+            assert all(c.geom(i)[0] % 8 == 0 and c.geom(i)[1] % 8 == 0 for i in range(c.n_planes)), c.name
+        if c.fam != "nv12" or c.name != "nv12_plane_by_plane":
+            assert all(c.pitch(i) % 32 == 0 and c.frame_stride(i) % 32 == 0 for i in range(c.n_planes)), c.name
+    # the row-major block map of the packed _sl / _g4 kernels: rows of more blocks than a workgroup holds, a grid with padding
+    lin = [c for c in NEW if c.linear]
+    assert {c.kernels for c in lin} == {(bv.K_SL[8],), (bv.K_SL[16],), (bv.K_G4[8],), (bv.K_G4[16],)}
+    for c in lin:
+        pw, ph = c.geom(0)[:2]
+        nbx, nby = pw // 8 + 1, ph // 8 + 1
+        wpf = -(-nbx * nby // dc.WG_CAP)
+        assert nbx > dc.WG_CAP and wpf >= 2 and (wpf * c.n) % 8 != 0 and (pw, ph) == ((4100, 20) if c.fam == "g4" else (4096, 16)), c.name
+    nv = [c for c in NEW if c.fam == "nv12"]
+    assert {c.bd for c in nv} == {8, 10} and {3, 5} <= {c.n for c in nv}
+    for c in nv:   # the two operand sets in different states; the three picture operands in every state over the list
+        if c.name not in ("nv12_pair_only", "nv12_luma_only"):
+            assert sum(c.state(x, 0) != c.state(x, 1) for x in bv.PLANE_OPERANDS) >= 2, c.name
+    for x in ("sl", "borders"):
+        assert {c.state(x) for c in nv} >= set(bv.THREE), x
+    only = {c.name: ([c.state(x, 0) in bv.PER_FRAME for x in bv.PLANE_OPERANDS], [c.state(x, 1) in bv.PER_FRAME for x in bv.PLANE_OPERANDS]) for c in nv}
+    assert only["nv12_pair_only"] == ([False] * 4, [True] * 4) and only["nv12_luma_only"] == ([True] * 4, [False] * 4)
+    assert any(c.fused == dc.FUSED_AUTO and len(c.kernels) == 3 and c.pitch(1) % 16 for c in nv), "the plane-by-plane fallback"
+    assert bv.FAR_STRIDE_SL % 2 == 0 and 2 * bv.FAR_STRIDE_SL >= 1 << 32
+    far = {(x, c.far_which, c.kernels) for c in NEW for x in bv.OPERANDS if c.state(x) == "far"}
+    both = [(bv.K_SP[8],), (bv.K_SP["f8"],)]   # map, vert bS and hor bS through the packed and the fused pair kernel, sl through the fused one
+    assert far == {(x, w, k) for x, w in (("map", ""), ("bs", "vert"), ("bs", "hor")) for k in both} | {("sl", "", (bv.K_SP["f8"],))}, far
+
+
+def test_slice_offsets_tell_the_frames_apart_by_tc_alone():
+    """chroma deblocking ignores beta: frame f's tC offsets occur in no other frame's array, and the poison's in none"""
+    seen = 0
+    for c in NEW:
+        if c.state("sl") not in bv.PER_FRAME:
+            continue
+        ops = bv.make_operands(c, bv.seed_of(c))
+        tcs = [set(np.unique(a[..., 1]).tolist()) for a in ops["sl"]]
+        assert all(a.shape == c.sl_grid() + (2,) and a.dtype == np.int8 for a in ops["sl"]), c.name
+        for f, g in itertools.combinations(range(c.n), 2):
+            assert not tcs[f] & tcs[g], (c.name, f, g)
+            assert (ops["sl"][f][..., 1] != ops["sl"][g][..., 1]).all()
+        assert all(bv.SL_POISON[1] not in t and len(t) == 2 for t in tcs), c.name
+        seen += 1
+    assert seen >= 20
+
+
+def test_pair_parameters_are_two_contents_behind_one_stride():
+    for c in NEW:
+        for i in range(c.n_planes):
+            if c.pair(i) and c.has_sao():
+                ops = bv.make_operands(c, bv.seed_of(c))
+                cb, cr = bv.operand_arrays(c, ops, "params", i, 0), bv.operand_arrays(c, ops, "params", i, 1)
+                st = c.state("params", i) if c.state("params", i) != "far" else "tight"
+                a, b = (bv.lay_out(x, st, bv.poison_entry("params", c.bd), bv.SAO_DT) for x in (cb, cr))
+                assert a[1] == b[1] and a[0].shape == b[0].shape and (a[0] != b[0]).any(), c.name
+                break
+
+
+def test_pair_chain_is_the_feature_tests_expectation(monkeypatch):
+    """the chain of this module on the vector of test_gpu_fused_sp.py = sao_sp_ref.chain_expected: sp_ref.dbk_expected, then
+    sao_sp_ref.sao, with the per-slice pairs and the layout"""
+    import sao_sp_ref as P
+    import sp_ref as S
+    v = P.chain_case(P.spec_of("140x132"))
+    monkeypatch.setattr(bv, "QP", S.QP)
+    c = bv.Case("tie", "dbk_sao_sp_fused", "h265", "P", 2 * v["w"], 2 * v["h"], fam="sp", n=2, unit_log2=S.UNIT_LOG2, ctb_log2=v["lg"] + 1,
+                offs=(S.TC_DIV2, 0, S.CB_OFF, S.CR_OFF))
+    for f in range(2):
+        for sl in (False, True):
+            dbk, want = P.chain_expected(v, f, sl, v["layout"])
+            got = bv.oracle_frame(c, 0, v["planes"][f], qmap=v["qp_map"], bs=v["bs"][f], sl=v["pairs"] if sl else None,
+                                  params=(v["pcb"][f], v["pcr"][f]), keep=v["keep"][f], layout=v["layout"])
+            assert np.array_equal(got, want) and (want != dbk).any() and (dbk != v["planes"][f]).any(), (f, sl)
+        d = dataclasses.replace(c, entry="filter_sp")
+        assert np.array_equal(bv.oracle_frame(d, 0, v["planes"][f], qmap=v["qp_map"], bs=v["bs"][f], sl=v["pairs"]), S.dbk_expected(v, f, True, True))
+
+
+def test_g4_chain_is_the_feature_tests_expectation(monkeypatch):
+    """likewise on a vector of test_gpu_g4.py: g4_ref.dbk_expected (direct and per slice), then g4_ref.sao_direct"""
+    spec = next(s for s in G.TILES8 if s[0] == "196x132")
+    v, s_ = G.dbk_case(spec, frames=2), G.sao_case(spec, frames=2)
+    monkeypatch.setattr(bv, "QP", G.QP)
+    c = bv.Case("tie", "dbk_sao_g4", "h265", "C", 2 * v["w"], 2 * v["h"], fam="g4", n=2, unit_log2=G.UNIT_LOG2, ctb_log2=s_["lw"] + 1,
+                offs=(G.TC_DIV2, 0, G.CQP, G.CQP))
+    lay = G.sao_layout(s_, 0)
+    for f in range(2):
+        for sl in (False, True):
+            mid = G.dbk_expected(v, f, sl)
+            want = G.sao_direct(mid, s_["params"][f], s_["lw"], s_["lh"], bit_depth=v["depth"], keep=s_["keep"][f], layout=lay)
+            got = bv.oracle_frame(c, 0, v["planes"][f], qmap=v["qp_map"], bs=v["bs"][f], sl=v["pairs"] if sl else None, params=s_["params"][f],
+                                  keep=s_["keep"][f], layout=lay)
+            assert np.array_equal(got, want) and (mid != v["planes"][f]).any() and (want != mid).any(), (f, sl)
+
+
+def test_luma_sl_chain_is_the_slice_offset_statement():
+    """the _sl luma cases: slice_offsets_ref.expected, then sao_borders_ref.sao_plane, composed by hand on the case's own operands"""
+    import slice_offsets_ref as SR
+    c = BY_NAME["sl_fused8_n2_shared_tight"]
+    ops = bv.make_operands(c, bv.seed_of(c))
+    for f in range(c.n):
+        mid = SR.expected(ops["frames"][0][f], *ops["bs"][0][f], ops["sl"][f], bv.SL_LOG2, qp=bv.QP, c_idx=0, qp_map=ops["map"][f],
+                          unit_log2=c.unit_log2, bit_depth=8)
+        want = R.sao_plane(mid, ops["params"][0][f], 4, 4, ops["borders"][f], keep=ops["keep"][0][f])
+        assert np.array_equal(bv.expected(c, ops, 0, f), want) and (mid != ops["frames"][0][f]).any() and (want != mid).any()
