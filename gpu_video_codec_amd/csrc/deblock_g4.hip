@@ -15,6 +15,7 @@
 
 #include "deblock_h265_quad4.h"
 #include "deblock_sl_dev.h"
+#include "launch_select.h"
 
 namespace {
 
@@ -84,23 +85,17 @@ __global__ __launch_bounds__(256) void dbk_h265_g4_kernel(const DbkH265Args h, c
     }
 }
 
-template <typename T>
-void launch_g4_t(const DbkH265Args &h, const DbkSlOffs &sl, int cf, dim3 grid, dim3 block, hipStream_t stream)
-{
-    if (cf == 1) hipLaunchKernelGGL((dbk_h265_g4_kernel<T, 1>), grid, block, 0, stream, h, sl);
-    else if (cf == 2) hipLaunchKernelGGL((dbk_h265_g4_kernel<T, 2>), grid, block, 0, stream, h, sl);
-    else hipLaunchKernelGGL((dbk_h265_g4_kernel<T, 3>), grid, block, 0, stream, h, sl);
-}
-
 } /* namespace */
 
 hipError_t dbk_launch_h265_g4(const DbkH265Args &h, const DbkSlOffs &sl, int sample_bytes, int chroma_format, hipStream_t stream)
 {
-    if (chroma_format < 1 || chroma_format > 3) return hipErrorInvalidValue;
-    if (h.base.n_frames <= 0 || h.base.nbx <= 0 || h.base.nby <= 0) return hipSuccess;
-    const dim3 block(64, 4, 1);
-    const dim3 grid((h.base.nbx + 63) / 64, (h.base.nby + 3) / 4, h.base.n_frames);
-    if (sample_bytes == 1) launch_g4_t<uint8_t>(h, sl, chroma_format, grid, block, stream);
-    else launch_g4_t<uint16_t>(h, sl, chroma_format, grid, block, stream);
+    using namespace dbksel;
+    if (!chroma_format_ok(chroma_format)) return hipErrorInvalidValue;
+    if (nothing_to_do(h.base)) return hipSuccess;
+    with_int<1, 2>(sample_bytes, [&](auto SB) {
+        with_int<1, 2, 3>(chroma_format, [&](auto CF) {
+            hipLaunchKernelGGL((dbk_h265_g4_kernel<sample_t<SB>, CF>), generic_grid(h.base), generic_block(), 0, stream, h, sl);
+        });
+    });
     return hipGetLastError();
 }

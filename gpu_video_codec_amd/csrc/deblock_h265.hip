@@ -11,6 +11,7 @@
 #include "deblock_h265.h"
 #include "deblock_h265_quad4.h"
 #include "deblock_kernels.h"
+#include "launch_select.h"
 
 namespace {
 
@@ -189,22 +190,18 @@ __global__ __launch_bounds__(256) void dbk_h265_chroma_bs_cf_kernel(const uint8_
     }
 }
 
-template <typename T, bool CHROMA>
-hipError_t launch_t(const DbkH265Args &h, hipStream_t stream)
-{
-    dim3 block(64, 4, 1);
-    dim3 grid((h.base.nbx + 63) / 64, (h.base.nby + 3) / 4, h.base.n_frames);
-    hipLaunchKernelGGL((dbk_h265_kernel<T, CHROMA>), grid, block, 0, stream, h);
-    return hipGetLastError();
-}
-
 } /* namespace */
 
 hipError_t dbk_launch_h265(const DbkH265Args &h, int sample_bytes, bool chroma, hipStream_t stream)
 {
-    if (h.base.n_frames <= 0 || h.base.nbx <= 0 || h.base.nby <= 0) return hipSuccess;
-    if (sample_bytes == 1) return chroma ? launch_t<uint8_t, true>(h, stream) : launch_t<uint8_t, false>(h, stream);
-    return chroma ? launch_t<uint16_t, true>(h, stream) : launch_t<uint16_t, false>(h, stream);
+    using namespace dbksel;
+    if (nothing_to_do(h.base)) return hipSuccess;
+    with_int<1, 2>(sample_bytes, [&](auto SB) {
+        with_bool(chroma, [&](auto CHROMA) {
+            hipLaunchKernelGGL((dbk_h265_kernel<sample_t<SB>, CHROMA>), generic_grid(h.base), generic_block(), 0, stream, h);
+        });
+    });
+    return hipGetLastError();
 }
 
 hipError_t dbk_launch_h265_bs(const void *flags, const void *mv0, const void *mv1, const void *ref0, const void *ref1, int w,
@@ -233,18 +230,15 @@ hipError_t dbk_launch_h265_chroma_bs(const uint8_t *vert, const uint8_t *hor, in
 
 hipError_t dbk_launch_h265_cf(const DbkH265Args &h, int sample_bytes, int chroma_format, hipStream_t stream)
 {
+    using namespace dbksel;
     if (chroma_format == 1) return dbk_launch_h265(h, sample_bytes, true, stream);
-    if (chroma_format != 2 && chroma_format != 3) return hipErrorInvalidValue;
-    if (h.base.n_frames <= 0 || h.base.nbx <= 0 || h.base.nby <= 0) return hipSuccess;
-    dim3 block(64, 4, 1);
-    dim3 grid((h.base.nbx + 63) / 64, (h.base.nby + 3) / 4, h.base.n_frames);
-    if (sample_bytes == 1) {
-        if (chroma_format == 2) hipLaunchKernelGGL((dbk_h265_cf_kernel<uint8_t, 2>), grid, block, 0, stream, h);
-        else hipLaunchKernelGGL((dbk_h265_cf_kernel<uint8_t, 3>), grid, block, 0, stream, h);
-    } else {
-        if (chroma_format == 2) hipLaunchKernelGGL((dbk_h265_cf_kernel<uint16_t, 2>), grid, block, 0, stream, h);
-        else hipLaunchKernelGGL((dbk_h265_cf_kernel<uint16_t, 3>), grid, block, 0, stream, h);
-    }
+    if (!chroma_format_ok(chroma_format)) return hipErrorInvalidValue;
+    if (nothing_to_do(h.base)) return hipSuccess;
+    with_int<1, 2>(sample_bytes, [&](auto SB) {
+        with_int<2, 3>(chroma_format, [&](auto CF) {
+            hipLaunchKernelGGL((dbk_h265_cf_kernel<sample_t<SB>, CF>), generic_grid(h.base), generic_block(), 0, stream, h);
+        });
+    });
     return hipGetLastError();
 }
 
@@ -252,7 +246,7 @@ hipError_t dbk_launch_h265_chroma_bs_cf(const uint8_t *vert, const uint8_t *hor,
                                         uint8_t *chor, hipStream_t stream)
 {
     if (chroma_format == 1) return dbk_launch_h265_chroma_bs(vert, hor, w, h, cvert, chor, stream);
-    if (chroma_format != 2 && chroma_format != 3) return hipErrorInvalidValue;
+    if (!dbksel::chroma_format_ok(chroma_format)) return hipErrorInvalidValue;
     const int cw = chroma_format == 3 ? w : w / 2, ch = h;
     const long long nv = (long long)(cw / 8 + 1) * (ch / 4), nh = (long long)(ch / 8 + 1) * (cw / 4);
     const long long n = nv > nh ? nv : nh;

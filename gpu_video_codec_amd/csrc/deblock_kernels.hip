@@ -27,6 +27,7 @@
 #include "deblock_packed16.h"
 #include "sao_packed.h"
 #include "deblock_sao_sp_fused.h"
+#include "launch_select.h"
 
 /*
  * Every launch goes through hipExtLaunchKernelGGL so that a caller can ask for the NEXT launch to stamp its own start and
@@ -1155,49 +1156,128 @@ static int wg_cap() { return g_dbk_diag.wg_cap; }
 static constexpr int wg_cap() { return 512; }
 #endif
 
-template <bool NT, bool LINEAR>
-static void launch_packed_t(const DbkArgs &a, int sample_bytes, bool chroma, int mode, dim3 grid, dim3 block, hipStream_t stream)
+/* ---- kernel selection (launch_select.h) ----
+ * The kernels of a family exist in generations.  Each generation has names of its own, so that the older kernels kept their machine
+ * code; it adds arguments and a template parameter, and it may drop a distinction that its kernels make at run time.  All of that is
+ * said here, once: fold_operands folds the run-time operands as the generation asks, kernel_exists is the table of template
+ * arguments a kernel was written for, and launch_packed_sel, launch_fused and launch_fused_multi name every kernel template once.  A new
+ * generation is one more enumerator with its line in fold_operands and kernel_exists and its branch in those three. */
+
+enum class Gen {
+    kRef,  /* reference-exact mode (DbkArgs): 4:2:0 only */
+    kH265, /* spec-exact mode (DbkH265Args, one-QP scalars); chroma with a QP map in 4:2:2 / 4:4:4 takes the _cf kernels */
+    kNox,  /* kH265 + the boundary bytes nx: the fused kernels' _nox twins */
+    kSl,   /* + per-slice offsets sl (the _sl twins): every format, with or without a QP map / boundary bytes in one kernel */
+    kG4,   /* kSl for chroma planes whose sizes are multiples of 4 (the _g4 twins) */
+};
+template <Gen G> using PlaneArgs = std::conditional_t<G == Gen::kRef, DbkArgs, DbkH265Args>;
+static const DbkArgs &base_of(const DbkArgs &a) { return a; }
+static const DbkArgs &base_of(const DbkH265Args &h) { return h.base; }
+
+/* template arguments of a kernel.  plane: a one-plane kernel's plane, 0 = luma, 1..3 = chroma of a picture of that chroma_format_idc;
+ * a multi-plane kernel's picture format */
+struct KernelSel {
+    int sb, plane;
+    bool wide, qm;
+};
+static KernelSel fold_operands(Gen g, bool multi, int sb, bool chroma, int chroma_format, const DbkArgs &a /* multi: the luma plane */)
 {
     const bool qm = a.qp_map != nullptr;
+    const bool own = g == Gen::kSl || g == Gen::kG4; /* kernels with every format as a template argument and no QPMAP one */
+    KernelSel k;
+    k.sb = sb;
+    k.qm = !own && qm; /* the _sl / _g4 kernels look at base.qp_map themselves: one kernel with a map and without */
+    /* the format as a template argument: _sl / _g4 always; kH265 / kNox only with a QP map (the _cf kernels, the _nox kernels' CF) --
+     * with one QP the format enters through QpC in the scalar tc alone (h265_one_qp_scalars) and 4:2:2 chroma CTBs arrive as square
+     * ones (dbk_launch_sao_rows_x2), so the 4:2:0 kernels run; kRef is 4:2:0 */
+    const int format = own || (g != Gen::kRef && qm) ? chroma_format : 1;
+    k.plane = multi || chroma ? format : 0; /* luma of a one-plane launch: 0 whatever the picture's format */
+    k.wide = sb == 2 && (multi || !chroma) && a.max_v > 2047; /* 12-bit luma: the WIDE variant of the core (deblock_packed.h) */
+    return k;
+}
+constexpr bool kernel_exists(Gen g, bool multi, int sb, int plane, bool wide, bool qm)
+{
+    const bool own = g == Gen::kSl || g == Gen::kG4;
+    /* no multi-plane kernel is "luma" (plane is the picture's format there), and the one-plane _g4 kernels are chroma's */
+    if (plane == 0 && (multi || g == Gen::kG4)) return false;
+    /* WIDE: 16-bit containers only; of the one-plane kernels luma's, of the multi-plane ones every format's (the luma plane is in it) */
+    if (wide && (sb == 1 || (!multi && plane != 0))) return false;
+    /* _sl / _g4: every format, no QPMAP argument (folded to false) */
+    if (own) return !qm;
+    /* kRef, kH265, kNox: luma and 4:2:0 with and without a QP map; 4:2:2 / 4:4:4 (the _cf kernels, the _nox kernels' CF 2 | 3) only with
+     * a QP map, and never reference-exact */
+    return plane <= 1 || (qm && g != Gen::kRef);
+}
+/* f(SB, PLANE, WIDE, QM) as integral constants */
+template <Gen G, bool MULTI, typename F>
+static void select_kernel(const KernelSel &k, F &&f)
+{
+    using namespace dbksel;
+    with_int<1, 2>(k.sb, [&](auto SB) {
+        with_int<0, 1, 2, 3>(k.plane, [&](auto PLANE) {
+            with_bool(k.wide, [&](auto WIDE) {
+                with_bool(k.qm, [&](auto QM) {
+                    if constexpr (kernel_exists(G, MULTI, SB, PLANE, WIDE, QM)) f(SB, PLANE, WIDE, QM);
+                });
+            });
+        });
+    });
+}
+
+/* the packed kernels of one plane; sl: kSl / kG4 */
+template <Gen G>
+static void launch_packed_sel(const PlaneArgs<G> &g, const DbkSlOffs *sl, const KernelSel &k, bool linear, dim3 grid, dim3 block, hipStream_t stream)
+{
+    static_assert(G != Gen::kNox, "the packed kernels have no _nox twins");
+    using namespace dbksel;
+    with_bool(linear, [&](auto LIN) {
+        select_kernel<G, false>(k, [&](auto SB, auto PLANE, auto WIDE, auto QM) {
+            [[maybe_unused]] constexpr bool C = PLANE != 0;
+            [[maybe_unused]] constexpr int CF = C ? (int)PLANE : 1;
+            if constexpr (G == Gen::kRef) {
+                if constexpr (SB == 2 && C) DBK_LAUNCH((dbk_packed16c_kernel<LIN, QM>), grid, block, stream, g);
+                else if constexpr (SB == 2) DBK_LAUNCH((dbk_packed16_kernel<0, false, LIN, QM, WIDE>), grid, block, stream, g);
+                else DBK_LAUNCH((dbk_packed_kernel<C, 0, false, LIN, QM>), grid, block, stream, g);
+            } else if constexpr (G == Gen::kH265) {
+                if constexpr (CF != 1 && SB == 2) DBK_LAUNCH((dbk_packed16_h265_cf_kernel<LIN, CF>), grid, block, stream, g);
+                else if constexpr (CF != 1) DBK_LAUNCH((dbk_packed_h265_cf_kernel<LIN, CF>), grid, block, stream, g);
+                else if constexpr (SB == 2) DBK_LAUNCH((dbk_packed16_h265_kernel<C, LIN, QM, WIDE>), grid, block, stream, g);
+                else DBK_LAUNCH((dbk_packed_h265_kernel<C, LIN, QM>), grid, block, stream, g);
+            } else if constexpr (G == Gen::kSl) {
+                if constexpr (SB == 2) DBK_LAUNCH((dbk_packed16_h265_sl_kernel<C, LIN, WIDE, CF>), grid, block, stream, g, *sl);
+                else DBK_LAUNCH((dbk_packed_h265_sl_kernel<C, LIN, CF>), grid, block, stream, g, *sl);
+            } else {
+                if constexpr (SB == 2) DBK_LAUNCH((dbk_packed16_h265_g4_kernel<LIN, CF>), grid, block, stream, g, *sl);
+                else DBK_LAUNCH((dbk_packed_h265_g4_kernel<LIN, CF>), grid, block, stream, g, *sl);
+            }
+        });
+    });
+}
+
 #ifdef HEVCDBK_DIAG
+/* the copy / ablation / queue kernels of the diagnostic library: true when one of them took the launch */
+template <bool LINEAR>
+static bool launch_packed_diag(const DbkArgs &a, int sample_bytes, bool chroma, int mode, dim3 grid, dim3 block, hipStream_t stream)
+{
+    constexpr bool NT = false;
+    const bool plain8 = sample_bytes == 1 && !chroma && !a.qp_map;
     if (mode == 1) { /* copy: the kernel's loads and stores, no arithmetic */
         if (sample_bytes == 2) DBK_LAUNCH((dbk_packed16_kernel<1, NT, LINEAR, false>), grid, block, stream, a);
         else DBK_LAUNCH_LDS((dbk_packed_kernel<false, 1, NT, LINEAR, false>), grid, block, g_dbk_diag.lds, stream, a);
-        return;
-    }
-    if (g_dbk_diag.lds && sample_bytes == 1 && !chroma && !qm) { /* occupancy experiment: unused dynamic LDS per workgroup */
+    } else if (g_dbk_diag.lds && plain8) { /* occupancy experiment: unused dynamic LDS per workgroup */
         DBK_LAUNCH_LDS((dbk_packed_kernel<false, 0, NT, LINEAR, false>), grid, block, g_dbk_diag.lds, stream, a);
-        return;
-    }
-    if (sample_bytes == 1 && !chroma && !qm && a.use_queue && block.x <= 512) {
+    } else if (plain8 && a.use_queue && block.x <= 512) {
         if (block.x <= 128) DBK_LAUNCH((dbk_packed_q_kernel<NT, LINEAR, 128>), grid, block, stream, a);
         else if (block.x <= 256) DBK_LAUNCH((dbk_packed_q_kernel<NT, LINEAR, 256>), grid, block, stream, a);
         else DBK_LAUNCH((dbk_packed_q_kernel<NT, LINEAR, 512>), grid, block, stream, a);
-        return;
-    }
-    if (sample_bytes == 1 && !chroma && !qm && (a.diag_ablate || a.diag_prio || a.diag_dummy || g_dbk_diag.mode3)) { /* timing only */
+    } else if (plain8 && (a.diag_ablate || a.diag_prio || a.diag_dummy || g_dbk_diag.mode3)) { /* timing only */
         DBK_LAUNCH((dbk_packed_kernel<false, 3, NT, LINEAR, false>), grid, block, stream, a);
-        return;
-    }
-#endif
-    (void)mode;
-    if (sample_bytes == 2 && chroma) {
-        if (qm) DBK_LAUNCH((dbk_packed16c_kernel<LINEAR, true>), grid, block, stream, a);
-        else DBK_LAUNCH((dbk_packed16c_kernel<LINEAR, false>), grid, block, stream, a);
-    } else if (sample_bytes == 2) {
-        if (a.max_v > 2047) { /* 12 bit: the WIDE variant of the core (deblock_packed.h) */
-            if (qm) DBK_LAUNCH((dbk_packed16_kernel<0, NT, LINEAR, true, true>), grid, block, stream, a);
-            else DBK_LAUNCH((dbk_packed16_kernel<0, NT, LINEAR, false, true>), grid, block, stream, a);
-        } else if (qm) DBK_LAUNCH((dbk_packed16_kernel<0, NT, LINEAR, true>), grid, block, stream, a);
-        else DBK_LAUNCH((dbk_packed16_kernel<0, NT, LINEAR, false>), grid, block, stream, a);
-    } else if (chroma) {
-        if (qm) DBK_LAUNCH((dbk_packed_kernel<true, 0, NT, LINEAR, true>), grid, block, stream, a);
-        else DBK_LAUNCH((dbk_packed_kernel<true, 0, NT, LINEAR, false>), grid, block, stream, a);
     } else {
-        if (qm) DBK_LAUNCH((dbk_packed_kernel<false, 0, NT, LINEAR, true>), grid, block, stream, a);
-        else DBK_LAUNCH((dbk_packed_kernel<false, 0, NT, LINEAR, false>), grid, block, stream, a);
+        return false;
     }
+    return true;
 }
+#endif
 
 /* work mapping of the packed kernels for plane geometry `a`: fills the row-major numbering fields of `b` and the launch
  * dimensions; returns true for the row-major (LINEAR) map, false for one workgroup per block row */
@@ -1350,7 +1430,7 @@ static bool plan_tile(const DbkArgs &a, DbkArgs &b, int sample_bytes, bool chrom
 
 hipError_t dbk_launch_packed(const DbkArgs &a, int sample_bytes, bool chroma, int mode, hipStream_t stream)
 {
-    if (a.n_frames <= 0 || a.nbx <= 0 || a.nby <= 0) return hipSuccess;
+    if (dbksel::nothing_to_do(a)) return hipSuccess;
     DbkArgs b = a;
 #ifdef HEVCDBK_DIAG
     b.diag_ablate = g_dbk_diag.ablate;
@@ -1432,11 +1512,12 @@ hipError_t dbk_launch_packed(const DbkArgs &a, int sample_bytes, bool chroma, in
 #endif
     dim3 grid, block;
     const bool linear = plan_packed(a, b, grid, block);
-    if (linear) {
-        launch_packed_t<false, true>(b, sample_bytes, chroma, mode, grid, block, stream);
-    } else {
-        launch_packed_t<false, false>(b, sample_bytes, chroma, mode, grid, block, stream);
-    }
+#ifdef HEVCDBK_DIAG
+    bool taken = false;
+    dbksel::with_bool(linear, [&](auto LIN) { taken = launch_packed_diag<LIN>(b, sample_bytes, chroma, mode, grid, block, stream); });
+    if (taken) return hipGetLastError();
+#endif
+    launch_packed_sel<Gen::kRef>(b, nullptr, fold_operands(Gen::kRef, false, sample_bytes == 2 ? 2 : 1, chroma, 1, b), linear, grid, block, stream);
     return hipGetLastError();
 }
 
@@ -1492,73 +1573,57 @@ bool dbk_packed_h265_supports(const DbkH265Args &h, int sample_bytes, bool chrom
            ((uintptr_t)a.src % 8) == 0 && ((uintptr_t)a.dst % 8) == 0;
 }
 
-hipError_t dbk_launch_packed_h265(const DbkH265Args &h, int sample_bytes, bool chroma, hipStream_t stream)
-{
-    return dbk_launch_packed_h265_cf(h, sample_bytes, chroma, 1, stream);
-}
-
 /* QpC of a one-QP chroma plane: Table 8-10 for 4:2:0, Min(qPi, 51) for the other formats (dbk::h265_chroma_qp_cf) */
 static int chroma_qp_of_format(int qpi, int chroma_format)
 {
     return chroma_format == 1 ? dbk::h265_chroma_qp(qpi) : dbk::h265_chroma_qp_cf<3>(qpi);
 }
 
-hipError_t dbk_launch_packed_h265_cf(const DbkH265Args &h, int sample_bytes, bool chroma, int chroma_format, hipStream_t stream)
+/* the scalar-QP operands of the packed and fused spec-exact kernels (kH265, kNox): beta', and tc' for bS 1 and bS 2 */
+static void h265_one_qp_scalars(DbkH265Args &d, bool chroma, int chroma_format)
 {
-    if (chroma && chroma_format != 1 && chroma_format != 2 && chroma_format != 3) return hipErrorInvalidValue;
-    if (h.base.n_frames <= 0 || h.base.nbx <= 0 || h.base.nby <= 0) return hipSuccess;
+    auto cl = [](int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); };
+    const int sh = d.base.shift, qp = d.qp; /* tc' and beta' scale with the bit depth, 8.7.2.5.3 */
+    d.beta_s = dbk::h265_beta(cl(qp + d.beta_off, 0, 51)) << sh;
+    if (chroma) {
+        d.tc_bs1 = 0;
+        d.tc_bs2 = dbk::h265_tc(cl(chroma_qp_of_format(qp + d.c_qp_offset, chroma_format) + 2 + d.tc_off, 0, 53)) << sh;
+    } else {
+        d.tc_bs1 = dbk::h265_tc(cl(qp + d.tc_off, 0, 53)) << sh;
+        d.tc_bs2 = dbk::h265_tc(cl(qp + 2 + d.tc_off, 0, 53)) << sh;
+    }
+}
+
+/* grids and blocks are plan_packed's in every generation */
+template <Gen G>
+static hipError_t launch_packed_h265(const DbkH265Args &h, const DbkSlOffs *sl, int sample_bytes, bool chroma, int chroma_format, hipStream_t stream)
+{
+    if (chroma && !dbksel::chroma_format_ok(chroma_format)) return hipErrorInvalidValue;
+    if (dbksel::nothing_to_do(h.base)) return hipSuccess;
     DbkH265Args g = h;
     dim3 grid, block;
     const bool linear = plan_packed(h.base, g.base, grid, block);
-    {
-        const int qp = h.qp;
-        auto cl = [](int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); };
-        const int sh = h.base.shift; /* tc' and beta' scale with the bit depth, 8.7.2.5.3 */
-        g.beta_s = dbk::h265_beta(cl(qp + h.beta_off, 0, 51)) << sh;
-        if (chroma) {
-            g.tc_bs1 = 0;
-            g.tc_bs2 = dbk::h265_tc(cl(chroma_qp_of_format(qp + h.c_qp_offset, chroma_format) + 2 + h.tc_off, 0, 53)) << sh;
-        } else {
-            g.tc_bs1 = dbk::h265_tc(cl(qp + h.tc_off, 0, 53)) << sh;
-            g.tc_bs2 = dbk::h265_tc(cl(qp + 2 + h.tc_off, 0, 53)) << sh;
-        }
-    }
-    if (chroma && g.base.qp_map && chroma_format != 1) { /* QP-map chroma of 4:2:2 / 4:4:4: the format's kernels */
-#define DBK_H265_CF_LAUNCH(LIN, CF)                                                                     \
-    do {                                                                                                \
-        if (sample_bytes == 2) DBK_LAUNCH((dbk_packed16_h265_cf_kernel<LIN, CF>), grid, block, stream, g); \
-        else DBK_LAUNCH((dbk_packed_h265_cf_kernel<LIN, CF>), grid, block, stream, g);                  \
-    } while (0)
-        if (linear) {
-            if (chroma_format == 2) DBK_H265_CF_LAUNCH(true, 2);
-            else DBK_H265_CF_LAUNCH(true, 3);
-        } else {
-            if (chroma_format == 2) DBK_H265_CF_LAUNCH(false, 2);
-            else DBK_H265_CF_LAUNCH(false, 3);
-        }
-#undef DBK_H265_CF_LAUNCH
-        return hipGetLastError();
-    }
-#define DBK_H265_LAUNCH(C, LIN)                                                                                       \
-    do {                                                                                                              \
-        if (sample_bytes == 2 && !C && g.base.max_v > 2047) { /* 12-bit luma */                                       \
-            if (g.base.qp_map) DBK_LAUNCH((dbk_packed16_h265_kernel<false, LIN, true, true>), grid, block, stream, g); \
-            else DBK_LAUNCH((dbk_packed16_h265_kernel<false, LIN, false, true>), grid, block, stream, g);  \
-        } else if (sample_bytes == 2) {                                                                               \
-            if (g.base.qp_map) DBK_LAUNCH((dbk_packed16_h265_kernel<C, LIN, true>), grid, block, stream, g); \
-            else DBK_LAUNCH((dbk_packed16_h265_kernel<C, LIN, false>), grid, block, stream, g);            \
-        } else if (g.base.qp_map) DBK_LAUNCH((dbk_packed_h265_kernel<C, LIN, true>), grid, block, stream, g); \
-        else DBK_LAUNCH((dbk_packed_h265_kernel<C, LIN, false>), grid, block, stream, g);                  \
-    } while (0)
-    if (linear) {
-        if (chroma) DBK_H265_LAUNCH(true, true);
-        else DBK_H265_LAUNCH(false, true);
-    } else {
-        if (chroma) DBK_H265_LAUNCH(true, false);
-        else DBK_H265_LAUNCH(false, false);
-    }
-#undef DBK_H265_LAUNCH
+    if constexpr (G == Gen::kH265) h265_one_qp_scalars(g, chroma, chroma_format);
+    launch_packed_sel<G>(g, sl, fold_operands(G, false, sample_bytes == 2 ? 2 : 1, chroma, chroma_format, g.base), linear, grid, block, stream);
     return hipGetLastError();
+}
+
+hipError_t dbk_launch_packed_h265(const DbkH265Args &h, int sample_bytes, bool chroma, hipStream_t stream)
+{
+    return launch_packed_h265<Gen::kH265>(h, nullptr, sample_bytes, chroma, 1, stream);
+}
+hipError_t dbk_launch_packed_h265_cf(const DbkH265Args &h, int sample_bytes, bool chroma, int chroma_format, hipStream_t stream)
+{
+    return launch_packed_h265<Gen::kH265>(h, nullptr, sample_bytes, chroma, chroma_format, stream);
+}
+hipError_t dbk_launch_packed_h265_sl(const DbkH265Args &h, const DbkSlOffs &sl, int sample_bytes, bool chroma, int chroma_format,
+                                     hipStream_t stream)
+{
+    return launch_packed_h265<Gen::kSl>(h, &sl, sample_bytes, chroma, chroma_format, stream);
+}
+hipError_t dbk_launch_packed_h265_g4(const DbkH265Args &h, const DbkSlOffs &sl, int sample_bytes, int chroma_format, hipStream_t stream)
+{
+    return launch_packed_h265<Gen::kG4>(h, &sl, sample_bytes, true, chroma_format, stream);
 }
 
 /* ---- deblocking + SAO in one kernel ---- */
@@ -1584,403 +1649,172 @@ bool dbk_deblock_sao_supports(const DbkArgs &d, const DbkSaoArgs &s, int sample_
 }
 
 /* 1-D grid of the fused kernel, a multiple of 8 workgroups */
-static unsigned fused_grid(int plane_w, int plane_h, int n_frames, int sample_bytes, DbkFusedGrid &g)
+static unsigned fused_grid(const DbkArgs &a, int sample_bytes, DbkFusedGrid &g)
 {
     const int tw = sample_bytes == 1 ? kFusedTileW : kFused16Tile, th = sample_bytes == 1 ? kFusedTile : kFused16Tile;
-    const unsigned long long tx = (plane_w + tw - 1) / tw, ty = (plane_h + th - 1) / th, tpf = tx * ty;
-    g.tiles_x = (uint32_t)tx;
-    g.tiles_per_frame = (uint32_t)tpf;
-    g.total = (uint32_t)(tpf * n_frames);
-    g.magic_tpf = tpf <= 1 ? 0u : (uint32_t)((1ull << 32) / tpf + 1ull);
-    g.magic_tx = tx <= 1 ? 0u : (uint32_t)((1ull << 32) / tx + 1ull);
-    const unsigned grid = (g.total + 7u) / 8u * 8u;
-    g.per_xcd = grid / 8u;
-    return grid;
+    const dbksel::RenumberedGrid r = dbksel::renumbered_grid((a.plane_w + tw - 1) / tw, (a.plane_h + th - 1) / th, a.n_frames);
+    g = r.g;
+    return r.wgs;
+}
+static dbksel::LaunchShape fused_shape(int sample_bytes)
+{
+    using dbksel::LaunchShape;
+    return sample_bytes == 1 ? LaunchShape{kFusedThreads, kFusedLds} : LaunchShape{kFused16Threads, kFused16Lds};
 }
 
-/* the scalar-QP operands of the packed spec-exact kernels, as dbk_launch_packed_h265 derives them */
-static void fused_h265_scalars(DbkH265Args &d, bool chroma, int chroma_format = 1)
-{
-    auto cl = [](int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); };
-    const int sh = d.base.shift, qp = d.qp;
-    d.beta_s = dbk::h265_beta(cl(qp + d.beta_off, 0, 51)) << sh;
-    if (chroma) {
-        d.tc_bs1 = 0;
-        d.tc_bs2 = dbk::h265_tc(cl(chroma_qp_of_format(qp + d.c_qp_offset, chroma_format) + 2 + d.tc_off, 0, 53)) << sh;
-    } else {
-        d.tc_bs1 = dbk::h265_tc(cl(qp + d.tc_off, 0, 53)) << sh;
-        d.tc_bs2 = dbk::h265_tc(cl(qp + 2 + d.tc_off, 0, 53)) << sh;
-    }
-}
+template <Gen G> using FusedArgs = std::conditional_t<G == Gen::kRef, DbkFusedArgs, DbkFusedH265Args>;
+template <Gen G> using FusedMultiArgs = std::conditional_t<G == Gen::kRef, DbkFusedMultiArgs, DbkFusedMultiH265Args>;
 
-/* launch K<..., QPMAP> with QPMAP = the plane carries a QP map */
-#define DBK_FUSED_LAUNCH(qm, K, threads, lds, ...)                                                 \
-    do {                                                                                           \
-        if (qm) DBK_LAUNCH_LDS((K<__VA_ARGS__, true>), grid, dim3(threads), lds, stream, fa);      \
-        else DBK_LAUNCH_LDS((K<__VA_ARGS__, false>), grid, dim3(threads), lds, stream, fa);        \
-    } while (0)
-
-hipError_t dbk_launch_deblock_sao(const DbkArgs &d, const DbkSaoArgs &s, int sample_bytes, bool chroma, hipStream_t stream)
+/* one plane: the same grid in every generation.  nxp: kNox, and kSl / kG4 where NULL stands for "no bytes"; sl: kSl / kG4 */
+template <Gen G>
+static hipError_t launch_fused(const PlaneArgs<G> &d, const DbkSaoArgs &s, const DbkSlOffs *sl, int sample_bytes, bool chroma, int chroma_format,
+                               hipStream_t stream, const DbkSaoNox *nxp)
 {
-    if (d.n_frames <= 0 || d.nbx <= 0 || d.nby <= 0) return hipSuccess;
-    DbkFusedArgs fa;
+    using namespace dbksel;
+    if (!chroma_format_ok(chroma_format) || (G == Gen::kG4 && !chroma)) return hipErrorInvalidValue;
+    if (nothing_to_do(base_of(d))) return hipSuccess;
+    FusedArgs<G> fa;
     fa.d = d;
+    fa.s = s;
 #ifdef HEVCDBK_DIAG
-    fa.d.diag_prio = g_dbk_diag.prio; /* wave priority experiment of the fused kernel (deblock_sao_fused.inc) */
+    if constexpr (G == Gen::kRef) fa.d.diag_prio = g_dbk_diag.prio; /* wave priority experiment of the fused kernel (deblock_sao_fused.inc) */
 #endif
-    fa.s = s;
-    const bool qm = d.qp_map != nullptr;
-    const dim3 grid(fused_grid(d.plane_w, d.plane_h, d.n_frames, sample_bytes, fa.g), 1, 1);
-    if (sample_bytes == 1) {
-        if (chroma) DBK_FUSED_LAUNCH(qm, dbk_sao_fused_kernel, kFusedThreads, kFusedLds, true);
-        else DBK_FUSED_LAUNCH(qm, dbk_sao_fused_kernel, kFusedThreads, kFusedLds, false);
-    } else {
-        if (chroma) DBK_FUSED_LAUNCH(qm, dbk_sao_fused16_kernel, kFused16Threads, kFused16Lds, true, false);
-        else if (d.max_v > 2047) DBK_FUSED_LAUNCH(qm, dbk_sao_fused16_kernel, kFused16Threads, kFused16Lds, false, true);
-        else DBK_FUSED_LAUNCH(qm, dbk_sao_fused16_kernel, kFused16Threads, kFused16Lds, false, false);
-    }
+    if constexpr (G == Gen::kH265 || G == Gen::kNox) h265_one_qp_scalars(fa.d, chroma, chroma_format);
+    const dim3 grid(fused_grid(base_of(d), sample_bytes, fa.g), 1, 1);
+    const LaunchShape sh = fused_shape(sample_bytes);
+    const DbkSaoNox nx = nxp ? *nxp : DbkSaoNox{nullptr, 0, 0}; /* no bytes: no direction is forbidden */
+    select_kernel<G, false>(fold_operands(G, false, sample_bytes == 1 ? 1 : 2, chroma, chroma_format, base_of(d)), [&](auto SB, auto PLANE, auto WIDE, auto QM) {
+        [[maybe_unused]] constexpr bool C = PLANE != 0;
+        [[maybe_unused]] constexpr int CF = C ? (int)PLANE : 1;
+        if constexpr (G == Gen::kRef) {
+            if constexpr (SB == 1) DBK_LAUNCH_LDS((dbk_sao_fused_kernel<C, QM>), grid, dim3(sh.threads), sh.lds, stream, fa);
+            else DBK_LAUNCH_LDS((dbk_sao_fused16_kernel<C, WIDE, QM>), grid, dim3(sh.threads), sh.lds, stream, fa);
+        } else if constexpr (G == Gen::kH265) {
+            if constexpr (CF != 1 && SB == 1) DBK_LAUNCH_LDS((dbk_sao_fused_h265_cf_kernel<CF>), grid, dim3(sh.threads), sh.lds, stream, fa);
+            else if constexpr (CF != 1) DBK_LAUNCH_LDS((dbk_sao_fused16_h265_cf_kernel<CF>), grid, dim3(sh.threads), sh.lds, stream, fa);
+            else if constexpr (SB == 1) DBK_LAUNCH_LDS((dbk_sao_fused_h265_kernel<C, QM>), grid, dim3(sh.threads), sh.lds, stream, fa);
+            else DBK_LAUNCH_LDS((dbk_sao_fused16_h265_kernel<C, WIDE, QM>), grid, dim3(sh.threads), sh.lds, stream, fa);
+        } else if constexpr (G == Gen::kNox) {
+            if constexpr (SB == 1) DBK_LAUNCH_LDS((dbk_sao_fused_h265_nox_kernel<C, QM, CF>), grid, dim3(sh.threads), sh.lds, stream, fa, nx);
+            else DBK_LAUNCH_LDS((dbk_sao_fused16_h265_nox_kernel<C, WIDE, QM, CF>), grid, dim3(sh.threads), sh.lds, stream, fa, nx);
+        } else if constexpr (G == Gen::kSl) {
+            if constexpr (SB == 1) DBK_LAUNCH_LDS((dbk_sao_fused_h265_sl_kernel<C, CF>), grid, dim3(sh.threads), sh.lds, stream, fa, nx, *sl);
+            else DBK_LAUNCH_LDS((dbk_sao_fused16_h265_sl_kernel<C, WIDE, CF>), grid, dim3(sh.threads), sh.lds, stream, fa, nx, *sl);
+        } else {
+            if constexpr (SB == 1) DBK_LAUNCH_LDS((dbk_sao_fused_h265_g4_kernel<CF>), grid, dim3(sh.threads), sh.lds, stream, fa, nx, *sl);
+            else DBK_LAUNCH_LDS((dbk_sao_fused16_h265_g4_kernel<CF>), grid, dim3(sh.threads), sh.lds, stream, fa, nx, *sl);
+        }
+    });
     return hipGetLastError();
 }
 
-hipError_t dbk_launch_deblock_sao_h265(const DbkH265Args &h, const DbkSaoArgs &s, int sample_bytes, bool chroma, hipStream_t stream)
+/* the planes of a picture in one launch: plane i's operands and grid in m.pl[i], the grids one after the other.  Returns the grid size */
+template <typename Multi, typename Plane>
+static unsigned fill_multi(Multi &m, const Plane *d, const DbkSaoArgs *s, int n, int sample_bytes)
 {
-    return dbk_launch_deblock_sao_h265_cf(h, s, sample_bytes, chroma, 1, stream);
-}
-
-/* one-QP chroma planes of 4:2:2 / 4:4:4 pictures take the 4:2:0 kernels: with one QP the format enters only through QpC in the
- * scalar tc (4:2:2 chroma CTBs arrive as square ones: dbk_launch_sao_rows_x2); with a QP map they take the _cf kernels */
-static bool fused_format_ok(int chroma_format)
-{
-    return chroma_format >= 1 && chroma_format <= 3;
-}
-
-hipError_t dbk_launch_deblock_sao_h265_cf(const DbkH265Args &h, const DbkSaoArgs &s, int sample_bytes, bool chroma, int chroma_format,
-                                          hipStream_t stream, const DbkSaoNox *nxp)
-{
-    if (!fused_format_ok(chroma_format)) return hipErrorInvalidValue;
-    if (h.base.n_frames <= 0 || h.base.nbx <= 0 || h.base.nby <= 0) return hipSuccess;
-    DbkFusedH265Args fa;
-    fa.d = h;
-    fa.s = s;
-    fused_h265_scalars(fa.d, chroma, chroma_format);
-    const bool qm = h.base.qp_map != nullptr;
-    const dim3 grid(fused_grid(h.base.plane_w, h.base.plane_h, h.base.n_frames, sample_bytes, fa.g), 1, 1);
-    if (nxp) { /* the same grid and choice of kernel, the _nox twins (deblock_sao_fused.inc) */
-        const DbkSaoNox nx = *nxp;
-        const int cf = chroma && qm ? chroma_format : 1; /* the format enters the kernel through a chroma plane's QP map only */
-#define DBK_NOX8(C, Q, F) DBK_LAUNCH_LDS((dbk_sao_fused_h265_nox_kernel<C, Q, F>), grid, dim3(kFusedThreads), kFusedLds, stream, fa, nx)
-#define DBK_NOX16(C, W, Q, F) DBK_LAUNCH_LDS((dbk_sao_fused16_h265_nox_kernel<C, W, Q, F>), grid, dim3(kFused16Threads), kFused16Lds, stream, fa, nx)
-        if (sample_bytes == 1) {
-            if (cf == 2) DBK_NOX8(true, true, 2);
-            else if (cf == 3) DBK_NOX8(true, true, 3);
-            else if (chroma && qm) DBK_NOX8(true, true, 1);
-            else if (chroma) DBK_NOX8(true, false, 1);
-            else if (qm) DBK_NOX8(false, true, 1);
-            else DBK_NOX8(false, false, 1);
-        } else {
-            const bool wide = !chroma && h.base.max_v > 2047;
-            if (cf == 2) DBK_NOX16(true, false, true, 2);
-            else if (cf == 3) DBK_NOX16(true, false, true, 3);
-            else if (chroma && qm) DBK_NOX16(true, false, true, 1);
-            else if (chroma) DBK_NOX16(true, false, false, 1);
-            else if (wide && qm) DBK_NOX16(false, true, true, 1);
-            else if (wide) DBK_NOX16(false, true, false, 1);
-            else if (qm) DBK_NOX16(false, false, true, 1);
-            else DBK_NOX16(false, false, false, 1);
-        }
-#undef DBK_NOX8
-#undef DBK_NOX16
-        return hipGetLastError();
-    }
-    if (chroma && qm && chroma_format != 1) {
-        if (sample_bytes == 1) {
-            if (chroma_format == 2) DBK_LAUNCH_LDS((dbk_sao_fused_h265_cf_kernel<2>), grid, dim3(kFusedThreads), kFusedLds, stream, fa);
-            else DBK_LAUNCH_LDS((dbk_sao_fused_h265_cf_kernel<3>), grid, dim3(kFusedThreads), kFusedLds, stream, fa);
-        } else {
-            if (chroma_format == 2) DBK_LAUNCH_LDS((dbk_sao_fused16_h265_cf_kernel<2>), grid, dim3(kFused16Threads), kFused16Lds, stream, fa);
-            else DBK_LAUNCH_LDS((dbk_sao_fused16_h265_cf_kernel<3>), grid, dim3(kFused16Threads), kFused16Lds, stream, fa);
-        }
-        return hipGetLastError();
-    }
-    if (sample_bytes == 1) {
-        if (chroma) DBK_FUSED_LAUNCH(qm, dbk_sao_fused_h265_kernel, kFusedThreads, kFusedLds, true);
-        else DBK_FUSED_LAUNCH(qm, dbk_sao_fused_h265_kernel, kFusedThreads, kFusedLds, false);
-    } else {
-        if (chroma) DBK_FUSED_LAUNCH(qm, dbk_sao_fused16_h265_kernel, kFused16Threads, kFused16Lds, true, false);
-        else if (h.base.max_v > 2047) DBK_FUSED_LAUNCH(qm, dbk_sao_fused16_h265_kernel, kFused16Threads, kFused16Lds, false, true);
-        else DBK_FUSED_LAUNCH(qm, dbk_sao_fused16_h265_kernel, kFused16Threads, kFused16Lds, false, false);
-    }
-    return hipGetLastError();
-}
-
-hipError_t dbk_launch_deblock_sao_multi(const DbkArgs *d, const DbkSaoArgs *s, int n, int sample_bytes, hipStream_t stream)
-{
-    if (n < 2 || n > 3) return hipErrorInvalidValue;
-    if (d[0].n_frames <= 0) return hipSuccess;
-    DbkFusedMultiArgs m;
     std::memset(&m, 0, sizeof(m));
     unsigned total = 0;
     for (int i = 0; i < 3; i++) {
         if (i < n) {
             m.pl[i].d = d[i];
             m.pl[i].s = s[i];
-            total += fused_grid(d[i].plane_w, d[i].plane_h, d[i].n_frames, sample_bytes, m.pl[i].g);
+            total += fused_grid(base_of(d[i]), sample_bytes, m.pl[i].g);
         }
         m.wg_end[i] = total;
     }
-    const dim3 grid(total, 1, 1);
-    const DbkFusedMultiArgs &fa = m;
-    const bool qm = d[0].qp_map != nullptr; /* the caller checked: all planes with a map, or none */
-    if (sample_bytes == 1) DBK_FUSED_LAUNCH(qm, dbk_sao_fused_multi_kernel, kFusedThreads, kFusedLds, 1, false);
-    else if (d[0].max_v > 2047) DBK_FUSED_LAUNCH(qm, dbk_sao_fused_multi_kernel, kFused16Threads, kFused16Lds, 2, true);
-    else DBK_FUSED_LAUNCH(qm, dbk_sao_fused_multi_kernel, kFused16Threads, kFused16Lds, 2, false);
-    return hipGetLastError();
+    return total;
 }
-
-hipError_t dbk_launch_deblock_sao_multi_h265(const DbkH265Args *h, const DbkSaoArgs *s, int n, int sample_bytes, hipStream_t stream)
+/* per-plane boundary bytes of a launch of n planes; nxp == NULL: none */
+template <typename Nox>
+static Nox nox_planes(const DbkSaoNox *nxp, int n)
 {
-    return dbk_launch_deblock_sao_multi_h265_cf(h, s, n, sample_bytes, 1, stream);
-}
-
-hipError_t dbk_launch_deblock_sao_multi_h265_cf(const DbkH265Args *h, const DbkSaoArgs *s, int n, int sample_bytes, int chroma_format,
-                                                hipStream_t stream, const DbkSaoNox *nxp)
-{
-    if (!fused_format_ok(chroma_format)) return hipErrorInvalidValue;
-    if (n < 2 || n > 3) return hipErrorInvalidValue;
-    if (h[0].base.n_frames <= 0) return hipSuccess;
-    DbkFusedMultiH265Args m;
-    std::memset(&m, 0, sizeof(m));
-    unsigned total = 0;
-    for (int i = 0; i < 3; i++) {
-        if (i < n) {
-            m.pl[i].d = h[i];
-            m.pl[i].s = s[i];
-            fused_h265_scalars(m.pl[i].d, i > 0, chroma_format);
-            total += fused_grid(h[i].base.plane_w, h[i].base.plane_h, h[i].base.n_frames, sample_bytes, m.pl[i].g);
-        }
-        m.wg_end[i] = total;
-    }
-    const dim3 grid(total, 1, 1);
-    const DbkFusedMultiH265Args &fa = m;
-    const bool qm = h[0].base.qp_map != nullptr; /* the caller checked: all planes with a map, or none */
-    if (nxp) { /* the same grid and choice of kernel, the _nox twins */
-        DbkSaoNox3 nx = {};
+    Nox nx = {};
+    if (nxp)
         for (int i = 0; i < n; i++) nx.pl[i] = nxp[i];
-        const int cf = qm ? chroma_format : 1;
-        const bool wide = h[0].base.max_v > 2047;
-#define DBK_NOXM(SB, W, Q, F)                                                                                                          \
-    DBK_LAUNCH_LDS((dbk_sao_fused_multi_h265_nox_kernel<SB, W, Q, F>), grid, dim3(SB == 1 ? kFusedThreads : kFused16Threads),          \
-                   SB == 1 ? kFusedLds : kFused16Lds, stream, fa, nx)
-#define DBK_NOXM_F(Q, F)                                                                                                               \
-    do {                                                                                                                               \
-        if (sample_bytes == 1) DBK_NOXM(1, false, Q, F);                                                                               \
-        else if (wide) DBK_NOXM(2, true, Q, F);                                                                                        \
-        else DBK_NOXM(2, false, Q, F);                                                                                                 \
-    } while (0)
-        if (cf == 2) DBK_NOXM_F(true, 2);
-        else if (cf == 3) DBK_NOXM_F(true, 3);
-        else if (qm) DBK_NOXM_F(true, 1);
-        else DBK_NOXM_F(false, 1);
-#undef DBK_NOXM_F
-#undef DBK_NOXM
-        return hipGetLastError();
-    }
-    if (qm && chroma_format != 1) { /* QP-map planes of 4:2:2 / 4:4:4 */
-#define DBK_FUSED_CF_LAUNCH(CF)                                                                                                      \
-    do {                                                                                                                             \
-        if (sample_bytes == 1) DBK_LAUNCH_LDS((dbk_sao_fused_multi_h265_cf_kernel<1, false, CF>), grid, dim3(kFusedThreads), kFusedLds, stream, fa); \
-        else if (h[0].base.max_v > 2047) DBK_LAUNCH_LDS((dbk_sao_fused_multi_h265_cf_kernel<2, true, CF>), grid, dim3(kFused16Threads), kFused16Lds, stream, fa); \
-        else DBK_LAUNCH_LDS((dbk_sao_fused_multi_h265_cf_kernel<2, false, CF>), grid, dim3(kFused16Threads), kFused16Lds, stream, fa); \
-    } while (0)
-        if (chroma_format == 2) DBK_FUSED_CF_LAUNCH(2);
-        else DBK_FUSED_CF_LAUNCH(3);
-#undef DBK_FUSED_CF_LAUNCH
-        return hipGetLastError();
-    }
-    if (sample_bytes == 1) DBK_FUSED_LAUNCH(qm, dbk_sao_fused_multi_h265_kernel, kFusedThreads, kFusedLds, 1, false);
-    else if (h[0].base.max_v > 2047) DBK_FUSED_LAUNCH(qm, dbk_sao_fused_multi_h265_kernel, kFused16Threads, kFused16Lds, 2, true);
-    else DBK_FUSED_LAUNCH(qm, dbk_sao_fused_multi_h265_kernel, kFused16Threads, kFused16Lds, 2, false);
-    return hipGetLastError();
+    return nx;
 }
 
-/* ---- per-slice deblocking offsets: the packed and fused kernels' _sl twins (grids and blocks as without the operand) ---- */
-
-hipError_t dbk_launch_packed_h265_sl(const DbkH265Args &h, const DbkSlOffs &sl, int sample_bytes, bool chroma, int chroma_format,
-                                     hipStream_t stream)
+/* n = 2 or 3 planes, plane 0 luma; the caller checked: all planes with a QP map, or none */
+template <Gen G>
+static hipError_t launch_fused_multi(const PlaneArgs<G> *d, const DbkSaoArgs *s, const DbkSlOffs *sl, int n, int sample_bytes, int chroma_format,
+                                     hipStream_t stream, const DbkSaoNox *nxp)
 {
-    if (chroma && chroma_format != 1 && chroma_format != 2 && chroma_format != 3) return hipErrorInvalidValue;
-    if (h.base.n_frames <= 0 || h.base.nbx <= 0 || h.base.nby <= 0) return hipSuccess;
-    DbkH265Args g = h;
-    dim3 grid, block;
-    const bool linear = plan_packed(h.base, g.base, grid, block);
-    const int cf = chroma ? chroma_format : 1;
-    const bool wide = !chroma && g.base.max_v > 2047; /* 12-bit luma */
-#define DBK_SL_LAUNCH(C, LIN, F)                                                                                        \
-    do {                                                                                                                \
-        if (sample_bytes == 2 && wide) DBK_LAUNCH((dbk_packed16_h265_sl_kernel<C, LIN, !C, F>), grid, block, stream, g, sl); \
-        else if (sample_bytes == 2) DBK_LAUNCH((dbk_packed16_h265_sl_kernel<C, LIN, false, F>), grid, block, stream, g, sl); \
-        else DBK_LAUNCH((dbk_packed_h265_sl_kernel<C, LIN, F>), grid, block, stream, g, sl);                           \
-    } while (0)
-#define DBK_SL_LAUNCH_F(LIN)                          \
-    do {                                              \
-        if (!chroma) DBK_SL_LAUNCH(false, LIN, 1);    \
-        else if (cf == 1) DBK_SL_LAUNCH(true, LIN, 1); \
-        else if (cf == 2) DBK_SL_LAUNCH(true, LIN, 2); \
-        else DBK_SL_LAUNCH(true, LIN, 3);             \
-    } while (0)
-    if (linear) DBK_SL_LAUNCH_F(true);
-    else DBK_SL_LAUNCH_F(false);
-#undef DBK_SL_LAUNCH_F
-#undef DBK_SL_LAUNCH
+    using namespace dbksel;
+    if (!chroma_format_ok(chroma_format)) return hipErrorInvalidValue;
+    if (n < 2 || n > 3) return hipErrorInvalidValue;
+    if (base_of(d[0]).n_frames <= 0) return hipSuccess;
+    FusedMultiArgs<G> m;
+    const dim3 grid(fill_multi(m, d, s, n, sample_bytes), 1, 1);
+    if constexpr (G == Gen::kH265 || G == Gen::kNox)
+        for (int i = 0; i < n; i++) h265_one_qp_scalars(m.pl[i].d, i > 0, chroma_format);
+    const LaunchShape sh = fused_shape(sample_bytes);
+    const DbkSaoNox3 nx = nox_planes<DbkSaoNox3>(nxp, n);
+    select_kernel<G, true>(fold_operands(G, true, sample_bytes == 1 ? 1 : 2, false, chroma_format, base_of(d[0])), [&](auto SB, auto CF, auto WIDE, auto QM) {
+        if constexpr (G == Gen::kRef) DBK_LAUNCH_LDS((dbk_sao_fused_multi_kernel<SB, WIDE, QM>), grid, dim3(sh.threads), sh.lds, stream, m);
+        else if constexpr (G == Gen::kH265 && CF != 1) DBK_LAUNCH_LDS((dbk_sao_fused_multi_h265_cf_kernel<SB, WIDE, CF>), grid, dim3(sh.threads), sh.lds, stream, m);
+        else if constexpr (G == Gen::kH265) DBK_LAUNCH_LDS((dbk_sao_fused_multi_h265_kernel<SB, WIDE, QM>), grid, dim3(sh.threads), sh.lds, stream, m);
+        else if constexpr (G == Gen::kNox) DBK_LAUNCH_LDS((dbk_sao_fused_multi_h265_nox_kernel<SB, WIDE, QM, CF>), grid, dim3(sh.threads), sh.lds, stream, m, nx);
+        else if constexpr (G == Gen::kSl) DBK_LAUNCH_LDS((dbk_sao_fused_multi_h265_sl_kernel<SB, WIDE, CF>), grid, dim3(sh.threads), sh.lds, stream, m, nx, *sl);
+        else DBK_LAUNCH_LDS((dbk_sao_fused_multi_h265_g4_kernel<SB, WIDE, CF>), grid, dim3(sh.threads), sh.lds, stream, m, nx, *sl);
+    });
     return hipGetLastError();
 }
 
-/* ---- chroma planes whose sizes are multiples of 4 (the _g4 entries): the _sl twins' twins, grids and blocks unchanged ---- */
-
-hipError_t dbk_launch_packed_h265_g4(const DbkH265Args &h, const DbkSlOffs &sl, int sample_bytes, int chroma_format, hipStream_t stream)
+hipError_t dbk_launch_deblock_sao(const DbkArgs &d, const DbkSaoArgs &s, int sample_bytes, bool chroma, hipStream_t stream)
 {
-    if (chroma_format != 1 && chroma_format != 2 && chroma_format != 3) return hipErrorInvalidValue;
-    if (h.base.n_frames <= 0 || h.base.nbx <= 0 || h.base.nby <= 0) return hipSuccess;
-    DbkH265Args g = h;
-    dim3 grid, block;
-    const bool linear = plan_packed(h.base, g.base, grid, block);
-#define DBK_G4_LAUNCH(LIN, F)                                                                                      \
-    do {                                                                                                           \
-        if (sample_bytes == 2) DBK_LAUNCH((dbk_packed16_h265_g4_kernel<LIN, F>), grid, block, stream, g, sl);      \
-        else DBK_LAUNCH((dbk_packed_h265_g4_kernel<LIN, F>), grid, block, stream, g, sl);                          \
-    } while (0)
-#define DBK_G4_LAUNCH_F(LIN)                               \
-    do {                                                   \
-        if (chroma_format == 1) DBK_G4_LAUNCH(LIN, 1);     \
-        else if (chroma_format == 2) DBK_G4_LAUNCH(LIN, 2); \
-        else DBK_G4_LAUNCH(LIN, 3);                        \
-    } while (0)
-    if (linear) DBK_G4_LAUNCH_F(true);
-    else DBK_G4_LAUNCH_F(false);
-#undef DBK_G4_LAUNCH_F
-#undef DBK_G4_LAUNCH
-    return hipGetLastError();
+    return launch_fused<Gen::kRef>(d, s, nullptr, sample_bytes, chroma, 1, stream, nullptr);
 }
-
-/* g4: the _g4 kernels (a chroma plane, or the planes of a picture whose chroma planes have sizes that are multiples of 4) */
-static hipError_t launch_deblock_sao_h265_sl(const DbkH265Args &h, const DbkSaoArgs &s, const DbkSlOffs &sl, int sample_bytes, bool chroma,
-                                             int chroma_format, hipStream_t stream, const DbkSaoNox *nxp, bool g4)
+hipError_t dbk_launch_deblock_sao_h265(const DbkH265Args &h, const DbkSaoArgs &s, int sample_bytes, bool chroma, hipStream_t stream)
 {
-    if (!fused_format_ok(chroma_format) || (g4 && !chroma)) return hipErrorInvalidValue;
-    if (h.base.n_frames <= 0 || h.base.nbx <= 0 || h.base.nby <= 0) return hipSuccess;
-    DbkFusedH265Args fa;
-    fa.d = h;
-    fa.s = s;
-    const dim3 grid(fused_grid(h.base.plane_w, h.base.plane_h, h.base.n_frames, sample_bytes, fa.g), 1, 1);
-    const DbkSaoNox nx = nxp ? *nxp : DbkSaoNox{nullptr, 0, 0}; /* no bytes: no direction is forbidden */
-    const int cf = chroma ? chroma_format : 1;
-    if (g4) {
-#define DBK_G48(F) DBK_LAUNCH_LDS((dbk_sao_fused_h265_g4_kernel<F>), grid, dim3(kFusedThreads), kFusedLds, stream, fa, nx, sl)
-#define DBK_G416(F) DBK_LAUNCH_LDS((dbk_sao_fused16_h265_g4_kernel<F>), grid, dim3(kFused16Threads), kFused16Lds, stream, fa, nx, sl)
-        if (sample_bytes == 1) {
-            if (cf == 1) DBK_G48(1);
-            else if (cf == 2) DBK_G48(2);
-            else DBK_G48(3);
-        } else {
-            if (cf == 1) DBK_G416(1);
-            else if (cf == 2) DBK_G416(2);
-            else DBK_G416(3);
-        }
-#undef DBK_G48
-#undef DBK_G416
-        return hipGetLastError();
-    }
-#define DBK_SL8(C, F) DBK_LAUNCH_LDS((dbk_sao_fused_h265_sl_kernel<C, F>), grid, dim3(kFusedThreads), kFusedLds, stream, fa, nx, sl)
-#define DBK_SL16(C, W, F) DBK_LAUNCH_LDS((dbk_sao_fused16_h265_sl_kernel<C, W, F>), grid, dim3(kFused16Threads), kFused16Lds, stream, fa, nx, sl)
-    if (sample_bytes == 1) {
-        if (!chroma) DBK_SL8(false, 1);
-        else if (cf == 1) DBK_SL8(true, 1);
-        else if (cf == 2) DBK_SL8(true, 2);
-        else DBK_SL8(true, 3);
-    } else {
-        if (!chroma && h.base.max_v > 2047) DBK_SL16(false, true, 1);
-        else if (!chroma) DBK_SL16(false, false, 1);
-        else if (cf == 1) DBK_SL16(true, false, 1);
-        else if (cf == 2) DBK_SL16(true, false, 2);
-        else DBK_SL16(true, false, 3);
-    }
-#undef DBK_SL8
-#undef DBK_SL16
-    return hipGetLastError();
+    return launch_fused<Gen::kH265>(h, s, nullptr, sample_bytes, chroma, 1, stream, nullptr);
 }
-
+hipError_t dbk_launch_deblock_sao_h265_cf(const DbkH265Args &h, const DbkSaoArgs &s, int sample_bytes, bool chroma, int chroma_format,
+                                          hipStream_t stream, const DbkSaoNox *nxp)
+{
+    return nxp ? launch_fused<Gen::kNox>(h, s, nullptr, sample_bytes, chroma, chroma_format, stream, nxp)
+               : launch_fused<Gen::kH265>(h, s, nullptr, sample_bytes, chroma, chroma_format, stream, nullptr);
+}
 hipError_t dbk_launch_deblock_sao_h265_sl(const DbkH265Args &h, const DbkSaoArgs &s, const DbkSlOffs &sl, int sample_bytes, bool chroma,
                                           int chroma_format, hipStream_t stream, const DbkSaoNox *nxp)
 {
-    return launch_deblock_sao_h265_sl(h, s, sl, sample_bytes, chroma, chroma_format, stream, nxp, false);
+    return launch_fused<Gen::kSl>(h, s, &sl, sample_bytes, chroma, chroma_format, stream, nxp);
 }
 hipError_t dbk_launch_deblock_sao_h265_g4(const DbkH265Args &h, const DbkSaoArgs &s, const DbkSlOffs &sl, int sample_bytes, int chroma_format,
                                           hipStream_t stream, const DbkSaoNox *nxp)
 {
-    return launch_deblock_sao_h265_sl(h, s, sl, sample_bytes, true, chroma_format, stream, nxp, true);
+    return launch_fused<Gen::kG4>(h, s, &sl, sample_bytes, true, chroma_format, stream, nxp);
 }
 
-static hipError_t launch_deblock_sao_multi_h265_sl(const DbkH265Args *h, const DbkSaoArgs *s, const DbkSlOffs &sl, int n, int sample_bytes,
-                                                   int chroma_format, hipStream_t stream, const DbkSaoNox *nxp, bool g4)
+hipError_t dbk_launch_deblock_sao_multi(const DbkArgs *d, const DbkSaoArgs *s, int n, int sample_bytes, hipStream_t stream)
 {
-    if (!fused_format_ok(chroma_format)) return hipErrorInvalidValue;
-    if (n < 2 || n > 3) return hipErrorInvalidValue;
-    if (h[0].base.n_frames <= 0) return hipSuccess;
-    DbkFusedMultiH265Args m;
-    std::memset(&m, 0, sizeof(m));
-    unsigned total = 0;
-    for (int i = 0; i < 3; i++) {
-        if (i < n) {
-            m.pl[i].d = h[i];
-            m.pl[i].s = s[i];
-            total += fused_grid(h[i].base.plane_w, h[i].base.plane_h, h[i].base.n_frames, sample_bytes, m.pl[i].g);
-        }
-        m.wg_end[i] = total;
-    }
-    const dim3 grid(total, 1, 1);
-    const DbkFusedMultiH265Args &fa = m;
-    DbkSaoNox3 nx = {};
-    if (nxp)
-        for (int i = 0; i < n; i++) nx.pl[i] = nxp[i];
-    const bool wide = h[0].base.max_v > 2047;
-#define DBK_SLM(SB, W, F)                                                                                                            \
-    do {                                                                                                                             \
-        if (g4)                                                                                                                      \
-            DBK_LAUNCH_LDS((dbk_sao_fused_multi_h265_g4_kernel<SB, W, F>), grid, dim3(SB == 1 ? kFusedThreads : kFused16Threads),    \
-                           SB == 1 ? kFusedLds : kFused16Lds, stream, fa, nx, sl);                                                   \
-        else                                                                                                                         \
-            DBK_LAUNCH_LDS((dbk_sao_fused_multi_h265_sl_kernel<SB, W, F>), grid, dim3(SB == 1 ? kFusedThreads : kFused16Threads),    \
-                           SB == 1 ? kFusedLds : kFused16Lds, stream, fa, nx, sl);                                                   \
-    } while (0)
-#define DBK_SLM_F(F)                                    \
-    do {                                                \
-        if (sample_bytes == 1) DBK_SLM(1, false, F);    \
-        else if (wide) DBK_SLM(2, true, F);             \
-        else DBK_SLM(2, false, F);                      \
-    } while (0)
-    if (chroma_format == 1) DBK_SLM_F(1);
-    else if (chroma_format == 2) DBK_SLM_F(2);
-    else DBK_SLM_F(3);
-#undef DBK_SLM_F
-#undef DBK_SLM
-    return hipGetLastError();
+    return launch_fused_multi<Gen::kRef>(d, s, nullptr, n, sample_bytes, 1, stream, nullptr);
 }
-
+hipError_t dbk_launch_deblock_sao_multi_h265(const DbkH265Args *h, const DbkSaoArgs *s, int n, int sample_bytes, hipStream_t stream)
+{
+    return launch_fused_multi<Gen::kH265>(h, s, nullptr, n, sample_bytes, 1, stream, nullptr);
+}
+hipError_t dbk_launch_deblock_sao_multi_h265_cf(const DbkH265Args *h, const DbkSaoArgs *s, int n, int sample_bytes, int chroma_format,
+                                                hipStream_t stream, const DbkSaoNox *nxp)
+{
+    return nxp ? launch_fused_multi<Gen::kNox>(h, s, nullptr, n, sample_bytes, chroma_format, stream, nxp)
+               : launch_fused_multi<Gen::kH265>(h, s, nullptr, n, sample_bytes, chroma_format, stream, nullptr);
+}
 hipError_t dbk_launch_deblock_sao_multi_h265_sl(const DbkH265Args *h, const DbkSaoArgs *s, const DbkSlOffs &sl, int n, int sample_bytes,
                                                 int chroma_format, hipStream_t stream, const DbkSaoNox *nxp)
 {
-    return launch_deblock_sao_multi_h265_sl(h, s, sl, n, sample_bytes, chroma_format, stream, nxp, false);
+    return launch_fused_multi<Gen::kSl>(h, s, &sl, n, sample_bytes, chroma_format, stream, nxp);
 }
 hipError_t dbk_launch_deblock_sao_multi_h265_g4(const DbkH265Args *h, const DbkSaoArgs *s, const DbkSlOffs &sl, int n, int sample_bytes,
                                                 int chroma_format, hipStream_t stream, const DbkSaoNox *nxp)
 {
-    return launch_deblock_sao_multi_h265_sl(h, s, sl, n, sample_bytes, chroma_format, stream, nxp, true);
+    return launch_fused_multi<Gen::kG4>(h, s, &sl, n, sample_bytes, chroma_format, stream, nxp);
 }
 
 /* a semi-planar 4:2:0 picture: h[0] / s[0] the luma plane, h[1] / s[1] the plane of pairs (deblock_sao_sp.hip) */
 hipError_t dbk_launch_deblock_sao_h265_nv12(const DbkH265Args *h, const DbkSaoArgs *s, const DbkSaoCtb *params_cr, const DbkSlOffs &sl,
                                             int cr_qp_offset, int sample_bytes, hipStream_t stream, const DbkSaoNox *nxp)
 {
+    using namespace dbksel;
     if (h[0].base.n_frames <= 0) return hipSuccess;
     if (h[1].base.n_frames != h[0].base.n_frames || !dbk_deblock_sao_supports(h[0].base, s[0], sample_bytes, false) ||
         !dbk_deblock_sao_sp_supports(h[1], s[1], sample_bytes))
@@ -1990,22 +1824,17 @@ hipError_t dbk_launch_deblock_sao_h265_nv12(const DbkH265Args *h, const DbkSaoAr
     y.s = s[0];
     c.d = h[1];
     c.s = s[1];
-    const unsigned y_wgs = fused_grid(h[0].base.plane_w, h[0].base.plane_h, h[0].base.n_frames, sample_bytes, y.g);
+    const unsigned y_wgs = fused_grid(h[0].base, sample_bytes, y.g);
     const unsigned c_wgs = dbk_deblock_sao_sp_grid(h[1].base.plane_w, h[1].base.plane_h, h[1].base.n_frames, sample_bytes, c.g);
     const dim3 grid(y_wgs + c_wgs, 1, 1);
-    DbkSaoNox2 nx = {};
-    if (nxp) {
-        nx.pl[0] = nxp[0];
-        nx.pl[1] = nxp[1];
-    }
-    if (sample_bytes == 1)
-        DBK_LAUNCH_LDS((dbk_sao_fused_multi_h265_sp_kernel<1, false>), grid, dim3(kFusedThreads), kFusedLds, stream, y, c, y_wgs, nx, sl, params_cr,
-                       cr_qp_offset);
-    else if (h[0].base.max_v > 2047)
-        DBK_LAUNCH_LDS((dbk_sao_fused_multi_h265_sp_kernel<2, true>), grid, dim3(kFused16Threads), kFused16Lds, stream, y, c, y_wgs, nx, sl, params_cr,
-                       cr_qp_offset);
-    else
-        DBK_LAUNCH_LDS((dbk_sao_fused_multi_h265_sp_kernel<2, false>), grid, dim3(kFused16Threads), kFused16Lds, stream, y, c, y_wgs, nx, sl,
-                       params_cr, cr_qp_offset);
+    const LaunchShape sh = fused_shape(sample_bytes);
+    const DbkSaoNox2 nx = nox_planes<DbkSaoNox2>(nxp, 2);
+    const bool wide = sample_bytes != 1 && h[0].base.max_v > 2047;
+    with_int<1, 2>(sample_bytes, [&](auto SB) {
+        with_bool(wide, [&](auto WIDE) {
+            if constexpr (SB == 2 || !WIDE)
+                DBK_LAUNCH_LDS((dbk_sao_fused_multi_h265_sp_kernel<SB, WIDE>), grid, dim3(sh.threads), sh.lds, stream, y, c, y_wgs, nx, sl, params_cr, cr_qp_offset);
+        });
+    });
     return hipGetLastError();
 }

@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include "deblock_sao_sp_fused.h"
+#include "launch_select.h"
 
 namespace {
 
@@ -62,22 +63,16 @@ bool dbk_deblock_sao_sp_supports(const DbkH265Args &h, const DbkSaoArgs &s, int 
 /* 1-D grid of the pair plane's tiles, a multiple of 8 workgroups */
 unsigned dbk_deblock_sao_sp_grid(int plane_w, int plane_h, int n_frames, int sample_bytes, DbkFusedGrid &g)
 {
-    unsigned long long tx;
-    const unsigned long long tpf = sample_bytes == 1 ? tiles_of<1>(plane_w, plane_h, tx) : tiles_of<2>(plane_w, plane_h, tx);
-    g.tiles_x = (uint32_t)tx;
-    g.tiles_per_frame = (uint32_t)tpf;
-    g.total = (uint32_t)(tpf * (unsigned long long)n_frames);
-    g.magic_tpf = tpf <= 1 ? 0u : (uint32_t)((1ull << 32) / tpf + 1ull);
-    g.magic_tx = tx <= 1 ? 0u : (uint32_t)((1ull << 32) / tx + 1ull);
-    const unsigned grid = (g.total + 7u) / 8u * 8u;
-    g.per_xcd = grid / 8u;
-    return grid;
+    const int tw = sample_bytes == 1 ? spf::Geo<1>::kTileW : spf::Geo<2>::kTileW, th = sample_bytes == 1 ? spf::Geo<1>::kTileH : spf::Geo<2>::kTileH;
+    const dbksel::RenumberedGrid r = dbksel::renumbered_grid((plane_w + tw - 1) / tw, (plane_h + th - 1) / th, n_frames);
+    g = r.g;
+    return r.wgs;
 }
 
 hipError_t dbk_launch_deblock_sao_h265_sp(const DbkH265Args &h, const DbkSaoArgs &s, const DbkSaoCtb *params_cr, const DbkSlOffs &sl,
                                           int cr_qp_offset, int sample_bytes, hipStream_t stream, const DbkSaoNox *nxp)
 {
-    if (h.base.n_frames <= 0 || h.base.nbx <= 0 || h.base.nby <= 0) return hipSuccess;
+    if (dbksel::nothing_to_do(h.base)) return hipSuccess;
     if (!dbk_deblock_sao_sp_supports(h, s, sample_bytes)) return hipErrorInvalidValue;
     DbkFusedH265Args fa;
     fa.d = h;

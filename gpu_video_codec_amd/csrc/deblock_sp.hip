@@ -22,6 +22,7 @@
 #include "deblock_packed16.h"
 #include "deblock_sp.h"
 #include "deblock_sp_dev.h"
+#include "launch_select.h"
 
 namespace {
 
@@ -272,11 +273,11 @@ __global__ __launch_bounds__(1024) void dbk_packed16_h265_sp_kernel(const DbkH26
 
 hipError_t dbk_launch_h265_sp(const DbkH265Args &h, const DbkSlOffs &sl, int cr_qp_offset, int sample_bytes, hipStream_t stream)
 {
-    if (h.base.n_frames <= 0 || h.base.nbx <= 0 || h.base.nby <= 0) return hipSuccess;
-    const dim3 block(64, 4, 1);
-    const dim3 grid((h.base.nbx + 63) / 64, (h.base.nby + 3) / 4, h.base.n_frames);
-    if (sample_bytes == 1) hipLaunchKernelGGL(dbk_h265_sp_kernel<uint8_t>, grid, block, 0, stream, h, sl, cr_qp_offset);
-    else hipLaunchKernelGGL(dbk_h265_sp_kernel<uint16_t>, grid, block, 0, stream, h, sl, cr_qp_offset);
+    using namespace dbksel;
+    if (nothing_to_do(h.base)) return hipSuccess;
+    with_int<1, 2>(sample_bytes, [&](auto SB) {
+        hipLaunchKernelGGL(dbk_h265_sp_kernel<sample_t<SB>>, generic_grid(h.base), generic_block(), 0, stream, h, sl, cr_qp_offset);
+    });
     return hipGetLastError();
 }
 
@@ -292,7 +293,7 @@ bool dbk_packed_h265_sp_supports(const DbkH265Args &h, int sample_bytes)
 
 hipError_t dbk_launch_packed_h265_sp(const DbkH265Args &h, const DbkSlOffs &sl, int cr_qp_offset, int sample_bytes, hipStream_t stream)
 {
-    if (h.base.n_frames <= 0 || h.base.nbx <= 0 || h.base.nby <= 0) return hipSuccess;
+    if (dbksel::nothing_to_do(h.base)) return hipSuccess;
     if (!dbk_packed_h265_sp_supports(h, sample_bytes)) return hipErrorInvalidValue;
     const dim3 block((unsigned)((h.base.nbx + 63) / 64 * 64), 1, 1);
     const dim3 grid((unsigned)h.base.nby, (unsigned)h.base.n_frames, 1);

@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 
 #include "deblock_kernels.h"
+#include "launch_select.h"
 #include "sao_packed.h"
 
 namespace {
@@ -370,134 +371,93 @@ __global__ __launch_bounds__(64 * WAVES) void sao8_g4_kernel(const DbkSaoArgs a,
 #include "sao8_kernel_body.inc"
 }
 
+/* ---- the launchers.  A kernel comes in three forms, with one body: plain (a, g), the _nox twin (a, g, nx) for calls with boundary
+ * bytes, and the _g4 form (a, g, nx; nx.nox may be NULL) for planes whose sizes are multiples of 4, not 8 ---- */
+#ifdef HEVCDBK_DIAG
+constexpr bool kNarrowStrips = true; /* sao8[_nox]_kernel<true, 1 | 2>: the wg_cap knob */
+#else
+constexpr bool kNarrowStrips = false;
+#endif
+
+template <bool G4, bool NOX, bool SWZ, int WAVES>
+void launch_sao8(const dbksel::SaoGrid &sg, hipStream_t stream, const DbkSaoArgs &a, const DbkSaoNox &nx)
+{
+    if constexpr (G4) hipLaunchKernelGGL((sao8_g4_kernel<SWZ, WAVES>), sg.grid, sg.block, 0, stream, a, sg.g, nx);
+    else if constexpr (NOX) hipLaunchKernelGGL((sao8_nox_kernel<SWZ, WAVES>), sg.grid, sg.block, 0, stream, a, sg.g, nx);
+    else hipLaunchKernelGGL((sao8_kernel<SWZ, WAVES>), sg.grid, sg.block, 0, stream, a, sg.g);
+}
+
+template <bool G4, bool NOX, typename T, bool SWZ, bool PK16>
+void launch_sao_t(const dbksel::SaoGrid &sg, hipStream_t stream, const DbkSaoArgs &a, const DbkSaoNox &nx)
+{
+    if constexpr (G4) hipLaunchKernelGGL((sao_g4_kernel<T, SWZ, PK16>), sg.grid, sg.block, 0, stream, a, sg.g, nx);
+    else if constexpr (NOX) hipLaunchKernelGGL((sao_nox_kernel<T, SWZ, PK16>), sg.grid, sg.block, 0, stream, a, sg.g, nx);
+    else hipLaunchKernelGGL((sao_kernel<T, SWZ, PK16>), sg.grid, sg.block, 0, stream, a, sg.g);
+}
+
+/* G4: the two predicates without their demand for multiples of 8, the _g4 kernels whether or not there are boundary bytes, and
+ * none of the diagnostic library's knobs */
+template <bool G4>
+hipError_t launch_sao(const DbkSaoArgs &a, int sample_bytes, hipStream_t stream, const DbkSaoNox *nxp)
+{
+    using namespace dbksel;
+    if (nothing_to_do(a)) return hipSuccess;
+    const bool small = (unsigned long long)a.pitch * (unsigned long long)a.plane_h < (1ull << 31); /* 32-bit buffer offsets */
+    const bool mult8 = G4 || (a.plane_w % 8 == 0 && a.plane_h % 8 == 0);
+    /* 8-bit planes whose rows and frames are 8-byte aligned take the packed kernel (every lane moves 8 bytes at once) */
+    const bool aligned8 = sample_bytes == 1 && a.pitch % 8 == 0 && a.frame_stride % 8 == 0 && ((uintptr_t)a.src % 8) == 0 &&
+                          ((uintptr_t)a.dst % 8) == 0 && mult8 && a.max_v == 255 && a.band_shift == 3 && small;
+    /* 16-bit containers up to 12 bit (the packed procedure's int16 fields; SaoOffsetVal scaled as the standard does), planes the
+     * buffer resources can address: the packed path in every wave off the picture border */
+    const bool pk16 = sample_bytes != 1 && a.max_v <= 4095 && a.band_shift >= 3 && (1 << (a.band_shift + 5)) - 1 == a.max_v &&
+                      a.pitch % 4 == 0 && a.frame_stride % 4 == 0 && ((uintptr_t)a.src % 4) == 0 && ((uintptr_t)a.dst % 4) == 0 && mult8 &&
+                      small;
+    int waves = 4; /* 64 x 64 regions (waves) side by side in one workgroup */
+    bool renumber = true;
+#ifdef HEVCDBK_DIAG
+    if constexpr (!G4) {
+        renumber = !g_dbk_diag.noswz; /* A/B knob of the diagnostic library: the plain 3-D numbering */
+        /* A/B knob: narrower workgroups of the packed 8-bit kernel.  They exist for the renumbered grid only (sao8_kernel<true, 1 | 2>):
+         * with the plain 3-D numbering -- the noswz knob, or a grid too large to renumber -- the launch is sao8_kernel<false, 4>, whose
+         * strips are 256 samples wide, and block / grid must be sized for that (half or three quarters of each strip row
+         * stayed unwritten when both knobs were set) */
+        const int knob = g_dbk_diag.wg_cap / 64;
+        if (aligned8 && renumber && (g_dbk_diag.wg_cap == 64 || g_dbk_diag.wg_cap == 128) && sao_strips(a, knob).exact) waves = knob;
+    }
+#endif
+    const SaoGrid sg = sao_grid(a, waves, renumber);
+    const DbkSaoNox nx = nxp ? *nxp : DbkSaoNox{nullptr, 0, 0}; /* no bytes: no direction is forbidden */
+    with_bool(nxp != nullptr, [&](auto HAS_NX) {
+        constexpr bool NOX = !G4 && HAS_NX; /* the _g4 kernels take nx either way */
+        with_bool(sg.swz, [&](auto SWZ) {
+            if (aligned8) {
+                with_int<1, 2, 4>(waves, [&](auto WAVES) {
+                    if constexpr (WAVES == 4 || (kNarrowStrips && SWZ && !G4)) launch_sao8<G4, NOX, SWZ, WAVES>(sg, stream, a, nx);
+                });
+            } else if (sample_bytes == 1) {
+                launch_sao_t<G4, NOX, uint8_t, SWZ, false>(sg, stream, a, nx);
+            } else {
+                with_bool(pk16 && SWZ, [&](auto PK16) { /* the packed form reads the renumbered grid */
+                    if constexpr (SWZ || !PK16) launch_sao_t<G4, NOX, uint16_t, SWZ, PK16>(sg, stream, a, nx);
+                });
+            }
+        });
+    });
+    return hipGetLastError();
+}
+
 } /* namespace */
 
 hipError_t dbk_launch_sao(const DbkSaoArgs &a, int sample_bytes, hipStream_t stream, const DbkSaoNox *nxp)
 {
-    if (a.n_frames <= 0 || a.plane_w <= 0 || a.plane_h <= 0) return hipSuccess;
-    int waves = 4; /* 64 x 64 regions (waves) side by side in one workgroup */
-#ifdef HEVCDBK_DIAG
-    if (g_dbk_diag.wg_cap == 64 || g_dbk_diag.wg_cap == 128) waves = g_dbk_diag.wg_cap / 64; /* A/B knob: narrower workgroups of the packed 8-bit kernel */
-#endif
-    const bool aligned8 = a.pitch % 8 == 0 && a.frame_stride % 8 == 0 && ((uintptr_t)a.src % 8) == 0 && ((uintptr_t)a.dst % 8) == 0 &&
-                          a.plane_w % 8 == 0 && a.plane_h % 8 == 0 && a.max_v == 255 && a.band_shift == 3 &&
-                          (unsigned long long)a.pitch * (unsigned long long)a.plane_h < (1ull << 31); /* 32-bit buffer offsets */
-    if (!(sample_bytes == 1 && aligned8)) waves = 4;
-#ifdef HEVCDBK_DIAG
-    /* the narrower strips of the wg_cap knob exist for the renumbered grid only (sao8_kernel<true, 1 | 2>): with the plain
-     * 3-D numbering -- the noswz knob, or a grid too large to renumber -- the launch below is sao8_kernel<false, 4>, whose
-     * strips are 256 samples wide, and block / grid must be sized for that (half or three quarters of each strip
-     * row stayed unwritten when both knobs were set) */
-    {
-        const unsigned long long tx0 = (unsigned long long)(a.plane_w + 64 * waves - 1) / (64 * waves), tpf0 = tx0 * ((a.plane_h + 63) / 64);
-        const unsigned long long tot0 = tpf0 * (unsigned long long)a.n_frames;
-        const bool swz0 = !g_dbk_diag.noswz && tot0 + 8 < (1ull << 31) && (tot0 + 8) * tpf0 < (1ull << 32) && tpf0 * tx0 < (1ull << 32);
-        if (!swz0) waves = 4;
-    }
-#endif
-    const int strip_w = 64 * waves;
-    const dim3 block(strip_w, 1, 1), grid3((a.plane_w + strip_w - 1) / strip_w, (a.plane_h + 63) / 64, a.n_frames);
-    /* the renumbered 1-D grid (sao_strip): strips per frame and in total small enough for exact reciprocal division
-     * (dividend < 2^32 / divisor) */
-    DbkFusedGrid g = {};
-    const unsigned long long tx = grid3.x, tpf = tx * grid3.y, total = tpf * (unsigned long long)a.n_frames;
-    bool swz = total + 8 < (1ull << 31) && (total + 8) * tpf < (1ull << 32) && tpf * tx < (1ull << 32);
-#ifdef HEVCDBK_DIAG
-    if (g_dbk_diag.noswz) swz = false; /* A/B knob of the diagnostic library: the plain 3-D numbering */
-#endif
-    if (swz) {
-        g.tiles_x = (uint32_t)tx;
-        g.tiles_per_frame = (uint32_t)tpf;
-        g.total = (uint32_t)total;
-        g.magic_tpf = tpf <= 1 ? 0u : (uint32_t)((1ull << 32) / tpf + 1ull);
-        g.magic_tx = tx <= 1 ? 0u : (uint32_t)((1ull << 32) / tx + 1ull);
-        g.per_xcd = (uint32_t)((total + 7) / 8);
-    }
-    const dim3 grid = swz ? dim3(g.per_xcd * 8u, 1, 1) : grid3;
-    if (nxp) { /* the same grid and choice of kernel, the _nox twins */
-        const DbkSaoNox nx = *nxp;
-        if (sample_bytes == 1 && aligned8) {
-#ifdef HEVCDBK_DIAG
-            if (waves == 1 && swz) hipLaunchKernelGGL((sao8_nox_kernel<true, 1>), grid, block, 0, stream, a, g, nx);
-            else if (waves == 2 && swz) hipLaunchKernelGGL((sao8_nox_kernel<true, 2>), grid, block, 0, stream, a, g, nx);
-            else
-#endif
-            if (swz) hipLaunchKernelGGL((sao8_nox_kernel<true, 4>), grid, block, 0, stream, a, g, nx);
-            else hipLaunchKernelGGL((sao8_nox_kernel<false, 4>), grid, block, 0, stream, a, g, nx);
-        } else if (sample_bytes == 1) {
-            if (swz) hipLaunchKernelGGL((sao_nox_kernel<uint8_t, true>), grid, block, 0, stream, a, g, nx);
-            else hipLaunchKernelGGL((sao_nox_kernel<uint8_t, false>), grid, block, 0, stream, a, g, nx);
-        } else {
-            const bool pk16 = a.max_v <= 4095 && a.band_shift >= 3 && (1 << (a.band_shift + 5)) - 1 == a.max_v && a.pitch % 4 == 0 &&
-                              a.frame_stride % 4 == 0 && ((uintptr_t)a.src % 4) == 0 && ((uintptr_t)a.dst % 4) == 0 && a.plane_w % 8 == 0 &&
-                              a.plane_h % 8 == 0 && (unsigned long long)a.pitch * (unsigned long long)a.plane_h < (1ull << 31);
-            if (swz && pk16) hipLaunchKernelGGL((sao_nox_kernel<uint16_t, true, true>), grid, block, 0, stream, a, g, nx);
-            else if (swz) hipLaunchKernelGGL((sao_nox_kernel<uint16_t, true>), grid, block, 0, stream, a, g, nx);
-            else hipLaunchKernelGGL((sao_nox_kernel<uint16_t, false>), grid, block, 0, stream, a, g, nx);
-        }
-        return hipGetLastError();
-    }
-    /* 8-bit planes whose rows and frames are 8-byte aligned take the packed kernel (every lane moves 8 bytes at once) */
-    if (sample_bytes == 1 && aligned8) {
-#ifdef HEVCDBK_DIAG
-        if (waves == 1 && swz) hipLaunchKernelGGL((sao8_kernel<true, 1>), grid, block, 0, stream, a, g);
-        else if (waves == 2 && swz) hipLaunchKernelGGL((sao8_kernel<true, 2>), grid, block, 0, stream, a, g);
-        else
-#endif
-        if (swz) hipLaunchKernelGGL((sao8_kernel<true, 4>), grid, block, 0, stream, a, g);
-        else hipLaunchKernelGGL((sao8_kernel<false, 4>), grid, block, 0, stream, a, g);
-    } else if (sample_bytes == 1) {
-        if (swz) hipLaunchKernelGGL((sao_kernel<uint8_t, true>), grid, block, 0, stream, a, g);
-        else hipLaunchKernelGGL((sao_kernel<uint8_t, false>), grid, block, 0, stream, a, g);
-    } else {
-        /* up to 12 bit (the packed procedure's int16 fields; SaoOffsetVal scaled as the standard does), planes the buffer
-         * resources can address: the packed path in every wave off the picture border */
-        const bool pk16 = a.max_v <= 4095 && a.band_shift >= 3 && (1 << (a.band_shift + 5)) - 1 == a.max_v && a.pitch % 4 == 0 &&
-                          a.frame_stride % 4 == 0 && ((uintptr_t)a.src % 4) == 0 && ((uintptr_t)a.dst % 4) == 0 && a.plane_w % 8 == 0 &&
-                          a.plane_h % 8 == 0 && (unsigned long long)a.pitch * (unsigned long long)a.plane_h < (1ull << 31);
-        if (swz && pk16) hipLaunchKernelGGL((sao_kernel<uint16_t, true, true>), grid, block, 0, stream, a, g);
-        else if (swz) hipLaunchKernelGGL((sao_kernel<uint16_t, true>), grid, block, 0, stream, a, g);
-        else hipLaunchKernelGGL((sao_kernel<uint16_t, false>), grid, block, 0, stream, a, g);
-    }
-    return hipGetLastError();
+    return launch_sao<false>(a, sample_bytes, stream, nxp);
 }
 
 /* planes whose sizes are multiples of 4 (the _g4 entries): dbk_launch_sao's grid and choice of kernel without its demand for multiples
  * of 8, the _g4 kernels; nxp == NULL: no boundary bytes */
 hipError_t dbk_launch_sao_g4(const DbkSaoArgs &a, int sample_bytes, hipStream_t stream, const DbkSaoNox *nxp)
 {
-    if (a.n_frames <= 0 || a.plane_w <= 0 || a.plane_h <= 0) return hipSuccess;
-    const bool small = (unsigned long long)a.pitch * (unsigned long long)a.plane_h < (1ull << 31); /* 32-bit buffer offsets */
-    const bool aligned8 = a.pitch % 8 == 0 && a.frame_stride % 8 == 0 && ((uintptr_t)a.src % 8) == 0 && ((uintptr_t)a.dst % 8) == 0 &&
-                          a.max_v == 255 && a.band_shift == 3 && small;
-    const dim3 block(256, 1, 1), grid3((a.plane_w + 255) / 256, (a.plane_h + 63) / 64, a.n_frames);
-    DbkFusedGrid g = {};
-    const unsigned long long tx = grid3.x, tpf = tx * grid3.y, total = tpf * (unsigned long long)a.n_frames;
-    const bool swz = total + 8 < (1ull << 31) && (total + 8) * tpf < (1ull << 32) && tpf * tx < (1ull << 32);
-    if (swz) {
-        g.tiles_x = (uint32_t)tx;
-        g.tiles_per_frame = (uint32_t)tpf;
-        g.total = (uint32_t)total;
-        g.magic_tpf = tpf <= 1 ? 0u : (uint32_t)((1ull << 32) / tpf + 1ull);
-        g.magic_tx = tx <= 1 ? 0u : (uint32_t)((1ull << 32) / tx + 1ull);
-        g.per_xcd = (uint32_t)((total + 7) / 8);
-    }
-    const dim3 grid = swz ? dim3(g.per_xcd * 8u, 1, 1) : grid3;
-    const DbkSaoNox nx = nxp ? *nxp : DbkSaoNox{nullptr, 0, 0};
-    if (sample_bytes == 1 && aligned8) {
-        if (swz) hipLaunchKernelGGL((sao8_g4_kernel<true, 4>), grid, block, 0, stream, a, g, nx);
-        else hipLaunchKernelGGL((sao8_g4_kernel<false, 4>), grid, block, 0, stream, a, g, nx);
-    } else if (sample_bytes == 1) {
-        if (swz) hipLaunchKernelGGL((sao_g4_kernel<uint8_t, true>), grid, block, 0, stream, a, g, nx);
-        else hipLaunchKernelGGL((sao_g4_kernel<uint8_t, false>), grid, block, 0, stream, a, g, nx);
-    } else {
-        const bool pk16 = a.max_v <= 4095 && a.band_shift >= 3 && (1 << (a.band_shift + 5)) - 1 == a.max_v && a.pitch % 4 == 0 &&
-                          a.frame_stride % 4 == 0 && ((uintptr_t)a.src % 4) == 0 && ((uintptr_t)a.dst % 4) == 0 && small;
-        if (swz && pk16) hipLaunchKernelGGL((sao_g4_kernel<uint16_t, true, true>), grid, block, 0, stream, a, g, nx);
-        else if (swz) hipLaunchKernelGGL((sao_g4_kernel<uint16_t, true>), grid, block, 0, stream, a, g, nx);
-        else hipLaunchKernelGGL((sao_g4_kernel<uint16_t, false>), grid, block, 0, stream, a, g, nx);
-    }
-    return hipGetLastError();
+    return launch_sao<true>(a, sample_bytes, stream, nxp);
 }
 
 /* ---- rectangular CTBs (4:2:2 chroma: CtbSizeY / 2 wide, CtbSizeY tall) ----------------------------------------------------

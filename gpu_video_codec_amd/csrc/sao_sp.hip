@@ -20,6 +20,7 @@
 #include <hip/hip_runtime.h>
 
 #include "deblock_kernels.h"
+#include "launch_select.h"
 #include "sao_sp.h"
 
 namespace {
@@ -212,34 +213,16 @@ bool dbk_sao_sp_packed_supports(const DbkSaoArgs &a, int sample_bytes)
 
 hipError_t dbk_launch_sao_sp(const DbkSaoArgs &a, const DbkSaoCtb *params_cr, int sample_bytes, hipStream_t stream, const DbkSaoNox *nxp)
 {
-    if (a.n_frames <= 0 || a.plane_w <= 0 || a.plane_h <= 0) return hipSuccess;
-    const dim3 block(256, 1, 1), grid3((a.plane_w + 255) / 256, (a.plane_h + 63) / 64, a.n_frames);
-    DbkFusedGrid g = {};
-    const unsigned long long tx = grid3.x, tpf = tx * grid3.y, total = tpf * (unsigned long long)a.n_frames;
-    const bool swz = total + 8 < (1ull << 31) && (total + 8) * tpf < (1ull << 32) && tpf * tx < (1ull << 32);
-    if (swz) {
-        g.tiles_x = (uint32_t)tx;
-        g.tiles_per_frame = (uint32_t)tpf;
-        g.total = (uint32_t)total;
-        g.magic_tpf = tpf <= 1 ? 0u : (uint32_t)((1ull << 32) / tpf + 1ull);
-        g.magic_tx = tx <= 1 ? 0u : (uint32_t)((1ull << 32) / tx + 1ull);
-        g.per_xcd = (uint32_t)((total + 7) / 8);
-    }
-    const dim3 grid = swz ? dim3(g.per_xcd * 8u, 1, 1) : grid3;
+    using namespace dbksel;
+    if (nothing_to_do(a)) return hipSuccess;
+    const SaoGrid sg = sao_grid(a);
     const DbkSaoNox nx = nxp ? *nxp : DbkSaoNox{nullptr, 0, 0};
     const bool packed = dbk_sao_sp_packed_supports(a, sample_bytes);
-    if (sample_bytes == 1 && packed) {
-        if (swz) hipLaunchKernelGGL(sao8_sp_kernel<true>, grid, block, 0, stream, a, params_cr, g, nx);
-        else hipLaunchKernelGGL(sao8_sp_kernel<false>, grid, block, 0, stream, a, params_cr, g, nx);
-    } else if (sample_bytes == 1) {
-        if (swz) hipLaunchKernelGGL((sao_sp_kernel<uint8_t, true>), grid, block, 0, stream, a, params_cr, g, nx);
-        else hipLaunchKernelGGL((sao_sp_kernel<uint8_t, false>), grid, block, 0, stream, a, params_cr, g, nx);
-    } else if (packed) {
-        if (swz) hipLaunchKernelGGL(sao16_sp_kernel<true>, grid, block, 0, stream, a, params_cr, g, nx);
-        else hipLaunchKernelGGL(sao16_sp_kernel<false>, grid, block, 0, stream, a, params_cr, g, nx);
-    } else {
-        if (swz) hipLaunchKernelGGL((sao_sp_kernel<uint16_t, true>), grid, block, 0, stream, a, params_cr, g, nx);
-        else hipLaunchKernelGGL((sao_sp_kernel<uint16_t, false>), grid, block, 0, stream, a, params_cr, g, nx);
-    }
+    with_bool(sg.swz, [&](auto SWZ) {
+        if (sample_bytes == 1 && packed) hipLaunchKernelGGL(sao8_sp_kernel<SWZ>, sg.grid, sg.block, 0, stream, a, params_cr, sg.g, nx);
+        else if (sample_bytes == 1) hipLaunchKernelGGL((sao_sp_kernel<uint8_t, SWZ>), sg.grid, sg.block, 0, stream, a, params_cr, sg.g, nx);
+        else if (packed) hipLaunchKernelGGL(sao16_sp_kernel<SWZ>, sg.grid, sg.block, 0, stream, a, params_cr, sg.g, nx);
+        else hipLaunchKernelGGL((sao_sp_kernel<uint16_t, SWZ>), sg.grid, sg.block, 0, stream, a, params_cr, sg.g, nx);
+    });
     return hipGetLastError();
 }

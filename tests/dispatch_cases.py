@@ -1,6 +1,6 @@
 """Which kernel the device entries launch: the launchers' guards restated in Python, and operand sets on both sides of each.
 
-Every guard below restates a predicate of the C++ launchers clause by clause; each clause names the line it restates.  predict()
+Every guard below restates a predicate of the C++ launchers clause by clause; each names the function or helper it restates.  predict()
 walks an operand set through the public entry it names (argument checks, AUTO / FUSED_AUTO choice, launcher) and returns the
 error the entry returns, or the launches it enqueues: kernel name, template arguments, grid, block and dynamic LDS.  The GPU
 tests (test_gpu_dispatch.py) compare that with what a captured call really enqueues, so a change to a guard or to the launch
@@ -17,11 +17,11 @@ import numpy as np
 ERR_ARG, ERR_UNSUPPORTED = -5, -8  # include/hevc_deblock.h
 TWO31, TWO32 = 1 << 31, 1 << 32
 
-WG_CAP = 512                                   # deblock_kernels.hip:1004 wg_cap()
-FUSED_TILE = {1: (192, 128), 2: (128, 128)}    # deblock_sao_fused.inc:26-27, 196 (tile w, h per sample width)
-FUSED_THREADS = {1: 448, 2: 320}               # deblock_sao_fused.inc:31, 199
-FUSED_LDS = {1: (128 + 8) * 208, 2: (128 + 8) * 288}  # deblock_sao_fused.inc:34, 201
-SAO_STRIP = 256                                # sao.hip:436, 456: 4 waves of 64-sample regions
+WG_CAP = 512                                   # deblock_kernels.hip wg_cap()
+FUSED_TILE = {1: (192, 128), 2: (128, 128)}    # kFusedTileW x kFusedTile, kFused16Tile (deblock_sao_fused.inc)
+FUSED_THREADS = {1: 448, 2: 320}               # kFusedThreads, kFused16Threads: fused_shape
+FUSED_LDS = {1: (128 + 8) * 208, 2: (128 + 8) * 288}  # kFusedLds, kFused16Lds: fused_shape
+SAO_STRIP = 256                                # dbksel::sao_grid: 4 waves of 64-sample regions
 
 
 # ---- operands ------------------------------------------------------------------------------------------------------------
@@ -56,11 +56,11 @@ class Plane:
         return (1 << self.bd) - 1
 
     @property
-    def nbx(self):  # deblock_host.cpp:164
+    def nbx(self):  # planes_to_args
         return self.w // 8 + 1
 
     @property
-    def nby(self):  # deblock_host.cpp:165
+    def nby(self):  # planes_to_args
         return self.h // 8 + 1
 
     def nbytes(self):
@@ -150,45 +150,45 @@ def _all(census, guard, clauses):
 # ---- restated guards ------------------------------------------------------------------------------------------------------
 
 def api_align_ok(p, census=_NULL):
-    """planes_to_args (deblock_host.cpp:181-184) and sao_args (deblock_host_h265.cpp:303-305): one 4-sample word"""
+    """planes_to_args (deblock_host.cpp) and sao_args (deblock_host_h265.cpp): one 4-sample word"""
     al = 4 * p.sb
     return _all(census, "api alignment", [("pitch %% %d" % al, p.P % al == 0), ("frame_stride %% %d" % al, p.fs % al == 0),
                                           ("src %% %d" % al, p.src_off % al == 0), ("dst %% %d" % al, p.dst_off % al == 0)])
 
 
 def packed_supports(p, census=_NULL, guard="dbk_packed_supports"):
-    """dbk_packed_supports (deblock_kernels.hip:985-997) with the default tables; dbk_packed_h265_supports (1332-1342) is the
-    same predicate (the Table 8-12 tc always fits, 1337)"""
-    c = [("pitch * plane_h < 2^31", p.P * p.h < TWO31)]                        # :988 / :1335
+    """dbk_packed_supports with the default tables; dbk_packed_h265_supports is the same predicate (the Table 8-12 tc always
+    fits)"""
+    c = [("pitch * plane_h < 2^31", p.P * p.h < TWO31)]
     if p.sb == 1:
-        c.append(("8-bit max_v == 255", p.max_v == 255))                         # :991 / :1338
+        c.append(("8-bit max_v == 255", p.max_v == 255))
     else:
-        c += [("max_v <= 4095", p.max_v <= 4095), ("pitch % 8", p.P % 8 == 0),  # :995-996 / :1340-1341
+        c += [("max_v <= 4095", p.max_v <= 4095), ("pitch % 8", p.P % 8 == 0),
               ("frame_stride % 8", p.fs % 8 == 0), ("src % 8", p.src_off % 8 == 0), ("dst % 8", p.dst_off % 8 == 0)]
     return _all(census, guard, c)
 
 
 def plan_packed(p, census=_NULL):
-    """plan_packed (deblock_kernels.hip:1053-1092) -> (linear, grid, block)"""
+    """plan_packed (deblock_kernels.hip) -> (linear, grid, block)"""
     cap, nbx, nby, n = WG_CAP, p.nbx, p.nby, p.n
     nb = nbx * nby
-    wg = (nb + 63) // 64 * 64 if nb < cap else cap                            # :1058
-    wpf = (nb + wg - 1) // wg                                                    # :1059
-    total = (wpf * n + 7) // 8 * 8                                               # :1060
-    want = census.clause("plan_packed", "nbx > cap", nbx > cap)                  # :1067
-    exact = _all(census, "plan_packed", [                                        # :1068-1069
+    wg = (nb + 63) // 64 * 64 if nb < cap else cap
+    wpf = (nb + wg - 1) // wg
+    total = (wpf * n + 7) // 8 * 8
+    want = census.clause("plan_packed", "nbx > cap", nbx > cap)  # want_linear
+    exact = _all(census, "plan_packed", [  # linear
         ("wpf >= 2", wpf >= 2), ("nbx >= 2", nbx >= 2), ("(nb + 1024) * nbx < 2^32", (nb + 1024) * nbx < TWO32),
         ("total * wpf < 2^32", total * wpf < TWO32), ("total < 2^31", total < TWO31)])
     linear = want and exact
     if linear:
-        return True, (total, 1, 1), (wg, 1, 1)                                   # :1080-1081
-    per_wg = min(nbx, cap)                                                       # :1088-1090
+        return True, (total, 1, 1), (wg, 1, 1)
+    per_wg = min(nbx, cap)
     bx = (per_wg + 63) // 64 * 64
     return False, (nby, n, (nbx + bx - 1) // bx), (bx, 1, 1)
 
 
 def generic_launch(p, h265, cf=1):
-    """launch_generic_t (deblock_kernels.hip:144-154), launch_t (deblock_h265.hip:220-227), dbk_launch_h265_cf"""
+    """launch_generic_t (its own dim3), dbk_launch_h265 / dbk_launch_h265_cf (dbksel::generic_grid / generic_block)"""
     grid, block = ((p.nbx + 63) // 64, (p.nby + 3) // 4, p.n), (64, 4, 1)
     t = "u8" if p.sb == 1 else "u16"
     if not h265:
@@ -199,7 +199,7 @@ def generic_launch(p, h265, cf=1):
 
 
 def packed_launch(p, h265, census=_NULL):
-    """launch_packed_t (deblock_kernels.hip:1033-1048) / dbk_launch_packed_h265_cf (1391-1408); QP maps of 4:2:0 planes
+    """launch_packed_sel<Gen::kRef> / <Gen::kH265> after fold_operands (deblock_kernels.hip); QP maps of 4:2:0 planes
     (the _cf kernels of 4:2:2 / 4:4:4 QP-map chroma are not among the cases)"""
     lin, grid, block = plan_packed(p, census)
     L, wide, qm = int(lin), int(p.sb == 2 and not p.chroma and p.max_v > 2047), int(p.qpmap > 0)
@@ -215,7 +215,7 @@ def packed_launch(p, h265, census=_NULL):
 
 
 def deblock_launch(p, h265, variant=KERNEL_AUTO, cf=1, census=_NULL):
-    """launch (deblock_host.cpp:227-237) / launch_h265 (deblock_host_h265.cpp:106-127): a launch or an error code"""
+    """launch (deblock_host.cpp) / launch_h265 (deblock_host_h265.cpp): a launch or an error code"""
     ok = packed_supports(p, census, "dbk_packed_h265_supports" if h265 else "dbk_packed_supports")
     if variant == KERNEL_PACKED and not ok:
         return ERR_UNSUPPORTED
@@ -225,12 +225,12 @@ def deblock_launch(p, h265, variant=KERNEL_AUTO, cf=1, census=_NULL):
 
 
 def multi_supports(planes, census=_NULL):
-    """dbk_multi_supports (deblock_kernels.hip:1294-1306) after planes_fuse's own checks (deblock_host.cpp:785-791)"""
+    """dbk_multi_supports after planes_fuse's own checks (deblock_host.cpp)"""
     if not (2 <= len(planes) <= 3) or planes[0].chroma or not all(q.chroma for q in planes[1:]):
         return False
     p0 = planes[0]
     each = all([packed_supports(q, census) for q in planes])
-    return _all(census, "dbk_multi_supports", [                                                 # :1300-1305
+    return _all(census, "dbk_multi_supports", [
         ("same sample width", all(q.sb == p0.sb for q in planes)), ("no QP map", not any(q.qpmap for q in planes)),
         ("same max_v", all(q.max_v == p0.max_v for q in planes)), ("same n_frames", all(q.n == p0.n for q in planes)),
         ("chroma nbx <= luma nbx", all(q.nbx <= p0.nbx for q in planes)), ("each plane packed", each),
@@ -238,7 +238,7 @@ def multi_supports(planes, census=_NULL):
 
 
 def multi_launch(planes):
-    """dbk_launch_packed_multi (deblock_kernels.hip:1308-1329)"""
+    """dbk_launch_packed_multi"""
     p0 = planes[0]
     rows = sum(q.nby for q in planes)
     bx = (min(p0.nbx, WG_CAP) + 63) // 64 * 64
@@ -249,7 +249,7 @@ def multi_launch(planes):
 
 
 def sao_strips(p):
-    """(tx, tpf, total) of dbk_launch_sao's strip grid (sao.hip:456-461)"""
+    """(tx, tpf, total) of dbk_launch_sao's strip grid: dbksel::sao_strips"""
     tx = (p.w + SAO_STRIP - 1) // SAO_STRIP
     tpf = tx * ((p.h + 63) // 64)
     return tx, tpf, tpf * p.n
@@ -257,25 +257,25 @@ def sao_strips(p):
 
 def sao_swz(p, census=_NULL):
     tx, tpf, total = sao_strips(p)
-    return _all(census, "sao swz", [("total + 8 < 2^31", total + 8 < TWO31),                     # sao.hip:462
+    return _all(census, "sao swz", [("total + 8 < 2^31", total + 8 < TWO31),                     # dbksel::renumbered_grid: exact
                                     ("(total + 8) * tpf < 2^32", (total + 8) * tpf < TWO32),
                                     ("tpf * tx < 2^32", tpf * tx < TWO32)])
 
 
 def sao_launch(p, census=_NULL):
-    """dbk_launch_sao (sao.hip:433-498), the product library"""
+    """dbk_launch_sao (launch_sao<false> in sao.hip), the product library"""
     tx, tpf, total = sao_strips(p)
     swz = sao_swz(p, census)
-    grid = ((total + 7) // 8 * 8, 1, 1) if swz else (tx, (p.h + 63) // 64, p.n)                  # :472-474
+    grid = ((total + 7) // 8 * 8, 1, 1) if swz else (tx, (p.h + 63) // 64, p.n)  # dbksel::sao_grid
     block = (SAO_STRIP, 1, 1)
     if p.sb == 1:
-        a8 = _all(census, "sao aligned8", [                                                     # :440-442
+        a8 = _all(census, "sao aligned8", [  # launch_sao: aligned8
             ("pitch % 8", p.P % 8 == 0), ("frame_stride % 8", p.fs % 8 == 0), ("src % 8", p.src_off % 8 == 0),
             ("dst % 8", p.dst_off % 8 == 0), ("pitch * h < 2^31", p.P * p.h < TWO31)])
         if a8:
             return Launch("sao8_kernel", (int(swz), 4), grid, block)
         return Launch("sao_kernel", ("u8", int(swz), 0), grid, block)
-    pk = _all(census, "sao pk16", [                                                               # :490-492
+    pk = _all(census, "sao pk16", [  # launch_sao: pk16
         ("max_v <= 4095", p.max_v <= 4095), ("pitch % 4", p.P % 4 == 0), ("frame_stride % 4", p.fs % 4 == 0),
         ("src % 4", p.src_off % 4 == 0), ("dst % 4", p.dst_off % 4 == 0), ("pitch * h < 2^31", p.P * p.h < TWO31)])
     return Launch("sao_kernel", ("u16", int(swz), int(swz and pk)), grid, block)
@@ -288,36 +288,36 @@ def fused_tiles(p):
 
 
 def fused_supports(p, census=_NULL):
-    """dbk_deblock_sao_supports (deblock_kernels.hip:1414-1433) for operands that passed sao_args / planes_to_args: by_count 0,
+    """dbk_deblock_sao_supports for operands that passed sao_args / planes_to_args: by_count 0,
     equal max_v, band_shift = bit depth - 5 and equal geometry always hold there"""
-    if not census.clause("dbk_deblock_sao_supports", "max_v <= 4095", p.max_v <= 4095):         # :1418 / :1421
+    if not census.clause("dbk_deblock_sao_supports", "max_v <= 4095", p.max_v <= 4095):
         return False
-    if not packed_supports(p, census):                                                           # :1423
+    if not packed_supports(p, census):
         return False
     al = 4 * p.sb
     tiles = fused_tiles(p)[2]
     return _all(census, "dbk_deblock_sao_supports", [
-        ("n_frames <= 65535", p.n <= 65535),                                                     # :1424
-        ("pitch * h < 2^31", p.P * p.h < TWO31), ("dst %% %d" % al, p.dst_off % al == 0),        # :1426-1427
-        ("tiles * n + 8 < 2^31", tiles * p.n + 8 < TWO31), ("tiles^2 < 2^32", tiles * tiles < TWO32),  # :1431-1432
+        ("n_frames <= 65535", p.n <= 65535),
+        ("pitch * h < 2^31", p.P * p.h < TWO31), ("dst %% %d" % al, p.dst_off % al == 0),
+        ("tiles * n + 8 < 2^31", tiles * p.n + 8 < TWO31), ("tiles^2 < 2^32", tiles * tiles < TWO32),
         ("(tiles * n + 8) * tiles < 2^32", (tiles * p.n + 8) * tiles < TWO32)])
 
 
 def fused_grid(p):
-    """fused_grid (deblock_kernels.hip:1436-1448): 1-D, a multiple of 8"""
+    """fused_grid -> dbksel::renumbered_grid: 1-D, a multiple of 8"""
     total = fused_tiles(p)[2] * p.n
     return (total + 7) // 8 * 8
 
 
 def fused_launch(p, h265, cf=1):
-    """dbk_launch_deblock_sao (1472-1492) / dbk_launch_deblock_sao_h265_cf (1506-1536), scalar QP"""
+    """launch_fused<Gen::kRef> / <Gen::kH265> (dbk_launch_deblock_sao / _h265_cf), scalar QP"""
     k = "dbk_sao_fused%s%s_kernel" % ("" if p.sb == 1 else "16", "_h265" if h265 else "")
     args = (int(p.chroma), 0) if p.sb == 1 else (int(p.chroma), int(not p.chroma and p.max_v > 2047), 0)
     return Launch(k, args, (fused_grid(p), 1, 1), (FUSED_THREADS[p.sb], 1, 1), FUSED_LDS[p.sb])
 
 
 def fused_multi_launch(planes, h265):
-    """dbk_launch_deblock_sao_multi[_h265_cf] (1538-1604), scalar QP"""
+    """launch_fused_multi<Gen::kRef> / <Gen::kH265> (dbk_launch_deblock_sao_multi[_h265_cf]), scalar QP"""
     p0 = planes[0]
     k = "dbk_sao_fused_multi%s_kernel" % ("_h265" if h265 else "")
     return Launch(k, (p0.sb, int(p0.sb == 2 and p0.max_v > 2047), 0), (sum(fused_grid(q) for q in planes), 1, 1),
@@ -325,7 +325,7 @@ def fused_multi_launch(planes, h265):
 
 
 def rows_x2_launch(p, ctb_log2_w, per_frame):
-    """dbk_launch_sao_rows_x2 (sao.hip:517-534): one thread per square-CTB entry"""
+    """dbk_launch_sao_rows_x2: one thread per square-CTB entry"""
     s = 1 << ctb_log2_w
     total = ((p.w + s - 1) // s) * ((p.h + s - 1) // s) * (p.n if per_frame else 1)
     return Launch("sao_rows_x2_kernel", (), ((total + 255) // 256, 1, 1), (256, 1, 1))
@@ -334,7 +334,7 @@ def rows_x2_launch(p, ctb_log2_w, per_frame):
 # ---- the entries ----------------------------------------------------------------------------------------------------------
 
 def _sao_args_rc(p):
-    """sao_args (deblock_host_h265.cpp:294-317) for the operands the cases vary"""
+    """sao_args (deblock_host_h265.cpp) for the operands the cases vary"""
     if not api_align_ok(p):
         return ERR_UNSUPPORTED
     if p.n > 65535 or p.h > 65535:
@@ -343,7 +343,7 @@ def _sao_args_rc(p):
 
 
 def _dbk_args_rc(p):
-    """planes_to_args (deblock_host.cpp:175-205)"""
+    """planes_to_args (deblock_host.cpp)"""
     if not api_align_ok(p):
         return ERR_UNSUPPORTED
     if p.n > 65535:
@@ -352,7 +352,7 @@ def _dbk_args_rc(p):
 
 
 def _dbk_sao_plane(p, h265, fused, cf, census):
-    """deblock_sao_plane[_h265[_cf]] (deblock_host_h265.cpp:357-445)"""
+    """deblock_sao_plane[_h265[_cf]] (deblock_host_h265.cpp)"""
     can = fused_supports(p, census)
     if fused == FUSED_ON and not can:
         return ERR_UNSUPPORTED
@@ -375,7 +375,7 @@ def predict(case, census=_NULL):
         r = deblock_launch(p, h265, case.variant, case.cf, census)
         return r if isinstance(r, int) else [r]
     if e == "filter_planes":
-        for p in pl:  # hevc_deblocking_filter_device_planes (deblock_host.cpp:827-830)
+        for p in pl:  # hevc_deblocking_filter_device_planes
             rc = _dbk_args_rc(p) or (ERR_ARG if p.n != pl[0].n else 0)
             if rc:
                 return rc

@@ -280,6 +280,9 @@ P1080 = [("960x540_8", 960, 540, 8, 1, False, 5), ("960x540_8m", 960, 540, 8, 1,
 FORMATS = [("422_964x24", 964, 24, 8, 2, True, 4), ("422_964x24_10", 964, 24, 10, 2, False, 5), ("444_20x28", 20, 28, 8, 3, True, 3),
            ("444_20x28_10", 20, 28, 10, 3, False, 4)]
 CASES = SMALL + WIDE + TILES8 + TILES16 + P1080 + FORMATS
+# 4:2:2 / 4:4:4 planes just over 512 blocks per row, two block rows: the packed kernels' row-major map in the formats' own kernels
+WIDE_FORMATS = [("422_4100x12", 4100, 12, 8, 2, True, 6), ("422_4100x12_10", 4100, 12, 10, 2, False, 6),
+                ("444_4100x12", 4100, 12, 8, 3, False, 6), ("444_4100x12_10", 4100, 12, 10, 3, True, 6)]
 CQP, TC_DIV2, QP = 2, 1, 37
 UNIT_LOG2 = 3
 SL_CTB_LOG2 = 4

@@ -106,9 +106,9 @@ def check(dst, want, what):
 
 # ---- deblocking: the 32-bit kernel and the packed kernels, both block-to-lane maps -----------------------------------------------
 
-@pytest.mark.parametrize("spec", G.CASES, ids=lambda s: s[0])
+@pytest.mark.parametrize("spec", G.CASES + G.WIDE_FORMATS, ids=lambda s: s[0])
 def test_filter_device(ctx, lib, spec):
-    from kernel_capture import kernels_enqueued
+    from kernel_capture import kernels_enqueued, parse_kernel
     L = lib.lib()
     c = G.dbk_case(spec, frames=2)
     so, dso = sl_operand(ctx, lib, c["pairs"])
@@ -128,6 +128,8 @@ def test_filter_device(ctx, lib, spec):
                 assert names(k)[0] == "dbk_h265_g4_kernel"
             else:
                 assert names(k)[0] in ("dbk_packed_h265_g4_kernel", "dbk_packed16_h265_g4_kernel"), names(k)
+                if variant != lib.KERNEL_PACKED | lib.MAP_ROWS and c["w"] // 8 + 1 > 512:  # rows wider than a workgroup: row-major
+                    assert parse_kernel(k[0][0])[1] == (1, c["cf"]), parse_kernel(k[0][0])
             assert call(None) == 0
             ctx.synchronize()
             check(pl.dst, want, (spec[0], sl, variant))
@@ -294,7 +296,7 @@ def picture_expected(pic, extra):
 
 
 def run_picture(ctx, lib, pic, what):
-    from kernel_capture import kernels_enqueued
+    from kernel_capture import kernels_enqueued, parse_kernel
     L = lib.lib()
     bo, dbo = borders_operand(ctx, lib, pic["layouts"])
     so, dso = sl_operand(ctx, lib, pic["pairs"], pic["sl_log2"])
@@ -325,6 +327,9 @@ def run_picture(ctx, lib, pic, what):
             big = [x for x in names(k) if x.startswith("dbk_") and "rows_x2" not in x]
             if fused == lib.FUSED_AUTO:
                 assert big == ["dbk_sao_fused_multi_h265_g4_kernel"], names(k)
+                # the instantiation of this container, depth (12 bit: the WIDE luma form) and chroma format
+                multi = [parse_kernel(x[0])[1] for x in k if parse_kernel(x[0])[0] == big[0]]
+                assert multi == [(pic["sb"], int(pic["depth"] == 12), pic["cf"])], multi
             else:
                 assert len([x for x in names(k) if x.endswith("_g4_kernel")]) == 4, names(k)   # deblocking and SAO of Cb and Cr
             assert call(None) == 0
@@ -342,10 +347,12 @@ def test_1080p_planes_in_one_launch(ctx, lib, depth):
     run_picture(ctx, lib, picture_case(1920, 1080, depth, 1, 2, 6, 1080 + depth), ("1080p", depth))
 
 
-@pytest.mark.parametrize("W,H,depth,cf,log2", [(1928, 24, 8, 2, 5), (1928, 24, 10, 2, 4), (72, 40, 8, 1, 4), (264, 248, 10, 1, 5)])
+@pytest.mark.parametrize("W,H,depth,cf,log2", [(1928, 24, 8, 2, 5), (1928, 24, 10, 2, 4), (72, 40, 8, 1, 4), (264, 248, 10, 1, 5),
+                                                 (1928, 24, 12, 2, 4), (72, 40, 12, 1, 4)])
 def test_other_pictures_in_one_launch(ctx, lib, W, H, depth, cf, log2):
     """4:2:2 chroma 964x24 of a 1928x24 picture (CTBs twice as tall as wide: the parameters and boundary bytes rewritten for square
-    CTBs), and small 4:2:0 pictures whose chroma planes are g4 in both directions"""
+    CTBs), and small 4:2:0 pictures whose chroma planes are g4 in both directions; each also at 12 bit, the WIDE luma form of the kernel.
+    (4:4:4 has no such picture: its chroma planes have the luma plane's size, and the entries refuse a luma plane that is no multiple of 8)"""
     run_picture(ctx, lib, picture_case(W, H, depth, cf, G.FRAMES, log2, W + H + depth), (W, H, depth, cf))   # five frames: every border CTB has been every kind
 
 
