@@ -51,7 +51,7 @@ EXPORTS = [
     "hevcdbk_h265_deblock_sao_device_g4", "hevcdbk_h265_deblock_sao_device_planes_g4",
     "hevcdbk_h265_filter_device_sp", "hevcdbk_sao_filter_device_sp", "hevcdbk_h265_deblock_sao_device_sp",
     "hevcdbk_h265_deblock_sao_device_sp_fused", "hevcdbk_h265_deblock_sao_device_nv12",
-    "hevcdbk_sao_stats_device", "hevcdbk_sao_pick_device",
+    "hevcdbk_sao_stats_device", "hevcdbk_sao_pick_device", "hevcdbk_sao_stats_device_sp",
 ]
 
 # chroma_format_idc of the spec-exact mode and SAO (HEVCDBK_CHROMA_*): 4:0:0, 4:2:0, 4:2:2, 4:4:4
@@ -332,6 +332,10 @@ def lib():
         L.hevcdbk_sao_stats_device.argtypes = [C.c_void_p, C.POINTER(DevicePlanes), C.c_void_p, C.c_size_t, C.c_size_t, C.c_uint, C.c_uint,
                                                C.c_void_p, C.c_uint, C.c_size_t, C.POINTER(SaoBorders), C.c_void_p, C.c_uint, C.c_size_t,
                                                C.c_void_p]
+        # the same of a semi-planar chroma plane: one ctb_log2, Cb's array and Cr's
+        L.hevcdbk_sao_stats_device_sp.argtypes = [C.c_void_p, C.POINTER(DevicePlanes), C.c_void_p, C.c_size_t, C.c_size_t, C.c_uint, C.c_void_p,
+                                                  C.c_uint, C.c_size_t, C.POINTER(SaoBorders), C.c_void_p, C.c_void_p, C.c_uint, C.c_size_t,
+                                                  C.c_void_p]
         L.hevcdbk_sao_pick_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint, C.c_size_t, C.c_uint, C.c_uint, C.c_uint, C.c_uint,
                                               C.c_uint, C.c_void_p, C.c_void_p, C.c_uint, C.c_size_t, C.c_void_p, C.c_void_p]
         L.hevc_deblock_sao_h265_device_planes.argtypes = [C.c_void_p, C.POINTER(DevicePlanes), C.c_uint, C.c_uint, C.POINTER(H265Params),

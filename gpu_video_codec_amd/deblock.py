@@ -472,13 +472,31 @@ class Context:
 
     def sao_stats_device(self, planes, org_ptr, ctb_log2, *, org_pitch=None, org_frame_stride=None, ctb_log2_h=None, chroma_format="420",
                          keep_ptr=None, keep_stride=0, keep_frame_stride=0, borders=None, out_ptr, out_stride, out_frame_stride=0,
-                         stream=None):
+                         stream=None, semi_planar=False, out_cr_ptr=None):
         """hevcdbk_sao_stats_device: per-CTB SAO statistics of the deblocked plane planes.src against the original at org_ptr (device
         memory, the same geometry and container; pitch and frame stride default to the plane's).  out_ptr: device memory for one
         _lib.SaoStats (numpy: _lib.SAO_STATS_DTYPE) per CTB, out_stride entries per CTB row, out_frame_stride entries between frames;
         every entry of the grid is written, nothing needs clearing.  ctb_log2 = log2 of this plane's CTB width; the height follows
-        from chroma_format as for sao_device unless ctb_log2_h says.  keep_ptr, borders: as for sao_device(g4=True)."""
+        from chroma_format as for sao_device unless ctb_log2_h says.  keep_ptr, borders: as for sao_device(g4=True).
+        semi_planar=True: hevcdbk_sao_stats_device_sp -- `planes` and the original are planes of interleaved Cb / Cr pairs of a 4:2:0
+        picture (plane_w x plane_h per component, multiples of 4); out_ptr takes Cb's statistics (the even samples), out_cr_ptr
+        (needed) Cr's, with one stride and one frame stride; the keep map and borders serve both components; square CTBs of
+        ctb_log2 3..5."""
         cf = _lib.chroma_format_idc(chroma_format)
+        if semi_planar:
+            if cf != _lib.CHROMA_420:
+                raise ValueError("semi_planar is 4:2:0 only")
+            if out_cr_ptr is None:
+                raise ValueError("semi_planar needs out_cr_ptr: the statistics of the odd samples")
+            if ctb_log2_h is not None and ctb_log2_h != ctb_log2:
+                raise ValueError("semi_planar takes square CTBs")
+            _chk(_lib.lib().hevcdbk_sao_stats_device_sp(self.handle, C.byref(planes), org_ptr, planes.pitch if org_pitch is None else org_pitch,
+                                                        planes.frame_stride if org_frame_stride is None else org_frame_stride, ctb_log2,
+                                                        keep_ptr, keep_stride, keep_frame_stride, None if borders is None else C.byref(borders),
+                                                        out_ptr, out_cr_ptr, out_stride, out_frame_stride, stream), self.handle)
+            return
+        if out_cr_ptr is not None:
+            raise ValueError("out_cr_ptr belongs to semi_planar=True")
         lh = _ctb_log2_h(ctb_log2, ctb_log2_h, cf, planes.is_chroma)
         _chk(_lib.lib().hevcdbk_sao_stats_device(self.handle, C.byref(planes), org_ptr, planes.pitch if org_pitch is None else org_pitch,
                                                  planes.frame_stride if org_frame_stride is None else org_frame_stride, ctb_log2, lh,

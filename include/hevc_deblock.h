@@ -908,6 +908,37 @@ HEVCDBK_API int hevcdbk_sao_stats_device(hevcdbk_context *ctx, const hevcdbk_dev
                                          hevcdbk_sao_stats *stats, unsigned stats_stride, size_t stats_frame_stride, void *hip_stream);
 
 /*
+ * The statistics pass on a semi-planar chroma plane (NV12's second plane and its 16-bit sibling): `rec` and `org` are planes of
+ * interleaved Cb / Cr pairs, and one launch fills one array per component.  The rule is that of hevcdbk_sao_stats_device per
+ * component: stats_cb is, byte for byte, what hevcdbk_sao_stats_device gives for the plane of the even samples of every row with the
+ * same keep map and the same borders, stats_cr the same for the odd samples.  A neighbour of a sample is the neighbouring PAIR's
+ * sample of the same component, never the adjacent sample of the row.  The keep map is one byte per 8x8 pairs and serves both
+ * components; borders is one byte per CTB of the per-component grid and serves both.  NV21 (Cr first) needs no flag: swap the outputs.
+ *   - `rec` is described as every _sp entry describes a pair plane: is_chroma = 1; plane_w x plane_h per component, multiples of 4 and
+ *     at least 8; pitch >= 2 * plane_w * sample_bytes, and org_pitch likewise; bit_depth 8..16 LSB-aligned.  Only src, the geometry and
+ *     the container are looked at.  ctb_log2 = 3..5, square CTBs: the range of hevcdbk_sao_filter_device_sp.
+ *   - stats_cb, stats_cr: two arrays with ONE stride and ONE frame stride (entries), the form hevcdbk_sao_pick_device reads (stats_a,
+ *     stats_b).  Every entry of both grids is written exactly once, zeros included, with plain stores; entries beyond the CTB columns
+ *     are not touched; with n_frames > 1 the frame stride is at least one grid.  No global atomics: the same bits every run.
+ *   - org, keep, borders: a frame stride of 0 = shared, as everywhere.
+ *   - Rows of both planes that start at a multiple of four pairs (bases, pitches and frame strides multiples of 8 * sample_bytes) take
+ *     loads of four pairs; any other address or pitch that is a multiple of the sample size runs sample by sample.
+ * Refusals, in this order, every one before the context is bound and with nothing enqueued: a NULL ctx, rec, rec->src, org, stats_cb or
+ * stats_cr, a bad depth / container, is_chroma = 0 -- HEVCDBK_ERR_ARG; plane_w or plane_h no multiple of 4 or below 8 --
+ * HEVCDBK_ERR_DIMENSIONS; then HEVCDBK_ERR_ARG for ctb_log2 outside 3..5, a pitch below two samples per pair, more than 65535 frames or
+ * rows, a keep_stride below ceil(plane_w / 8), borders without bytes or with a stride below the CTB columns, a stats_stride below the
+ * CTB columns, an output at an address that is no multiple of 4, a frame stride below one grid with n_frames > 1, and two outputs whose
+ * extents (first entry to last) overlap; last, a sample at an address that is no multiple of its size -- HEVCDBK_ERR_UNSUPPORTED.
+ * The chain of an NV12 picture's chroma: hevcdbk_h265_filter_device_sp -> this -> hevcdbk_sao_pick_device(stats_cb, stats_cr) ->
+ * hevcdbk_sao_filter_device_sp(params_cb, params_cr).  Asynchronous on hip_stream (NULL = the context's compute stream).
+ */
+HEVCDBK_API int hevcdbk_sao_stats_device_sp(hevcdbk_context *ctx, const hevcdbk_device_planes *rec, const void *org, size_t org_pitch,
+                                            size_t org_frame_stride, unsigned ctb_log2, const uint8_t *keep, unsigned keep_stride,
+                                            size_t keep_frame_stride, const hevcdbk_sao_borders *borders, hevcdbk_sao_stats *stats_cb,
+                                            hevcdbk_sao_stats *stats_cr, unsigned stats_stride, size_t stats_frame_stride,
+                                            void *hip_stream);
+
+/*
  * From statistics to parameters: the library's own rule, integers only, "parity unpinned" like the rest.
  * cost = deltaD * 256 + lambda_q8 * bits in int64, lambda_q8 <= 2^24 (else HEVCDBK_ERR_ARG); M = (1 << (Min(bitDepth, 10) - 5)) - 1;
  * log2OffsetScale is 0.

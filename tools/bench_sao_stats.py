@@ -4,7 +4,12 @@ and on a flat one (every sample in ONE band bin and in no edge bin: what content
 existing SAO pass (the leg of tools/bench_sao.py: seeded per-CTB parameters, one third off / band / edge) take turns in this one
 process on the same planes; both move two planes' worth of bytes -- the statistics pass reads two, SAO reads one and writes one.
 Wall clock over back-to-back launches that end in a synchronise; the median over the rounds is reported, and the spread between
-them.  The pick launch is timed once per depth, for the record.  One JSON line per (depth, content).  Diagnostic."""
+them.  The pick launch is timed once per depth, for the record.  One JSON line per (depth, content).  Diagnostic.
+
+--semi-planar: the statistics of a plane of interleaved Cb / Cr pairs (960x540 and 1920x1080 pairs, 64 frames, 32-sample CTBs, noise
+and flat) in three forms that take turns on the same buffers: (a) one hevcdbk_sao_stats_device_sp launch; (b) two
+hevcdbk_sao_stats_device launches on planes that are already split; (c) as (b) after the two strided copies that split rec and the
+two that split org (torch, on the stream the launches use).  Every form fills the same two arrays, compared once per row."""
 import argparse, json, os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -36,8 +41,101 @@ def frames_of(content, w, h, bd, rng):
     return rec, org
 
 
+def semi_planar(a):
+    import torch
+    ctx = deblock.Context(0)
+    dev = torch.device("cuda", 0)
+    side = torch.cuda.Stream(dev)            # one stream of its own for the copies and the launches: the default stream's handle is 0,
+    torch.cuda.set_stream(side)              # which the entries read as "the context's compute stream"
+    stream = side.cuda_stream
+    assert stream
+    n, L = a.frames, 5
+    lines = []
+    for (w, h) in [tuple(int(x) for x in s.split("x")) for s in a.sizes.split(",")]:
+        rows, cols = (h + 31) >> L, (w + 31) >> L
+        g = rows * cols
+        for bd in [int(x) for x in a.depths.split(",")]:
+            sb = 1 if bd == 8 else 2
+            tdt, ndt = (torch.uint8, np.uint8) if sb == 1 else (torch.int16, np.uint16)
+            for content in a.contents.split(","):
+                rng = np.random.default_rng(11)
+                org = rng.integers(0, 1 << bd, (4, h, w, 2)).astype(ndt)
+                rec = rng.integers(0, 1 << bd, (4, h, w, 2)).astype(ndt) if content == "noise" else np.full((4, h, w, 2), (1 << bd) // 3, ndt)
+                frames = lambda x: torch.from_numpy(x.view(np.uint8 if sb == 1 else np.int16)).to(dev).repeat(n // 4 + 1, 1, 1, 1)[:n].contiguous()
+                t_rec, t_org = frames(rec), frames(np.roll(org, 1, axis=0))                     # (n, h, w, 2) pairs
+                split = [torch.empty((n, h, w), dtype=tdt, device=dev) for _ in range(4)]       # rec Cb, rec Cr, org Cb, org Cr
+                st = [torch.zeros((n * g, 96), dtype=torch.int32, device=dev) for _ in range(2)]
+
+                def planes(t, pitch_samples, chroma):
+                    p = _lib.DevicePlanes()
+                    p.src, p.dst, p.pitch, p.frame_stride, p.n_frames = t.data_ptr(), 0, pitch_samples * sb, pitch_samples * h * sb, n
+                    p.plane_w, p.plane_h, p.bit_depth, p.sample_bytes, p.is_chroma = w, h, bd, sb, chroma
+                    return p
+                psp, pcb, pcr = planes(t_rec, 2 * w, 1), planes(split[0], w, 1), planes(split[1], w, 1)
+
+                def form_a():
+                    ctx.sao_stats_device(psp, t_org.data_ptr(), L, out_ptr=st[0].data_ptr(), out_cr_ptr=st[1].data_ptr(), out_stride=cols,
+                                         out_frame_stride=g, stream=stream, semi_planar=True)
+
+                def form_b():
+                    for c, p in enumerate((pcb, pcr)):
+                        ctx.sao_stats_device(p, split[2 + c].data_ptr(), L, ctb_log2_h=L, out_ptr=st[c].data_ptr(), out_stride=cols, out_frame_stride=g,
+                                             stream=stream)
+
+                def copies():
+                    for c in (0, 1):
+                        split[c].copy_(t_rec[..., c])
+                        split[2 + c].copy_(t_org[..., c])
+
+                def form_c():
+                    copies()
+                    form_b()
+                forms = {"a_sp": form_a, "b_two_planar": form_b, "c_split_and_two_planar": form_c}
+                results = {}
+                for k in ("c_split_and_two_planar", "a_sp"):                                    # c first: it fills the split planes
+                    for t in st:
+                        t.fill_(-1)
+                    forms[k]()
+                    torch.cuda.synchronize(dev)
+                    results[k] = [t.cpu().numpy().copy() for t in st]
+                same = all(np.array_equal(x, y) for x, y in zip(results["a_sp"], results["c_split_and_two_planar"]))
+                sync = lambda: torch.cuda.synchronize(dev)
+
+                def timed_t(fn, steps, warm):
+                    for _ in range(warm):
+                        fn()
+                    sync()
+                    t0 = time.perf_counter()
+                    for _ in range(steps):
+                        fn()
+                    sync()
+                    return (time.perf_counter() - t0) / steps * 1e3
+                timed_t(form_c, 60, 0)   # settle the clocks
+                ms = {k: [] for k in forms}
+                for _ in range(a.rounds):
+                    for k, fn in forms.items():
+                        ms[k].append(timed_t(fn, a.steps, 10))
+                med = {k: float(np.median(v)) for k, v in ms.items()}
+                spread = {k: float(max(v) - min(v)) for k, v in ms.items()}
+                nbytes = 4 * n * w * h * sb                                                     # two pair planes read
+                line = {"stage": "sao_stats_sp", "pairs": "%dx%d" % (w, h), "bit_depth": bd, "content": content, "frames": n, "ctb": 1 << L,
+                        "ms_per_call": med, "rounds_ms": ms, "spread_ms": spread, "outputs_identical": bool(same),
+                        "a_over_b": med["a_sp"] / med["b_two_planar"], "c_over_a": med["c_split_and_two_planar"] / med["a_sp"],
+                        "a_loses_to_b_beyond_spread": bool(med["a_sp"] - med["b_two_planar"] > max(spread["a_sp"], spread["b_two_planar"])),
+                        "a_frac_of_8TBps_for_2_pair_planes_read": nbytes / (med["a_sp"] * 1e-3) / 8e12}
+                lines.append(line)
+                print(json.dumps(line), flush=True)
+                del t_rec, t_org, split, st
+    if a.out:
+        with open(a.out, "a") as fh:
+            for line in lines:
+                fh.write(json.dumps(line) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--semi-planar", action="store_true", help="the pair-plane entry against two planar launches, with and without the split copies")
+    ap.add_argument("--sizes", default="960x540,1920x1080", help="--semi-planar: pairs per row x rows")
     ap.add_argument("--width", type=int, default=3840)
     ap.add_argument("--height", type=int, default=2160)
     ap.add_argument("--frames", type=int, default=64)
@@ -48,6 +146,10 @@ def main():
     ap.add_argument("--ctb-log2", type=int, default=6)
     ap.add_argument("--out", default=None, help="append the JSON lines to this file as well")
     a = ap.parse_args()
+    if a.semi_planar:
+        if a.contents == "flat,blocky,noise":
+            a.contents = "noise,flat"
+        return semi_planar(a)
     w, h, n, L = a.width, a.height, a.frames, a.ctb_log2
     ctx = deblock.Context(0)
     rows, cols = (h + (1 << L) - 1) >> L, (w + (1 << L) - 1) >> L
