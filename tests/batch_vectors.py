@@ -31,7 +31,12 @@ over "not applied", which no content can show.
 
 sao8<3d> (the SAO grid past the guard of its renumbered form, where the frame index is the grid's z) needs planes of 0.76 GB:
 its two cases (Giant, at the end of this file) are flat planes with random windows compared through dispatch_cases' windowed
-oracle, and "differs in every check window" stands in for "differs in every cell" there.
+oracle, and "differs in every check window" stands in for "differs in every cell" there.  The same forms of the _g4 kernels, of the
+sample-by-sample _nox kernels and of the 8-bit kernels of a plane of pairs have a Giant case each, seven in all.
+
+The instantiations that one case alone reaches are listed with that case in PINNED (kernel name and template arguments): the six
+packed kernels that run the row-major block map with a QP map outside the _sl / _g4 generations (LINEAR_QM) and the reference-exact
+multi-plane fused kernel at 12 bit.
 
 Expected output of frame f = the trusted CPU statement run on frame f's samples with frame f's operands: oracle.filter_plane
 (reference-exact), oracle.h265.filter_plane (spec-exact luma), rext_oracle.filter_chroma_plane (spec-exact chroma),
@@ -814,11 +819,39 @@ def cases():
     add("far_map_ref", "filter", "ref", "Y", 256, 128, n=3, st=_st(map="far", bs="shared"))
     add("far_vert_h265", "filter", "h265", "Y", 256, 128, n=3, st=_st(bs="far"), far_which="vert")
     add("far_hor_ref", "filter", "ref", "Y", 256, 128, n=3, st=_st(bs="far"), far_which="hor")
+    # ---- the row-major block map with a QP map per frame in the six packed kernels that had no case (PINNED below): planes 4096
+    # samples wide have 513 blocks per row, more than a workgroup holds.  Units of 16 and 32 luma samples: 513 blocks are no whole
+    # number of units, so the unit of row-major block k is not that of raster block k
+    for k, (tag, mode, pl, w, h, bd, cf, u, n) in enumerate(LINEAR_QM):
+        add("map_%s_%s_%s" % (mode, tag, ("tight", "padded")[k % 2]), "filter", mode, pl, w, h, bd=bd, cf=cf, n=n, unit_log2=u,
+            st=_st(map=("tight", "padded")[k % 2], bs="shared"), in_place=(k % 3 == 1))
+    # ---- ("ref", 1, 12) beside the map_*_multi_cf* loop above: the reference-exact multi-plane fused kernel's WIDE form with QP maps
+    # and with bS per frame (PINNED below).  Here at the end of the list, so that the metamorphic tests, which take the first case of
+    # a family, keep the cases they had
+    add("map_ref_multi_cf1_12_padded", "dbk_sao_planes", "ref", "YUV", 256, 128, bd=12, cf=1, n=3, fused=ON,
+        st=_st(map="padded", bs="shared", params="shared"))
+    add("bs_ref_multi_cf1_12_tight", "dbk_sao_planes", "ref", "YUV", 256, 128, bd=12, cf=1, n=3, fused=ON, st=_st(bs="tight", params="shared"))
     out += cases_x()
     names = [c.name for c in out]
     assert len(set(names)) == len(names)
     return out
 
+
+# (tag, mode, planes, luma w, h, bit depth, chroma_format_idc, log2 of the QP-map unit, frames): chroma planes of 4096 x 16 (4:2:0)
+# and 4096 x 32 (4:2:2, 4:4:4), luma of 4096 x 16
+LINEAR_QM = [("c420_lin8", "ref", "C", 8192, 32, 8, 1, 5, 3), ("c420_lin10_n5", "ref", "C", 8192, 32, 10, 1, 4, 5),
+             ("lin12", "h265", "Y", 4096, 16, 12, 1, 5, 3), ("c422_lin8", "h265", "C", 8192, 32, 8, 2, 4, 3),
+             ("c422_lin10", "h265", "C", 8192, 32, 10, 2, 5, 3), ("c444_lin10", "h265", "C", 4096, 32, 10, 3, 4, 3)]
+# case -> (kernel, template arguments) its capture must show: the instantiations that only these cases reach.  The CPU test holds the
+# dispatch restatement's prediction against this table, the GPU test the stream capture
+PINNED = {"map_ref_c420_lin8_tight": ("dbk_packed_kernel", (1, 0, 0, 1, 1)),
+          "map_ref_c420_lin10_n5_padded": ("dbk_packed16c_kernel", (1, 1)),
+          "map_h265_lin12_tight": ("dbk_packed16_h265_kernel", (0, 1, 1, 1)),
+          "map_h265_c422_lin8_padded": ("dbk_packed_h265_cf_kernel", (1, 2)),
+          "map_h265_c422_lin10_tight": ("dbk_packed16_h265_cf_kernel", (1, 2)),
+          "map_h265_c444_lin10_padded": ("dbk_packed16_h265_cf_kernel", (1, 3)),
+          "map_ref_multi_cf1_12_padded": ("dbk_sao_fused_multi_kernel", (2, 1, 1)),
+          "bs_ref_multi_cf1_12_tight": ("dbk_sao_fused_multi_kernel", (2, 1, 0))}
 
 K_SL = {"g": "dbk_h265_sl_kernel", 8: "dbk_packed_h265_sl_kernel", 16: "dbk_packed16_h265_sl_kernel", "f8": "dbk_sao_fused_h265_sl_kernel",
         "f16": "dbk_sao_fused16_h265_sl_kernel", "multi": "dbk_sao_fused_multi_h265_sl_kernel"}
@@ -978,69 +1011,162 @@ def cases_x():
     return out
 
 
-# ---- sao8<3d>: the SAO grid past the guard of its renumbered (swz) form, where the frame index is blockIdx.z ----------------
+# ---- the 3-D forms: the SAO grid past the guard of its renumbered (swz) form, where the frame index is blockIdx.z ---------------
+
+GIANT_STRIP_ROWS = (65535 + 63) // 64       # the entries take plane_h <= 65535: no plane has more rows of 64-row strips
+
 
 @dataclasses.dataclass
 class Giant:
-    """SAO alone on two 8-bit frames of a plane whose strip count is just past the swz guard (dbksel::renumbered_grid, restated by
-    dispatch_cases.sao_swz), parameters (64-sample CTBs), keep map and borders all per frame in one state.  The plane is flat
+    """SAO alone on flat frames of a plane whose strip count is just past the swz guard (dbksel::renumbered_grid, restated by
+    dispatch_cases.sao_swz), parameters (64-sample CTBs; a plane of pairs: 32, the largest its entry takes), keep map and borders all per frame in one state.  The plane is flat
     except for random windows (dispatch_cases.Windows); outside the windows' CTBs every CTB is edge offset, which leaves flat
     samples as they are, so the expected plane is flat outside the check windows and the windowed oracle inside.
     The per-cell census cannot be had on a plane of this size; the rule that stands in for it (giant_census): for every
     operand X and every ordered pair f != g, frame f's expectation differs from the oracle's output with frame g's X IN EVERY
-    CHECK WINDOW (each holds offset CTBs, kept blocks and forbidden borders), and for the padded state also against the
-    operand read at the tight stride."""
+    CHECK WINDOW (each holds offset CTBs, kept blocks and forbidden borders; on a plane of pairs in every check window of Cb and of
+    Cr), and for the padded state also against the operand read at the tight stride.
+
+    kind "": sao8_nox_kernel<false, 4> on two 8-bit frames 65536 samples wide, the height solved from the guard.
+    The other kinds are the same forms of the _g4 kernels (g4), of the sample-by-sample _nox kernels (nox) and of the kernels of a
+    plane of Cb / Cr pairs (sp).  Their planes have the most strip rows an entry takes (plane_h <= 65535) and the first strip count
+    per row at which the guard fails; the last strip is 4 samples or pairs wide (g4, sp: sizes in multiples of 4) or 8 (nox).  The
+    planes of pairs have two rows of strips instead (strip_rows; giants() says why), the second 4 rows tall.
+    The 16-bit ones run ONE frame: two would need 3 GB per buffer, for a template whose strip-to-frame code (the body's first lines,
+    sao_kernel_body.inc) is the 8-bit sibling's, which runs two."""
     name: str
     state: str
     n: int = 2
-    w: int = 65536
+    width: int = 65536
     flat: int = 128
     ctb_log2: int = 6
+    kind: str = ""
+    bd: int = 8
+    pad: int = 0             # bytes of row padding behind a row's samples
+    kernel: tuple = ("sao8_nox_kernel", (0, 4))   # what the capture must show
+    strip_rows: int = GIANT_STRIP_ROWS            # rows of strips; fewer than the most: the last row of strips holds one block row
 
     @property
-    def h(self):   # the first strip-row count at which the swz guard fails for n frames
+    def sb(self):
+        return 1 if self.bd == 8 else 2
+
+    @property
+    def comps(self):
+        return 2 if self.kind == "sp" else 1
+
+    @property
+    def unit(self):          # the sizes are multiples of this
+        return 8 if self.kind in ("", "nox") else 4
+
+    @property
+    def strips_x(self):      # the first strip count per row at which the swz guard fails for n frames of strip_rows strip rows
+        return dc.first_false(lambda t: dc.sao_swz(dc.Plane(dc.SAO_STRIP * t, 64 * self.strip_rows, n=self.n)), 1, 1 << 20)
+
+    @property
+    def w(self):             # samples; kind sp: pairs
+        return dc.SAO_STRIP * (self.strips_x - 1) + self.unit if self.kind else self.width
+
+    @property
+    def h(self):
+        if self.kind and self.strip_rows < GIANT_STRIP_ROWS:
+            return 64 * (self.strip_rows - 1) + self.unit
+        if self.kind:
+            return 65535 // self.unit * self.unit
+        # the first strip-row count at which the swz guard fails for n frames
         return 64 * dc.first_false(lambda t: dc.sao_swz(dc.Plane(self.w, 64 * t, n=self.n)), 1, 1 << 12)
 
+    @property
+    def row_bytes(self):
+        return self.w * self.comps * self.sb
+
     def plane(self):
-        return dc.Plane(self.w, self.h, n=self.n, fs_pad=4096)
+        """w, h, P, fs, n, nbytes() of the plane; kind sp: w counts pairs, as the launcher's strips do"""
+        return dc.Plane(self.w, self.h, bd=self.bd, pitch=self.row_bytes + self.pad, n=self.n, fs_pad=4096)
 
     def grid(self):
-        return self.h >> 6, self.w >> 6
+        return -(-self.h >> self.ctb_log2), -(-self.w >> self.ctb_log2)
+
+    def keep_shape(self):
+        return -(-self.h // 8), -(-self.w // 8)
 
     def dispatch_case(self):
         return dc.Case(self.name, "sao", [self.plane()], ctb_log2=6, params_per_frame=True)
+
+    def launch(self):
+        """the launch the dispatch restatement predicts"""
+        if self.kind == "sp":
+            return dc.sao_sp_launch(self.plane())
+        return dc.sao_twin_launch(self.plane(), self.kind or "nox")
 
     def families(self):
         return [l.family for l in dc.predict(self.dispatch_case())]
 
 
 def giants():
-    return [Giant("sao8_3d_tight", "tight"), Giant("sao8_3d_padded", "padded")]
+    return [Giant("sao8_3d_tight", "tight"), Giant("sao8_3d_padded", "padded"),
+            # rows of 11524 + 4 bytes are 8-byte aligned: the packed 8-bit kernel; 8 bytes more are not
+            Giant("g4_sao8_3d_tight", "tight", kind="g4", pad=4, kernel=("sao8_g4_kernel", (0, 4))),
+            Giant("g4_sao_u8_3d_padded", "padded", kind="g4", pad=8, kernel=("sao_g4_kernel", ("u8", 0, 0))),
+            Giant("nox_sao_u8_3d_tight", "tight", kind="nox", pad=4, kernel=("sao_nox_kernel", ("u8", 0, 0))),
+            # pairs: 1024 rows of strips need two frames of 1.51e9 bytes, twice the bytes -- and the time -- of every other case here.
+            # The guard counts strips, not samples: TWO rows of strips, the second one block row of 4 (68 rows of 5931268 pairs), pass it
+            # with the same two frames in 1.61e9 bytes.  Rows of pairs + 8 bytes are 16-byte aligned: the packed pair kernel; 4 bytes
+            # more are not
+            Giant("sp_sao8_3d_padded", "padded", kind="sp", ctb_log2=5, pad=8, strip_rows=2, kernel=("sao8_sp_kernel", (0,))),
+            Giant("sp_sao_u8_3d_tight", "tight", kind="sp", ctb_log2=5, pad=12, strip_rows=2, kernel=("sao_sp_kernel", ("u8", 0))),
+            # 16 bit: one frame (the class docstring says why); no packed form reads the 3-D grid
+            Giant("g4_sao_u16_3d", "padded", n=1, kind="g4", bd=10, flat=0x0202, pad=8, kernel=("sao_g4_kernel", ("u16", 0, 0))),
+            Giant("nox_sao_u16_3d", "tight", n=1, kind="nox", bd=10, flat=0x0202, pad=8, kernel=("sao_nox_kernel", ("u16", 0, 0)))]
+
+
+def giant_rects(w, h, unit, size=(128, 256)):
+    """content windows at the first and the last rows and columns and in the middle, nine in all; the last ones end with the plane, so
+    that a last block column or row of 4 samples lies in them.  128 rows: every window holds a border between two rows of CTBs"""
+    wy, wx = min(size[0], h), size[1]
+    al = lambda v: v // unit * unit
+    ys, xs = sorted({0, al(h // 2 - wy // 2), al(h - wy)}), sorted({0, al(w // 2 - wx // 2), al(w - wx)})
+    if len(ys) == 1:   # a plane no taller than a window: nine windows side by side, each from the first row to the last
+        xs = [al((w - wx) * k // 8) for k in range(9)]
+    return [(y, y + wy, x, x + wx) for y, x in itertools.product(ys, xs)]
 
 
 def giant_operands(g, seed=5):
-    """windows[f] (dispatch_cases.Windows, the same rectangles, content per frame), params[f], keep[f], borders[f] (layouts)"""
+    """windows[f] (one dispatch_cases.Windows per component: the same rectangles, content per frame and component), params[f] (a plane
+    of pairs: (Cb array, Cr array)), keep[f], borders[f] (layouts)"""
     rng = np.random.default_rng(seed)
     p = g.plane()
     rows, cols = g.grid()
-    base = dc.standard_windows(g.w, g.h, 8, g.flat, p.P, seed=seed, size=(64, 256))
-    wins = [dc.Windows(g.w, g.h, 8, g.flat, base.content, seed + 17 * f) for f in range(g.n)]
+    if g.kind:
+        base = dc.Windows(g.w, g.h, g.bd, g.flat, giant_rects(g.w, g.h, g.unit), seed)
+    else:
+        base = dc.standard_windows(g.w, g.h, 8, g.flat, p.P, seed=seed, size=(64, 256))
+    wins = [[dc.Windows(g.w, g.h, g.bd, g.flat, base.content, seed + 17 * f + 1000 * k) for k in range(g.comps)] for f in range(g.n)]
     touch = np.zeros((rows, cols), bool)
-    for y0, y1, x0, x1 in base.check(64):
-        touch[y0 >> 6:(y1 + 63) >> 6, x0 >> 6:(x1 + 63) >> 6] = True
-    bt, bc, bb = rng.integers(0, 2, (rows, cols)), rng.integers(0, 4, (rows, cols)), rng.integers(0, 32, (rows, cols))
-    bm, sg = rng.integers(0, 7, (rows, cols, 4)), rng.integers(0, 2, (rows, cols, 4)) * 2 - 1
-    kb = rng.integers(0, 3, (g.h // 8, g.w // 8))
+    L, m = g.ctb_log2, (1 << g.ctb_log2) - 1
+    for y0, y1, x0, x1 in base.check(1 << L):
+        touch[y0 >> L:(y1 + m) >> L, x0 >> L:(x1 + m) >> L] = True
+
+    def draw():
+        bt, bc, bb = rng.integers(0, 2, (rows, cols)), rng.integers(0, 4, (rows, cols)), rng.integers(0, 32, (rows, cols))
+        bm, sg = rng.integers(0, 7, (rows, cols, 4)), rng.integers(0, 2, (rows, cols, 4)) * 2 - 1
+
+        def make(f):
+            q = np.zeros((rows, cols), SAO_DT)
+            edge = ((bt + f) % 2 == 1) | ~touch      # band offset only where a check window is: it would move the flat samples
+            q["type"] = np.where(edge, 2, 1)
+            q["cls"] = np.where(edge, (bc + f) % 4, (bb + 8 * f) % 32)
+            mag = 1 + (bm + 2 * f) % 7
+            q["offset"] = np.where(edge[..., None], mag * np.array([1, 1, -1, -1]), mag * sg)
+            return q
+        return make
+    make_p = [draw()]
+    kb = rng.integers(0, 3, g.keep_shape())
     fb = rng.integers(0, 3, rows * cols)
-    out = {"windows": wins, "params": [], "keep": [], "borders": []}
+    make_p += [draw() for _ in range(g.comps - 1)]
+    out = {"windows": wins, "touch": touch, "params": [], "keep": [], "borders": []}
     for f in range(g.n):
-        q = np.zeros((rows, cols), SAO_DT)
-        edge = ((bt + f) % 2 == 1) | ~touch      # band offset only where a check window is: it would move the flat samples
-        q["type"] = np.where(edge, 2, 1)
-        q["cls"] = np.where(edge, (bc + f) % 4, (bb + 8 * f) % 32)
-        mag = 1 + (bm + 2 * f) % 7
-        q["offset"] = np.where(edge[..., None], mag * np.array([1, 1, -1, -1]), mag * sg)
-        out["params"].append(q)
+        q = [m(f) for m in make_p]
+        out["params"].append(q[0] if g.comps == 1 else tuple(q))
         out["keep"].append(((kb + f) % 3 == 0).astype(np.uint8))
         out["borders"].append(R.layout(rows, cols, None, slice_starts=range(1, rows * cols), flags=((fb + f) % 3 != 0).astype(np.int64),
                                        col_starts=[3 + 2 * f], row_starts=[1 + f], tiles_across=False))
@@ -1048,24 +1174,36 @@ def giant_operands(g, seed=5):
 
 
 def giant_windows(g, ops, f, *, params=None, keep=None, layout=None, nox=None):
-    """[(rect, expected samples)] of frame f's check windows; an operand given replaces frame f's own (nox: the NOX bytes)"""
+    """[(rect, expected samples)] of frame f's check windows ((h, w, 2) on a plane of pairs); an operand given replaces frame f's own
+    (nox: the NOX bytes)"""
     prm = ops["params"][f] if params is None else params
     kp = ops["keep"][f] if keep is None else keep
     lay = ops["borders"][f] if layout is None else layout
+    L, m = g.ctb_log2, (1 << g.ctb_log2) - 1
 
-    def op(a, y0, x0):
-        h, w = a.shape
-        cy, cx, kh, kw = y0 >> 6, x0 >> 6, (h + 63) >> 6, (w + 63) >> 6
-        pc, kc = prm[cy:cy + kh, cx:cx + kw], kp[y0 >> 3:(y0 + h) >> 3, x0 >> 3:(x0 + w) >> 3]
-        if nox is not None:
-            return sao_plane_nox(a, pc, 6, 6, np.asarray(nox)[cy:cy + kh, cx:cx + kw], keep=kc)
-        lc = dict(lay, slice_idx=np.asarray(lay["slice_idx"])[cy:cy + kh, cx:cx + kw], tile_idx=np.asarray(lay["tile_idx"])[cy:cy + kh, cx:cx + kw])
-        return R.sao_plane(a, pc, 6, 6, lc, keep=kc)
-    return dc.windowed(ops["windows"][f], op, 6)
+    def op_of(q):
+        def op(a, y0, x0):
+            h, w = a.shape
+            cy, cx, kh, kw = y0 >> L, x0 >> L, (h + m) >> L, (w + m) >> L
+            pc, kc = q[cy:cy + kh, cx:cx + kw], kp[y0 >> 3:(y0 + h + 7) >> 3, x0 >> 3:(x0 + w + 7) >> 3]
+            if nox is not None:
+                return sao_plane_nox(a, pc, L, L, np.asarray(nox)[cy:cy + kh, cx:cx + kw], bit_depth=g.bd, keep=kc)
+            lc = dict(lay, slice_idx=np.asarray(lay["slice_idx"])[cy:cy + kh, cx:cx + kw], tile_idx=np.asarray(lay["tile_idx"])[cy:cy + kh, cx:cx + kw])
+            return R.sao_plane(a, pc, L, L, lc, bit_depth=g.bd, keep=kc)
+        return op
+    per_comp = [dc.windowed(win, op_of(q), L) for win, q in zip(ops["windows"][f], prm if g.comps == 2 else [prm])]
+    if g.comps == 1:
+        return per_comp[0]
+    return [(r, np.stack([a, b], axis=-1)) for (r, a), (_, b) in zip(*per_comp)]
 
 
-def giant_arrays(g, ops, x):
-    return [R.expected_nox(l) for l in ops["borders"]] if x == "borders" else ops[x]
+def giant_arrays(g, ops, x, which=0):
+    """the per-frame arrays of operand x as the library reads them (the parameters of a plane of pairs: which = 0 Cb's, 1 Cr's)"""
+    if x == "borders":
+        return [R.expected_nox(l) for l in ops["borders"]]
+    if x == "params" and g.comps == 2:
+        return [q[which] for q in ops["params"]]
+    return ops[x]
 
 
 def giant_census(g, ops):
@@ -1074,18 +1212,22 @@ def giant_census(g, ops):
     exp = [giant_windows(g, ops, f) for f in range(g.n)]
     kw = {"params": "params", "keep": "keep", "borders": "layout"}
 
-    def equal_windows(f, got):
-        return [r for (r, a), (_, b) in zip(exp[f], got) if np.array_equal(a, b)]
+    def equal_windows(f, got):   # a plane of pairs: a window in which either component is left equal
+        def same(a, b):
+            return np.array_equal(a, b) if a.ndim == 2 else any(np.array_equal(a[..., k], b[..., k]) for k in range(2))
+        return [r for (r, a), (_, b) in zip(exp[f], got) if same(a, b)]
     for x in ("params", "keep", "borders"):
         for f, k in itertools.permutations(range(g.n), 2):
             eq = equal_windows(f, giant_windows(g, ops, f, **{kw[x]: ops[x][k]}))
             if eq:
                 bad.append((x, f, k, eq))
         if g.state == "padded":
-            arrs = giant_arrays(g, ops, x)
-            buf, _ = lay_out(arrs, "padded", poison_entry(x), operand_dtype(x))
+            def tight_read(f, which=0):
+                arrs = giant_arrays(g, ops, x, which)
+                buf, _ = lay_out(arrs, "padded", poison_entry(x, g.bd), operand_dtype(x))
+                return buf[f * arrs[0].size:(f + 1) * arrs[0].size].reshape(arrs[0].shape)
             for f in range(1, g.n):
-                rd = buf[f * arrs[0].size:(f + 1) * arrs[0].size].reshape(arrs[0].shape)
+                rd = (tight_read(f, 0), tight_read(f, 1)) if x == "params" and g.comps == 2 else tight_read(f)
                 eq = equal_windows(f, giant_windows(g, ops, f, **{("nox" if x == "borders" else kw[x]): rd}))
                 if eq:
                     bad.append((x, f, "tight", eq))

@@ -198,11 +198,13 @@ def generic_launch(p, h265, cf=1):
     return Launch("dbk_h265_kernel", (t, int(p.chroma)), grid, block)
 
 
-def packed_launch(p, h265, census=_NULL):
-    """launch_packed_sel<Gen::kRef> / <Gen::kH265> after fold_operands (deblock_kernels.hip); QP maps of 4:2:0 planes
-    (the _cf kernels of 4:2:2 / 4:4:4 QP-map chroma are not among the cases)"""
+def packed_launch(p, h265, census=_NULL, cf=1):
+    """launch_packed_sel<Gen::kRef> / <Gen::kH265> after fold_operands (deblock_kernels.hip): the format is a template argument
+    only for spec-exact chroma of 4:2:2 / 4:4:4 with a QP map (the _cf kernels); with one QP those planes take the 4:2:0 kernels"""
     lin, grid, block = plan_packed(p, census)
     L, wide, qm = int(lin), int(p.sb == 2 and not p.chroma and p.max_v > 2047), int(p.qpmap > 0)
+    if h265 and p.chroma and cf != 1 and qm:
+        return Launch("dbk_packed16_h265_cf_kernel" if p.sb == 2 else "dbk_packed_h265_cf_kernel", (L, cf), grid, block)
     if h265:
         if p.sb == 2:
             return Launch("dbk_packed16_h265_kernel", (int(p.chroma), L, qm, wide), grid, block)
@@ -221,7 +223,7 @@ def deblock_launch(p, h265, variant=KERNEL_AUTO, cf=1, census=_NULL):
         return ERR_UNSUPPORTED
     if variant == KERNEL_GENERIC or not ok:
         return generic_launch(p, h265, cf)
-    return packed_launch(p, h265, census)
+    return packed_launch(p, h265, census, cf)
 
 
 def multi_supports(planes, census=_NULL):
@@ -281,6 +283,29 @@ def sao_launch(p, census=_NULL):
     return Launch("sao_kernel", ("u16", int(swz), int(swz and pk)), grid, block)
 
 
+def sao_twin_launch(p, twin, census=_NULL):
+    """launch_sao<false> with boundary bytes (twin "nox") and launch_sao<true> (twin "g4": dbk_launch_sao_g4, planes in multiples of
+    4) in sao.hip: dbk_launch_sao's grid and predicates -- the demand for multiples of 8 is met by the first and waived for the second
+    -- and the kernel's twin of that name"""
+    l = sao_launch(p, census)
+    return dataclasses.replace(l, kernel=l.kernel.replace("_kernel", "_%s_kernel" % twin))
+
+
+def sao_sp_launch(p, census=_NULL):
+    """dbk_launch_sao_sp (sao_sp.hip) on a plane of p.w x p.h Cb / Cr pairs (p.P, p.fs in bytes): the strips are 256 pairs by 64 rows,
+    so dbksel::sao_grid is sao_launch's on the pair counts; dbk_sao_sp_packed_supports chooses the packed kernels"""
+    tx, tpf, total = sao_strips(p)
+    swz = sao_swz(p, census)
+    grid = ((total + 7) // 8 * 8, 1, 1) if swz else (tx, (p.h + 63) // 64, p.n)
+    piece = 16 * p.sb  # a lane's row piece
+    packed = _all(census, "sao sp packed", [
+        ("pitch %% %d" % piece, p.P % piece == 0), ("frame_stride %% %d" % piece, p.fs % piece == 0), ("src %% %d" % piece, p.src_off % piece == 0),
+        ("dst %% %d" % piece, p.dst_off % piece == 0), ("pitch * h < 2^31", p.P * p.h < TWO31), ("max_v", p.max_v == 255 if p.sb == 1 else p.max_v <= 4095)])
+    if packed:
+        return Launch("sao8_sp_kernel" if p.sb == 1 else "sao16_sp_kernel", (int(swz),), grid, (SAO_STRIP, 1, 1))
+    return Launch("sao_sp_kernel", ("u8" if p.sb == 1 else "u16", int(swz)), grid, (SAO_STRIP, 1, 1))
+
+
 def fused_tiles(p):
     tw, th = FUSED_TILE[p.sb]
     tx, ty = (p.w + tw - 1) // tw, (p.h + th - 1) // th
@@ -317,10 +342,11 @@ def fused_launch(p, h265, cf=1):
 
 
 def fused_multi_launch(planes, h265):
-    """launch_fused_multi<Gen::kRef> / <Gen::kH265> (dbk_launch_deblock_sao_multi[_h265_cf]), scalar QP"""
+    """launch_fused_multi<Gen::kRef> / <Gen::kH265> (dbk_launch_deblock_sao_multi[_h265_cf]) of a 4:2:0 picture; QPMAP is folded
+    from the luma plane's map (fold_operands)"""
     p0 = planes[0]
     k = "dbk_sao_fused_multi%s_kernel" % ("_h265" if h265 else "")
-    return Launch(k, (p0.sb, int(p0.sb == 2 and p0.max_v > 2047), 0), (sum(fused_grid(q) for q in planes), 1, 1),
+    return Launch(k, (p0.sb, int(p0.sb == 2 and p0.max_v > 2047), int(p0.qpmap > 0)), (sum(fused_grid(q) for q in planes), 1, 1),
                   (FUSED_THREADS[p0.sb], 1, 1), FUSED_LDS[p0.sb])
 
 

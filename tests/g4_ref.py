@@ -179,7 +179,7 @@ def border_params(w, h, lw, lh, depth, frames, rng):
     bottom and on the right border run through edge class 0, 1, 2, 3 and band offset -- CTB i of a border in frame f is kind
     (i + f) % 5 -- so that with five frames every border CTB has been everything; the others random.  Offsets are never zero."""
     rows, cols = ctb_grid(w, h, lw, lh)
-    shift = max(depth - 10, 0)
+    shift = min(max(depth - 10, 0), 4)   # above 14 bit: as far as the int8 entry holds the scaled value
     out = []
     for f in range(frames):
         p = rx.random_sao_params(w, h, lw, lh, rng, depth)
@@ -283,6 +283,12 @@ CASES = SMALL + WIDE + TILES8 + TILES16 + P1080 + FORMATS
 # 4:2:2 / 4:4:4 planes just over 512 blocks per row, two block rows: the packed kernels' row-major map in the formats' own kernels
 WIDE_FORMATS = [("422_4100x12", 4100, 12, 8, 2, True, 6), ("422_4100x12_10", 4100, 12, 10, 2, False, 6),
                 ("444_4100x12", 4100, 12, 8, 3, False, 6), ("444_4100x12_10", 4100, 12, 10, 3, True, 6)]
+# SAO above 12 bit: no packed procedure holds these samples, every 16-bit _g4 plane takes the sample-by-sample kernel on the
+# renumbered grid (sao_g4_kernel<u16, true, false>).  Full-range content (sao_case(content="full")): the clip at max_v acts.
+# The GPU test runs each with rows of a multiple of 16 bytes and of 8 bytes more; the entries refuse 16-bit rows that are no multiple
+# of one 4-sample word (8 bytes), so no smaller misalignment reaches the kernel
+DEEP = [("12x12_14", 12, 12, 14, 1, False, 3), ("28x20_14", 28, 20, 14, 1, False, 4), ("12x12_16", 12, 12, 16, 1, False, 3),
+        ("28x20_16", 28, 20, 16, 1, False, 4)]
 CQP, TC_DIV2, QP = 2, 1, 37
 UNIT_LOG2 = 3
 SL_CTB_LOG2 = 4
@@ -323,7 +329,13 @@ def sao_case(spec, frames=FRAMES, content="noise"):
     name, w, h, depth, cf, _, lw = spec
     lh = lw + (1 if cf == 2 else 0)
     rng = np.random.default_rng(seed_of(name) + 7)
-    planes = [noise_plane(w, h, depth, rng) if content == "noise" else blocky_plane(w, h, depth, rng) for _ in range(frames)]
+    if content == "full":   # h265_vectors.sao_full_range (runs of 0 and max_v, ramps through every band, spikes) of the next multiple of 8, cropped
+        import h265_vectors as hv
+        planes = [np.ascontiguousarray(hv.sao_full_range(depth, lw, rng, w=pad8(w), h=pad8(h))[0][:h, :w]) for _ in range(frames)]
+        for p in planes:   # the last sample one below max_v: in the frame in which the last CTB is a band-offset one (border_params),
+            p[-1, -1] = (1 << depth) - 2   # fit_bands puts its first, positive offset on this sample's band, and the sum is clipped
+    else:
+        planes = [noise_plane(w, h, depth, rng) if content == "noise" else blocky_plane(w, h, depth, rng) for _ in range(frames)]
     params = border_params(w, h, lw, lh, depth, frames, rng)
     fit_bands(planes, params, lw, lh, depth)
     return {"name": name, "w": w, "h": h, "depth": depth, "sb": 1 if depth == 8 else 2, "cf": cf, "lw": lw, "lh": lh,

@@ -149,6 +149,25 @@ def test_packed_linear_cases_have_padding_workgroups_and_a_partial_last_one():
         assert (dc.fused_tiles(p)[2] * c.n) % 8 != 0, c.name
 
 
+def test_pinned_cases_predict_their_kernel():
+    """the cases written for one instantiation each: the dispatch restatement predicts exactly that kernel with those template
+    arguments (the GPU test holds the capture against the same table), the six row-major ones on a grid of 513 blocks per row with
+    QP-map units of 16 or 32 luma samples, as the older row-major cases have them"""
+    assert set(bv.PINNED) <= set(BY_NAME) and len({v for v in bv.PINNED.values()}) == len(bv.PINNED)
+    for name, (kernel, args) in bv.PINNED.items():
+        c = BY_NAME[name]
+        got = [(l.kernel, l.args) for l in dc.predict(bv.dispatch_case(c)) if l.family != "sao rows x2"]
+        assert got == [(kernel, args)], (name, got)
+    lin = [BY_NAME[n] for n, (k, _) in bv.PINNED.items() if k.startswith("dbk_packed")]
+    assert len(lin) == len(bv.LINEAR_QM) == 6 and {c.n for c in lin} == {3, 5}
+    for c in lin:
+        p = bv.dispatch_case(c).planes[0]
+        assert p.w == 4096 and p.nbx == 513 > dc.WG_CAP and c.state("map") in bv.PER_FRAME and c.unit_log2 in (4, 5), c.name
+        assert bv.families(c) == ["packed linear"]
+    multi = BY_NAME["map_ref_multi_cf1_12_padded"]
+    assert (multi.mode, multi.planes, multi.w, multi.h, multi.bd, multi.fused, multi.state("map")) == ("ref", "YUV", 256, 128, 12, dc.FUSED_ON, "padded")
+
+
 def test_padded_gaps_hold_poison_and_odd_strides_occur():
     odd = 0
     for c in CASES:
@@ -237,24 +256,73 @@ def test_giant_3d_family_and_census(name):
     """the plane is the first past the swz guard for its frame count, the launch is sao8<3d> with the frame in the grid's z, and
     frame g's parameters, keep map or borders (padded: the operand read at the tight stride) change frame f in every check window"""
     g = {x.name: x for x in bv.giants()}[name]
-    assert g.n > 1 and g.families() == ["sao8<3d>"]
-    (launch,) = dc.predict(g.dispatch_case())
-    assert launch.kernel == "sao8_kernel" and launch.args[0] == 0 and launch.grid[2] == g.n
-    assert dc.sao_swz(dc.Plane(g.w, g.h - 64, n=g.n)) and not dc.sao_swz(g.plane())
     p = g.plane()
-    assert 2 * p.nbytes() < 4 << 30     # source + destination: below the 6.07 GiB the dispatch tests already need
+    tx, tpf, total = dc.sao_strips(p)
+    launch = g.launch()
+    assert (launch.kernel, launch.args) == g.kernel and launch.grid == (tx, tpf // tx, g.n) and dc.api_align_ok(p), (name, launch)
+    if not g.kind:
+        assert g.n > 1 and g.families() == ["sao8<3d>"]
+        (l0,) = dc.predict(g.dispatch_case())
+        assert l0.kernel == "sao8_kernel" and l0.args[0] == 0 and l0.grid[2] == g.n
+        assert dc.sao_swz(dc.Plane(g.w, g.h - 64, n=g.n)) and not dc.sao_swz(p)
+        assert 2 * p.nbytes() < 4 << 30     # source + destination: below the 6.07 GiB the dispatch tests already need
+    else:
+        # the smallest plane of its kind past the guard: the most strip rows an entry takes, one strip per row fewer passes the guard,
+        # and the last strip holds one block column of 4 (g4, pairs) or 8 samples
+        assert g.n > 1 or g.bd > 8
+        assert tpf // tx == g.strip_rows and g.w == 256 * (tx - 1) + g.unit and g.ctb_log2 == (5 if g.kind == "sp" else 6)
+        if g.kind == "sp":   # two rows of strips, the second one block row: the same guard, half the bytes of 1024 rows of strips
+            assert g.strip_rows == 2 and g.h == 64 + g.unit and p.nbytes() < bv.Giant("x", "tight", kind="sp", pad=g.pad).plane().nbytes() * 0.55
+        else:
+            assert g.strip_rows == bv.GIANT_STRIP_ROWS and g.h <= 65535 < g.h + g.unit
+        assert not dc.sao_swz(p) and dc.sao_swz(dc.Plane(256 * (tx - 1), g.h, n=g.n))
+        assert (g.kind == "nox") == (g.w % 8 == 0 and g.h % 8 == 0) and g.w % 4 == 0 and g.h % 4 == 0
+        assert 2 * (p.nbytes() + 256) < 6.07 * (1 << 30)     # source + destination: what the dispatch tests already need
+        assert p.P * p.h < 1 << 31 or g.bd > 8               # the 8-bit packed kernels' own guard
     ops = bv.giant_operands(g)
-    assert len(ops["windows"][0].check(64)) >= 9
+    checks = ops["windows"][0][0].check(1 << g.ctb_log2)
+    assert len(checks) >= 9
+    if g.kind:   # a check window on each of the four plane borders; the last block column and the last block row in content windows
+        content = ops["windows"][0][0].content
+        assert {0} <= {r[0] for r in checks} and {0} <= {r[2] for r in checks} and g.h in {r[1] for r in checks} and g.w in {r[3] for r in checks}
+        assert any(r[1] == g.h for r in content) and any(r[3] == g.w for r in content)
     for x in ("params", "keep", "borders"):
-        a, b = bv.giant_arrays(g, ops, x)[:2]
-        assert a.shape == b.shape and (np.asarray(a).view(np.uint8) != np.asarray(b).view(np.uint8)).any()
-    assert (ops["params"][0]["type"] != 0).all() and (ops["keep"][0] != ops["keep"][1]).mean() > 0.5
+        for which in range(g.comps if x == "params" else 1):
+            arrs = bv.giant_arrays(g, ops, x, which)
+            assert len(arrs) == g.n
+            for a, b in itertools.permutations(arrs, 2):
+                assert a.shape == b.shape and (np.asarray(a).view(np.uint8) != np.asarray(b).view(np.uint8)).any()
+    first = ops["params"][0] if g.comps == 1 else ops["params"][0][0]
+    assert (first["type"] != 0).all() and (g.n == 1 or (ops["keep"][0] != ops["keep"][1]).mean() > 0.5)
+    if g.comps == 2:   # Cb and Cr differ in type in CTBs of a check window: the pair kernels' general path
+        cb, cr = ops["params"][0]
+        assert ((cb["type"] != cr["type"]) & ops["touch"]).sum() >= 9 and not ((cb["type"] != cr["type"]) & ~ops["touch"]).any()
     bad = bv.giant_census(g, ops)
     assert not bad, [(x, f, k, e[:2]) for x, f, k, e in bad]
 
 
 def test_giant_3d_states():
-    assert {g.state for g in bv.giants()} == {"tight", "padded"}
+    gs = bv.giants()
+    assert {g.state for g in gs} == {"tight", "padded"} and len({g.name for g in gs}) == len(gs)
+    assert {g.state for g in gs if g.n > 1 and g.kind} == {"tight", "padded"}
+    # the seven 3-D forms beside sao8_nox_kernel<false, 4>; the two semi-planar 16-bit forms need more than 4e9 bytes per buffer
+    assert {g.kernel for g in gs if g.kind} == {("sao8_g4_kernel", (0, 4)), ("sao_g4_kernel", ("u8", 0, 0)), ("sao_nox_kernel", ("u8", 0, 0)),
+                                                ("sao8_sp_kernel", (0,)), ("sao_sp_kernel", ("u8", 0)), ("sao_g4_kernel", ("u16", 0, 0)),
+                                                ("sao_nox_kernel", ("u16", 0, 0))}
+
+
+def test_unreached_pair_forms_need_more_than_4e9_bytes():
+    """sao_sp_kernel<u16, false> and sao16_sp_kernel<false> in the giants' construction (the most strip rows, the first strip count or
+    frame count past the guard), from the restated guards: the figures of profiles/launch_select/branch_census.md"""
+    one = bv.Giant("x", "tight", n=1, kind="sp", ctb_log2=5, bd=10, pad=8)
+    p = one.plane()
+    assert (one.launch().kernel, one.launch().args) == ("sao_sp_kernel", ("u16", 0)) and (one.w, one.h) == (16132, 65532) and p.nbytes() > 4.2e9
+    assert p.P * p.h >= 1 << 31        # ... and far past what the packed form addresses
+    # the packed 16-bit form needs pitch * plane_h < 2^31: at 65532 rows at most 8192 pairs a row, 32 strips; the guard fails by frames
+    w = dc.first_false(lambda k: 16 * k * one.h < 1 << 31, 1, 1 << 16) * 4 - 4
+    n = dc.first_false(lambda k: dc.sao_swz(dc.Plane(w, one.h, bd=10, pitch=4 * w, n=k)), 1, 1 << 16)
+    l = dc.sao_sp_launch(dc.Plane(w, one.h, bd=10, pitch=4 * w, n=n))
+    assert (w, n) == (8192, 4) and (l.kernel, l.args) == ("sao16_sp_kernel", (0,)) and n * 4 * w * one.h > 8.5e9
 
 
 # ---- the _sl, _g4, _sp and NV12 families ---------------------------------------------------------------------------------------------

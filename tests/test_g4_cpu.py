@@ -111,6 +111,29 @@ def test_sao_vectors_hold_what_tells_the_picture_edge_from_padding(spec):
     assert c["params"][0].shape == (rows, cols) and c["keep"][0].shape == ((c["h"] + 7) // 8, (c["w"] + 7) // 8)
 
 
+@pytest.mark.parametrize("spec", G.DEEP, ids=lambda s: s[0])
+def test_deep_sao_vectors_are_full_range_and_clip_at_max_v(spec):
+    """14 and 16 bit, 12 x 12 and 28 x 20: g4 planes above the packed procedures' 12 bit, on content that holds 0 and max_v; in every
+    case an offset lands above max_v and is clipped there, a keep map and borders (the layouts of the GPU test) change the output"""
+    import h265_vectors as hv
+    assert spec[3] in (14, 16) and spec[1:3] in ((12, 12), (28, 20)) and G.is_g4(*spec[1:3])
+    c = G.sao_case(spec, content="full")
+    max_v = (1 << c["depth"]) - 1
+    cen = G.sao_census(c["planes"], c["params"], c["lw"], c["lh"], c["depth"])
+    assert G.census_ok(cen, c["w"], c["h"]), (spec[0], cen)
+    assert all(p.min() == 0 and p.max() == max_v and p.dtype == np.uint16 for p in c["planes"])
+    tags = set().union(*(hv.sao_census(p, q, c["lw"], c["depth"]) for p, q in zip(c["planes"], c["params"])))
+    assert "clip_hi" in tags and "clip_lo" in tags, spec[0]
+    cuts = 0
+    for f in range(len(c["planes"])):
+        free = G.sao_direct(c["planes"][f], c["params"][f], c["lw"], c["lh"], bit_depth=c["depth"])
+        kept = G.sao_direct(c["planes"][f], c["params"][f], c["lw"], c["lh"], bit_depth=c["depth"], keep=c["keep"][f])
+        cut = G.sao_direct(c["planes"][f], c["params"][f], c["lw"], c["lh"], bit_depth=c["depth"], layout=G.sao_layout(c, f))
+        assert (free != kept).any(), (spec[0], f)
+        cuts += int((free != cut).any())
+    assert cuts >= 2, (spec[0], cuts)   # the borders: in two frames at the least (2 x 2 CTBs: a layout may forbid nothing that is looked at)
+
+
 # ---- the library ------------------------------------------------------------------------------------------------------------------
 
 def test_new_symbols_are_exported(L):

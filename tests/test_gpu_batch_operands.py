@@ -354,6 +354,8 @@ def check_identity(c, run):
     names = [parse_kernel(k[0]) for k in got]
     rew = (sum(n == "sao_rows_x2_kernel" for n, _ in names), sum(n == "sao_nox_rows_x2_kernel" for n, _ in names))
     assert rew == bv.rewrites_422(c), (c.name, rew, names)
+    if c.name in bv.PINNED:   # the instantiation only this case reaches: its name and template arguments, not its family alone
+        assert names == [bv.PINNED[c.name]], (c.name, names)
     if c.fam:   # the dispatch restatement does not know these families: the literal names the case was written for (these kernels
         # take the borders as an argument of the one kernel: there is no _nox_ twin whose name could be asserted)
         ran = [n for n, _ in names if "rows_x2" not in n]
@@ -364,6 +366,8 @@ def check_identity(c, run):
         return ran
     fams = [dc.family_of(n.replace("_nox_", "_"), a) for n, a in names if "rows_x2" not in n]
     assert fams == bv.families(c), (c.name, fams, bv.families(c), names)
+    if "dbk_generic_kernel" in [n for n, _ in names]:   # its launcher selects on sample width, plane kind and QP map: the arguments too
+        assert names == [(l.kernel, l.args) for l in dc.predict(bv.dispatch_case(c))], (c.name, names)
     if c.uses("borders"):
         assert all("_nox_" in n for n, _ in names if "sao" in n and "rows_x2" not in n), (c.name, names)
     return fams
@@ -554,42 +558,56 @@ def test_device_batch_per_frame_qp_maps_semi_planar(ctx):
         x.free()
 
 
-# ---- sao8<3d>: the frame index from the grid's z, on a plane just past the guard of the renumbered grid ---------------------------
+# ---- the 3-D forms: the frame index from the grid's z, on planes just past the guard of the renumbered grid ------------------------
 
 @pytest.mark.parametrize("name", [g.name for g in bv.giants()])
 def test_giant_3d(ctx, name):
-    """two flat frames with random windows, parameters / keep map / borders per frame: every byte of both frames (flat outside the
-    check windows, the windowed oracle inside), the gap between the frames and the operand buffers; the kernel is sao8<3d>"""
+    """flat frames with random windows, parameters / keep map / borders per frame: every byte of every frame (flat outside the check
+    windows, the windowed oracle inside, the row padding as it was filled), the gap between the frames and the operand buffers; the
+    capture shows the case's kernel with its template arguments on the 3-D grid (strips per row, strip rows, frames)"""
     lib, L = _lib(), _lib().lib()
     g = {x.name: x for x in bv.giants()}[name]
     p = g.plane()
     ops = bv.giant_operands(g)
     rows, cols = g.grid()
+    kr, kc = g.keep_shape()
+    px = g.comps * g.sb                              # bytes per sample position of a row: a pair of 8-bit samples is two
+    flat_byte = g.flat & 0xFF
+    assert g.flat == (flat_byte if g.sb == 1 else flat_byte * 0x0101)   # the flat value is one byte repeated: a memset makes the plane
     base = _device_used()
-    src, dst = ctx.alloc(p.nbytes()), ctx.alloc(p.nbytes())
+    src, dst = ctx.alloc(p.nbytes() + GUARD), ctx.alloc(p.nbytes() + GUARD)   # GUARD bytes behind the last row of the last frame
     bufs = [src, dst]
     try:
-        assert L.hevcdbk_memset_d(ctx.handle, src.ptr, g.flat, p.nbytes()) == 0
-        assert L.hevcdbk_memset_d(ctx.handle, dst.ptr, DST_FILL, p.nbytes()) == 0
+        assert L.hevcdbk_memset_d(ctx.handle, src.ptr, flat_byte, p.nbytes() + GUARD) == 0
+        assert L.hevcdbk_memset_d(ctx.handle, dst.ptr, DST_FILL, p.nbytes() + GUARD) == 0
         for f in range(g.n):
-            win = ops["windows"][f]
-            for i, (y0, y1, x0, x1) in enumerate(win.content):
-                data = win.window_data(i)
+            wins = ops["windows"][f]
+            for i, (y0, y1, x0, x1) in enumerate(wins[0].content):
+                data = np.stack([w.window_data(i) for w in wins], axis=-1)   # (rows, samples, components): pairs interleaved
+                data = np.ascontiguousarray(data).view(np.uint8).reshape(y1 - y0, (x1 - x0) * px)
                 for r in range(y1 - y0):
-                    src.upload(data[r], f * p.fs + (y0 + r) * p.P + x0)
+                    src.upload(data[r], f * p.fs + (y0 + r) * p.P + x0 * px)
         dev = {}
-        for x in ("params", "keep", "borders"):
-            img, stride = bv.lay_out(bv.giant_arrays(g, ops, x), g.state, bv.poison_entry(x), bv.operand_dtype(x))
+        for x, which in (("params", 0), ("params_cr", 1), ("keep", 0), ("borders", 0)):
+            if x == "params_cr" and g.comps == 1:
+                continue
+            y = "params" if x == "params_cr" else x
+            img, stride = bv.lay_out(bv.giant_arrays(g, ops, y, which), g.state, bv.poison_entry(y, g.bd), bv.operand_dtype(y))
             dev[x] = (Dev(ctx, img), stride)
             bufs.append(dev[x][0])
         dp = lib.DevicePlanes()
         dp.src, dp.dst, dp.pitch, dp.frame_stride, dp.n_frames = src.ptr, dst.ptr, p.P, p.fs, g.n
-        dp.plane_w, dp.plane_h, dp.bit_depth, dp.sample_bytes, dp.is_chroma = g.w, g.h, 8, 1, 0
+        dp.plane_w, dp.plane_h, dp.bit_depth, dp.sample_bytes, dp.is_chroma = g.w, g.h, g.bd, g.sb, int(g.kind == "sp")
         bo = lib.SaoBorders(dev["borders"][0].ptr, cols, dev["borders"][1])
 
         def call(h, s):
-            return L.hevcdbk_sao_filter_device_nox(h, C.byref(dp), dev["params"][0].ptr, cols, dev["params"][1], 6, 6, dev["keep"][0].ptr,
-                                                   g.w // 8, dev["keep"][1], C.byref(bo), s)
+            if g.kind == "sp":
+                assert dev["params"][1] == dev["params_cr"][1]
+                return L.hevcdbk_sao_filter_device_sp(h, C.byref(dp), dev["params"][0].ptr, dev["params_cr"][0].ptr, cols, dev["params"][1], g.ctb_log2,
+                                                      dev["keep"][0].ptr, kc, dev["keep"][1], C.byref(bo), s)
+            entry = L.hevcdbk_sao_filter_device_g4 if g.kind == "g4" else L.hevcdbk_sao_filter_device_nox
+            return entry(h, C.byref(dp), dev["params"][0].ptr, cols, dev["params"][1], g.ctb_log2, g.ctb_log2, dev["keep"][0].ptr, kc, dev["keep"][1],
+                         C.byref(bo), s)
         assert call(ctx.handle, None) == 0
         ctx.synchronize()
         used = (_device_used() - base) / (1 << 30)
@@ -601,17 +619,20 @@ def test_giant_3d(ctx, name):
             for y in range(0, g.h, chunk):
                 n = min(chunk, g.h - y)
                 got = dst.download(n * p.P, f * p.fs + y * p.P).reshape(n, p.P)
-                exp = np.full((n, p.P), g.flat, np.uint8)
+                exp = np.full((n, p.P), flat_byte, np.uint8)
+                exp[:, g.row_bytes:] = DST_FILL      # the row padding: as the destination was filled
                 for (y0, y1, x0, x1), e in exp_win:
                     a, b = max(y0, y), min(y1, y + n)
                     if a < b:
-                        exp[a - y:b - y, x0:x1] = e[a - y0:b - y0]
+                        eb = np.ascontiguousarray(e).view(np.uint8).reshape(y1 - y0, (x1 - x0) * px)
+                        exp[a - y:b - y, x0 * px:x1 * px] = eb[a - y0:b - y0]
                 if not np.array_equal(got, exp):
                     rr, cc = np.nonzero(got != exp)
-                    pytest.fail("%s frame %d: %d bytes differ in rows %d..%d, first at row %d col %d (got %d want %d)" % (
+                    pytest.fail("%s frame %d: %d bytes differ in rows %d..%d, first at row %d byte %d (got %d want %d)" % (
                         name, f, rr.size, y, y + n, y + rr[0], cc[0], got[rr[0], cc[0]], exp[rr[0], cc[0]]))
-        gap = dst.download(p.fs - p.P * g.h, p.P * g.h)
-        assert (gap == DST_FILL).all(), (name, "bytes between the frames were written")
+        for f in range(g.n):    # the gap behind each frame; behind the last one the guard bytes
+            gap = dst.download(p.fs - p.P * g.h if f < g.n - 1 else GUARD, f * p.fs + p.P * g.h)
+            assert (gap == DST_FILL).all(), (name, "bytes between or behind the frames were written")
         for x, (b, _) in dev.items():
             assert b.untouched(), (name, x, "operand buffer written")
         from gpu_video_codec_amd import deblock
@@ -622,8 +643,10 @@ def test_giant_3d(ctx, name):
             cap.close()
         assert rc == 0
         names = [parse_kernel(k[0]) for k in got]
-        assert [dc.family_of(n.replace("_nox_", "_"), a) for n, a in names] == ["sao8<3d>"] == g.families(), names
-        assert names[0][0] == "sao8_nox_kernel" and got[0][1][2] == g.n, (names, got)
+        if not g.kind:
+            assert [dc.family_of(n.replace("_nox_", "_"), a) for n, a in names] == ["sao8<3d>"] == g.families(), names
+        tx, tpf, _ = dc.sao_strips(p)
+        assert names == [g.kernel] and got[0][1] == (tx, tpf // tx, g.n) and got[0][2] == (dc.SAO_STRIP, 1, 1), (names, got)
     finally:
         for b in bufs:
             b.free()

@@ -156,11 +156,12 @@ def test_packed_maps_really_differ_on_a_wide_plane(ctx, lib):
 
 # ---- SAO ------------------------------------------------------------------------------------------------------------------------------
 
-@pytest.mark.parametrize("spec", G.CASES, ids=lambda s: s[0])
+@pytest.mark.parametrize("spec", G.CASES + G.DEEP, ids=lambda s: s[0])
 def test_sao(ctx, lib, spec):
-    from kernel_capture import kernels_enqueued
+    from kernel_capture import kernels_enqueued, parse_kernel
     L = lib.lib()
-    c = G.sao_case(spec)
+    deep = spec in G.DEEP   # 14 and 16 bit, full-range content: sao_g4_kernel<u16, true, false> (test_g4_cpu.py holds the clip census)
+    c = G.sao_case(spec, content="full" if deep else "noise")
     cen = G.sao_census(c["planes"], c["params"], c["lw"], c["lh"], c["depth"])
     assert G.census_ok(cen, c["w"], c["h"]), cen
     n = len(c["planes"])
@@ -180,6 +181,8 @@ def test_sao(ctx, lib, spec):
                 assert rc == 0 and names(k)[-1] in ("sao8_g4_kernel", "sao_g4_kernel"), (rc, names(k))
                 if c["sb"] == 1:
                     assert names(k)[-1] == ("sao8_g4_kernel" if aligned else "sao_g4_kernel")
+                if deep:   # the renumbered grid, sample by sample: one workgroup row of 8 for these planes of one strip
+                    assert [parse_kernel(x[0]) for x in k] == [("sao_g4_kernel", ("u16", 1, 0))] and k[0][1] == (8, 1, 1), k
                 assert call(None) == 0
                 ctx.synchronize()
                 check(pl.dst, want, (spec[0], borders, keep, aligned))

@@ -51,13 +51,21 @@ def laid_out(frames, pitch, gap, off):
     return out
 
 
+def captured(call):
+    """[(kernel, template arguments)] that call(stream) enqueues, from a stream capture (never instantiated, never launched)"""
+    from kernel_capture import kernels_enqueued, parse_kernel
+    _, k = kernels_enqueued(call)
+    return [parse_kernel(x[0]) for x in k]
+
+
 def gpu_stats(ctx, recs, orgs, bd, lw, lh, *, keeps=None, noxs=None, pitch=None, tight=False, org_pitch=None, rec_off=0, org_off=0, rec_gap=0,
-              org_gap=0):
+              org_gap=0, launched=None):
     """recs (n, h, w); orgs, keeps, noxs: (n, ...) = per frame, (1, ...) = shared, None = absent; the stride of keeps and noxs is
     their last dimension, their frame stride their last two (columns and rows beyond the map's or the grid's: padding the entry
     must not read).  pitch, org_pitch (default: pitch), rec_off / org_off (how far the plane's first sample lies behind the start of
     its allocation) and rec_gap / org_gap (what a frame stride has beyond the rows of a frame) are in samples.  Returns (n, rows,
-    cols) statistics after comparing every other int32 of the output buffer with the sentinel and the sources with what was uploaded"""
+    cols) statistics after comparing every other int32 of the output buffer with the sentinel and the sources with what was uploaded.
+    launched: a list that receives the kernels of a capture of the same call, on the same buffers"""
     from gpu_video_codec_amd import _lib
     recs = np.asarray(recs)
     n, h, w = recs.shape
@@ -86,10 +94,14 @@ def gpu_stats(ctx, recs, orgs, bd, lw, lh, *, keeps=None, noxs=None, pitch=None,
         kw.update(borders=_lib.SaoBorders(dn.ptr, noxs.shape[2], 0 if noxs.shape[0] == 1 else noxs.shape[1] * noxs.shape[2]))
     p = dev_planes(drec, n, w, h, bd, sb, pitch)
     p.src, p.frame_stride = drec.ptr + rec_off * sb, (pitch * h + rec_gap) * sb
-    ctx.sao_stats_device(p, dorg.ptr + org_off * sb, lw, ctb_log2_h=lh, org_pitch=org_pitch * sb,
-                         org_frame_stride=0 if np.asarray(orgs).shape[0] == 1 else (org_pitch * h + org_gap) * sb,
-                         out_ptr=dout.ptr + guard * 384, out_stride=stride, out_frame_stride=fstride, **kw)
+    def call(stream=None):
+        ctx.sao_stats_device(p, dorg.ptr + org_off * sb, lw, ctb_log2_h=lh, org_pitch=org_pitch * sb,
+                             org_frame_stride=0 if np.asarray(orgs).shape[0] == 1 else (org_pitch * h + org_gap) * sb,
+                             out_ptr=dout.ptr + guard * 384, out_stride=stride, out_frame_stride=fstride, stream=stream, **kw)
+    call()
     ctx.synchronize()
+    if launched is not None:
+        launched += captured(call)
     raw = dout.download(total * 384).view(np.uint32).reshape(total, 96)
     assert drec.download(hrec.nbytes).tobytes() == hrec.tobytes() and dorg.download(horg.nbytes).tobytes() == horg.tobytes(), "a source plane changed"
     got = np.zeros((n, rows, cols), S.STATS_DTYPE)
@@ -128,9 +140,12 @@ def test_statistics_are_the_references(ctx, name, keep):
     for kind in ("absent", "zero", "random", "layout"):
         nox = border_bytes(v, kind)
         want = S.stats_plane(v["rec"], v["org"], v["lw"], v["lh"], v["bd"], keep=v["keep"] if keep else None, nox=nox)
+        ran = []
         got = gpu_stats(ctx, v["rec"][None], v["org"][None], v["bd"], v["lw"], v["lh"], keeps=v["keep"][None] if keep else None,
-                        noxs=None if nox is None else nox[None], pitch=S.pitch_of(name))
+                        noxs=None if nox is None else nox[None], pitch=S.pitch_of(name), launched=ran)
         same(got[0], want, (name, keep, kind))
+        # which kernel ran, from a capture of the same call: rows of a multiple of four samples take four samples per load
+        assert ran == [("sao_stats_kernel", ("u8" if v["bd"] == 8 else "u16", int(S.pitch_of(name) % 4 == 0)))], (name, ran)
 
 
 @pytest.mark.parametrize("case", ["plus", "minus", "checkerboard"])
@@ -281,5 +296,10 @@ def test_closed_loop_on_the_device(ctx, name):
         measured = S.sse_per_ctb(v["org"], out, lw, lh) - S.sse_per_ctb(v["org"], v["rec"], lw, lh)
         print(name, lam, "delta SSE", int(measured.sum()))
         assert np.array_equal(measured, dd) and int(dd.sum()) < 0 and (dd <= 0).all(), (name, lam)
+    # the pick has one kernel and nothing to select: named here from a capture of the call above, one workgroup per CTB
+    from kernel_capture import kernels_enqueued, parse_kernel
+    _, k = kernels_enqueued(lambda s: ctx.sao_pick_device(dst.ptr, cols, cols, rows, bd, 1024, out_ptr=dprm.ptr, out_stride=cols,
+                                                          delta_d_ptr=ddd.ptr, stream=s))
+    assert [(parse_kernel(x[0]), x[1], x[2]) for x in k] == [(("sao_pick_kernel", ()), (cols, rows, 1), (64, 1, 1))], k
     for b in (drec, dorg, ddst, dk, dn, dst, dprm, ddd):
         b.free()

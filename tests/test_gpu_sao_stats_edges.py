@@ -93,7 +93,10 @@ def test_alignment_matrix(ctx, aligned, depth, name):
     vec = all(quad(kw.get(k, 0)) for k in ("rec_off", "org_off", "rec_gap", "org_gap")) and quad(kw.get("pitch", V.ALIGN_W)) and \
         quad(kw.get("org_pitch", kw.get("pitch", V.ALIGN_W)))
     assert vec == (name in V.VECTOR_LOADS)                            # a condition on the vectors: which side of the choice this is
-    got = gpu_stats(ctx, rec, org, V.DEPTHS[depth][0], lw, lh, keeps=keeps, noxs=noxs, **kw)
+    ran = []
+    got = gpu_stats(ctx, rec, org, V.DEPTHS[depth][0], lw, lh, keeps=keeps, noxs=noxs, launched=ran, **kw)
+    # which kernel ran, from a capture of the same call: four samples per load exactly for the layouts of VECTOR_LOADS
+    assert ran == [("sao_stats_kernel", ("u8" if depth == "8b" else "u16", int(name in V.VECTOR_LOADS)))], (depth, name, ran)
     for f in range(V.ALIGN_FRAMES):
         same(got[f], want[f], (depth, name, "reference", f))
         same(got[f], base[f], (depth, name, "aligned call", f))

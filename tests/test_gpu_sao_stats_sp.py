@@ -9,7 +9,7 @@ import pytest
 import rext_oracle as ro
 import sao_stats_ref as S
 import sao_stats_sp_ref as P
-from test_gpu_sao_stats import GAP, GUARD, PAD, SENTINEL, ctx, dev_planes, gpu_stats, laid_out, up  # noqa: F401 (ctx is the module's fixture)
+from test_gpu_sao_stats import GAP, GUARD, PAD, SENTINEL, captured, ctx, dev_planes, gpu_stats, laid_out, up  # noqa: F401 (ctx is the module's fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -17,11 +17,12 @@ GPU_DEPTHS = ("8b", "10b", "14b", "16b")
 
 
 def gpu_stats_sp(ctx, recs, orgs, bd, lg, *, keeps=None, noxs=None, pitch=None, org_pitch=None, rec_off=0, org_off=0, rec_gap=0, org_gap=0,
-                 tight=False):
+                 tight=False, launched=None):
     """recs (n, h, w, 2); orgs, keeps, noxs: (n, ...) = per frame, (1, ...) = shared, None = absent; the stride of keeps and noxs is
     their last dimension, their frame stride their last two.  pitch, org_pitch (default: pitch; default 2 w), rec_off / org_off and
     rec_gap / org_gap are in SAMPLES, as in gpu_stats.  Returns (n, 2, rows, cols) statistics, [:, 0] Cb's, after comparing every
-    other int32 of the output buffer with the sentinel and every source with what was uploaded"""
+    other int32 of the output buffer with the sentinel and every source with what was uploaded.  launched: a list that receives the
+    kernels of a capture of the same call, on the same buffers"""
     from gpu_video_codec_amd import _lib
     recs, orgs = np.asarray(recs), np.asarray(orgs)
     n, h, w, _ = recs.shape
@@ -49,10 +50,15 @@ def gpu_stats_sp(ctx, recs, orgs, bd, lg, *, keeps=None, noxs=None, pitch=None, 
     drec, dorg = sources[0][0], sources[1][0]
     p = dev_planes(drec, n, w, h, bd, sb, pitch)
     p.src, p.frame_stride, p.is_chroma = drec.ptr + rec_off * sb, (pitch * h + rec_gap) * sb, 1
-    ctx.sao_stats_device(p, dorg.ptr + org_off * sb, lg, org_pitch=org_pitch * sb,
-                         org_frame_stride=0 if orgs.shape[0] == 1 else (org_pitch * h + org_gap) * sb, out_ptr=dout.ptr + guard * 384,
-                         out_cr_ptr=dout.ptr + (one + guard) * 384, out_stride=stride, out_frame_stride=fstride, semi_planar=True, **kw)
+    def call(stream=None):
+        ctx.sao_stats_device(p, dorg.ptr + org_off * sb, lg, org_pitch=org_pitch * sb,
+                             org_frame_stride=0 if orgs.shape[0] == 1 else (org_pitch * h + org_gap) * sb, out_ptr=dout.ptr + guard * 384,
+                             out_cr_ptr=dout.ptr + (one + guard) * 384, out_stride=stride, out_frame_stride=fstride, semi_planar=True,
+                             stream=stream, **kw)
+    call()
     ctx.synchronize()
+    if launched is not None:
+        launched += captured(call)
     rest = dout.download(total * 384).view(np.uint32).reshape(total, 96).copy()
     for d, host in sources:
         assert d.download(host.nbytes).tobytes() == host.tobytes(), "a source or an operand changed"
@@ -94,7 +100,9 @@ def test_statistics_are_the_references(ctx, depth, lg):
 def test_pitch_of_2w_plus_10_samples_runs_sample_by_sample(ctx, depth, lg):
     w, h = P.PLANES[0]
     rec, org = P.content(w, h, depth, "full")
-    got = gpu_stats_sp(ctx, rec, org, P.DEPTHS[depth][0], lg, keeps=P.keep_map(w, h), noxs=P.border_bytes(w, h, lg), pitch=2 * w + 10)
+    ran = []
+    got = gpu_stats_sp(ctx, rec, org, P.DEPTHS[depth][0], lg, keeps=P.keep_map(w, h), noxs=P.border_bytes(w, h, lg), pitch=2 * w + 10, launched=ran)
+    assert ran == [("sao_stats_sp_kernel", ("u8" if depth == "8b" else "u16", 0))], (depth, lg, ran)
     same(got[0], P.reference(w, h, depth, "full", lg, True, True)[0], (depth, lg))
 
 
@@ -138,7 +146,10 @@ def test_load_choice(ctx, aligned, depth, name):
     rec, org, keeps, noxs, want = aligned[depth]
     kw = P.ALIGNMENTS[name]
     assert P.takes_wide_loads(kw) == (name in P.WIDE_LOADS)            # a condition on the vectors: which side of the choice this is
-    got = gpu_stats_sp(ctx, rec, org, P.DEPTHS[depth][0], P.ALIGN_LG, keeps=keeps, noxs=noxs, **kw)
+    ran = []
+    got = gpu_stats_sp(ctx, rec, org, P.DEPTHS[depth][0], P.ALIGN_LG, keeps=keeps, noxs=noxs, launched=ran, **kw)
+    # which kernel ran, from a capture of the same call: four samples per load exactly for the layouts of WIDE_LOADS
+    assert ran == [("sao_stats_sp_kernel", ("u8" if depth == "8b" else "u16", int(name in P.WIDE_LOADS)))], (depth, name, ran)
     for f in range(P.ALIGN_FRAMES):
         same(got[f], want[f], (depth, name, f))
     assert got[0].tobytes() != got[1].tobytes() and got[1].tobytes() != got[2].tobytes()
