@@ -52,6 +52,7 @@ EXPORTS = [
     "hevcdbk_h265_filter_device_sp", "hevcdbk_sao_filter_device_sp", "hevcdbk_h265_deblock_sao_device_sp",
     "hevcdbk_h265_deblock_sao_device_sp_fused", "hevcdbk_h265_deblock_sao_device_nv12",
     "hevcdbk_sao_stats_device", "hevcdbk_sao_pick_device", "hevcdbk_sao_stats_device_sp",
+    "hevcdbk_sao_decide_device",
 ]
 
 # chroma_format_idc of the spec-exact mode and SAO (HEVCDBK_CHROMA_*): 4:0:0, 4:2:0, 4:2:2, 4:4:4
@@ -174,6 +175,17 @@ SAO_STATS_DTYPE = [("eo_count", "<i4", (4, 4)), ("eo_sum", "<i4", (4, 4)), ("bo_
 class SaoStats(C.Structure):
     """hevcdbk_sao_stats: the statistics of one CTB (384 bytes)"""
     _fields_ = [("eo_count", (C.c_int32 * 4) * 4), ("eo_sum", (C.c_int32 * 4) * 4), ("bo_count", C.c_int32 * 32), ("bo_sum", C.c_int32 * 32)]
+
+
+# numpy dtype of hevcdbk_sao_decision: per CTB, what hevcdbk_sao_decide_device chose (merge: 0 own, 1 left, 2 up) and at what cost
+SAO_DECISION_DTYPE = [("delta_d", "<i8"), ("cost_luma", "<i8"), ("cost_chroma", "<i8"), ("merge", "u1"), ("flag_bits", "u1"), ("cand", "u1"),
+                      ("zero", "u1", (5,))]
+
+
+class SaoDecision(C.Structure):
+    """hevcdbk_sao_decision: the decision of one CTB (32 bytes)"""
+    _fields_ = [("delta_d", C.c_int64), ("cost_luma", C.c_int64), ("cost_chroma", C.c_int64), ("merge", C.c_uint8), ("flag_bits", C.c_uint8),
+                ("cand", C.c_uint8), ("zero", C.c_uint8 * 5)]
 
 
 class DeviceInfo(C.Structure):
@@ -338,6 +350,10 @@ def lib():
                                                   C.c_void_p]
         L.hevcdbk_sao_pick_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint, C.c_size_t, C.c_uint, C.c_uint, C.c_uint, C.c_uint,
                                               C.c_uint, C.c_void_p, C.c_void_p, C.c_uint, C.c_size_t, C.c_void_p, C.c_void_p]
+        # the decision per CTB: three statistics arrays, two index arrays, three parameter arrays and the records
+        L.hevcdbk_sao_decide_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint, C.c_size_t, C.c_uint, C.c_uint, C.c_uint,
+                                                C.c_uint, C.c_uint, C.c_uint, C.c_uint, C.c_void_p, C.c_void_p, C.c_uint, C.c_size_t, C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.c_uint, C.c_size_t, C.c_void_p, C.c_uint, C.c_size_t, C.c_void_p]
         L.hevc_deblock_sao_h265_device_planes.argtypes = [C.c_void_p, C.POINTER(DevicePlanes), C.c_uint, C.c_uint, C.POINTER(H265Params),
                                                           C.POINTER(SaoPlane), C.c_int, C.c_void_p]
         L.hevcdbk_set_host_threads.argtypes = [C.c_void_p, C.c_uint]

@@ -1,0 +1,93 @@
+/*
+ * sao_decide_host.cpp -- C-ABI entry of the SAO decision per CTB: hevcdbk_sao_decide_device (own parameters, merge left or merge up
+ * over Y, Cb and Cr from the statistics of hevcdbk_sao_stats_device / _sp).  Every operand is checked before the context is looked
+ * into or the device is touched, in the order the header lists; nothing is enqueued on refusal.  Kernels: sao_decide.hip.
+ */
+#include "deblock_ctx.h"
+#include "deblock_host_args.h"
+#include "sao_decide_launch.h"
+
+using namespace dbkh;
+
+static_assert(sizeof(hevcdbk_sao_decision) == 32 && sizeof(DbkSaoDecision) == 32, "hevcdbk_sao_decision is 32 bytes");
+static_assert(offsetof(hevcdbk_sao_decision, merge) == offsetof(DbkSaoDecision, merge) && offsetof(hevcdbk_sao_decision, cand) == offsetof(DbkSaoDecision, cand),
+              "the kernels' record is the header's");
+
+extern "C" {
+
+int hevcdbk_sao_decide_device(hevcdbk_context *ctx, const hevcdbk_sao_stats *stats_y, const hevcdbk_sao_stats *stats_cb,
+                              const hevcdbk_sao_stats *stats_cr, unsigned stats_stride, size_t stats_frame_stride, unsigned ctbs_x,
+                              unsigned ctbs_y, unsigned n_frames, unsigned bit_depth_luma, unsigned bit_depth_chroma, unsigned lambda_q8_luma,
+                              unsigned lambda_q8_chroma, const uint16_t *slice_idx, const uint16_t *tile_idx, unsigned idx_stride,
+                              size_t idx_frame_stride, hevcdbk_sao_ctb *params_y, hevcdbk_sao_ctb *params_cb, hevcdbk_sao_ctb *params_cr,
+                              unsigned params_stride, size_t params_frame_stride, hevcdbk_sao_decision *decision, unsigned decision_stride,
+                              size_t decision_frame_stride, void *hip_stream)
+{
+    const bool chroma = stats_cb != nullptr;
+    if (!ctx || !stats_y || !params_y || !decision) return HEVCDBK_ERR_ARG;
+    if (chroma != (stats_cr != nullptr)) return HEVCDBK_ERR_ARG;
+    if (chroma && (!params_cb || !params_cr)) return HEVCDBK_ERR_ARG;
+    if (bit_depth_luma < 8 || bit_depth_luma > 16 || (chroma && (bit_depth_chroma < 8 || bit_depth_chroma > 16))) return HEVCDBK_ERR_ARG;
+    if (lambda_q8_luma > (1u << 24) || (chroma && lambda_q8_chroma > (1u << 24))) return HEVCDBK_ERR_ARG;
+    if (ctbs_x == 0 || ctbs_y == 0 || ctbs_x > 65535 || ctbs_y > 65535) return HEVCDBK_ERR_DIMENSIONS;
+    const bool idx = slice_idx || tile_idx;
+    if (stats_stride < ctbs_x || params_stride < ctbs_x || decision_stride < ctbs_x || (idx && idx_stride < ctbs_x)) return HEVCDBK_ERR_ARG;
+    if (stats_stride > 0x7fffffffu || params_stride > 0x7fffffffu || decision_stride > 0x7fffffffu || idx_stride > 0x7fffffffu) return HEVCDBK_ERR_ARG;
+    if (n_frames > 1 && (params_frame_stride < (size_t)params_stride * ctbs_y || decision_frame_stride < (size_t)decision_stride * ctbs_y))
+        return HEVCDBK_ERR_ARG; /* an output cannot be shared */
+    if (n_frames > 65535) return HEVCDBK_ERR_ARG;
+    if ((uintptr_t)stats_y % 4 != 0 || (uintptr_t)stats_cb % 4 != 0 || (uintptr_t)stats_cr % 4 != 0 || (uintptr_t)decision % 8 != 0 ||
+        (uintptr_t)slice_idx % 2 != 0 || (uintptr_t)tile_idx % 2 != 0)
+        return HEVCDBK_ERR_ARG;
+    if (n_frames > 0) { /* from an array's first entry to its last: no output's extent meets another's, or that of the statistics */
+        struct Extent {
+            uintptr_t lo, hi;
+        };
+        auto extent = [&](const void *p, unsigned stride, size_t frame_stride, size_t entry) {
+            const unsigned long long n = (unsigned long long)(n_frames - 1) * frame_stride + (unsigned long long)(ctbs_y - 1) * stride + ctbs_x;
+            return Extent{(uintptr_t)p, (uintptr_t)p + (uintptr_t)(n * entry)};
+        };
+        Extent e[7];
+        int n_out = 0, n_all;
+        e[n_out++] = extent(params_y, params_stride, params_frame_stride, sizeof(hevcdbk_sao_ctb));
+        e[n_out++] = extent(decision, decision_stride, decision_frame_stride, sizeof(hevcdbk_sao_decision));
+        if (chroma) {
+            e[n_out++] = extent(params_cb, params_stride, params_frame_stride, sizeof(hevcdbk_sao_ctb));
+            e[n_out++] = extent(params_cr, params_stride, params_frame_stride, sizeof(hevcdbk_sao_ctb));
+        }
+        n_all = n_out;
+        e[n_all++] = extent(stats_y, stats_stride, stats_frame_stride, sizeof(hevcdbk_sao_stats));
+        if (chroma) {
+            e[n_all++] = extent(stats_cb, stats_stride, stats_frame_stride, sizeof(hevcdbk_sao_stats));
+            e[n_all++] = extent(stats_cr, stats_stride, stats_frame_stride, sizeof(hevcdbk_sao_stats));
+        }
+        for (int i = 0; i < n_out; i++)
+            for (int k = i + 1; k < n_all; k++)
+                if (e[i].lo < e[k].hi && e[k].lo < e[i].hi) return HEVCDBK_ERR_ARG;
+    }
+    DbkSaoDecideArgs a = {};
+    a.stats_y = reinterpret_cast<const int32_t *>(stats_y);
+    a.stats_cb = reinterpret_cast<const int32_t *>(stats_cb);
+    a.stats_cr = reinterpret_cast<const int32_t *>(stats_cr);
+    a.stats_stride = (int)stats_stride; a.stats_frame_stride = (long long)stats_frame_stride;
+    a.ctbs_x = (int)ctbs_x; a.ctbs_y = (int)ctbs_y; a.n_frames = (int)n_frames;
+    a.max_offset_luma = (1 << ((bit_depth_luma < 10 ? bit_depth_luma : 10) - 5)) - 1;
+    a.lambda_luma = (long long)lambda_q8_luma;
+    if (chroma) {
+        a.max_offset_chroma = (1 << ((bit_depth_chroma < 10 ? bit_depth_chroma : 10) - 5)) - 1;
+        a.lambda_chroma = (long long)lambda_q8_chroma;
+        a.params_cb = reinterpret_cast<DbkSaoCtb *>(params_cb);
+        a.params_cr = reinterpret_cast<DbkSaoCtb *>(params_cr);
+    }
+    a.slice_idx = slice_idx; a.tile_idx = tile_idx;
+    a.idx_stride = (int)idx_stride; a.idx_frame_stride = (long long)idx_frame_stride;
+    a.params_y = reinterpret_cast<DbkSaoCtb *>(params_y);
+    a.params_stride = (int)params_stride; a.params_frame_stride = (long long)params_frame_stride;
+    a.decision = reinterpret_cast<DbkSaoDecision *>(decision);
+    a.decision_stride = (int)decision_stride; a.decision_frame_stride = (long long)decision_frame_stride;
+    if (int rc = bind(ctx)) return rc;
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->compute;
+    return hip_ok(ctx, dbk_launch_sao_decide(a, s), "SAO decide launch") ? HEVCDBK_OK : HEVCDBK_ERR_HIP;
+}
+
+} /* extern "C" */

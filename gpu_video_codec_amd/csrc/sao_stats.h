@@ -266,4 +266,18 @@ DBK_HD long long pick_ctb(const BinPick *a, const BinPick *b, long long lambda, 
     return write(a, type, cls, pa) + write(b, type, cls, *pb);
 }
 
+/* the least cost pick_ctb found -- the cost of the candidate it wrote into pa (and *pb), by the same terms: what a caller needs who
+ * weighs the choice against something else (sao_decide.h).  pa, pb: what pick_ctb(a, b, lambda, ...) gave */
+DBK_HD long long pick_cost(const BinPick *a, const BinPick *b, long long lambda, const DbkSaoCtb &pa, const DbkSaoCtb *pb)
+{
+    auto four = [](const BinPick *p, const DbkSaoCtb &c) {
+        long long cost = 0;
+        for (int k = 0; k < 4; k++) cost += p[c.type == 2 ? 4 * c.cls + k : 16 + ((c.cls + k) & 31)].cost;
+        return cost;
+    };
+    if (pa.type == 0) return lambda;
+    if (pa.type == 2) return lambda * 4 + four(a, pa) + (b ? four(b, *pb) : 0);
+    return b ? lambda * 12 + four(a, pa) + four(b, *pb) : lambda * 7 + four(a, pa);
+}
+
 } /* namespace saostats */

@@ -512,6 +512,22 @@ class Context:
                                                 n_frames, bit_depth, lambda_q8, out_ptr, out_b_ptr, out_stride, out_frame_stride,
                                                 delta_d_ptr, stream), self.handle)
 
+    def sao_decide_device(self, stats_ptr, stats_stride, ctbs_x, ctbs_y, bit_depth, lambda_q8, *, out_ptr, out_stride, decision_ptr,
+                          decision_stride, n_frames=1, stats_frame_stride=0, out_frame_stride=0, decision_frame_stride=0, stats_cb_ptr=None,
+                          stats_cr_ptr=None, out_cb_ptr=None, out_cr_ptr=None, bit_depth_chroma=None, lambda_q8_chroma=None,
+                          slice_idx_ptr=None, tile_idx_ptr=None, idx_stride=0, idx_frame_stride=0, stream=None):
+        """hevcdbk_sao_decide_device: per CTB own parameters, merge left or merge up (H.265 7.3.8.3) over Y, Cb and Cr at once, by the
+        rule of include/hevc_deblock.h.  stats_ptr: luma's statistics; stats_cb_ptr / stats_cr_ptr (both or neither): the chroma
+        components' on the same grid, with the same strides.  out_ptr / out_cb_ptr / out_cr_ptr: the final hevcdbk_sao_ctb per CTB, as
+        sao_device reads them.  decision_ptr: one _lib.SaoDecision (numpy: _lib.SAO_DECISION_DTYPE) per CTB.  bit_depth_chroma and
+        lambda_q8_chroma default to luma's.  slice_idx_ptr, tile_idx_ptr: uint16 per CTB, as sao_borders_device takes them; a CTB
+        merges only with a neighbour of its own slice and tile."""
+        _chk(_lib.lib().hevcdbk_sao_decide_device(self.handle, stats_ptr, stats_cb_ptr, stats_cr_ptr, stats_stride, stats_frame_stride, ctbs_x,
+                                                  ctbs_y, n_frames, bit_depth, bit_depth if bit_depth_chroma is None else bit_depth_chroma,
+                                                  lambda_q8, lambda_q8 if lambda_q8_chroma is None else lambda_q8_chroma, slice_idx_ptr,
+                                                  tile_idx_ptr, idx_stride, idx_frame_stride, out_ptr, out_cb_ptr, out_cr_ptr, out_stride,
+                                                  out_frame_stride, decision_ptr, decision_stride, decision_frame_stride, stream), self.handle)
+
     def deblock_sao_device(self, planes, qp, params_ptr, params_stride, ctb_log2, *, params_frame_stride=0, keep_ptr=None,
                            keep_stride=0, keep_frame_stride=0, tc_table=None, beta_table=None, fused=_lib.FUSED_AUTO, stream=None):
         """hevc_deblock_sao_device: reference-exact deblocking followed by SAO, src -> dst, one kernel where it applies.

@@ -963,6 +963,61 @@ HEVCDBK_API int hevcdbk_sao_pick_device(hevcdbk_context *ctx, const hevcdbk_sao_
                                         hevcdbk_sao_ctb *params_b, unsigned params_stride, size_t params_frame_stride, int64_t *delta_d,
                                         void *hip_stream);
 
+/*
+ * The SAO decision per CTB as 7.3.8.3 codes it: own parameters, sao_merge_left_flag or sao_merge_up_flag.  One flag takes the
+ * neighbour's FINAL parameters of Y, Cb and Cr at once, so the decision is serial in raster order; on the device it runs along the
+ * anti-diagonals of the CTB grid.  The chain is deblocking -> statistics -> decide -> SAO, nothing read back in between: for a planar
+ * picture the three statistics arrays come from three hevcdbk_sao_stats_device calls, for NV12 from one such call (luma) and one
+ * hevcdbk_sao_stats_device_sp call (stats_cb, stats_cr), and params_y / params_cb / params_cr are what hevcdbk_sao_filter_device_* /
+ * _sp read.  The rule is the library's own, an extension of the pick rule above: integers only, "parity unpinned".
+ *   - All three statistics arrays lie on ONE CTB grid (a chroma CTB grid has the luma grid's counts in every chroma format) with one
+ *     stride and one frame stride (entries; 0 = shared).  stats_cb and stats_cr are both given or both NULL; both NULL is 4:0:0 or
+ *     luma alone, and params_cb, params_cr, bit_depth_chroma and lambda_q8_chroma are then not looked at.
+ *   - slice_idx, tile_idx: as hevcdbk_h265_sao_borders_device takes them, with one stride (idx_stride entries per CTB row) and one
+ *     frame stride (entries; 0 = shared); either may be NULL = one slice / one tile.  A left candidate exists iff cx > 0 and the
+ *     left CTB has the same slice index and the same tile index; an up candidate likewise with cy > 0.  For a conforming stream that
+ *     is the condition of 7.3.8.3.  It is NOT the boundary byte of hevcdbk_sao_borders: slices with filtering across them enabled
+ *     still do not merge.
+ *   - pd(S, p) = the sum over the four bins p uses of n o^2 - 2 o s.  M_y, M_c: the pick rule's limit for each depth; both lambdas
+ *     are at most 2^24.  The candidates of a CTB with statistics S_y, S_cb, S_cr, in this order:
+ *       NEW   exactly what hevcdbk_sao_pick_device gives for S_y alone with lambda_q8_luma and for (S_cb, S_cr) jointly with
+ *             lambda_q8_chroma; C_y, C_c = those picks' least costs (deltaD * 256 + lambda * bits); F = the number of candidates
+ *             that exist (each flag coded as 0);
+ *       LEFT  the left CTB's FINAL triple; C_y = 256 * pd(S_y, p_y), C_c = 256 * (pd(S_cb, p_cb) + pd(S_cr, p_cr)); F = 1;
+ *       UP    the upper CTB's FINAL triple; C_y, C_c as for LEFT; F = 1 + (1 if a left candidate exists).
+ *     The lowest J = lambda_c * C_y + lambda_l * C_c + lambda_l * lambda_c * F wins (D_y / lambda_l + D_c / lambda_c + R cleared of
+ *     its divisions; without chroma J = C_y + lambda_l * F), on a tie the earliest.  J is compared exactly, in 128 bits.
+ *   - params_*: the final triples, one stride and one frame stride; a merged CTB holds a copy of its neighbour's.
+ *     log2_sao_offset_scale stays 0.  decision: the record below per CTB, its own stride and frame stride (entries).  Every entry of
+ *     every output grid is written, with plain stores; entries beyond the CTB columns are not touched.  The same bits every run.
+ *   - The slice-level slice_sao_luma_flag / slice_sao_chroma_flag are the caller's to set, from the records summed over a slice.
+ * Refusals, in this order, every one before the context is bound and with nothing enqueued: a NULL ctx, stats_y, params_y or
+ * decision, exactly one of stats_cb / stats_cr, chroma statistics without params_cb or params_cr, a bit depth outside 8..16, a lambda
+ * above 2^24 -- HEVCDBK_ERR_ARG; ctbs_x or ctbs_y of 0 or above 65535 -- HEVCDBK_ERR_DIMENSIONS; then HEVCDBK_ERR_ARG for a stride
+ * (stats, params, decision; idx when an index array is given) below ctbs_x, a params_frame_stride or decision_frame_stride below one
+ * grid with n_frames > 1, more than 65535 frames, statistics at an address that is no multiple of 4, a decision at one that is no
+ * multiple of 8, an index array at an odd address, and an output whose extent (first entry to last) meets that of another output
+ * or of a statistics array.  Two small launches, asynchronous on hip_stream (NULL = the context's compute stream).
+ */
+typedef struct hevcdbk_sao_decision {   /* one per CTB, 32 bytes, DEVICE memory */
+    int64_t delta_d;      /* predicted change of the SSE under the FINAL parameters, the components summed */
+    int64_t cost_luma;    /* C_y of the chosen candidate */
+    int64_t cost_chroma;  /* C_c of the chosen candidate, 0 without chroma */
+    uint8_t merge;        /* 0 = own parameters, 1 = sao_merge_left_flag, 2 = sao_merge_up_flag */
+    uint8_t flag_bits;    /* F of the chosen candidate */
+    uint8_t cand;         /* bit 0: a left candidate existed, bit 1: an up candidate existed */
+    uint8_t zero[5];
+} hevcdbk_sao_decision;
+
+HEVCDBK_API int hevcdbk_sao_decide_device(hevcdbk_context *ctx, const hevcdbk_sao_stats *stats_y, const hevcdbk_sao_stats *stats_cb,
+                                          const hevcdbk_sao_stats *stats_cr, unsigned stats_stride, size_t stats_frame_stride,
+                                          unsigned ctbs_x, unsigned ctbs_y, unsigned n_frames, unsigned bit_depth_luma,
+                                          unsigned bit_depth_chroma, unsigned lambda_q8_luma, unsigned lambda_q8_chroma,
+                                          const uint16_t *slice_idx, const uint16_t *tile_idx, unsigned idx_stride, size_t idx_frame_stride,
+                                          hevcdbk_sao_ctb *params_y, hevcdbk_sao_ctb *params_cb, hevcdbk_sao_ctb *params_cr,
+                                          unsigned params_stride, size_t params_frame_stride, hevcdbk_sao_decision *decision,
+                                          unsigned decision_stride, size_t decision_frame_stride, void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

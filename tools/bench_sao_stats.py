@@ -9,7 +9,10 @@ them.  The pick launch is timed once per depth, for the record.  One JSON line p
 --semi-planar: the statistics of a plane of interleaved Cb / Cr pairs (960x540 and 1920x1080 pairs, 64 frames, 32-sample CTBs, noise
 and flat) in three forms that take turns on the same buffers: (a) one hevcdbk_sao_stats_device_sp launch; (b) two
 hevcdbk_sao_stats_device launches on planes that are already split; (c) as (b) after the two strided copies that split rec and the
-two that split org (torch, on the stream the launches use).  Every form fills the same two arrays, compared once per row."""
+two that split org (torch, on the stream the launches use).  Every form fills the same two arrays, compared once per row.
+
+--decide: the decision per CTB (hevcdbk_sao_decide_device: own parameters, merge left or merge up over Y, Cb and Cr) for 64 frames of
+3840x2160 at 64- and 16-sample CTBs, taking turns with the luma statistics pass and the two pick launches on the same batch."""
 import argparse, json, os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -132,8 +135,68 @@ def semi_planar(a):
                 fh.write(json.dumps(line) + "\n")
 
 
+def decide(a):
+    """--decide: hevcdbk_sao_decide_device (Y, Cb, Cr on one CTB grid) on a.frames frames of a.width x a.height at each CTB size of
+    a.ctbs, taking turns in this process with the luma statistics pass and with the two pick launches (luma alone, Cb and Cr jointly)
+    that produce what the decision's NEW candidates are -- on the same batch.  The three statistics arrays are those of the luma
+    plane against three different originals: real statistics, one record per CTB.  One JSON line per CTB size."""
+    w, h, n, bd, lam = a.width, a.height, a.frames, 8, 1024
+    ctx = deblock.Context(0)
+    b = deblock.DeviceBatch(ctx, w, h, n, bit_depth=bd, per_frame_bs=False)
+    dorg = ctx.alloc(b.frame_bytes * (n + 2))
+    rec, org = frames_of("blocky", w, h, bd, np.random.default_rng(11))
+    for f in range(n + 2):
+        if f < n:
+            b.upload_frame(f, rec[f % 4])
+        dorg.upload(org[(f + 1) % 4], f * b.frame_bytes)
+    p = b.planes()
+    lines = []
+    for L in [int(x) for x in a.ctbs.split(",")]:
+        rows, cols = (h + (1 << L) - 1) >> L, (w + (1 << L) - 1) >> L
+        g = rows * cols
+        dst = [ctx.alloc(g * n * 384) for _ in range(3)]
+        dprm = [ctx.alloc(g * n * 6) for _ in range(3)]
+        ddec = ctx.alloc(g * n * 32)
+        stats = lambda c=0: ctx.sao_stats_device(p, dorg.ptr + c * b.frame_bytes, L, out_ptr=dst[c].ptr, out_stride=cols, out_frame_stride=g)
+        for c in range(3):
+            stats(c)
+
+        def picks():
+            ctx.sao_pick_device(dst[0].ptr, cols, cols, rows, bd, lam, out_ptr=dprm[0].ptr, out_stride=cols, n_frames=n, stats_frame_stride=g,
+                                out_frame_stride=g)
+            ctx.sao_pick_device(dst[1].ptr, cols, cols, rows, bd, lam, out_ptr=dprm[1].ptr, out_stride=cols, n_frames=n, stats_frame_stride=g,
+                                out_frame_stride=g, stats_b_ptr=dst[2].ptr, out_b_ptr=dprm[2].ptr)
+
+        def dec():
+            ctx.sao_decide_device(dst[0].ptr, cols, cols, rows, bd, lam, out_ptr=dprm[0].ptr, out_stride=cols, decision_ptr=ddec.ptr,
+                                  decision_stride=cols, n_frames=n, stats_frame_stride=g, out_frame_stride=g, decision_frame_stride=g,
+                                  stats_cb_ptr=dst[1].ptr, stats_cr_ptr=dst[2].ptr, out_cb_ptr=dprm[1].ptr, out_cr_ptr=dprm[2].ptr)
+        forms = {"stats_luma": stats, "two_picks": picks, "decide": dec}
+        timed(ctx, stats, 30, 0)   # settle the clocks
+        ms = {k: [] for k in forms}
+        for _ in range(a.rounds):
+            for k, fn in forms.items():
+                ms[k].append(timed(ctx, fn, a.steps, 5))
+        med = {k: float(np.median(v)) for k, v in ms.items()}
+        merge = np.bincount(ddec.download(g * n * 32).view(np.dtype(_lib.SAO_DECISION_DTYPE))["merge"], minlength=3)
+        line = {"stage": "sao_decide", "workload": "%dx%d %d-bit x %d, %d-sample CTBs, Y + Cb + Cr on one grid" % (w, h, bd, n, 1 << L),
+                "ctbs": g * n, "lambda_q8": lam, "ms_per_call": med, "rounds_ms": ms, "spread_ms": {k: float(max(v) - min(v)) for k, v in ms.items()},
+                "decide_over_stats_luma": med["decide"] / med["stats_luma"], "decide_over_two_picks": med["decide"] / med["two_picks"],
+                "decide_slower_than_stats_luma": bool(med["decide"] > med["stats_luma"]), "merge_0_left_up": [int(x) for x in merge]}
+        lines.append(line)
+        print(json.dumps(line), flush=True)
+        for d in dst + dprm + [ddec]:
+            d.free()
+    if a.out:
+        with open(a.out, "a") as fh:
+            for line in lines:
+                fh.write(json.dumps(line) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--decide", action="store_true", help="the decision per CTB against the luma statistics pass and the two pick launches")
+    ap.add_argument("--ctbs", default="6,4", help="--decide: log2 of the CTB sizes")
     ap.add_argument("--semi-planar", action="store_true", help="the pair-plane entry against two planar launches, with and without the split copies")
     ap.add_argument("--sizes", default="960x540,1920x1080", help="--semi-planar: pairs per row x rows")
     ap.add_argument("--width", type=int, default=3840)
@@ -146,6 +209,8 @@ def main():
     ap.add_argument("--ctb-log2", type=int, default=6)
     ap.add_argument("--out", default=None, help="append the JSON lines to this file as well")
     a = ap.parse_args()
+    if a.decide:
+        return decide(a)
     if a.semi_planar:
         if a.contents == "flat,blocky,noise":
             a.contents = "noise,flat"
