@@ -52,7 +52,7 @@ EXPORTS = [
     "hevcdbk_h265_filter_device_sp", "hevcdbk_sao_filter_device_sp", "hevcdbk_h265_deblock_sao_device_sp",
     "hevcdbk_h265_deblock_sao_device_sp_fused", "hevcdbk_h265_deblock_sao_device_nv12",
     "hevcdbk_sao_stats_device", "hevcdbk_sao_pick_device", "hevcdbk_sao_stats_device_sp",
-    "hevcdbk_sao_decide_device",
+    "hevcdbk_sao_decide_device", "hevcdbk_sao_pick_device_os", "hevcdbk_sao_decide_device_os",
 ]
 
 # chroma_format_idc of the spec-exact mode and SAO (HEVCDBK_CHROMA_*): 4:0:0, 4:2:0, 4:2:2, 4:4:4
@@ -354,6 +354,10 @@ def lib():
         L.hevcdbk_sao_decide_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint, C.c_size_t, C.c_uint, C.c_uint, C.c_uint,
                                                 C.c_uint, C.c_uint, C.c_uint, C.c_uint, C.c_void_p, C.c_void_p, C.c_uint, C.c_size_t, C.c_void_p,
                                                 C.c_void_p, C.c_void_p, C.c_uint, C.c_size_t, C.c_void_p, C.c_uint, C.c_size_t, C.c_void_p]
+        # the two with log2_sao_offset_scale: one scale after the depth, two after the two depths
+        L.hevcdbk_sao_pick_device_os.argtypes = L.hevcdbk_sao_pick_device.argtypes[:9] + [C.c_uint] + L.hevcdbk_sao_pick_device.argtypes[9:]
+        L.hevcdbk_sao_decide_device_os.argtypes = (L.hevcdbk_sao_decide_device.argtypes[:11] + [C.c_uint, C.c_uint] +
+                                                   L.hevcdbk_sao_decide_device.argtypes[11:])
         L.hevc_deblock_sao_h265_device_planes.argtypes = [C.c_void_p, C.POINTER(DevicePlanes), C.c_uint, C.c_uint, C.POINTER(H265Params),
                                                           C.POINTER(SaoPlane), C.c_int, C.c_void_p]
         L.hevcdbk_set_host_threads.argtypes = [C.c_void_p, C.c_uint]

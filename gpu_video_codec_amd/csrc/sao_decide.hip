@@ -57,6 +57,12 @@ hipError_t dbk_launch_sao_decide(const DbkSaoDecideArgs &a, hipStream_t stream)
     if (a.n_frames <= 0 || a.ctbs_x <= 0 || a.ctbs_y <= 0) return hipSuccess;
     hipLaunchKernelGGL(sao_decide_new_kernel, dim3(a.ctbs_x, a.ctbs_y, a.n_frames), dim3(64), 0, stream, a);
     if (hipError_t e = hipGetLastError()) return e;
+    return dbk_launch_sao_decide_merge(a, stream);
+}
+
+hipError_t dbk_launch_sao_decide_merge(const DbkSaoDecideArgs &a, hipStream_t stream)
+{
+    if (a.n_frames <= 0 || a.ctbs_x <= 0 || a.ctbs_y <= 0) return hipSuccess;
     if (a.ctbs_x + a.ctbs_y > 2) hipLaunchKernelGGL(sao_decide_merge_kernel, dim3(a.n_frames), dim3(saodecide::kChunk), 0, stream, a);
     return hipGetLastError();
 }

@@ -1,11 +1,13 @@
 /*
- * sao_decide_host.cpp -- C-ABI entry of the SAO decision per CTB: hevcdbk_sao_decide_device (own parameters, merge left or merge up
- * over Y, Cb and Cr from the statistics of hevcdbk_sao_stats_device / _sp).  Every operand is checked before the context is looked
- * into or the device is touched, in the order the header lists; nothing is enqueued on refusal.  Kernels: sao_decide.hip.
+ * sao_decide_host.cpp -- C-ABI entries of the SAO decision per CTB: hevcdbk_sao_decide_device (own parameters, merge left or merge up
+ * over Y, Cb and Cr from the statistics of hevcdbk_sao_stats_device / _sp) and hevcdbk_sao_decide_device_os (the same with
+ * log2_sao_offset_scale_luma / _chroma).  Every operand is checked before the context is looked
+ * into or the device is touched, in the order the header lists; nothing is enqueued on refusal.  Kernels: sao_decide.hip, sao_pick_os.hip.
  */
 #include "deblock_ctx.h"
 #include "deblock_host_args.h"
 #include "sao_decide_launch.h"
+#include "sao_pick_os_launch.h"
 
 using namespace dbkh;
 
@@ -15,13 +17,14 @@ static_assert(offsetof(hevcdbk_sao_decision, merge) == offsetof(DbkSaoDecision, 
 
 extern "C" {
 
-int hevcdbk_sao_decide_device(hevcdbk_context *ctx, const hevcdbk_sao_stats *stats_y, const hevcdbk_sao_stats *stats_cb,
-                              const hevcdbk_sao_stats *stats_cr, unsigned stats_stride, size_t stats_frame_stride, unsigned ctbs_x,
-                              unsigned ctbs_y, unsigned n_frames, unsigned bit_depth_luma, unsigned bit_depth_chroma, unsigned lambda_q8_luma,
-                              unsigned lambda_q8_chroma, const uint16_t *slice_idx, const uint16_t *tile_idx, unsigned idx_stride,
-                              size_t idx_frame_stride, hevcdbk_sao_ctb *params_y, hevcdbk_sao_ctb *params_cb, hevcdbk_sao_ctb *params_cr,
-                              unsigned params_stride, size_t params_frame_stride, hevcdbk_sao_decision *decision, unsigned decision_stride,
-                              size_t decision_frame_stride, void *hip_stream)
+/* hevcdbk_sao_decide_device (scale == nullptr: the NEW kernel without scales) and hevcdbk_sao_decide_device_os (scale[0], scale[1] =
+ * log2_offset_scale_luma, _chroma): one list of checks, the two of the scales in the places the header names */
+static int sao_decide(hevcdbk_context *ctx, const hevcdbk_sao_stats *stats_y, const hevcdbk_sao_stats *stats_cb, const hevcdbk_sao_stats *stats_cr,
+                      unsigned stats_stride, size_t stats_frame_stride, unsigned ctbs_x, unsigned ctbs_y, unsigned n_frames, unsigned bit_depth_luma,
+                      unsigned bit_depth_chroma, const unsigned *scale, unsigned lambda_q8_luma, unsigned lambda_q8_chroma, const uint16_t *slice_idx,
+                      const uint16_t *tile_idx, unsigned idx_stride, size_t idx_frame_stride, hevcdbk_sao_ctb *params_y, hevcdbk_sao_ctb *params_cb,
+                      hevcdbk_sao_ctb *params_cr, unsigned params_stride, size_t params_frame_stride, hevcdbk_sao_decision *decision,
+                      unsigned decision_stride, size_t decision_frame_stride, void *hip_stream)
 {
     const bool chroma = stats_cb != nullptr;
     if (!ctx || !stats_y || !params_y || !decision) return HEVCDBK_ERR_ARG;
@@ -29,6 +32,8 @@ int hevcdbk_sao_decide_device(hevcdbk_context *ctx, const hevcdbk_sao_stats *sta
     if (chroma && (!params_cb || !params_cr)) return HEVCDBK_ERR_ARG;
     if (bit_depth_luma < 8 || bit_depth_luma > 16 || (chroma && (bit_depth_chroma < 8 || bit_depth_chroma > 16))) return HEVCDBK_ERR_ARG;
     if (lambda_q8_luma > (1u << 24) || (chroma && lambda_q8_chroma > (1u << 24))) return HEVCDBK_ERR_ARG;
+    auto legal = [](unsigned depth) { return depth > 10 ? depth - 10 : 0u; }; /* the largest scale a stream codes at this depth */
+    if (scale && (scale[0] > legal(bit_depth_luma) || (chroma && scale[1] > legal(bit_depth_chroma)))) return HEVCDBK_ERR_ARG;
     if (ctbs_x == 0 || ctbs_y == 0 || ctbs_x > 65535 || ctbs_y > 65535) return HEVCDBK_ERR_DIMENSIONS;
     const bool idx = slice_idx || tile_idx;
     if (stats_stride < ctbs_x || params_stride < ctbs_x || decision_stride < ctbs_x || (idx && idx_stride < ctbs_x)) return HEVCDBK_ERR_ARG;
@@ -85,9 +90,40 @@ int hevcdbk_sao_decide_device(hevcdbk_context *ctx, const hevcdbk_sao_stats *sta
     a.params_stride = (int)params_stride; a.params_frame_stride = (long long)params_frame_stride;
     a.decision = reinterpret_cast<DbkSaoDecision *>(decision);
     a.decision_stride = (int)decision_stride; a.decision_frame_stride = (long long)decision_frame_stride;
+    if (scale && (scale[0] > 2 || (chroma && scale[1] > 2))) return HEVCDBK_ERR_UNSUPPORTED; /* 31 << 3 leaves int8_t */
     if (int rc = bind(ctx)) return rc;
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->compute;
-    return hip_ok(ctx, dbk_launch_sao_decide(a, s), "SAO decide launch") ? HEVCDBK_OK : HEVCDBK_ERR_HIP;
+    if (!scale) return hip_ok(ctx, dbk_launch_sao_decide(a, s), "SAO decide launch") ? HEVCDBK_OK : HEVCDBK_ERR_HIP;
+    const DbkSaoDecideOsArgs o = {a, (int)scale[0], chroma ? (int)scale[1] : 0};
+    return hip_ok(ctx, dbk_launch_sao_decide_os(o, s), "SAO decide launch") ? HEVCDBK_OK : HEVCDBK_ERR_HIP;
+}
+
+int hevcdbk_sao_decide_device(hevcdbk_context *ctx, const hevcdbk_sao_stats *stats_y, const hevcdbk_sao_stats *stats_cb,
+                              const hevcdbk_sao_stats *stats_cr, unsigned stats_stride, size_t stats_frame_stride, unsigned ctbs_x,
+                              unsigned ctbs_y, unsigned n_frames, unsigned bit_depth_luma, unsigned bit_depth_chroma, unsigned lambda_q8_luma,
+                              unsigned lambda_q8_chroma, const uint16_t *slice_idx, const uint16_t *tile_idx, unsigned idx_stride,
+                              size_t idx_frame_stride, hevcdbk_sao_ctb *params_y, hevcdbk_sao_ctb *params_cb, hevcdbk_sao_ctb *params_cr,
+                              unsigned params_stride, size_t params_frame_stride, hevcdbk_sao_decision *decision, unsigned decision_stride,
+                              size_t decision_frame_stride, void *hip_stream)
+{
+    return sao_decide(ctx, stats_y, stats_cb, stats_cr, stats_stride, stats_frame_stride, ctbs_x, ctbs_y, n_frames, bit_depth_luma, bit_depth_chroma,
+                      nullptr, lambda_q8_luma, lambda_q8_chroma, slice_idx, tile_idx, idx_stride, idx_frame_stride, params_y, params_cb, params_cr,
+                      params_stride, params_frame_stride, decision, decision_stride, decision_frame_stride, hip_stream);
+}
+
+int hevcdbk_sao_decide_device_os(hevcdbk_context *ctx, const hevcdbk_sao_stats *stats_y, const hevcdbk_sao_stats *stats_cb,
+                                 const hevcdbk_sao_stats *stats_cr, unsigned stats_stride, size_t stats_frame_stride, unsigned ctbs_x,
+                                 unsigned ctbs_y, unsigned n_frames, unsigned bit_depth_luma, unsigned bit_depth_chroma,
+                                 unsigned log2_offset_scale_luma, unsigned log2_offset_scale_chroma, unsigned lambda_q8_luma,
+                                 unsigned lambda_q8_chroma, const uint16_t *slice_idx, const uint16_t *tile_idx, unsigned idx_stride,
+                                 size_t idx_frame_stride, hevcdbk_sao_ctb *params_y, hevcdbk_sao_ctb *params_cb, hevcdbk_sao_ctb *params_cr,
+                                 unsigned params_stride, size_t params_frame_stride, hevcdbk_sao_decision *decision, unsigned decision_stride,
+                                 size_t decision_frame_stride, void *hip_stream)
+{
+    const unsigned scale[2] = {log2_offset_scale_luma, log2_offset_scale_chroma};
+    return sao_decide(ctx, stats_y, stats_cb, stats_cr, stats_stride, stats_frame_stride, ctbs_x, ctbs_y, n_frames, bit_depth_luma, bit_depth_chroma,
+                      scale, lambda_q8_luma, lambda_q8_chroma, slice_idx, tile_idx, idx_stride, idx_frame_stride, params_y, params_cb, params_cr,
+                      params_stride, params_frame_stride, decision, decision_stride, decision_frame_stride, hip_stream);
 }
 
 } /* extern "C" */

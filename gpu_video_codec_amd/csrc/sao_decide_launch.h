@@ -6,3 +6,5 @@
 
 /* the NEW launch, then the MERGE launch (none for a grid of one CTB), on one stream */
 hipError_t dbk_launch_sao_decide(const DbkSaoDecideArgs &a, hipStream_t stream);
+/* the MERGE launch alone, for whoever wrote the NEW triples and records with a launch of its own (sao_pick_os.hip) */
+hipError_t dbk_launch_sao_decide_merge(const DbkSaoDecideArgs &a, hipStream_t stream);

@@ -1,11 +1,12 @@
 /*
  * sao_stats_host.cpp -- C-ABI entries of SAO parameter estimation: hevcdbk_sao_stats_device (per-CTB statistics of a deblocked plane
  * against the original), hevcdbk_sao_stats_device_sp (the same of a plane of interleaved Cb / Cr pairs, one array per component) and
- * hevcdbk_sao_pick_device (hevcdbk_sao_ctb from those statistics).  Every operand is checked before the context is looked into or the
- * device is touched; nothing is enqueued on refusal.  Kernels: sao_stats.hip, sao_stats_sp.hip.
+ * hevcdbk_sao_pick_device / _os (hevcdbk_sao_ctb from those statistics, the second with log2_sao_offset_scale).  Every operand is checked before the context is looked into or the
+ * device is touched; nothing is enqueued on refusal.  Kernels: sao_stats.hip, sao_stats_sp.hip, sao_pick_os.hip.
  */
 #include "deblock_ctx.h"
 #include "deblock_host_args.h"
+#include "sao_pick_os_launch.h"
 #include "sao_stats_launch.h"
 #include "sao_stats_sp_launch.h"
 
@@ -105,13 +106,16 @@ int hevcdbk_sao_stats_device_sp(hevcdbk_context *ctx, const hevcdbk_device_plane
     return hip_ok(ctx, dbk_launch_sao_stats_sp(sp, (int)sb, s), "SAO statistics launch") ? HEVCDBK_OK : HEVCDBK_ERR_HIP;
 }
 
-int hevcdbk_sao_pick_device(hevcdbk_context *ctx, const hevcdbk_sao_stats *stats_a, const hevcdbk_sao_stats *stats_b, unsigned stats_stride,
-                            size_t stats_frame_stride, unsigned ctbs_x, unsigned ctbs_y, unsigned n_frames, unsigned bit_depth,
-                            unsigned lambda_q8, hevcdbk_sao_ctb *params_a, hevcdbk_sao_ctb *params_b, unsigned params_stride,
-                            size_t params_frame_stride, int64_t *delta_d, void *hip_stream)
+/* hevcdbk_sao_pick_device (scale == nullptr: the kernel without a scale) and hevcdbk_sao_pick_device_os (*scale = log2_offset_scale):
+ * one list of checks, the two of the scale in the places the header names */
+static int sao_pick(hevcdbk_context *ctx, const hevcdbk_sao_stats *stats_a, const hevcdbk_sao_stats *stats_b, unsigned stats_stride,
+                    size_t stats_frame_stride, unsigned ctbs_x, unsigned ctbs_y, unsigned n_frames, unsigned bit_depth, const unsigned *scale,
+                    unsigned lambda_q8, hevcdbk_sao_ctb *params_a, hevcdbk_sao_ctb *params_b, unsigned params_stride, size_t params_frame_stride,
+                    int64_t *delta_d, void *hip_stream)
 {
     if (!ctx || !stats_a || !params_a || (stats_b != nullptr) != (params_b != nullptr)) return HEVCDBK_ERR_ARG;
     if (bit_depth < 8 || bit_depth > 16 || lambda_q8 > (1u << 24)) return HEVCDBK_ERR_ARG;
+    if (scale && *scale > (bit_depth > 10 ? bit_depth - 10 : 0u)) return HEVCDBK_ERR_ARG; /* no stream codes it */
     if (ctbs_x == 0 || ctbs_y == 0 || ctbs_x > 0x7fffffffu || ctbs_y > 65535 || n_frames > 65535) return HEVCDBK_ERR_DIMENSIONS;
     if (stats_stride < ctbs_x || params_stride < ctbs_x || stats_stride > 0x7fffffffu || params_stride > 0x7fffffffu) return HEVCDBK_ERR_ARG;
     if ((uintptr_t)stats_a % 4 != 0 || (uintptr_t)stats_b % 4 != 0 || (uintptr_t)delta_d % 8 != 0) return HEVCDBK_ERR_ARG;
@@ -127,9 +131,30 @@ int hevcdbk_sao_pick_device(hevcdbk_context *ctx, const hevcdbk_sao_stats *stats
     a.params_b = reinterpret_cast<DbkSaoCtb *>(params_b);
     a.params_stride = (int)params_stride; a.params_frame_stride = (long long)params_frame_stride;
     a.delta_d = reinterpret_cast<long long *>(delta_d);
+    if (scale && *scale > 2) return HEVCDBK_ERR_UNSUPPORTED; /* 31 << 3 leaves int8_t */
     if (int rc = bind(ctx)) return rc;
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->compute;
-    return hip_ok(ctx, dbk_launch_sao_pick(a, s), "SAO pick launch") ? HEVCDBK_OK : HEVCDBK_ERR_HIP;
+    if (!scale) return hip_ok(ctx, dbk_launch_sao_pick(a, s), "SAO pick launch") ? HEVCDBK_OK : HEVCDBK_ERR_HIP;
+    const DbkSaoPickOsArgs o = {a, (int)*scale};
+    return hip_ok(ctx, dbk_launch_sao_pick_os(o, s), "SAO pick launch") ? HEVCDBK_OK : HEVCDBK_ERR_HIP;
+}
+
+int hevcdbk_sao_pick_device(hevcdbk_context *ctx, const hevcdbk_sao_stats *stats_a, const hevcdbk_sao_stats *stats_b, unsigned stats_stride,
+                            size_t stats_frame_stride, unsigned ctbs_x, unsigned ctbs_y, unsigned n_frames, unsigned bit_depth,
+                            unsigned lambda_q8, hevcdbk_sao_ctb *params_a, hevcdbk_sao_ctb *params_b, unsigned params_stride,
+                            size_t params_frame_stride, int64_t *delta_d, void *hip_stream)
+{
+    return sao_pick(ctx, stats_a, stats_b, stats_stride, stats_frame_stride, ctbs_x, ctbs_y, n_frames, bit_depth, nullptr, lambda_q8, params_a,
+                    params_b, params_stride, params_frame_stride, delta_d, hip_stream);
+}
+
+int hevcdbk_sao_pick_device_os(hevcdbk_context *ctx, const hevcdbk_sao_stats *stats_a, const hevcdbk_sao_stats *stats_b, unsigned stats_stride,
+                               size_t stats_frame_stride, unsigned ctbs_x, unsigned ctbs_y, unsigned n_frames, unsigned bit_depth,
+                               unsigned log2_offset_scale, unsigned lambda_q8, hevcdbk_sao_ctb *params_a, hevcdbk_sao_ctb *params_b,
+                               unsigned params_stride, size_t params_frame_stride, int64_t *delta_d, void *hip_stream)
+{
+    return sao_pick(ctx, stats_a, stats_b, stats_stride, stats_frame_stride, ctbs_x, ctbs_y, n_frames, bit_depth, &log2_offset_scale, lambda_q8,
+                    params_a, params_b, params_stride, params_frame_stride, delta_d, hip_stream);
 }
 
 } /* extern "C" */

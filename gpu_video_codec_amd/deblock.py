@@ -504,10 +504,18 @@ class Context:
                                                  out_ptr, out_stride, out_frame_stride, stream), self.handle)
 
     def sao_pick_device(self, stats_ptr, stats_stride, ctbs_x, ctbs_y, bit_depth, lambda_q8, *, out_ptr, out_stride, n_frames=1,
-                        stats_frame_stride=0, out_frame_stride=0, stats_b_ptr=None, out_b_ptr=None, delta_d_ptr=None, stream=None):
+                        stats_frame_stride=0, out_frame_stride=0, stats_b_ptr=None, out_b_ptr=None, delta_d_ptr=None, stream=None,
+                        log2_offset_scale=None):
         """hevcdbk_sao_pick_device: one hevcdbk_sao_ctb per CTB (out_ptr, out_stride entries per row) from the statistics at stats_ptr,
         by the rule of include/hevc_deblock.h with lambda_q8 = lambda * 256.  stats_b_ptr / out_b_ptr: Cr beside Cb -- one type and
-        one edge class for both.  delta_d_ptr: ctbs_x * ctbs_y * n_frames int64, the predicted change of the SSE per CTB."""
+        one edge class for both.  delta_d_ptr: ctbs_x * ctbs_y * n_frames int64, the predicted change of the SSE per CTB.
+        log2_offset_scale: an integer, 0 included, calls hevcdbk_sao_pick_device_os with it (log2_sao_offset_scale: offsets in units
+        of 2^k, k at most Max(0, bit_depth - 10) and at most 2); None calls hevcdbk_sao_pick_device."""
+        if log2_offset_scale is not None:
+            _chk(_lib.lib().hevcdbk_sao_pick_device_os(self.handle, stats_ptr, stats_b_ptr, stats_stride, stats_frame_stride, ctbs_x, ctbs_y,
+                                                       n_frames, bit_depth, int(log2_offset_scale), lambda_q8, out_ptr, out_b_ptr, out_stride,
+                                                       out_frame_stride, delta_d_ptr, stream), self.handle)
+            return
         _chk(_lib.lib().hevcdbk_sao_pick_device(self.handle, stats_ptr, stats_b_ptr, stats_stride, stats_frame_stride, ctbs_x, ctbs_y,
                                                 n_frames, bit_depth, lambda_q8, out_ptr, out_b_ptr, out_stride, out_frame_stride,
                                                 delta_d_ptr, stream), self.handle)
@@ -515,13 +523,27 @@ class Context:
     def sao_decide_device(self, stats_ptr, stats_stride, ctbs_x, ctbs_y, bit_depth, lambda_q8, *, out_ptr, out_stride, decision_ptr,
                           decision_stride, n_frames=1, stats_frame_stride=0, out_frame_stride=0, decision_frame_stride=0, stats_cb_ptr=None,
                           stats_cr_ptr=None, out_cb_ptr=None, out_cr_ptr=None, bit_depth_chroma=None, lambda_q8_chroma=None,
-                          slice_idx_ptr=None, tile_idx_ptr=None, idx_stride=0, idx_frame_stride=0, stream=None):
+                          slice_idx_ptr=None, tile_idx_ptr=None, idx_stride=0, idx_frame_stride=0, stream=None, log2_offset_scale=None,
+                          log2_offset_scale_chroma=None):
         """hevcdbk_sao_decide_device: per CTB own parameters, merge left or merge up (H.265 7.3.8.3) over Y, Cb and Cr at once, by the
         rule of include/hevc_deblock.h.  stats_ptr: luma's statistics; stats_cb_ptr / stats_cr_ptr (both or neither): the chroma
         components' on the same grid, with the same strides.  out_ptr / out_cb_ptr / out_cr_ptr: the final hevcdbk_sao_ctb per CTB, as
         sao_device reads them.  decision_ptr: one _lib.SaoDecision (numpy: _lib.SAO_DECISION_DTYPE) per CTB.  bit_depth_chroma and
         lambda_q8_chroma default to luma's.  slice_idx_ptr, tile_idx_ptr: uint16 per CTB, as sao_borders_device takes them; a CTB
-        merges only with a neighbour of its own slice and tile."""
+        merges only with a neighbour of its own slice and tile.  log2_offset_scale: an integer, 0 included, calls
+        hevcdbk_sao_decide_device_os with it for luma and log2_offset_scale_chroma (defaults to luma's) for Cb and Cr; None calls
+        hevcdbk_sao_decide_device."""
+        if log2_offset_scale is None and log2_offset_scale_chroma is not None:
+            raise ValueError("log2_offset_scale_chroma needs log2_offset_scale")
+        if log2_offset_scale is not None:
+            kc = log2_offset_scale if log2_offset_scale_chroma is None else log2_offset_scale_chroma
+            _chk(_lib.lib().hevcdbk_sao_decide_device_os(self.handle, stats_ptr, stats_cb_ptr, stats_cr_ptr, stats_stride, stats_frame_stride,
+                                                         ctbs_x, ctbs_y, n_frames, bit_depth, bit_depth if bit_depth_chroma is None else bit_depth_chroma,
+                                                         int(log2_offset_scale), int(kc), lambda_q8,
+                                                         lambda_q8 if lambda_q8_chroma is None else lambda_q8_chroma, slice_idx_ptr, tile_idx_ptr,
+                                                         idx_stride, idx_frame_stride, out_ptr, out_cb_ptr, out_cr_ptr, out_stride,
+                                                         out_frame_stride, decision_ptr, decision_stride, decision_frame_stride, stream), self.handle)
+            return
         _chk(_lib.lib().hevcdbk_sao_decide_device(self.handle, stats_ptr, stats_cb_ptr, stats_cr_ptr, stats_stride, stats_frame_stride, ctbs_x,
                                                   ctbs_y, n_frames, bit_depth, bit_depth if bit_depth_chroma is None else bit_depth_chroma,
                                                   lambda_q8, lambda_q8 if lambda_q8_chroma is None else lambda_q8_chroma, slice_idx_ptr,

@@ -941,7 +941,7 @@ HEVCDBK_API int hevcdbk_sao_stats_device_sp(hevcdbk_context *ctx, const hevcdbk_
 /*
  * From statistics to parameters: the library's own rule, integers only, "parity unpinned" like the rest.
  * cost = deltaD * 256 + lambda_q8 * bits in int64, lambda_q8 <= 2^24 (else HEVCDBK_ERR_ARG); M = (1 << (Min(bitDepth, 10) - 5)) - 1;
- * log2OffsetScale is 0.
+ * log2OffsetScale is 0 in this entry; hevcdbk_sao_pick_device_os below takes it.
  *   - The offset of a bin (n, s): 0 if n = 0; otherwise o0 = sign(s) * ((2|s| + n) / (2n)), clamped to [0, M] for edge categories 1
  *     and 2, to [-M, 0] for categories 3 and 4 and to [-M, M] for bands; the search walks from o0 towards 0 one step at a time and
  *     keeps the o with the least (n o^2 - 2 o s) * 256 + lambda * bits(o), on a tie the one nearer 0;
@@ -962,6 +962,35 @@ HEVCDBK_API int hevcdbk_sao_pick_device(hevcdbk_context *ctx, const hevcdbk_sao_
                                         unsigned n_frames, unsigned bit_depth, unsigned lambda_q8, hevcdbk_sao_ctb *params_a,
                                         hevcdbk_sao_ctb *params_b, unsigned params_stride, size_t params_frame_stride, int64_t *delta_d,
                                         void *hip_stream);
+
+/*
+ * The same with log2_sao_offset_scale_luma / _chroma of the PPS range extension, k = log2_offset_scale: offsets are coded in units of
+ * 2^k, so that at 11 and 12 bit they reach +-(31 << k) on samples that span 0..4095.  The operands of hevcdbk_sao_pick_device with
+ * log2_offset_scale after bit_depth; the statistics do not change (band index rec >> (bitDepth - 5)).  Integers only; with
+ * M = (1 << (Min(bitDepth, 10) - 5)) - 1 as above:
+ *   - The offset of a bin (n, s) in coded units q: 0 if n = 0; otherwise q0 = sign(s) * ((2|s| + (n << k)) / (2 * (n << k))) -- the
+ *     mean divided by 2^k, rounded half away from zero in ONE division, not round(s / n) >> k -- clamped to [0, M] for edge
+ *     categories 1 and 2, to [-M, 0] for categories 3 and 4 and to [-M, M] for bands; the search walks from q0 towards 0 one step at
+ *     a time and keeps the q with the least (n o^2 - 2 o s) * 256 + lambda * bits(q), where o = q * 2^k (a multiplication: a negative
+ *     value is never shifted), on a tie the q nearer 0; bits is the bits(o) above, taken on the coded q.
+ *   - The candidates of a CTB, their order, their side costs (lambda * 1, lambda * 4, lambda * 7, jointly lambda * 2 plus per
+ *     component lambda * 5) and the tie rule (the earliest; in the joint form the band wins only when strictly less than everything
+ *     before it) are exactly those above.  delta_d and every cost are taken on o.
+ *   - params_a / params_b hold SaoOffsetVal = q * 2^k in offset[]: the SAO entries read them without change.
+ *   - Range: n < 2^31 and |o| <= 124, so a bin's cost is below 2^54 and a CTB's below 2^58, in int64.
+ *   - At k = 0 every output is byte for byte that of hevcdbk_sao_pick_device.  On the device the candidates of a CTB are compared
+ *     by the lanes of a wave together, not walked by one lane; the result is the rule's, whichever entry runs.
+ * Refusals: those of hevcdbk_sao_pick_device in its order -- NULL operands and pairing, then the depth, the lambda and, with them,
+ * log2_offset_scale > Max(0, bit_depth - 10), which no stream codes -- HEVCDBK_ERR_ARG; the grid -- HEVCDBK_ERR_DIMENSIONS; strides,
+ * addresses, the frame stride -- HEVCDBK_ERR_ARG; and LAST, before the context is bound and with nothing enqueued, a legal
+ * log2_offset_scale > 2 -- HEVCDBK_ERR_UNSUPPORTED: it occurs at depths 13..16 only and needs offsets beyond int8_t (31 << 3 = 248).
+ * Wide offsets on the applying side (hevcdbk_sao_ctb.offset[] is int8_t) are out of scope.
+ */
+HEVCDBK_API int hevcdbk_sao_pick_device_os(hevcdbk_context *ctx, const hevcdbk_sao_stats *stats_a, const hevcdbk_sao_stats *stats_b,
+                                           unsigned stats_stride, size_t stats_frame_stride, unsigned ctbs_x, unsigned ctbs_y,
+                                           unsigned n_frames, unsigned bit_depth, unsigned log2_offset_scale, unsigned lambda_q8,
+                                           hevcdbk_sao_ctb *params_a, hevcdbk_sao_ctb *params_b, unsigned params_stride,
+                                           size_t params_frame_stride, int64_t *delta_d, void *hip_stream);
 
 /*
  * The SAO decision per CTB as 7.3.8.3 codes it: own parameters, sao_merge_left_flag or sao_merge_up_flag.  One flag takes the
@@ -988,7 +1017,7 @@ HEVCDBK_API int hevcdbk_sao_pick_device(hevcdbk_context *ctx, const hevcdbk_sao_
  *     The lowest J = lambda_c * C_y + lambda_l * C_c + lambda_l * lambda_c * F wins (D_y / lambda_l + D_c / lambda_c + R cleared of
  *     its divisions; without chroma J = C_y + lambda_l * F), on a tie the earliest.  J is compared exactly, in 128 bits.
  *   - params_*: the final triples, one stride and one frame stride; a merged CTB holds a copy of its neighbour's.
- *     log2_sao_offset_scale stays 0.  decision: the record below per CTB, its own stride and frame stride (entries).  Every entry of
+ *     log2_sao_offset_scale stays 0 (hevcdbk_sao_decide_device_os below takes it).  decision: the record below per CTB, its own stride and frame stride (entries).  Every entry of
  *     every output grid is written, with plain stores; entries beyond the CTB columns are not touched.  The same bits every run.
  *   - The slice-level slice_sao_luma_flag / slice_sao_chroma_flag are the caller's to set, from the records summed over a slice.
  * Refusals, in this order, every one before the context is bound and with nothing enqueued: a NULL ctx, stats_y, params_y or
@@ -1017,6 +1046,31 @@ HEVCDBK_API int hevcdbk_sao_decide_device(hevcdbk_context *ctx, const hevcdbk_sa
                                           hevcdbk_sao_ctb *params_y, hevcdbk_sao_ctb *params_cb, hevcdbk_sao_ctb *params_cr,
                                           unsigned params_stride, size_t params_frame_stride, hevcdbk_sao_decision *decision,
                                           unsigned decision_stride, size_t decision_frame_stride, void *hip_stream);
+
+/*
+ * The same with log2_sao_offset_scale_luma and log2_sao_offset_scale_chroma: the operands of hevcdbk_sao_decide_device with the two
+ * scales after the two depths.  NEW is what hevcdbk_sao_pick_device_os gives for S_y alone with log2_offset_scale_luma and for
+ * (S_cb, S_cr) jointly with log2_offset_scale_chroma; C_y, C_c are those picks' least costs.  LEFT and UP do not change: pd(S, p)
+ * works on the stored, scaled offsets, so the merge walk along the anti-diagonals is the one above.  params_* hold
+ * SaoOffsetVal = q * 2^k.  J stays below 2^83, inside the 128 bits it is compared in.  log2_offset_scale_chroma is not looked at
+ * without chroma statistics.  At scales of 0 every output is byte for byte that of hevcdbk_sao_decide_device.
+ * Refusals, in this order, every one before the context is bound and with nothing enqueued: those of hevcdbk_sao_decide_device up
+ * to and including the depths and the lambdas, then a scale above Max(0, bit depth - 10) of its component -- HEVCDBK_ERR_ARG; the
+ * grid -- HEVCDBK_ERR_DIMENSIONS; every further refusal of hevcdbk_sao_decide_device in its order -- HEVCDBK_ERR_ARG; and LAST a
+ * legal scale above 2 (depths 13..16: offsets beyond int8_t) -- HEVCDBK_ERR_UNSUPPORTED.
+ * What stays out: scales above 2 (wide offsets, on the applying side as well); a CABAC-accurate rate (bits() is the bin count of the
+ * truncated unary code); the slice-level slice_sao_luma_flag / slice_sao_chroma_flag, the caller's to set; and routing
+ * hevcdbk_sao_pick_device / hevcdbk_sao_decide_device to the kernels of the _os entries -- they keep their own.
+ */
+HEVCDBK_API int hevcdbk_sao_decide_device_os(hevcdbk_context *ctx, const hevcdbk_sao_stats *stats_y, const hevcdbk_sao_stats *stats_cb,
+                                             const hevcdbk_sao_stats *stats_cr, unsigned stats_stride, size_t stats_frame_stride,
+                                             unsigned ctbs_x, unsigned ctbs_y, unsigned n_frames, unsigned bit_depth_luma,
+                                             unsigned bit_depth_chroma, unsigned log2_offset_scale_luma, unsigned log2_offset_scale_chroma,
+                                             unsigned lambda_q8_luma, unsigned lambda_q8_chroma, const uint16_t *slice_idx,
+                                             const uint16_t *tile_idx, unsigned idx_stride, size_t idx_frame_stride, hevcdbk_sao_ctb *params_y,
+                                             hevcdbk_sao_ctb *params_cb, hevcdbk_sao_ctb *params_cr, unsigned params_stride,
+                                             size_t params_frame_stride, hevcdbk_sao_decision *decision, unsigned decision_stride,
+                                             size_t decision_frame_stride, void *hip_stream);
 
 #ifdef __cplusplus
 }

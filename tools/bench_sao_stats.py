@@ -12,7 +12,9 @@ hevcdbk_sao_stats_device launches on planes that are already split; (c) as (b) a
 two that split org (torch, on the stream the launches use).  Every form fills the same two arrays, compared once per row.
 
 --decide: the decision per CTB (hevcdbk_sao_decide_device: own parameters, merge left or merge up over Y, Cb and Cr) for 64 frames of
-3840x2160 at 64- and 16-sample CTBs, taking turns with the luma statistics pass and the two pick launches on the same batch."""
+3840x2160 at 64- and 16-sample CTBs, taking turns with the luma statistics pass and the two pick launches on the same batch -- and
+with the _os entries (log2_sao_offset_scale, the candidates compared by a wave's lanes together) at a scale of 0, where they write the
+same bytes."""
 import argparse, json, os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -138,7 +140,7 @@ def semi_planar(a):
 def decide(a):
     """--decide: hevcdbk_sao_decide_device (Y, Cb, Cr on one CTB grid) on a.frames frames of a.width x a.height at each CTB size of
     a.ctbs, taking turns in this process with the luma statistics pass and with the two pick launches (luma alone, Cb and Cr jointly)
-    that produce what the decision's NEW candidates are -- on the same batch.  The three statistics arrays are those of the luma
+    that produce what the decision's NEW candidates are, and with the _os forms of both at a scale of 0 -- on the same batch.  The three statistics arrays are those of the luma
     plane against three different originals: real statistics, one record per CTB.  One JSON line per CTB size."""
     w, h, n, bd, lam = a.width, a.height, a.frames, 8, 1024
     ctx = deblock.Context(0)
@@ -161,28 +163,44 @@ def decide(a):
         for c in range(3):
             stats(c)
 
-        def picks():
+        def picks(scale=None):
             ctx.sao_pick_device(dst[0].ptr, cols, cols, rows, bd, lam, out_ptr=dprm[0].ptr, out_stride=cols, n_frames=n, stats_frame_stride=g,
-                                out_frame_stride=g)
+                                out_frame_stride=g, log2_offset_scale=scale)
             ctx.sao_pick_device(dst[1].ptr, cols, cols, rows, bd, lam, out_ptr=dprm[1].ptr, out_stride=cols, n_frames=n, stats_frame_stride=g,
-                                out_frame_stride=g, stats_b_ptr=dst[2].ptr, out_b_ptr=dprm[2].ptr)
+                                out_frame_stride=g, stats_b_ptr=dst[2].ptr, out_b_ptr=dprm[2].ptr, log2_offset_scale=scale)
 
-        def dec():
+        def dec(scale=None):
             ctx.sao_decide_device(dst[0].ptr, cols, cols, rows, bd, lam, out_ptr=dprm[0].ptr, out_stride=cols, decision_ptr=ddec.ptr,
                                   decision_stride=cols, n_frames=n, stats_frame_stride=g, out_frame_stride=g, decision_frame_stride=g,
-                                  stats_cb_ptr=dst[1].ptr, stats_cr_ptr=dst[2].ptr, out_cb_ptr=dprm[1].ptr, out_cr_ptr=dprm[2].ptr)
-        forms = {"stats_luma": stats, "two_picks": picks, "decide": dec}
+                                  stats_cb_ptr=dst[1].ptr, stats_cr_ptr=dst[2].ptr, out_cb_ptr=dprm[1].ptr, out_cr_ptr=dprm[2].ptr,
+                                  log2_offset_scale=scale)
+        # the _os entries at a scale of 0 write what the entries without a scale write: compared once, before the turns
+        outputs = {}
+        for k, fn in (("decide", dec), ("decide_os", lambda: dec(0)), ("two_picks", picks), ("two_picks_os", lambda: picks(0))):
+            fn()
+            ctx.synchronize()
+            outputs[k] = [d.download(g * n * 6).tobytes() for d in dprm] + ([ddec.download(g * n * 32).tobytes()] if k.startswith("decide") else [])
+        forms = {"stats_luma": stats, "two_picks": picks, "two_picks_os": lambda: picks(0), "decide": dec, "decide_os": lambda: dec(0)}
         timed(ctx, stats, 30, 0)   # settle the clocks
         ms = {k: [] for k in forms}
         for _ in range(a.rounds):
             for k, fn in forms.items():
                 ms[k].append(timed(ctx, fn, a.steps, 5))
         med = {k: float(np.median(v)) for k, v in ms.items()}
+        dec()
+        ctx.synchronize()
         merge = np.bincount(ddec.download(g * n * 32).view(np.dtype(_lib.SAO_DECISION_DTYPE))["merge"], minlength=3)
+        spread = {k: float(max(v) - min(v)) for k, v in ms.items()}
+        slower = lambda new, old: bool(med[new] - med[old] > max(spread[new], spread[old]))
         line = {"stage": "sao_decide", "workload": "%dx%d %d-bit x %d, %d-sample CTBs, Y + Cb + Cr on one grid" % (w, h, bd, n, 1 << L),
-                "ctbs": g * n, "lambda_q8": lam, "ms_per_call": med, "rounds_ms": ms, "spread_ms": {k: float(max(v) - min(v)) for k, v in ms.items()},
+                "ctbs": g * n, "lambda_q8": lam, "ms_per_call": med, "rounds_ms": ms, "spread_ms": spread,
                 "decide_over_stats_luma": med["decide"] / med["stats_luma"], "decide_over_two_picks": med["decide"] / med["two_picks"],
-                "decide_slower_than_stats_luma": bool(med["decide"] > med["stats_luma"]), "merge_0_left_up": [int(x) for x in merge]}
+                "decide_slower_than_stats_luma": bool(med["decide"] > med["stats_luma"]), "merge_0_left_up": [int(x) for x in merge],
+                "decide_os_over_decide": med["decide_os"] / med["decide"], "two_picks_os_over_two_picks": med["two_picks_os"] / med["two_picks"],
+                "decide_os_over_stats_luma": med["decide_os"] / med["stats_luma"],
+                "decide_os_slower_than_decide_beyond_spread": slower("decide_os", "decide"),
+                "two_picks_os_slower_than_two_picks_beyond_spread": slower("two_picks_os", "two_picks"),
+                "os_outputs_identical_at_scale_0": bool(outputs["decide"] == outputs["decide_os"] and outputs["two_picks"] == outputs["two_picks_os"])}
         lines.append(line)
         print(json.dumps(line), flush=True)
         for d in dst + dprm + [ddec]:
