@@ -49,7 +49,11 @@ struct hevcdbk_context {
     int large_bar = -1; /* hipDeviceAttributeIsLargeBar, asked once */
     unsigned host_threads = 0; /* threads copying during a call, the caller included; 0 = default (4) */
     std::vector<hevcdbk_strip_trace> trace; /* the strips of the last large-frame call (hevcdbk_last_frame_trace) */
-    std::vector<void *> registered; /* hevcdbk_host_register'ed ranges still registered: released with the context */
+    /* page-locked host ranges this context made: hevcdbk_host_register'ed ones still registered (released with the context) and
+     * hevcdbk_host_malloc_pinned ones not yet freed.  is_pinned_host() answers from them: a plane is page-locked when it lies
+     * wholly inside one of these ranges */
+    struct HostRange { void *p; size_t bytes; };
+    std::vector<HostRange> registered, pinned;
 };
 
 namespace dbkh {
@@ -64,7 +68,28 @@ int bind(hevcdbk_context *ctx);                                             /* h
 int grow_pinned(hevcdbk_context *ctx, Growable &g, size_t bytes);
 int grow_device(hevcdbk_context *ctx, Growable &g, size_t bytes);
 bool bad_depth(unsigned bit_depth, unsigned sample_bytes);
-bool is_pinned_host(const void *p, void **dev_ptr = nullptr);
+/* true when the `bytes` at p lie in ONE page-locked range this context made (hevcdbk_host_register, hevcdbk_host_malloc_pinned),
+ * which the GPU can DMA from directly; *dev_ptr (if asked for) = the address a KERNEL uses for p */
+bool is_pinned_host(const hevcdbk_context *ctx, const void *p, size_t bytes, void **dev_ptr = nullptr);
+/* the bytes a plane of h rows spans: pitch * (h - 1) + row_bytes */
+inline size_t plane_span(size_t pitch, size_t row_bytes, unsigned h) { return h ? pitch * (h - 1) + row_bytes : 0; }
+
+/* Every path out of a host-frame operator that is not HEVCDBK_OK waits for the GPU: kernels and DMAs of earlier strips or frames may
+ * still be storing into the ring, the push buffer or the caller's own page-locked planes, and the header promises that transfers
+ * have completed when the operators return.  Declared before the crew's scope guard (CrewScope / Scope), so it runs after the
+ * crew has been waited for, and before the caller gets its planes back.  Errors are ignored here: the call is failing already. */
+struct GpuDrain {
+    hevcdbk_context *ctx;
+    bool ok = false; /* set on the way out of a call that succeeded: it has waited for its own work */
+    ~GpuDrain()
+    {
+        if (ok) return;
+        (void)hipStreamSynchronize(ctx->h2d);
+        (void)hipStreamSynchronize(ctx->compute);
+        (void)hipStreamSynchronize(ctx->d2h);
+        (void)hipGetLastError();
+    }
+};
 int check_frame(const hevcdbk_frame &f, bool &chroma);
 int check_bs(const hevcdbk_bs *bs, unsigned W, unsigned H, bool chroma);
 int planes_to_args(const hevcdbk_device_planes *p, unsigned qp, const hevcdbk_tables *tables, DbkArgs &a);

@@ -99,13 +99,26 @@ bool bad_depth(unsigned bit_depth, unsigned sample_bytes)
            (sample_bytes == 1 && bit_depth != 8);
 }
 
-/* true when p is page-locked host memory the GPU can DMA from directly; *dev_ptr (if asked for) = the address a KERNEL uses for
- * it: the same as p for hipHostMalloc memory, possibly another for a hipHostRegister'ed range */
-bool is_pinned_host(const void *p, void **dev_ptr)
+/* true when the `bytes` at p are page-locked host memory the GPU can DMA from directly; *dev_ptr (if asked for) = the address a
+ * KERNEL uses for p: the same as p for hipHostMalloc memory, possibly another for a hipHostRegister'ed range.  Only ranges this
+ * context made (hevcdbk_host_register, hevcdbk_host_malloc_pinned) count, and the LAST byte has to lie in the range the first one
+ * lies in: a plane that begins inside a registered range and runs past its end, and memory somebody else page-locked -- of which
+ * the runtime tells us the kind of a byte, not where its allocation ends -- are pageable memory to every caller of this (staged by
+ * the crew), not memory a kernel or a DMA engine may be pointed at.  Pageable planes cost no query of the runtime. */
+bool is_pinned_host(const hevcdbk_context *ctx, const void *p, size_t bytes, void **dev_ptr)
 {
+    const uint8_t *first = (const uint8_t *)p, *last = first + (bytes ? bytes - 1 : 0);
+    bool known = false;
+    for (const auto *list : {&ctx->registered, &ctx->pinned})
+        for (const hevcdbk_context::HostRange &r : *list)
+            if (!known && first >= (const uint8_t *)r.p && first < (const uint8_t *)r.p + r.bytes) {
+                if (last >= (const uint8_t *)r.p + r.bytes) return false;
+                known = true;
+            }
+    if (!known) return false;
     hipPointerAttribute_t at;
     if (hipPointerGetAttributes(&at, p) != hipSuccess) {
-        (void)hipGetLastError(); /* ordinary malloc memory: not an error for us */
+        (void)hipGetLastError();
         return false;
     }
     if (at.type != hipMemoryTypeHost) return false;
@@ -582,7 +595,7 @@ void hevcdbk_destroy(hevcdbk_context *ctx)
     delete ctx->crew; /* joins the crew's threads (asleep between calls) */
     (void)hipSetDevice(ctx->device);
     (void)hipDeviceSynchronize();
-    for (void *p : ctx->registered) (void)hipHostUnregister(p);
+    for (const auto &r : ctx->registered) (void)hipHostUnregister(r.p);
     for (auto &g : ctx->pin) if (g.p) (void)hipHostFree(g.p);
     for (auto &g : ctx->dev) if (g.p) (void)hipFree(g.p);
     if (ctx->pin_bs.p) (void)hipHostFree(ctx->pin_bs.p);
@@ -666,6 +679,7 @@ int hevcdbk_host_malloc_pinned(hevcdbk_context *ctx, size_t bytes, void **hptr)
     if (!ctx || !hptr) return HEVCDBK_ERR_ARG;
     if (int rc = bind(ctx)) return rc;
     HIP_TRY(ctx, hipHostMalloc(hptr, bytes ? bytes : 1, hipHostMallocDefault));
+    ctx->pinned.push_back({*hptr, bytes ? bytes : 1});
     return HEVCDBK_OK;
 }
 int hevcdbk_host_free_pinned(hevcdbk_context *ctx, void *hptr)
@@ -673,6 +687,11 @@ int hevcdbk_host_free_pinned(hevcdbk_context *ctx, void *hptr)
     if (!ctx) return HEVCDBK_ERR_ARG;
     if (int rc = bind(ctx)) return rc;
     HIP_TRY(ctx, hipHostFree(hptr));
+    for (size_t i = 0; i < ctx->pinned.size(); i++)
+        if (ctx->pinned[i].p == hptr) {
+            ctx->pinned.erase(ctx->pinned.begin() + (long)i);
+            break;
+        }
     return HEVCDBK_OK;
 }
 int hevcdbk_host_register(hevcdbk_context *ctx, void *ptr, size_t bytes)
@@ -680,7 +699,7 @@ int hevcdbk_host_register(hevcdbk_context *ctx, void *ptr, size_t bytes)
     if (!ctx || !ptr || bytes == 0) return HEVCDBK_ERR_ARG;
     if (int rc = bind(ctx)) return rc;
     HIP_TRY(ctx, hipHostRegister(ptr, bytes, hipHostRegisterDefault));
-    ctx->registered.push_back(ptr);
+    ctx->registered.push_back({ptr, bytes});
     return HEVCDBK_OK;
 }
 int hevcdbk_host_unregister(hevcdbk_context *ctx, void *ptr)
@@ -688,7 +707,7 @@ int hevcdbk_host_unregister(hevcdbk_context *ctx, void *ptr)
     if (!ctx || !ptr) return HEVCDBK_ERR_ARG;
     if (int rc = bind(ctx)) return rc;
     for (size_t i = 0; i < ctx->registered.size(); i++)
-        if (ctx->registered[i] == ptr) {
+        if (ctx->registered[i].p == ptr) {
             /* transfers of the host-frame operators have completed when they return; the streaming operator synchronises too */
             HIP_TRY(ctx, hipHostUnregister(ptr));
             ctx->registered.erase(ctx->registered.begin() + (long)i);
@@ -1046,6 +1065,7 @@ int hevc_deblocking_filter(hevcdbk_context *ctx, hevcdbk_frame *frame, const hev
     const unsigned pw[3] = {W, W / 2, W / 2}, ph[3] = {H, H / 2, H / 2};
     if (int rc = check_bs(bs, W, H, chroma)) return rc;
     if (int rc = bind(ctx)) return rc;
+    GpuDrain drain{ctx}; /* every return below that is not HEVCDBK_OK waits for the GPU */
 
     /* staging (the reference allocates per call, gpu.cu:1103-1169 + 1236-1244; here it persists): the planes sit
      * one after the other, 256-byte aligned, in ONE pinned and ONE device buffer, so a small frame moves in one DMA */
@@ -1095,7 +1115,7 @@ int hevc_deblocking_filter(hevcdbk_context *ctx, hevcdbk_frame *frame, const hev
      * where one DMA of the packed staging buffer beats three DMAs of the caller's planes */
     bool zc[3] = {false, false, false};
     if (!small)
-        for (int i = 0; i < npl; i++) zc[i] = is_pinned_host(frame->plane[i]);
+        for (int i = 0; i < npl; i++) zc[i] = is_pinned_host(ctx, frame->plane[i], plane_span(frame->pitch[i], (size_t)pw[i] * sb, ph[i]));
 #ifdef HEVCDBK_DIAG /* "dmacopy": small frames through DMA copies around the kernel instead (for A/B runs) */
     const bool host_direct = !g_dbk_diag.dmacopy;
 #else
@@ -1112,8 +1132,8 @@ int hevc_deblocking_filter(hevcdbk_context *ctx, hevcdbk_frame *frame, const hev
         bool direct = true;
         void *kplane[3] = {nullptr, nullptr, nullptr}; /* the planes as a kernel addresses them */
         for (int i = 0; i < npl && direct; i++)
-            direct = frame->pitch[i] % (4 * sb) == 0 && (uintptr_t)frame->plane[i] % (4 * sb) == 0 && is_pinned_host(frame->plane[i], &kplane[i]) &&
-                     kplane[i] != nullptr;
+            direct = frame->pitch[i] % (4 * sb) == 0 && (uintptr_t)frame->plane[i] % (4 * sb) == 0 &&
+                     is_pinned_host(ctx, frame->plane[i], plane_span(frame->pitch[i], (size_t)pw[i] * sb, ph[i]), &kplane[i]) && kplane[i] != nullptr;
         if (!direct)
             for (int i = 0; i < npl; i++) {
                 const size_t rb = (size_t)pw[i] * sb;
@@ -1166,6 +1186,7 @@ int hevc_deblocking_filter(hevcdbk_context *ctx, hevcdbk_frame *frame, const hev
             timing->total_s = timing->exec_s;
             timing->pipelined_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - wall0).count();
         }
+        drain.ok = true;
         return HEVCDBK_OK;
     }
     if (small) {
@@ -1229,7 +1250,7 @@ int hevc_deblocking_filter(hevcdbk_context *ctx, hevcdbk_frame *frame, const hev
             const size_t rb = (size_t)pw[i] * sb;
             void *dp = nullptr;
             if (!zc[i]) kout[i] = hplane[i]; /* hipHostMalloc memory: one address for host and device */
-            else if (frame->pitch[i] == rb && (uintptr_t)frame->plane[i] % 4 == 0 && is_pinned_host(frame->plane[i], &dp) && dp)
+            else if (frame->pitch[i] == rb && (uintptr_t)frame->plane[i] % (4 * sb) == 0 && is_pinned_host(ctx, frame->plane[i], rb * ph[i], &dp) && dp)
                 kout[i] = (uint8_t *)dp;
         }
         {
@@ -1404,7 +1425,7 @@ int hevc_deblocking_filter(hevcdbk_context *ctx, hevcdbk_frame *frame, const hev
                 ctx->trace[k].unstage_end_s = since(gout[k].done_ns.load());
             }
         HIP_TRY(ctx, hipStreamSynchronize(ctx->compute));
-        if (x_k_streams == 2 || x_h2d_streams == 2) HIP_TRY(ctx, hipStreamSynchronize(ctx->d2h));
+        if (x_direct_in || x_k_streams == 2 || x_h2d_streams == 2) HIP_TRY(ctx, hipStreamSynchronize(ctx->d2h)); /* the experiments that put ev[12]'s wait or work of their own on d2h */
         const auto wall1s = std::chrono::steady_clock::now();
         if (timing) {
             double copy = 0.0, exec = 0.0, push_covered = 0.0;
@@ -1427,6 +1448,7 @@ int hevc_deblocking_filter(hevcdbk_context *ctx, hevcdbk_frame *frame, const hev
             timing->total_s = timing->exec_s + timing->copy_s;
             timing->pipelined_s = std::chrono::duration<double>(wall1s - wall0).count();
         }
+        drain.ok = true;
         return HEVCDBK_OK;
     }
 
@@ -1448,6 +1470,7 @@ int hevc_deblocking_filter(hevcdbk_context *ctx, hevcdbk_frame *frame, const hev
         timing->total_s = timing->exec_s + timing->copy_s; /* gpu.cu:1302 */
         timing->pipelined_s = std::chrono::duration<double>(wall1 - wall0).count();
     }
+    drain.ok = true;
     return HEVCDBK_OK;
 }
 
@@ -1481,6 +1504,7 @@ extern "C" int hevc_deblocking_filter_sequence(hevcdbk_context *ctx, hevcdbk_fra
     }
     if (int rc = check_bs(bs, W, H, chroma)) return rc;
     if (int rc = bind(ctx)) return rc;
+    GpuDrain drain{ctx}; /* every return below that is not HEVCDBK_OK waits for the GPU (after the crew: its Scope is declared later) */
     /* Small 8-bit 4:2:0 frames: per-frame DMA and launch costs outweigh the data, so the frames travel in groups -- packed
      * back to back into one pinned chunk, ONE DMA each way and ONE batched fused launch per group (the file operator's path) */
     {
@@ -1534,6 +1558,7 @@ extern "C" int hevc_deblocking_filter_sequence(hevcdbk_context *ctx, hevcdbk_fra
                 std::memset(timing, 0, sizeof(*timing));
                 timing->pipelined_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - wall0).count();
             }
+            drain.ok = true;
             return HEVCDBK_OK;
         }
     }
@@ -1559,7 +1584,7 @@ extern "C" int hevc_deblocking_filter_sequence(hevcdbk_context *ctx, hevcdbk_fra
         }
         bool pageable = fbytes > ((size_t)2 << 20) && n_frames >= 2;
         for (unsigned i = 0; i < n_frames && pageable; i++)
-            for (int k = 0; k < npl && pageable; k++) pageable = !is_pinned_host(frames[i].plane[k]);
+            for (int k = 0; k < npl && pageable; k++) pageable = !is_pinned_host(ctx, frames[i].plane[k], plane_span(frames[i].pitch[k], row_bytes[k], ph[k]));
         uint8_t *dpush = pageable ? push_buffer(ctx, (size_t)K * fbytes) : nullptr;
         if (dpush) {
             if (int rc = grow_pinned(ctx, ctx->pin[1], (size_t)K * fbytes)) return rc;
@@ -1663,6 +1688,7 @@ extern "C" int hevc_deblocking_filter_sequence(hevcdbk_context *ctx, hevcdbk_fra
                 std::memset(timing, 0, sizeof(*timing));
                 timing->pipelined_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - wall0).count();
             }
+            drain.ok = true;
             return HEVCDBK_OK;
         }
     }
@@ -1699,7 +1725,7 @@ extern "C" int hevc_deblocking_filter_sequence(hevcdbk_context *ctx, hevcdbk_fra
         for (int k = 0; k < npl; k++) {
             const void *hsrc = fr.plane[k];
             size_t hpitch = fr.pitch[k];
-            pinned[(size_t)i * 3 + k] = is_pinned_host(fr.plane[k]); /* asked once per plane: the query is not free */
+            pinned[(size_t)i * 3 + k] = is_pinned_host(ctx, fr.plane[k], plane_span(fr.pitch[k], row_bytes[k], ph[k])); /* asked once per plane: the query is not free */
             if (!pinned[(size_t)i * 3 + k]) {
                 if (int rc = grow_pinned(ctx, ctx->seq_pin[s][k], plane_bytes[k])) return rc;
                 for (unsigned r = 0; r < ph[k]; r++)
@@ -1744,6 +1770,7 @@ extern "C" int hevc_deblocking_filter_sequence(hevcdbk_context *ctx, hevcdbk_fra
         std::memset(timing, 0, sizeof(*timing));
         timing->pipelined_s = std::chrono::duration<double>(wall1 - wall0).count(); /* whole sequence */
     }
+    drain.ok = true;
     return HEVCDBK_OK;
 }
 
@@ -1759,6 +1786,7 @@ int filter_chunk(hevcdbk_context *ctx, uint8_t *host, size_t k, unsigned W, unsi
     const size_t nv = hevcdbk_num_vert_bs(W, H), nh = hevcdbk_num_hor_bs(W, H);
     const size_t ncv = hevcdbk_num_vert_bs(W / 2, H / 2);
     if (int rc = check_bs(bs, W, H, true)) return rc;
+    GpuDrain drain{ctx}; /* a chunk that fails leaves nothing in flight from or into `host` (the file operators free it next) */
     Growable &dbuf = ctx->dev[1 + (slot & 1)];
     if (int rc = grow_device(ctx, dbuf, k * fb)) return rc;
     uint8_t *d = (uint8_t *)dbuf.p;
@@ -1786,6 +1814,7 @@ int filter_chunk(hevcdbk_context *ctx, uint8_t *host, size_t k, unsigned W, unsi
     HIP_TRY(ctx, hipMemcpyAsync(host, d, k * fb, hipMemcpyDeviceToHost, s));
     if (done) HIP_TRY(ctx, hipEventRecord(done, s));
     else HIP_TRY(ctx, hipStreamSynchronize(s));
+    drain.ok = true;
     return HEVCDBK_OK;
 }
 

@@ -215,6 +215,7 @@ int hevcdbk_h265_filter_frame_cf(hevcdbk_context *ctx, hevcdbk_frame *frame, int
         map_rows = (H + (1u << qp->ctu_log2) - 1) >> qp->ctu_log2;
     }
     if (int rc = bind(ctx)) return rc;
+    GpuDrain drain{ctx}; /* every return below that is not HEVCDBK_OK waits for the GPU */
 
     size_t plane_bytes[3] = {0, 0, 0}, plane_off[3] = {0, 0, 0}, frame_bytes = 0;
     for (int i = 0; i < npl; i++) {
@@ -305,6 +306,7 @@ int hevcdbk_h265_filter_frame_cf(hevcdbk_context *ctx, hevcdbk_frame *frame, int
         timing->total_s = timing->exec_s + timing->copy_s;
         timing->pipelined_s = std::chrono::duration<double>(wall1 - wall0).count();
     }
+    drain.ok = true;
     return HEVCDBK_OK;
 }
 

@@ -102,21 +102,18 @@ public:
             for (uint64_t i = 0; i < kRing; i++) ln.ring[i].seq.store(i, std::memory_order_relaxed);
         }
         const unsigned in_first = workers <= 1 ? workers : ((workers + 1) / 2 < 2 ? (workers + 1) / 2 : 2);
-        for (unsigned i = 0; i < workers; i++) {
-            th_.emplace_back([this, i, in_first] { worker(i < in_first ? LANE_IN : LANE_OUT); });
-            if (cpus) (void)pthread_setaffinity_np(th_.back().native_handle(), sizeof(cpu_set_t), cpus); /* best effort */
+        try {
+            th_.reserve(workers);
+            for (unsigned i = 0; i < workers; i++) {
+                th_.emplace_back([this, i, in_first] { worker(i < in_first ? LANE_IN : LANE_OUT); });
+                if (cpus) (void)pthread_setaffinity_np(th_.back().native_handle(), sizeof(cpu_set_t), cpus); /* best effort */
+            }
+        } catch (...) { /* a thread did not start (EAGAIN under a process limit): the ones that did are joined, not left joinable in th_ */
+            stop();
+            throw;
         }
     }
-    ~StageCrew()
-    {
-        {
-            std::lock_guard<std::mutex> lk(m_);
-            quit_ = true;
-            active_.store(0, std::memory_order_release);
-        }
-        cv_.notify_all();
-        for (auto &t : th_) t.join();
-    }
+    ~StageCrew() { stop(); }
     StageCrew(const StageCrew &) = delete;
     StageCrew &operator=(const StageCrew &) = delete;
 
@@ -157,6 +154,18 @@ public:
     }
 
 private:
+    void stop()
+    {
+        {
+            std::lock_guard<std::mutex> lk(m_);
+            quit_ = true;
+            active_.store(0, std::memory_order_release);
+        }
+        cv_.notify_all();
+        for (auto &t : th_) t.join();
+        th_.clear();
+    }
+
     static constexpr uint64_t kRing = 256;
     struct Slot {
         std::atomic<uint64_t> seq{0};

@@ -157,8 +157,13 @@ HEVCDBK_API unsigned hevcdbk_get_host_threads(const hevcdbk_context *ctx);
 /*
  * For callers that hand the same buffers in again and again (a decoder's picture pool): page-locks [ptr, ptr+bytes) in
  * place (hipHostRegister; the reference's equivalent is allocating the planes with cudaMallocHost, gpu.cu:1092-1099).
- * Planes inside a registered range are DMA'd where they lie, with no staging copy, by hevc_deblocking_filter,
- * hevc_deblocking_filter_sequence and the h265 / SAO host entries.  The caller unregisters before freeing the memory.
+ * Planes that lie WHOLLY inside a registered range are worked on or DMA'd where they lie, with no staging copy, by
+ * hevc_deblocking_filter and hevc_deblocking_filter_sequence; a plane that begins in a range and runs past its end is staged
+ * like pageable memory.  The spec-exact host entries (hevc_deblocking_filter_h265, hevcdbk_h265_filter_frame_cf) always copy
+ * the frame through the page-locked ring or the BAR, registered or not.  Memory page-locked by other means (hipHostMalloc or
+ * hipHostRegister called by the application, another context) is staged like pageable memory as well: of such memory the runtime
+ * tells the kind of a byte, not where its allocation ends.  Transfers of the host-frame operators have completed
+ * when they return, with an error code too.  The caller unregisters before freeing the memory.
  */
 HEVCDBK_API int hevcdbk_host_register(hevcdbk_context *ctx, void *ptr, size_t bytes);
 HEVCDBK_API int hevcdbk_host_unregister(hevcdbk_context *ctx, void *ptr);
@@ -185,7 +190,7 @@ HEVCDBK_API int hevcdbk_last_frame_trace(const hevcdbk_context *ctx, hevcdbk_str
  * Streaming form for a SEQUENCE of host frames of one geometry (the multi-frame case the reference does
  * not have).  Three frames are in flight: H2D of frame n+1, the kernels of frame n and
  * D2H of frame n-1 overlap on the context's three streams.  Planes that already are page-locked
- * (hevcdbk_host_malloc_pinned, hipHostMalloc, hipHostRegister) are DMA'd in place with no staging copy;
+ * through THIS context (hevcdbk_host_malloc_pinned, hevcdbk_host_register) are DMA'd in place with no staging copy;
  * pageable planes go through the context's pinned ring.  bs / tables are shared by all frames;
  * timing->pipelined_s is the wall time of the whole sequence.  A per-CTU QP map is not accepted here.  Sequences of small
  * 8-bit 4:2:0 frames (<= 2 MiB per frame, at least 4 of them) travel in groups of up to 64 frames instead: packed back to

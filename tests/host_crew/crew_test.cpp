@@ -1,6 +1,12 @@
 // tests/host_crew/crew_test.cpp -- CPU test of csrc/host_crew.h, the staging crew of the host-frame operator: many rounds of
 // strip-shaped copies (tight and pitched rows, more jobs than the ring holds, 0..7 crew threads), every byte checked, built
 // plain and with -fsanitize=thread by tests/test_abi_cpu.py.  No HIP here: the crew never makes a HIP call.
+// The plain build also makes thread creation fail (its own pthread_create, forwarding to the C library's): a crew whose k-th thread
+// does not start must throw, leave no thread behind and not end the process; ThreadSanitizer intercepts pthread_create itself.
+#include <dirent.h>
+#include <dlfcn.h>
+
+#include <cerrno>
 #include <cstdio>
 #include <cstdlib>
 #include <memory>
@@ -55,10 +61,61 @@ static int round_of(StageCrew &crew, unsigned W, unsigned H, size_t user_pitch, 
     return bad;
 }
 
+#ifndef CREW_TSAN
+static int g_fail_create_at = 0, g_creates = 0;
+extern "C" int pthread_create(pthread_t *t, const pthread_attr_t *a, void *(*fn)(void *), void *arg)
+{
+    using Fn = int (*)(pthread_t *, const pthread_attr_t *, void *(*)(void *), void *);
+    static Fn real = (Fn)dlsym(RTLD_NEXT, "pthread_create");
+    if (g_fail_create_at && ++g_creates == g_fail_create_at) return EAGAIN;
+    return real(t, a, fn, arg);
+}
+
+static int threads_of_process()
+{
+    int n = 0;
+    if (DIR *d = opendir("/proc/self/task")) {
+        while (const dirent *e = readdir(d)) n += e->d_name[0] != '.';
+        closedir(d);
+    }
+    return n;
+}
+
+/* workers = 3, the k-th creation fails: the constructor throws, every thread it started is gone, a crew made afterwards works */
+static int creation_fails(int k)
+{
+    /* a joined thread leaves /proc/self/task a moment after join() returns: both counts are taken once that has settled */
+    auto settled = [](int want) {
+        for (const int64_t t0 = crew_now_ns(); threads_of_process() > want && crew_now_ns() - t0 < 10000000000ll;) sched_yield(); /* 10 s at most */
+        return threads_of_process();
+    };
+    const int before = settled(1);
+    bool threw = false;
+    g_creates = 0;
+    g_fail_create_at = k;
+    try {
+        StageCrew crew(3, true);
+    } catch (const std::exception &) {
+        threw = true;
+    }
+    g_fail_create_at = 0;
+    int bad = 0;
+    if (!threw) { std::printf("host_crew: creation %d failed and the constructor did not throw\n", k); bad++; }
+    if (settled(before) != before) { std::printf("host_crew: creation %d failed and %d threads stayed\n", k, threads_of_process() - before); bad++; }
+    StageCrew crew(3, true);
+    if (crew.workers() != 3 || round_of(crew, 720, 288, 736, 7, 3, true, 51u + (uint32_t)k) != 0) { std::printf("host_crew: the crew after failure %d does not work\n", k); bad++; }
+    return bad;
+}
+#endif
+
 int main(int argc, char **argv)
 {
     const int rounds = argc > 1 ? std::atoi(argv[1]) : 6;
     int fails = 0;
+#ifndef CREW_TSAN
+    for (int k = 1; k <= 3; k++) fails += creation_fails(k);
+    std::printf("host_crew: thread creation failures handled\n");
+#endif
     for (unsigned workers : {0u, 1u, 3u, 7u})
         for (int stream = 0; stream < 2; stream++) {
             StageCrew crew(workers, stream != 0);

@@ -1,0 +1,803 @@
+/*
+ * host_frame_sim.cpp -- the host-frame operators of csrc/deblock_host.cpp and csrc/deblock_host_h265.cpp (hevc_deblocking_filter,
+ * hevc_deblocking_filter_sequence, hevcdbk_filter_yuv_file, hevc_deblocking_filter_h265, hevcdbk_h265_filter_frame_cf) on the CPU,
+ * the two real sources linked against the model of the HIP runtime in hip_model.cpp.
+ *
+ *   host_frame_sim check SEED N        N cases made from SEED; one line per violation, then "K violations"
+ *   host_frame_sim strips W H SB CHROMA [BAR [PITCHED]]   the strips of one pageable frame (PITCHED: rows 16 samples apart from tight), as hevcdbk_last_frame_trace reports them
+ *   host_frame_sim crewfail            thread creation fails inside ensure_crew (plain builds only)
+ *
+ * What a case must satisfy after every call (the letters are used in the violation lines):
+ *   (a) every sample = the marker transform of the input with the hash of the operands the caller passed; padding and guard bytes unchanged
+ *   (b) every row of every plane written by exactly one kernel operation
+ *   (c) no access violation in the model, no synchronous copy of pageable memory
+ *   (d) every stream empty on return, after an injected failure too
+ *   (e) an injected failure gives a non-OK code and leaves every row either as the input or as the finished result
+ *   (f) hevcdbk_last_frame_trace tiles every plane
+ *   (g) the next call on the same context, another frame through another transport, satisfies (a)
+ * Operand arrays the h265 entries upload with hipMemcpyAsync straight from the caller's memory (units, bS, QP map) are page-locked
+ * here: pageable ones make the runtime copy synchronously, which is slow and not wrong, and would drown (c).
+ */
+#include <dlfcn.h>
+#include <pthread.h>
+#include <sys/mman.h>
+#include <unistd.h>
+
+#include <cerrno>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <map>
+#include <string>
+#include <vector>
+
+#include <hip/hip_runtime_api.h>
+
+#include "../../include/hevc_deblock.h"
+#ifdef HEVCDBK_DIAG
+#include "../../gpu_video_codec_amd/csrc/hevcdbk_diag.h"
+#endif
+#include "hip_model.h"
+
+namespace {
+
+struct Rng {
+    uint64_t s;
+    uint32_t next() { s = s * 6364136223846793005ull + 1442695040888963407ull; return (uint32_t)(s >> 33); }
+    uint32_t below(uint32_t n) { return next() % n; }
+    bool coin() { return next() & 1; }
+};
+
+int g_violations = 0;
+std::string g_case;
+void violation(const char *prop, const std::string &what)
+{
+    g_violations++;
+    if (g_violations <= 200) std::printf("violation (%s) %s: %s\n", prop, g_case.c_str(), what.c_str());
+}
+
+enum Entry { E_FILTER, E_SEQUENCE, E_FILE, E_H265, E_H265_CF, N_ENTRIES };
+const char *const kEntry[N_ENTRIES] = {"hevc_deblocking_filter", "hevc_deblocking_filter_sequence", "hevcdbk_filter_yuv_file",
+                                       "hevc_deblocking_filter_h265", "hevcdbk_h265_filter_frame_cf"};
+/* the last four: page-locked by the application itself, not through the context (hipHostMalloc; hipHostRegister of the whole plane,
+ * of all but its last byte, and as two adjacent ranges) -- the library must stage them like pageable memory */
+enum Mem { MEM_PAGEABLE, MEM_PINNED, MEM_REG, MEM_REG_SHORT, MEM_REG_ALIGN4, MEM_OWN_PINNED, MEM_OWN_REG, MEM_OWN_REG_SHORT, MEM_OWN_REG_TWO, N_MEM };
+const char *const kMem[N_MEM] = {"pageable", "pinned", "registered", "registered-1", "registered+4", "own-pinned", "own-registered", "own-registered-1",
+                                 "own-registered-2ranges"};
+const char *const kSched[3] = {"eager", "lazy", "random"};
+constexpr size_t kGuard = 64;
+
+/* one plane of a caller's frame, with guard bytes around it and (pitched) padding behind every row */
+struct Plane {
+    int mem = MEM_PAGEABLE;
+    uint8_t *base = nullptr; /* the allocation */
+    size_t total = 0, off = 0, pitch = 0, rb = 0;
+    unsigned h = 0;
+    std::vector<uint8_t> in; /* the allocation as it was before the call */
+    uint8_t *p() const { return base + off; }
+    size_t span() const { return pitch * (h - 1) + rb; }
+};
+
+void plane_alloc(Plane &pl, hevcdbk_context *ctx, int mem, size_t rb, unsigned h, bool pitched, unsigned sb, Rng &r)
+{
+    pl.mem = mem;
+    pl.rb = rb;
+    pl.h = h;
+    pl.pitch = pitched ? rb + 16 * sb : rb;
+    pl.off = kGuard + (mem == MEM_REG_ALIGN4 ? 4 : 0);
+    pl.total = pl.off + pl.span() + kGuard;
+    if (mem == MEM_PAGEABLE) pl.base = (uint8_t *)aligned_alloc(64, (pl.total + 63) / 64 * 64);
+    else if (mem == MEM_PINNED) hevcdbk_host_malloc_pinned(ctx, pl.total, (void **)&pl.base);
+    else if (mem == MEM_OWN_PINNED) (void)hipHostMalloc((void **)&pl.base, pl.total, hipHostMallocDefault);
+    else pl.base = (uint8_t *)model_region_alloc(pl.total);
+    if (!pl.base) { std::printf("out of memory\n"); std::exit(2); }
+    pl.in.resize(pl.total);
+    for (size_t i = 0; i < pl.total; i += 4) {
+        const uint32_t v = r.next();
+        std::memcpy(&pl.in[i], &v, pl.total - i < 4 ? pl.total - i : 4);
+    }
+    std::memcpy(pl.base, pl.in.data(), pl.total);
+}
+/* registrations belong to a context: made for every context the plane is used with */
+void plane_register(const Plane &pl, hevcdbk_context *ctx)
+{
+    if (pl.mem < MEM_REG || pl.mem == MEM_OWN_PINNED) return;
+    const size_t n = pl.mem == MEM_REG_SHORT || pl.mem == MEM_OWN_REG_SHORT ? pl.off + pl.span() - 1 : pl.total;
+    bool ok;
+    if (pl.mem == MEM_OWN_REG_TWO) {
+        const size_t half = (pl.off + pl.span() / 2) & ~(size_t)63;
+        ok = hipHostRegister(pl.base, half, hipHostRegisterDefault) == hipSuccess &&
+             hipHostRegister(pl.base + half, pl.total - half, hipHostRegisterDefault) == hipSuccess;
+    } else if (pl.mem >= MEM_OWN_REG) ok = hipHostRegister(pl.base, n, hipHostRegisterDefault) == hipSuccess;
+    else ok = hevcdbk_host_register(ctx, pl.base, n) == HEVCDBK_OK;
+    if (!ok) violation("c", "registering the plane failed");
+}
+void plane_free(Plane &pl, hevcdbk_context *ctx)
+{
+    if (pl.mem == MEM_PAGEABLE) free(pl.base);
+    else if (pl.mem == MEM_PINNED) hevcdbk_host_free_pinned(ctx, pl.base);
+    else if (pl.mem == MEM_OWN_PINNED) (void)hipHostFree(pl.base);
+    else {
+        if (pl.mem == MEM_OWN_REG_TWO) (void)hipHostUnregister(pl.base + ((pl.off + pl.span() / 2) & ~(size_t)63));
+        if (pl.mem >= MEM_OWN_REG) (void)hipHostUnregister(pl.base);
+        model_region_free(pl.base);
+    }
+    pl.base = nullptr;
+}
+
+/* (a) / (e): 0 = every row is the result, 1 = every row is input or result, 2 = something else; padding and guards in every case */
+int plane_state(const Plane &pl, uint64_t hash, int chroma)
+{
+    int state = 0;
+    for (size_t i = 0; i < pl.off; i++)
+        if (pl.base[i] != pl.in[i]) return 2;
+    for (size_t i = pl.off + pl.span(); i < pl.total; i++)
+        if (pl.base[i] != pl.in[i]) return 2;
+    for (unsigned y = 0; y < pl.h; y++) {
+        const uint8_t *got = pl.p() + y * pl.pitch, *was = pl.in.data() + pl.off + y * pl.pitch;
+        bool is_out = true, is_in = true;
+        for (size_t x = 0; x < pl.rb; x++) {
+            is_in = is_in && got[x] == was[x];
+            is_out = is_out && got[x] == (uint8_t)(was[x] ^ model_m(hash, chroma, y, (unsigned)x));
+        }
+        if (!is_out) state = is_in ? (state < 1 ? 1 : state) : 2;
+        if (state == 2) return 2;
+        if (y + 1 < pl.h)
+            for (size_t x = pl.rb; x < pl.pitch; x++)
+                if (got[x] != was[x]) return 2;
+    }
+    return state;
+}
+
+/* page-locked operand arrays (see the head of the file) */
+struct Locked {
+    uint8_t *p = nullptr;
+    size_t n = 0;
+};
+Locked locked_random(hevcdbk_context *ctx, size_t n, Rng &r, unsigned mod)
+{
+    Locked l;
+    l.n = n;
+    hevcdbk_host_malloc_pinned(ctx, n, (void **)&l.p);
+    for (size_t i = 0; i < n; i++) l.p[i] = (uint8_t)(r.next() % mod);
+    return l;
+}
+
+struct Case {
+    int entry, sched, threads, mem[3], n_frames, cf;
+    bool large_bar, supports, chroma, pitched, user_bs, qp_map, units, push_unmapped;
+    unsigned W, H, sb, bit_depth, qp;
+    uint32_t seed;
+#ifdef HEVCDBK_DIAG
+    bool k_push, k_direct_out, k_direct_in, k_h2d2, k_k2, k_dmacopy, k_strips;
+#endif
+};
+
+Case make_case(Rng &r, uint32_t seed)
+{
+    Case c{};
+    c.seed = seed;
+    const uint32_t e = r.below(16);
+    c.entry = e < 8 ? E_FILTER : e < 10 ? E_SEQUENCE : e < 12 ? E_FILE : e < 14 ? E_H265 : E_H265_CF;
+    c.sched = (int)r.below(3);
+    const int th[3] = {1, 2, 5};
+    c.threads = th[r.below(3)];
+    c.large_bar = r.coin();
+    c.supports = r.coin();
+    c.push_unmapped = c.large_bar && r.below(8) == 0;
+    static const unsigned shapes[6][3] = {{16, 16, 1}, {352, 288, 1}, {1440, 1088, 1}, {8, 4096, 0}, {512, 1032, 0}, {4096, 72, 0}};
+    static const unsigned weight[6] = {28, 28, 8, 12, 14, 10};
+    unsigned pick = r.below(100), s = 0;
+    while (pick >= weight[s]) pick -= weight[s++];
+    c.W = shapes[s][0];
+    c.H = shapes[s][1];
+    c.chroma = shapes[s][2] && r.below(4) != 0;
+    c.sb = r.below(3) == 0 ? 2 : 1;
+    c.bit_depth = c.sb == 2 ? 10 : 8;
+    c.pitched = r.below(3) == 0;
+    /* memory the context locked itself twice to three times as often as each of the others: only it reaches the zero-copy transports */
+    static const int mem_pick[15] = {MEM_PAGEABLE, MEM_PAGEABLE, MEM_PINNED, MEM_PINNED, MEM_PINNED, MEM_REG, MEM_REG, MEM_REG, MEM_REG_SHORT,
+                                     MEM_REG_ALIGN4, MEM_REG_ALIGN4, MEM_OWN_PINNED, MEM_OWN_REG, MEM_OWN_REG_SHORT, MEM_OWN_REG_TWO};
+    for (int i = 0; i < 3; i++) c.mem[i] = mem_pick[r.below(15)];
+    if (r.coin()) c.mem[1] = c.mem[2] = c.mem[0]; /* a frame in one kind of memory as often as a mixed one */
+    c.user_bs = r.coin();
+    c.qp_map = r.below(3) == 0;
+    c.units = r.coin();
+    c.qp = 20 + r.below(32);
+    static const int nf[5] = {1, 2, 3, 4, 7};
+    c.n_frames = nf[r.below(5)];
+    c.cf = HEVCDBK_CHROMA_420;
+    if (c.entry == E_SEQUENCE) {
+        c.qp_map = false;
+        const uint32_t form = r.below(3);
+        if (form == 0) { /* frames above 2 MiB, all pageable: the form that is pushed through the BAR */
+            c.W = 1440; c.H = 1088; c.chroma = true;
+            c.mem[0] = c.mem[1] = c.mem[2] = MEM_PAGEABLE;
+            if (r.below(4) != 0) { c.large_bar = true; c.push_unmapped = false; }
+            if (c.n_frames < 2) c.n_frames = 2;
+        } else if (form == 1) { /* at least four small 8-bit 4:2:0 frames: the form that travels in chunks */
+            if (c.W != 16) { c.W = 352; c.H = 288; }
+            c.chroma = true; c.sb = 1; c.bit_depth = 8;
+            if (c.n_frames < 4) c.n_frames = 4;
+        }
+    } else if (c.entry == E_FILE) {
+        c.W = 352; c.H = 288; c.chroma = true; c.sb = 1; c.bit_depth = 8;
+        c.n_frames = r.below(4) == 0 ? 70 : 3;
+        c.qp_map = false;
+    } else if (c.entry == E_H265_CF) {
+        c.cf = c.chroma ? (int)(1 + r.below(3)) : (r.coin() ? HEVCDBK_CHROMA_400 : HEVCDBK_CHROMA_420);
+    }
+    if (c.entry != E_SEQUENCE && c.entry != E_FILE) c.n_frames = 1;
+#ifdef HEVCDBK_DIAG
+    c.k_push = r.below(4) != 0; c.k_direct_out = r.below(4) != 0; c.k_direct_in = r.below(5) < 2; c.k_h2d2 = r.below(4) == 0;
+    c.k_k2 = r.below(4) == 0; c.k_dmacopy = r.below(3) == 0; c.k_strips = r.coin();
+#endif
+    return c;
+}
+
+std::string describe(const Case &c)
+{
+    char b[400];
+    std::snprintf(b, sizeof b, "seed=%u %s %ux%u %s sb=%u %s mem=%s/%s/%s bs=%d map=%d units=%d frames=%d cf=%d bar=%d%s sched=%s threads=%d supports=%d", c.seed,
+                  kEntry[c.entry], c.W, c.H, c.chroma ? "yuv" : "y", c.sb, c.pitched ? "pitched" : "tight", kMem[c.mem[0]], kMem[c.mem[1]], kMem[c.mem[2]],
+                  c.user_bs, c.qp_map, c.units, c.n_frames, c.cf, c.large_bar, c.push_unmapped ? "(unmapped)" : "", kSched[c.sched], c.threads, c.supports);
+    std::string s = b;
+#ifdef HEVCDBK_DIAG
+    std::snprintf(b, sizeof b, " diag: push=%d dout=%d din=%d h2d2=%d k2=%d dmacopy=%d strips=%d", c.k_push, c.k_direct_out, c.k_direct_in, c.k_h2d2, c.k_k2,
+                  c.k_dmacopy, c.k_strips);
+    s += b;
+#endif
+    return s;
+}
+
+void set_knobs(const Case &c)
+{
+#ifdef HEVCDBK_DIAG
+    setenv("HEVCDBK_HOST_PUSH", c.k_push ? "1" : "0", 1);
+    setenv("HEVCDBK_HOST_DIRECT_OUT", c.k_direct_out ? "1" : "0", 1);
+    setenv("HEVCDBK_HOST_DIRECT_IN", c.k_direct_in ? "1" : "0", 1);
+    setenv("HEVCDBK_HOST_H2D_STREAMS2", c.k_h2d2 ? "1" : "0", 1);
+    setenv("HEVCDBK_HOST_K_STREAMS2", c.k_k2 ? "1" : "0", 1);
+    if (c.k_strips) { setenv("HEVCDBK_HOST_FIRST_STRIP_KB", "32", 1); setenv("HEVCDBK_HOST_STRIP_KB", "64", 1); }
+    else { unsetenv("HEVCDBK_HOST_FIRST_STRIP_KB"); unsetenv("HEVCDBK_HOST_STRIP_KB"); }
+    hevcdbk_diag_set(c.k_dmacopy ? "dmacopy" : "");
+#else
+    (void)c;
+#endif
+}
+
+/* the operands of a call and the hashes its kernels must arrive at */
+struct Operands {
+    std::vector<uint8_t> vert, hor, cvert, chor; /* reference mode: the caller's arrays, or the default pattern */
+    Locked map, v4, h4, units[5];
+    hevcdbk_bs bs{};
+    hevcdbk_qp qp{};
+    hevcdbk_h265_units u{};
+    hevcdbk_h265_params prm{1, -1, 1, 2};
+    uint64_t hash[3] = {0, 0, 0};
+    unsigned pw[3] = {0, 0, 0}, ph[3] = {0, 0, 0};
+    int npl = 1;
+};
+
+size_t nv4(unsigned w, unsigned h) { return (size_t)(w / 8 + 1) * (h / 4); }
+size_t nh4(unsigned w, unsigned h) { return (size_t)(h / 8 + 1) * (w / 4); }
+
+void make_operands(const Case &c, hevcdbk_context *ctx, Rng &r, Operands &o)
+{
+    const bool h265 = c.entry == E_H265 || c.entry == E_H265_CF;
+    const unsigned sw = c.cf == HEVCDBK_CHROMA_444 ? 1 : 2, sh = c.cf == HEVCDBK_CHROMA_420 ? 2 : 1;
+    o.npl = c.chroma ? 3 : 1;
+    o.pw[0] = c.W; o.ph[0] = c.H;
+    o.pw[1] = o.pw[2] = c.W / sw; o.ph[1] = o.ph[2] = c.H / sh;
+    o.qp.qp = c.qp;
+    o.qp.ctu_log2 = 4 + r.below(3);
+    o.qp.map_stride = ((c.W + (1u << o.qp.ctu_log2) - 1) >> o.qp.ctu_log2) + r.below(3);
+    const size_t map_rows = (c.H + (1u << o.qp.ctu_log2) - 1) >> o.qp.ctu_log2;
+    if (c.qp_map) {
+        o.map = locked_random(ctx, map_rows * o.qp.map_stride, r, 52);
+        o.qp.map = o.map.p;
+    }
+    const int max_v = (1 << c.bit_depth) - 1;
+    if (!h265) {
+        const size_t nv = hevcdbk_num_vert_bs(c.W, c.H), nh = hevcdbk_num_hor_bs(c.W, c.H);
+        const size_t ncv = c.chroma ? hevcdbk_num_vert_bs(c.W / 2, c.H / 2) : 0, nch = c.chroma ? hevcdbk_num_hor_bs(c.W / 2, c.H / 2) : 0;
+        o.vert.resize(nv); o.hor.resize(nh); o.cvert.resize(ncv + 1); o.chor.resize(nch + 1);
+        hevcdbk_default_bs(c.W, c.H, o.vert.data(), o.hor.data());
+        if (c.chroma) hevcdbk_default_bs(c.W / 2, c.H / 2, o.cvert.data(), o.chor.data());
+        if (c.user_bs) {
+            for (auto *v : {&o.vert, &o.hor, &o.cvert, &o.chor})
+                for (auto &b : *v) b = (uint8_t)r.below(3);
+            o.bs.vert = o.vert.data(); o.bs.n_vert = nv; o.bs.hor = o.hor.data(); o.bs.n_hor = nh;
+            if (c.chroma) { o.bs.chroma_vert = o.cvert.data(); o.bs.n_chroma_vert = ncv; o.bs.chroma_hor = o.chor.data(); o.bs.n_chroma_hor = nch; }
+        }
+        const unsigned *tc = hevcdbk_default_tc_table(), *beta = hevcdbk_default_beta_table();
+        uint8_t tc8[52], beta8[52];
+        for (int i = 0; i < 52; i++) { tc8[i] = (uint8_t)tc[i]; beta8[i] = (uint8_t)beta[i]; }
+        const unsigned q = c.qp > 51 ? 51 : c.qp, shift = c.bit_depth - 8;
+        for (int i = 0; i < o.npl; i++) {
+            uint64_t h = kModelHash0;
+            h = model_fold(h, tc8, 52);
+            h = model_fold(h, beta8, 52);
+            h = model_fold_int(h, (int)(tc[q] << shift));
+            h = model_fold_int(h, (int)(beta[q] << shift));
+            h = model_fold_int(h, max_v);
+            if (c.qp_map) { h = model_fold_int(h, (int)o.qp.map_stride); h = model_fold_int(h, (int)o.qp.ctu_log2); }
+            h = model_fold(h, i ? o.cvert.data() : o.vert.data(), i ? ncv : nv);
+            h = model_fold(h, i ? o.chor.data() : o.hor.data(), i ? nch : nh);
+            if (c.qp_map) h = model_fold(h, o.map.p, o.map.n);
+            o.hash[i] = h;
+        }
+        return;
+    }
+    /* spec-exact mode: units (the bS are derived on the device) or the caller's 4-sample bS; chroma bS always derived */
+    const size_t nv = nv4(c.W, c.H), nh = nh4(c.W, c.H), ncv = c.chroma ? nv4(o.pw[1], o.ph[1]) : 0, nch = c.chroma ? nh4(o.pw[1], o.ph[1]) : 0;
+    std::vector<uint8_t> vert(nv), hor(nh), cvert(ncv), chor(nch);
+    const bool one_launch = c.cf == HEVCDBK_CHROMA_420 || !c.chroma;
+    bool chroma_done = false;
+    if (c.units) {
+        const size_t U = (size_t)(c.W / 4) * (c.H / 4);
+        const size_t bytes[5] = {2 * U, 4 * U, 4 * U, 4 * U, 4 * U}; /* flags, mv0, mv1, ref0, ref1 */
+        uint64_t h = kModelHash0 ^ 0xb5;
+        for (int k = 0; k < 5; k++) {
+            o.units[k] = locked_random(ctx, bytes[k], r, 256);
+            h = model_fold(h, o.units[k].p, bytes[k]);
+        }
+        o.u.flags = (const uint16_t *)o.units[0].p; o.u.mv0 = (const int16_t *)o.units[1].p; o.u.mv1 = (const int16_t *)o.units[2].p;
+        o.u.ref0 = (const int32_t *)o.units[3].p; o.u.ref1 = (const int32_t *)o.units[4].p;
+        model_derived(h, vert.data(), nv);
+        model_derived(h + 0x1000u, hor.data(), nh);
+        if (c.chroma && one_launch) {
+            model_derived(h + 0x2000u, cvert.data(), ncv);
+            model_derived(h + 0x3000u, chor.data(), nch);
+            chroma_done = true;
+        }
+    } else {
+        o.v4 = locked_random(ctx, nv, r, 3);
+        o.h4 = locked_random(ctx, nh, r, 3);
+        std::memcpy(vert.data(), o.v4.p, nv);
+        std::memcpy(hor.data(), o.h4.p, nh);
+        o.bs.vert = o.v4.p; o.bs.n_vert = nv; o.bs.hor = o.h4.p; o.bs.n_hor = nh;
+    }
+    if (c.chroma && !chroma_done) {
+        uint64_t h = kModelHash0 ^ 0xb5;
+        h = model_fold(h, vert.data(), nv);
+        h = model_fold(h, hor.data(), nh);
+        model_derived(h, cvert.data(), ncv);
+        model_derived(h + 0x1000u, chor.data(), nch);
+    }
+    for (int i = 0; i < o.npl; i++) {
+        uint64_t h = kModelHash0 ^ 0x265;
+        h = model_fold_int(h, (int)(c.qp > 51 ? 51 : c.qp));
+        h = model_fold_int(h, o.prm.tc_offset_div2 * 2);
+        h = model_fold_int(h, o.prm.beta_offset_div2 * 2);
+        h = model_fold_int(h, i == 1 ? o.prm.cb_qp_offset : i == 2 ? o.prm.cr_qp_offset : 0);
+        h = model_fold_int(h, max_v);
+        if (c.qp_map) { h = model_fold_int(h, (int)o.qp.map_stride); h = model_fold_int(h, (int)o.qp.ctu_log2); }
+        h = model_fold(h, i ? cvert.data() : vert.data(), i ? ncv : nv);
+        h = model_fold(h, i ? chor.data() : hor.data(), i ? nch : nh);
+        if (c.qp_map) h = model_fold(h, o.map.p, o.map.n);
+        o.hash[i] = h;
+    }
+}
+void free_operands(hevcdbk_context *ctx, Operands &o)
+{
+    for (Locked *l : {&o.map, &o.v4, &o.h4, &o.units[0], &o.units[1], &o.units[2], &o.units[3], &o.units[4]})
+        if (l->p) hevcdbk_host_free_pinned(ctx, l->p);
+}
+
+/* a file of the file operator: an anonymous memory file, named through /proc */
+struct MemFile {
+    int fd = -1;
+    std::string name;
+    MemFile() { fd = memfd_create("host_frame_sim_yuv", 0); name = "/proc/self/fd/" + std::to_string(fd); }
+    ~MemFile() { if (fd >= 0) close(fd); }
+};
+
+struct Frames {
+    std::vector<Plane> planes; /* [frame * npl + plane] */
+    std::vector<hevcdbk_frame> frames;
+    MemFile in, out;
+    std::vector<uint8_t> file_in;
+};
+
+int call_entry(const Case &c, hevcdbk_context *ctx, Operands &o, Frames &f, bool timing)
+{
+    hevcdbk_timing t;
+    hevcdbk_timing *tp = timing ? &t : nullptr;
+    const hevcdbk_bs *bs = c.user_bs ? &o.bs : nullptr;
+    switch (c.entry) {
+    case E_FILTER: return hevc_deblocking_filter(ctx, &f.frames[0], bs, &o.qp, nullptr, tp);
+    case E_SEQUENCE: return hevc_deblocking_filter_sequence(ctx, f.frames.data(), (unsigned)c.n_frames, bs, &o.qp, nullptr, tp);
+    case E_FILE: {
+        unsigned n = 0;
+        if (ftruncate(f.out.fd, 0) != 0) return HEVCDBK_ERR_IO;
+        const int rc = hevcdbk_filter_yuv_file(ctx, f.in.name.c_str(), f.out.name.c_str(), c.W, c.H, c.qp, bs, nullptr, &n, tp);
+        if (rc == HEVCDBK_OK && n != (unsigned)c.n_frames) violation("a", "the file operator counted " + std::to_string(n) + " frames");
+        return rc;
+    }
+    case E_H265: return hevc_deblocking_filter_h265(ctx, &f.frames[0], c.units ? &o.u : nullptr, c.units ? nullptr : &o.bs, &o.qp, &o.prm, tp);
+    default: return hevcdbk_h265_filter_frame_cf(ctx, &f.frames[0], c.cf, c.units ? &o.u : nullptr, c.units ? nullptr : &o.bs, &o.qp, &o.prm, tp);
+    }
+}
+
+/* (b): the rows the kernel operations wrote */
+void check_rows(const Case &c, const Operands &o)
+{
+    const auto &w = model_writes();
+    if (c.entry == E_SEQUENCE || c.entry == E_FILE) {
+        size_t rows = 0, want = 0;
+        for (const ModelWrite &m : w) rows += (size_t)(m.r1 - m.r0) * (size_t)m.frames;
+        for (int i = 0; i < o.npl; i++) want += (size_t)o.ph[i] * (size_t)c.n_frames;
+        if (rows != want) violation("b", std::to_string(rows) + " rows written by kernel operations, " + std::to_string(want) + " rows in the planes");
+        for (const ModelWrite &m : w)
+            if (m.r0 != 0 || (int)m.r1 != m.plane_h) violation("b", "a kernel operation of a whole-frame entry wrote part of a plane");
+        return;
+    }
+    std::map<const void *, std::vector<std::pair<unsigned, unsigned>>> by_plane;
+    std::map<const void *, int> height;
+    for (const ModelWrite &m : w) { by_plane[m.dst].push_back({m.r0, m.r1}); height[m.dst] = m.plane_h; }
+    if ((int)by_plane.size() != o.npl) violation("b", std::to_string(by_plane.size()) + " planes written, " + std::to_string(o.npl) + " in the frame");
+    for (auto &kv : by_plane) {
+        std::vector<int> n((size_t)height[kv.first], 0);
+        for (auto &rg : kv.second)
+            for (unsigned y = rg.first; y < rg.second && y < n.size(); y++) n[y]++;
+        for (size_t y = 0; y < n.size(); y++)
+            if (n[y] != 1) { violation("b", "row " + std::to_string(y) + " written by " + std::to_string(n[y]) + " kernel operations"); break; }
+    }
+}
+
+/* (f) */
+void check_trace(const Case &c, hevcdbk_context *ctx, const Operands &o)
+{
+    unsigned n = 0;
+    hevcdbk_last_frame_trace(ctx, nullptr, 0, &n);
+    if (n == 0) return; /* a small frame: no strips */
+    std::vector<hevcdbk_strip_trace> tr(n);
+    hevcdbk_last_frame_trace(ctx, tr.data(), n, &n);
+    for (int i = 0; i < o.npl; i++) {
+        unsigned at = 0;
+        size_t bytes = 0;
+        bool first = true;
+        for (const hevcdbk_strip_trace &t : tr) {
+            if (t.plane != i) continue;
+            if (t.row_begin != at) violation("f", "plane " + std::to_string(i) + ": a strip begins at row " + std::to_string(t.row_begin) + ", the one before ended at " + std::to_string(at));
+            if (!first && (t.row_begin + 4) % 8 != 0) violation("f", "a strip begins off the block-row grid");
+            if (t.row_end <= t.row_begin) violation("f", "an empty strip");
+            at = t.row_end;
+            bytes += t.bytes;
+            first = false;
+        }
+        if (at != o.ph[i]) violation("f", "plane " + std::to_string(i) + ": the strips end at row " + std::to_string(at));
+        if (bytes != (size_t)o.pw[i] * o.ph[i] * c.sb) violation("f", "the strips' bytes do not sum to the plane");
+    }
+}
+
+/* which way the data went, from what the kernel operations were given (the fault-free run) */
+std::string transport_of(const Case &c, hevcdbk_context *ctx, const Frames &f)
+{
+    const auto &w = model_writes();
+    if (w.empty()) return "none";
+    const char in = model_kind_of(w[0].src), out = model_kind_of(w[0].dst);
+    unsigned strips = 0;
+    hevcdbk_last_frame_trace(ctx, nullptr, 0, &strips);
+    std::string t;
+    switch (c.entry) {
+    case E_FILTER: {
+        if (!strips) return in == 'd' ? "small_dma" : out == 'r' || (const uint8_t *)w[0].dst == f.planes[0].p() ? "small_direct" : "small_staged";
+        t = in == 'f' ? "strips_bar_push" : in == 'd' ? "strips_h2d" : "strips_direct_in";
+        const bool caller = out == 'r' || (const uint8_t *)w[0].dst == f.planes[0].p();
+        return t + (out == 'd' ? "+d2h" : caller ? "+kout_caller" : "+kout_ring");
+    }
+    case E_SEQUENCE: return w[0].frames > 1 ? "sequence_chunks" : in == 'f' ? "sequence_bar_push" : "sequence_dma";
+    case E_FILE: return "file_chunks";
+    default: return in == 'f' ? "h265_bar_push" : "h265_dma";
+    }
+}
+
+struct Tally {
+    std::map<std::string, int> ran, refused, transports, scheds, faults; /* faults: cases per kind of injected failure, and per entry and kind */
+} g_tally;
+
+hevcdbk_context *new_context(const Case &c)
+{
+    hevcdbk_context *ctx = nullptr;
+    if (hevcdbk_create(0, &ctx) != HEVCDBK_OK) { std::printf("hevcdbk_create failed\n"); std::exit(2); }
+    hevcdbk_set_host_threads(ctx, (unsigned)c.threads);
+    return ctx;
+}
+
+ModelCase model_case(const Case &c, int fault_kind, int fault_at)
+{
+    ModelCase m;
+    m.sched = c.sched;
+    m.seed = c.seed * 977u + (uint32_t)fault_at;
+    m.large_bar = c.large_bar;
+    m.supports = c.supports;
+    m.push_unmapped = c.push_unmapped;
+    m.fault_kind = fault_kind;
+    m.fault_at = fault_at;
+    return m;
+}
+
+void check_model(const char *when)
+{
+    for (const std::string &v : model_violations()) violation("c", std::string(when) + ": " + v);
+    if (model_sync_pageable_copies()) violation("c", std::string(when) + ": " + std::to_string(model_sync_pageable_copies()) + " synchronous copies of pageable memory");
+    if (model_pending_ops()) {
+        violation("d", std::string(when) + ": " + std::to_string(model_pending_ops()) + " operations still queued when the entry returned");
+        model_drain();
+    }
+}
+
+/* (g): another frame through another transport on the same context */
+void follow_up(const Case &c, hevcdbk_context *ctx, Rng &r, const char *when)
+{
+    Case d = c;
+    d.entry = E_FILTER;
+    d.user_bs = !c.user_bs;
+    d.qp_map = false;
+    d.qp = c.qp ^ 1;
+    d.cf = HEVCDBK_CHROMA_420;
+    d.n_frames = 1;
+    const bool was_small = c.chroma && c.supports && (size_t)c.W * c.H * c.sb * 3 / 2 <= ((size_t)2 << 20) && c.entry == E_FILTER;
+    d.chroma = !was_small;
+    d.W = was_small ? 64 : 32;
+    d.H = was_small ? 72 : 32;
+    d.sb = 1; d.bit_depth = 8; d.pitched = !c.pitched;
+    Operands o;
+    make_operands(d, ctx, r, o);
+    Frames f;
+    f.planes.resize((size_t)o.npl);
+    f.frames.resize(1);
+    hevcdbk_frame &fr = f.frames[0];
+    std::memset(&fr, 0, sizeof fr);
+    fr.width = d.W; fr.height = d.H; fr.bit_depth = 8; fr.sample_bytes = 1;
+    for (int i = 0; i < o.npl; i++) {
+        plane_alloc(f.planes[(size_t)i], ctx, c.mem[0] == MEM_PAGEABLE ? MEM_PINNED : MEM_PAGEABLE, o.pw[i], o.ph[i], d.pitched, 1, r);
+        fr.plane[i] = f.planes[(size_t)i].p();
+        fr.pitch[i] = f.planes[(size_t)i].pitch;
+    }
+    model_begin(model_case(d, FAULT_NONE, 0));
+    const int rc = call_entry(d, ctx, o, f, false);
+    if (rc != HEVCDBK_OK) violation("g", std::string(when) + ": the next call on the context returned " + std::to_string(rc) + " (" + hevcdbk_last_error(ctx) + ")");
+    else
+        for (int i = 0; i < o.npl; i++)
+            if (plane_state(f.planes[(size_t)i], o.hash[i], i != 0) != 0) violation("g", std::string(when) + ": plane " + std::to_string(i) + " of the next call is wrong");
+    check_model(when);
+    for (Plane &p : f.planes) plane_free(p, ctx);
+    free_operands(ctx, o);
+}
+
+void build_frames(const Case &c, hevcdbk_context *ctx, const Operands &o, Rng &r, Frames &f)
+{
+    if (c.entry == E_FILE) {
+        const size_t fb = (size_t)c.W * c.H * 3 / 2;
+        f.file_in.resize(fb * (size_t)c.n_frames);
+        for (auto &b : f.file_in) b = (uint8_t)r.next();
+        if (write(f.in.fd, f.file_in.data(), f.file_in.size()) != (ssize_t)f.file_in.size()) { std::printf("memfd write failed\n"); std::exit(2); }
+        return;
+    }
+    f.planes.resize((size_t)(c.n_frames * o.npl));
+    f.frames.resize((size_t)c.n_frames);
+    for (int n = 0; n < c.n_frames; n++) {
+        hevcdbk_frame &fr = f.frames[(size_t)n];
+        std::memset(&fr, 0, sizeof fr);
+        fr.width = c.W; fr.height = c.H; fr.bit_depth = c.bit_depth; fr.sample_bytes = c.sb;
+        for (int i = 0; i < o.npl; i++) {
+            Plane &pl = f.planes[(size_t)(n * o.npl + i)];
+            plane_alloc(pl, ctx, c.mem[i], (size_t)o.pw[i] * c.sb, o.ph[i], c.pitched, c.sb, r);
+            fr.plane[i] = pl.p();
+            fr.pitch[i] = pl.pitch;
+        }
+    }
+}
+
+/* the planes after a call: ok = every row the result; else every row input or result */
+void check_planes(const Case &c, const Operands &o, Frames &f, bool ok, const char *when)
+{
+    if (c.entry == E_FILE) {
+        if (!ok) return; /* the output file of a failed call is the caller's to delete */
+        const size_t fb = (size_t)c.W * c.H * 3 / 2, ysz = (size_t)c.W * c.H;
+        std::vector<uint8_t> got(f.file_in.size());
+        if (pread(f.out.fd, got.data(), got.size(), 0) != (ssize_t)got.size()) { violation("a", "the output file is short"); return; }
+        for (size_t n = 0; n < (size_t)c.n_frames; n++)
+            for (int i = 0; i < 3; i++) {
+                const size_t off = n * fb + (i == 0 ? 0 : i == 1 ? ysz : ysz + ysz / 4);
+                for (unsigned y = 0; y < o.ph[i]; y++)
+                    for (unsigned x = 0; x < o.pw[i]; x++) {
+                        const size_t at = off + (size_t)y * o.pw[i] + x;
+                        if (got[at] != (uint8_t)(f.file_in[at] ^ model_m(o.hash[i], i != 0, y, x))) {
+                            violation("a", std::string(when) + ": frame " + std::to_string(n) + " plane " + std::to_string(i) + " row " + std::to_string(y) + " of the output file is wrong");
+                            return;
+                        }
+                    }
+            }
+        return;
+    }
+    for (int n = 0; n < c.n_frames; n++)
+        for (int i = 0; i < o.npl; i++) {
+            const int st = plane_state(f.planes[(size_t)(n * o.npl + i)], o.hash[i], i != 0);
+            if (ok && st != 0) violation("a", std::string(when) + ": frame " + std::to_string(n) + " plane " + std::to_string(i) + (st == 1 ? " has rows left as the input" : " holds wrong bytes"));
+            if (!ok && st == 2) violation("e", std::string(when) + ": frame " + std::to_string(n) + " plane " + std::to_string(i) + " holds bytes that are neither the input nor the result");
+        }
+}
+
+void run_case(uint32_t seed)
+{
+    Rng r{0x51ed270b1ull * (seed + 1)};
+    const Case c = make_case(r, seed);
+    g_case = describe(c);
+    set_knobs(c);
+    const Rng r_data = r; /* every run of the case builds the same frame and operands */
+
+    int calls[FAULT_KINDS] = {};
+    /* the fault-free run */
+    {
+        Rng rr = r_data;
+        hevcdbk_context *ctx = new_context(c);
+        Operands o;
+        make_operands(c, ctx, rr, o);
+        Frames f;
+        build_frames(c, ctx, o, rr, f);
+        for (const Plane &p : f.planes) plane_register(p, ctx);
+        model_begin(model_case(c, FAULT_NONE, 0));
+        const int rc = call_entry(c, ctx, o, f, (seed & 1) != 0);
+        for (int k = 0; k < FAULT_KINDS; k++) calls[k] = model_calls(k);
+        if (rc == HEVCDBK_ERR_ARG || rc == HEVCDBK_ERR_UNSUPPORTED) {
+            g_tally.refused[kEntry[c.entry]]++;
+            check_model("refused");
+            for (int k = 0; k < FAULT_KINDS; k++) calls[k] = 0;
+        } else {
+            g_tally.ran[kEntry[c.entry]]++;
+            g_tally.scheds[kSched[c.sched]]++;
+            if (rc != HEVCDBK_OK) violation("a", "returned " + std::to_string(rc) + " (" + hevcdbk_last_error(ctx) + ")");
+            else {
+                g_tally.transports[transport_of(c, ctx, f)]++;
+                check_planes(c, o, f, true, "fault-free");
+                check_rows(c, o);
+                if (c.entry == E_FILTER) check_trace(c, ctx, o);
+            }
+            check_model("fault-free");
+            follow_up(c, ctx, rr, "after the fault-free call");
+        }
+        for (Plane &p : f.planes) plane_free(p, ctx);
+        free_operands(ctx, o);
+        hevcdbk_destroy(ctx);
+    }
+    /* one kind of HIP call, failing at each of its calls in turn */
+    std::vector<int> kinds;
+    for (int k = 1; k < FAULT_KINDS; k++)
+        if (calls[k]) kinds.push_back(k);
+    if (kinds.empty()) return;
+    /* one time in three from the kinds few transports make, where the case makes any: else they are drawn too seldom to count on */
+    std::vector<int> rare;
+    for (int k : kinds)
+        if (k == FAULT_MEMCPY2D_ASYNC || k == FAULT_EXT_MALLOC || k == FAULT_STREAM_WAIT_EVENT || k == FAULT_EVENT_QUERY) rare.push_back(k);
+    if (!rare.empty() && r.below(3) == 0) kinds = rare;
+    const int kind = kinds[r.below((uint32_t)kinds.size())];
+    g_tally.faults[model_fault_name(kind)]++;
+    g_tally.faults[std::string(kEntry[c.entry]) + "/" + model_fault_name(kind)]++;
+    for (int at = 1; at <= calls[kind]; at++) {
+        const std::string when = std::string(model_fault_name(kind)) + " #" + std::to_string(at) + " fails";
+        Rng rr = r_data;
+        hevcdbk_context *ctx = new_context(c);
+        Operands o;
+        make_operands(c, ctx, rr, o);
+        Frames f;
+        build_frames(c, ctx, o, rr, f);
+        for (const Plane &p : f.planes) plane_register(p, ctx);
+        model_begin(model_case(c, kind, at));
+        const int rc = call_entry(c, ctx, o, f, (seed & 1) != 0);
+        /* the one failure the library is built to survive: no fine-grained memory for the BAR push -> ring and DMA.  And a call that
+         * polled less often than the fault-free run did (the crew's threads are real) never reached its failing hipEventQuery */
+        const bool survivable = kind == FAULT_EXT_MALLOC || model_calls(kind) < at;
+        if (rc == HEVCDBK_OK && !survivable) violation("e", when + ": the entry returned HEVCDBK_OK");
+        check_planes(c, o, f, rc == HEVCDBK_OK, when.c_str());
+        check_model(when.c_str());
+        follow_up(c, ctx, rr, when.c_str());
+        for (Plane &p : f.planes) plane_free(p, ctx);
+        free_operands(ctx, o);
+        hevcdbk_destroy(ctx);
+    }
+}
+
+int cmd_check(uint32_t seed, int n)
+{
+    for (int i = 0; i < n; i++) run_case(seed * 100003u + (uint32_t)i);
+    for (auto &kv : g_tally.ran) std::printf("ran %s %d\n", kv.first.c_str(), kv.second);
+    for (auto &kv : g_tally.refused) std::printf("refused %s %d\n", kv.first.c_str(), kv.second);
+    for (auto &kv : g_tally.transports) std::printf("transport %s %d\n", kv.first.c_str(), kv.second);
+    for (auto &kv : g_tally.scheds) std::printf("scheduler %s %d\n", kv.first.c_str(), kv.second);
+    for (auto &kv : g_tally.faults) std::printf("fault %s %d\n", kv.first.c_str(), kv.second);
+    std::printf("%d violations\n", g_violations);
+    return g_violations ? 1 : 0;
+}
+
+int cmd_strips(unsigned W, unsigned H, unsigned sb, bool chroma, bool bar, bool pitched)
+{
+    Case c{};
+    c.entry = E_FILTER; c.W = W; c.H = H; c.sb = sb; c.bit_depth = sb == 2 ? 10 : 8; c.chroma = chroma; c.large_bar = bar; c.supports = true; c.pitched = pitched;
+    c.threads = 2; c.qp = 35; c.n_frames = 1; c.cf = HEVCDBK_CHROMA_420; c.sched = SCHED_EAGER;
+    g_case = describe(c);
+    Rng r{12345};
+    hevcdbk_context *ctx = new_context(c);
+    Operands o;
+    make_operands(c, ctx, r, o);
+    Frames f;
+    build_frames(c, ctx, o, r, f);
+    model_begin(model_case(c, FAULT_NONE, 0));
+    const int rc = call_entry(c, ctx, o, f, false);
+    if (rc != HEVCDBK_OK) { std::printf("error %d\n", rc); return 1; }
+    check_planes(c, o, f, true, "strips");
+    unsigned n = 0;
+    hevcdbk_last_frame_trace(ctx, nullptr, 0, &n);
+    std::vector<hevcdbk_strip_trace> tr(n);
+    hevcdbk_last_frame_trace(ctx, tr.data(), n, &n);
+    for (const hevcdbk_strip_trace &t : tr) std::printf("strip %d %u %u %zu\n", t.plane, t.row_begin, t.row_end, t.bytes);
+    for (Plane &p : f.planes) plane_free(p, ctx);
+    free_operands(ctx, o);
+    hevcdbk_destroy(ctx);
+    return g_violations ? 1 : 0;
+}
+
+} /* namespace */
+
+#ifndef SIM_SANITIZED
+/* thread creation that can be made to fail: the sanitizers intercept pthread_create themselves, so the plain builds only */
+static int g_fail_create_at = 0, g_creates = 0;
+extern "C" int pthread_create(pthread_t *t, const pthread_attr_t *a, void *(*fn)(void *), void *arg)
+{
+    using Fn = int (*)(pthread_t *, const pthread_attr_t *, void *(*)(void *), void *);
+    static Fn real = (Fn)dlsym(RTLD_NEXT, "pthread_create");
+    if (g_fail_create_at && ++g_creates == g_fail_create_at) return EAGAIN;
+    return real(t, a, fn, arg);
+}
+static int cmd_crewfail()
+{
+    Case c{};
+    c.entry = E_FILTER; c.W = 512; c.H = 1032; c.sb = 1; c.bit_depth = 8; c.large_bar = true; c.supports = true;
+    c.threads = 4; c.qp = 30; c.n_frames = 1; c.cf = HEVCDBK_CHROMA_420; c.sched = SCHED_RANDOM;
+    for (int at = 1; at <= 3; at++) {
+        g_case = describe(c) + " thread creation #" + std::to_string(at) + " fails";
+        Rng r{777};
+        hevcdbk_context *ctx = new_context(c);
+        Operands o;
+        make_operands(c, ctx, r, o);
+        Frames f;
+        build_frames(c, ctx, o, r, f);
+        model_begin(model_case(c, FAULT_NONE, 0));
+        g_creates = 0;
+        g_fail_create_at = at;
+        const int rc = call_entry(c, ctx, o, f, false);
+        g_fail_create_at = 0;
+        if (rc != HEVCDBK_ERR_NOMEM) violation("e", "returned " + std::to_string(rc) + ", not HEVCDBK_ERR_NOMEM");
+        check_planes(c, o, f, false, "thread creation fails");
+        check_model("thread creation fails");
+        model_begin(model_case(c, FAULT_NONE, 0));
+        const int rc2 = call_entry(c, ctx, o, f, false);
+        if (rc2 != HEVCDBK_OK) violation("g", "the next call returned " + std::to_string(rc2));
+        check_planes(c, o, f, true, "the call after");
+        check_model("the call after");
+        for (Plane &p : f.planes) plane_free(p, ctx);
+        free_operands(ctx, o);
+        hevcdbk_destroy(ctx);
+    }
+    std::printf("%d violations\n", g_violations);
+    return g_violations ? 1 : 0;
+}
+#endif
+
+int main(int argc, char **argv)
+{
+    std::setvbuf(stdout, nullptr, _IOLBF, 0);
+    const std::string cmd = argc > 1 ? argv[1] : "";
+    if (cmd == "check" && argc == 4) return cmd_check((uint32_t)std::strtoul(argv[2], nullptr, 10), std::atoi(argv[3]));
+    if (cmd == "strips" && argc >= 6)
+        return cmd_strips((unsigned)std::atoi(argv[2]), (unsigned)std::atoi(argv[3]), (unsigned)std::atoi(argv[4]), std::atoi(argv[5]) != 0,
+                          argc > 6 ? std::atoi(argv[6]) != 0 : true, argc > 7 && std::atoi(argv[7]) != 0);
+#ifndef SIM_SANITIZED
+    if (cmd == "crewfail") return cmd_crewfail();
+#endif
+    std::fprintf(stderr, "usage: host_frame_sim check SEED N | strips W H SB CHROMA [BAR [PITCHED]] | crewfail\n");
+    return 2;
+}
