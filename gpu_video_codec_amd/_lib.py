@@ -53,6 +53,7 @@ EXPORTS = [
     "hevcdbk_h265_deblock_sao_device_sp_fused", "hevcdbk_h265_deblock_sao_device_nv12",
     "hevcdbk_sao_stats_device", "hevcdbk_sao_pick_device", "hevcdbk_sao_stats_device_sp",
     "hevcdbk_sao_decide_device", "hevcdbk_sao_pick_device_os", "hevcdbk_sao_decide_device_os",
+    "hevcdbk_sao_decide_device_sf", "hevcdbk_sao_slice_flags_device", "hevcdbk_sao_slice_flags_workspace",
 ]
 
 # chroma_format_idc of the spec-exact mode and SAO (HEVCDBK_CHROMA_*): 4:0:0, 4:2:0, 4:2:2, 4:4:4
@@ -180,6 +181,15 @@ class SaoStats(C.Structure):
 # numpy dtype of hevcdbk_sao_decision: per CTB, what hevcdbk_sao_decide_device chose (merge: 0 own, 1 left, 2 up) and at what cost
 SAO_DECISION_DTYPE = [("delta_d", "<i8"), ("cost_luma", "<i8"), ("cost_chroma", "<i8"), ("merge", "u1"), ("flag_bits", "u1"), ("cand", "u1"),
                       ("zero", "u1", (5,))]
+
+
+# numpy dtype of hevcdbk_sao_slice_record: per slice and frame, the totals T_c of the flag pairs c = 0..3 in 128 bits and the pair chosen
+SAO_SLICE_RECORD_DTYPE = [("cost_lo", "<u8", (4,)), ("cost_hi", "<i8", (4,)), ("n_ctbs", "<u4"), ("flags", "u1"), ("zero", "u1", (3,))]
+
+
+class SaoSliceRecord(C.Structure):
+    """hevcdbk_sao_slice_record: what hevcdbk_sao_slice_flags_device found for one slice of one frame (72 bytes)"""
+    _fields_ = [("cost_lo", C.c_uint64 * 4), ("cost_hi", C.c_int64 * 4), ("n_ctbs", C.c_uint32), ("flags", C.c_uint8), ("zero", C.c_uint8 * 3)]
 
 
 class SaoDecision(C.Structure):
@@ -358,6 +368,14 @@ def lib():
         L.hevcdbk_sao_pick_device_os.argtypes = L.hevcdbk_sao_pick_device.argtypes[:9] + [C.c_uint] + L.hevcdbk_sao_pick_device.argtypes[9:]
         L.hevcdbk_sao_decide_device_os.argtypes = (L.hevcdbk_sao_decide_device.argtypes[:11] + [C.c_uint, C.c_uint] +
                                                    L.hevcdbk_sao_decide_device.argtypes[11:])
+        # the slice-level flags: given (flag bytes, n_slices, their frame stride) or chosen (n_slices, flag bytes and their frame stride,
+        # slice records and theirs, the workspace and its size), before the stream
+        os_args = L.hevcdbk_sao_decide_device_os.argtypes
+        L.hevcdbk_sao_decide_device_sf.argtypes = os_args[:-1] + [C.c_void_p, C.c_uint, C.c_size_t, C.c_void_p]
+        L.hevcdbk_sao_slice_flags_device.argtypes = os_args[:-1] + [C.c_uint, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                                                    C.c_void_p]
+        L.hevcdbk_sao_slice_flags_workspace.argtypes = [C.c_uint, C.c_uint, C.c_uint, C.c_uint]
+        L.hevcdbk_sao_slice_flags_workspace.restype = C.c_size_t
         L.hevc_deblock_sao_h265_device_planes.argtypes = [C.c_void_p, C.POINTER(DevicePlanes), C.c_uint, C.c_uint, C.POINTER(H265Params),
                                                           C.POINTER(SaoPlane), C.c_int, C.c_void_p]
         L.hevcdbk_set_host_threads.argtypes = [C.c_void_p, C.c_uint]

@@ -524,7 +524,7 @@ class Context:
                           decision_stride, n_frames=1, stats_frame_stride=0, out_frame_stride=0, decision_frame_stride=0, stats_cb_ptr=None,
                           stats_cr_ptr=None, out_cb_ptr=None, out_cr_ptr=None, bit_depth_chroma=None, lambda_q8_chroma=None,
                           slice_idx_ptr=None, tile_idx_ptr=None, idx_stride=0, idx_frame_stride=0, stream=None, log2_offset_scale=None,
-                          log2_offset_scale_chroma=None):
+                          log2_offset_scale_chroma=None, slice_flags_ptr=None, n_slices=None, slice_flags_frame_stride=0):
         """hevcdbk_sao_decide_device: per CTB own parameters, merge left or merge up (H.265 7.3.8.3) over Y, Cb and Cr at once, by the
         rule of include/hevc_deblock.h.  stats_ptr: luma's statistics; stats_cb_ptr / stats_cr_ptr (both or neither): the chroma
         components' on the same grid, with the same strides.  out_ptr / out_cb_ptr / out_cr_ptr: the final hevcdbk_sao_ctb per CTB, as
@@ -532,9 +532,22 @@ class Context:
         lambda_q8_chroma default to luma's.  slice_idx_ptr, tile_idx_ptr: uint16 per CTB, as sao_borders_device takes them; a CTB
         merges only with a neighbour of its own slice and tile.  log2_offset_scale: an integer, 0 included, calls
         hevcdbk_sao_decide_device_os with it for luma and log2_offset_scale_chroma (defaults to luma's) for Cb and Cr; None calls
-        hevcdbk_sao_decide_device."""
+        hevcdbk_sao_decide_device.  slice_flags_ptr (with n_slices): one byte per slice on the device, bit 0 slice_sao_luma_flag, bit 1
+        slice_sao_chroma_flag -- calls hevcdbk_sao_decide_device_sf, with a log2_offset_scale of 0 where none is given."""
         if log2_offset_scale is None and log2_offset_scale_chroma is not None:
             raise ValueError("log2_offset_scale_chroma needs log2_offset_scale")
+        if slice_flags_ptr is not None:
+            if n_slices is None:
+                raise ValueError("slice_flags_ptr needs n_slices")
+            kl = 0 if log2_offset_scale is None else int(log2_offset_scale)
+            kc = kl if log2_offset_scale_chroma is None else int(log2_offset_scale_chroma)
+            _chk(_lib.lib().hevcdbk_sao_decide_device_sf(self.handle, stats_ptr, stats_cb_ptr, stats_cr_ptr, stats_stride, stats_frame_stride,
+                                                         ctbs_x, ctbs_y, n_frames, bit_depth, bit_depth if bit_depth_chroma is None else bit_depth_chroma,
+                                                         kl, kc, lambda_q8, lambda_q8 if lambda_q8_chroma is None else lambda_q8_chroma,
+                                                         slice_idx_ptr, tile_idx_ptr, idx_stride, idx_frame_stride, out_ptr, out_cb_ptr, out_cr_ptr,
+                                                         out_stride, out_frame_stride, decision_ptr, decision_stride, decision_frame_stride,
+                                                         slice_flags_ptr, n_slices, slice_flags_frame_stride, stream), self.handle)
+            return
         if log2_offset_scale is not None:
             kc = log2_offset_scale if log2_offset_scale_chroma is None else log2_offset_scale_chroma
             _chk(_lib.lib().hevcdbk_sao_decide_device_os(self.handle, stats_ptr, stats_cb_ptr, stats_cr_ptr, stats_stride, stats_frame_stride,
@@ -549,6 +562,31 @@ class Context:
                                                   lambda_q8, lambda_q8 if lambda_q8_chroma is None else lambda_q8_chroma, slice_idx_ptr,
                                                   tile_idx_ptr, idx_stride, idx_frame_stride, out_ptr, out_cb_ptr, out_cr_ptr, out_stride,
                                                   out_frame_stride, decision_ptr, decision_stride, decision_frame_stride, stream), self.handle)
+
+    @staticmethod
+    def sao_slice_flags_workspace(ctbs_x, ctbs_y, n_frames=1, n_slices=1):
+        """hevcdbk_sao_slice_flags_workspace: the bytes of device memory sao_slice_flags_device needs as its workspace"""
+        return int(_lib.lib().hevcdbk_sao_slice_flags_workspace(ctbs_x, ctbs_y, n_frames, n_slices))
+
+    def sao_slice_flags_device(self, stats_ptr, stats_stride, ctbs_x, ctbs_y, bit_depth, lambda_q8, *, out_ptr, out_stride, decision_ptr,
+                               decision_stride, n_slices, slice_flags_ptr, workspace_ptr, workspace_bytes, slice_flags_frame_stride=0,
+                               slice_record_ptr=None, slice_record_frame_stride=0, n_frames=1, stats_frame_stride=0, out_frame_stride=0,
+                               decision_frame_stride=0, stats_cb_ptr=None, stats_cr_ptr=None, out_cb_ptr=None, out_cr_ptr=None,
+                               bit_depth_chroma=None, lambda_q8_chroma=None, slice_idx_ptr=None, tile_idx_ptr=None, idx_stride=0,
+                               idx_frame_stride=0, stream=None, log2_offset_scale=0, log2_offset_scale_chroma=None):
+        """hevcdbk_sao_slice_flags_device: slice_sao_luma_flag / slice_sao_chroma_flag chosen per slice (bit 0 / bit 1 of one byte per
+        slice and frame at slice_flags_ptr) and the decision of sao_decide_device under them, by the rule of include/hevc_deblock.h.
+        The operands of sao_decide_device; slice_record_ptr: one _lib.SaoSliceRecord (numpy: _lib.SAO_SLICE_RECORD_DTYPE) per slice and
+        frame, or None; workspace_ptr: device memory, 16-byte aligned, of at least sao_slice_flags_workspace(...) bytes."""
+        kc = log2_offset_scale if log2_offset_scale_chroma is None else log2_offset_scale_chroma
+        _chk(_lib.lib().hevcdbk_sao_slice_flags_device(self.handle, stats_ptr, stats_cb_ptr, stats_cr_ptr, stats_stride, stats_frame_stride, ctbs_x,
+                                                       ctbs_y, n_frames, bit_depth, bit_depth if bit_depth_chroma is None else bit_depth_chroma,
+                                                       int(log2_offset_scale), int(kc), lambda_q8,
+                                                       lambda_q8 if lambda_q8_chroma is None else lambda_q8_chroma, slice_idx_ptr, tile_idx_ptr,
+                                                       idx_stride, idx_frame_stride, out_ptr, out_cb_ptr, out_cr_ptr, out_stride, out_frame_stride,
+                                                       decision_ptr, decision_stride, decision_frame_stride, n_slices, slice_flags_ptr,
+                                                       slice_flags_frame_stride, slice_record_ptr, slice_record_frame_stride, workspace_ptr,
+                                                       workspace_bytes, stream), self.handle)
 
     def deblock_sao_device(self, planes, qp, params_ptr, params_stride, ctb_log2, *, params_frame_stride=0, keep_ptr=None,
                            keep_stride=0, keep_frame_stride=0, tc_table=None, beta_table=None, fused=_lib.FUSED_AUTO, stream=None):

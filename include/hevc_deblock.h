@@ -1024,7 +1024,8 @@ HEVCDBK_API int hevcdbk_sao_pick_device_os(hevcdbk_context *ctx, const hevcdbk_s
  *   - params_*: the final triples, one stride and one frame stride; a merged CTB holds a copy of its neighbour's.
  *     log2_sao_offset_scale stays 0 (hevcdbk_sao_decide_device_os below takes it).  decision: the record below per CTB, its own stride and frame stride (entries).  Every entry of
  *     every output grid is written, with plain stores; entries beyond the CTB columns are not touched.  The same bits every run.
- *   - The slice-level slice_sao_luma_flag / slice_sao_chroma_flag are the caller's to set, from the records summed over a slice.
+ *   - The slice-level slice_sao_luma_flag / slice_sao_chroma_flag are both taken as 1 here; hevcdbk_sao_slice_flags_device below
+ *     chooses them per slice, and hevcdbk_sao_decide_device_sf decides under given ones.
  * Refusals, in this order, every one before the context is bound and with nothing enqueued: a NULL ctx, stats_y, params_y or
  * decision, exactly one of stats_cb / stats_cr, chroma statistics without params_cb or params_cr, a bit depth outside 8..16, a lambda
  * above 2^24 -- HEVCDBK_ERR_ARG; ctbs_x or ctbs_y of 0 or above 65535 -- HEVCDBK_ERR_DIMENSIONS; then HEVCDBK_ERR_ARG for a stride
@@ -1064,7 +1065,8 @@ HEVCDBK_API int hevcdbk_sao_decide_device(hevcdbk_context *ctx, const hevcdbk_sa
  * grid -- HEVCDBK_ERR_DIMENSIONS; every further refusal of hevcdbk_sao_decide_device in its order -- HEVCDBK_ERR_ARG; and LAST a
  * legal scale above 2 (depths 13..16: offsets beyond int8_t) -- HEVCDBK_ERR_UNSUPPORTED.
  * What stays out: scales above 2 (wide offsets, on the applying side as well); a CABAC-accurate rate (bits() is the bin count of the
- * truncated unary code); the slice-level slice_sao_luma_flag / slice_sao_chroma_flag, the caller's to set; and routing
+ * truncated unary code); the slice-level slice_sao_luma_flag / slice_sao_chroma_flag, both 1 here (hevcdbk_sao_decide_device_sf and
+ * hevcdbk_sao_slice_flags_device below take and choose them); and routing
  * hevcdbk_sao_pick_device / hevcdbk_sao_decide_device to the kernels of the _os entries -- they keep their own.
  */
 HEVCDBK_API int hevcdbk_sao_decide_device_os(hevcdbk_context *ctx, const hevcdbk_sao_stats *stats_y, const hevcdbk_sao_stats *stats_cb,
@@ -1076,6 +1078,82 @@ HEVCDBK_API int hevcdbk_sao_decide_device_os(hevcdbk_context *ctx, const hevcdbk
                                              hevcdbk_sao_ctb *params_cb, hevcdbk_sao_ctb *params_cr, unsigned params_stride,
                                              size_t params_frame_stride, hevcdbk_sao_decision *decision, unsigned decision_stride,
                                              size_t decision_frame_stride, void *hip_stream);
+
+/*
+ * The decision under slice_sao_luma_flag / slice_sao_chroma_flag (7.3.6.1), which gate the sao() syntax of every CTB of a slice
+ * (7.3.8.3): the operands of hevcdbk_sao_decide_device_os, then the flags before hip_stream.
+ *   - slice_flags: DEVICE memory, one byte per slice of a frame, indexed by the value in slice_idx (slice_idx == NULL: every CTB is
+ *     in slice 0); bit 0 = slice_sao_luma_flag (L), bit 1 = slice_sao_chroma_flag (C), higher bits ignored, bit 1 ignored without
+ *     chroma statistics.  slice_flags_frame_stride: bytes between frames, 0 = shared.  A CTB whose slice_idx >= n_slices has flags 0
+ *     (the convention of hevcdbk_h265_slice_offsets_device).  slice_flags == NULL is hevcdbk_sao_decide_device_os itself: the same
+ *     launches, n_slices not looked at.
+ *   - A CTB with L = C = 0: all three parameter entries are "not applied" (six zero bytes each) and its record is all zero -- no
+ *     candidate exists, nothing is coded.  Otherwise the candidates and F are those of hevcdbk_sao_decide_device_os, but in NEW the
+ *     luma part is that entry's luma pick only if L, else "not applied" with C_y = 0 (sao_type_idx_luma is not coded), and the chroma
+ *     part is the joint Cb / Cr pick only if C, else both "not applied" with C_c = 0.  LEFT, UP, J, the tie rule and delta_d do
+ *     not change: a candidate lies in the CTB's own slice and holds "not applied" where the flag is 0, so pd gives 0 there.
+ *   - With every flag byte 3 the outputs are byte for byte those of hevcdbk_sao_decide_device_os.
+ * Refusals: those of hevcdbk_sao_decide_device_os in its order, and with the stride checks n_slices of 0 or above 65536, with the
+ * frame-stride checks a non-zero slice_flags_frame_stride below n_slices with n_frames > 1, with the extents slice_flags meeting an
+ * output -- HEVCDBK_ERR_ARG; a legal scale above 2 stays LAST.  Two small launches, asynchronous on hip_stream.
+ */
+HEVCDBK_API int hevcdbk_sao_decide_device_sf(hevcdbk_context *ctx, const hevcdbk_sao_stats *stats_y, const hevcdbk_sao_stats *stats_cb,
+                                             const hevcdbk_sao_stats *stats_cr, unsigned stats_stride, size_t stats_frame_stride,
+                                             unsigned ctbs_x, unsigned ctbs_y, unsigned n_frames, unsigned bit_depth_luma,
+                                             unsigned bit_depth_chroma, unsigned log2_offset_scale_luma, unsigned log2_offset_scale_chroma,
+                                             unsigned lambda_q8_luma, unsigned lambda_q8_chroma, const uint16_t *slice_idx,
+                                             const uint16_t *tile_idx, unsigned idx_stride, size_t idx_frame_stride, hevcdbk_sao_ctb *params_y,
+                                             hevcdbk_sao_ctb *params_cb, hevcdbk_sao_ctb *params_cr, unsigned params_stride,
+                                             size_t params_frame_stride, hevcdbk_sao_decision *decision, unsigned decision_stride,
+                                             size_t decision_frame_stride, const uint8_t *slice_flags, unsigned n_slices,
+                                             size_t slice_flags_frame_stride, void *hip_stream);
+
+/*
+ * The flags chosen per slice, and the decision under them: filter -> statistics -> this call -> SAO yields on the device everything
+ * 7.3.6.1 and 7.3.8.3 code for SAO, nothing read back.  The operands of hevcdbk_sao_decide_device_os, then n_slices, slice_flags
+ * (OUTPUT, needed: [frame][slice], slice_flags_frame_stride bytes between frames), slice_record (OUTPUT, may be NULL: the record below
+ * per slice and frame, its frame stride in entries) and the workspace: the caller's DEVICE memory, 16-byte aligned, of at least
+ * hevcdbk_sao_slice_flags_workspace() bytes (a pure host function; about 150 bytes per CTB and frame); its contents afterwards
+ * are unspecified.  The call allocates nothing and uses none of the context's scratch.
+ *   - For a frame, a slice s < n_slices and a flag pair c = L + 2 C in {1, 2, 3}: T_c(s) = the sum, over the frame's CTBs whose slice
+ *     index is s, of the chosen candidate's J in the decision of hevcdbk_sao_decide_device_sf with that slice's flags equal to c;
+ *     T_0(s) = 0.  A merge candidate lies inside one slice, so T_c(s) depends on no other slice's flags and the best pair per slice
+ *     is a minimum per slice.  The sums are exact: a CTB's J stays below 2^83, a total needs 128 bits (64 do not do: totals pass
+ *     2^70 with statistics at the int32 ends and lambdas of 2^20 and 2^24).
+ *   - The pair with the least T wins in the order 0, 1, 2, 3, on a tie the earliest -- the one that codes less.  Without chroma
+ *     statistics only pairs 0 and 1 exist (cost entries 2 and 3 of the record are 0).  A slice with no CTB in the frame gets 0.
+ *   - With chroma J is cleared of its divisions, so at lambdas of 0 every J is 0 and every slice ties to "no SAO": the degeneracy
+ *     the decision itself has at a lambda of 0.
+ *   - params_* and decision are then exactly what hevcdbk_sao_decide_device_sf writes under the chosen slice_flags.  Every entry of
+ *     every output grid is written, with plain stores.  The same bits every run.
+ * Refusals: those of hevcdbk_sao_decide_device_sf in its order (slice_flags_frame_stride, and slice_record's, below n_slices with
+ * n_frames > 1: an output cannot be shared); then HEVCDBK_ERR_ARG for a NULL slice_flags, a NULL workspace or one at an address that
+ * is no multiple of 16, workspace_bytes below the size function's value, a slice_record at an address that is no multiple of 8, and
+ * slice_flags, slice_record or the workspace meeting another output or the statistics; a legal scale above 2 --
+ * HEVCDBK_ERR_UNSUPPORTED; and LAST n_slices > 600 -- HEVCDBK_ERR_UNSUPPORTED: MaxSliceSegmentsPerPicture is 600 at the highest
+ * levels, and the cap lets the totals of a frame live in LDS.  Three small launches, asynchronous on hip_stream.
+ */
+typedef struct hevcdbk_sao_slice_record {   /* one per slice and frame, 72 bytes, DEVICE memory */
+    uint64_t cost_lo[4];  /* T_c as a 128-bit two's complement number, index = the flag pair c; entry 0 is 0 */
+    int64_t  cost_hi[4];
+    uint32_t n_ctbs;      /* CTBs of the frame with this slice index */
+    uint8_t  flags;       /* the byte written to slice_flags */
+    uint8_t  zero[3];
+} hevcdbk_sao_slice_record;
+
+HEVCDBK_API size_t hevcdbk_sao_slice_flags_workspace(unsigned ctbs_x, unsigned ctbs_y, unsigned n_frames, unsigned n_slices);
+
+HEVCDBK_API int hevcdbk_sao_slice_flags_device(hevcdbk_context *ctx, const hevcdbk_sao_stats *stats_y, const hevcdbk_sao_stats *stats_cb,
+                                               const hevcdbk_sao_stats *stats_cr, unsigned stats_stride, size_t stats_frame_stride,
+                                               unsigned ctbs_x, unsigned ctbs_y, unsigned n_frames, unsigned bit_depth_luma,
+                                               unsigned bit_depth_chroma, unsigned log2_offset_scale_luma, unsigned log2_offset_scale_chroma,
+                                               unsigned lambda_q8_luma, unsigned lambda_q8_chroma, const uint16_t *slice_idx,
+                                               const uint16_t *tile_idx, unsigned idx_stride, size_t idx_frame_stride, hevcdbk_sao_ctb *params_y,
+                                               hevcdbk_sao_ctb *params_cb, hevcdbk_sao_ctb *params_cr, unsigned params_stride,
+                                               size_t params_frame_stride, hevcdbk_sao_decision *decision, unsigned decision_stride,
+                                               size_t decision_frame_stride, unsigned n_slices, uint8_t *slice_flags,
+                                               size_t slice_flags_frame_stride, hevcdbk_sao_slice_record *slice_record,
+                                               size_t slice_record_frame_stride, void *workspace, size_t workspace_bytes, void *hip_stream);
 
 #ifdef __cplusplus
 }

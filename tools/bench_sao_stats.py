@@ -14,7 +14,11 @@ two that split org (torch, on the stream the launches use).  Every form fills th
 --decide: the decision per CTB (hevcdbk_sao_decide_device: own parameters, merge left or merge up over Y, Cb and Cr) for 64 frames of
 3840x2160 at 64- and 16-sample CTBs, taking turns with the luma statistics pass and the two pick launches on the same batch -- and
 with the _os entries (log2_sao_offset_scale, the candidates compared by a wave's lanes together) at a scale of 0, where they write the
-same bytes."""
+same bytes.
+
+--slice-flags: hevcdbk_sao_slice_flags_device (slice_sao_luma_flag / slice_sao_chroma_flag chosen per slice, and the decision under
+them) against hevcdbk_sao_decide_device_os on the same arrays, taking turns, at 64- and 16-sample CTBs with the frame in 8 and in 135
+slices of whole CTB rows.  The yardstick is THREE _os decisions: what a caller had to run before summing on the host."""
 import argparse, json, os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -211,8 +215,82 @@ def decide(a):
                 fh.write(json.dumps(line) + "\n")
 
 
+def slice_flags(a):
+    """--slice-flags: one JSON line per (CTB size, slices per frame); the statistics arrays are those of --decide"""
+    w, h, n, bd, lam = a.width, a.height, a.frames, 8, 1024
+    ctx = deblock.Context(0)
+    b = deblock.DeviceBatch(ctx, w, h, n, bit_depth=bd, per_frame_bs=False)
+    dorg = ctx.alloc(b.frame_bytes * (n + 2))
+    rec, org = frames_of("blocky", w, h, bd, np.random.default_rng(11))
+    for f in range(n + 2):
+        if f < n:
+            b.upload_frame(f, rec[f % 4])
+        dorg.upload(org[(f + 1) % 4], f * b.frame_bytes)
+    p = b.planes()
+    lines = []
+    for L in [int(x) for x in a.ctbs.split(",")]:
+        rows, cols = (h + (1 << L) - 1) >> L, (w + (1 << L) - 1) >> L
+        g = rows * cols
+        dst = [ctx.alloc(g * n * 384) for _ in range(3)]
+        dprm = [ctx.alloc(g * n * 6) for _ in range(3)]
+        ddec = ctx.alloc(g * n * 32)
+        for c in range(3):
+            ctx.sao_stats_device(p, dorg.ptr + c * b.frame_bytes, L, out_ptr=dst[c].ptr, out_stride=cols, out_frame_stride=g)
+        need = ctx.sao_slice_flags_workspace(cols, rows, n, 600)
+        dws = ctx.alloc(need)
+        for n_slices in [int(x) for x in a.slices.split(",")]:
+            sl = (np.arange(rows)[:, None] * min(n_slices, rows) // rows + np.zeros((1, cols), np.int64)).astype(np.uint16)
+            dsl = ctx.alloc(sl.nbytes)
+            dsl.upload(sl.view(np.uint8).ravel())
+            dfl, dsr = ctx.alloc(n * n_slices), ctx.alloc(n * n_slices * 72)
+            common = dict(out_ptr=dprm[0].ptr, out_stride=cols, decision_ptr=ddec.ptr, decision_stride=cols, n_frames=n, stats_frame_stride=g,
+                          out_frame_stride=g, decision_frame_stride=g, stats_cb_ptr=dst[1].ptr, stats_cr_ptr=dst[2].ptr, out_cb_ptr=dprm[1].ptr,
+                          out_cr_ptr=dprm[2].ptr, slice_idx_ptr=dsl.ptr, idx_stride=cols, idx_frame_stride=0)
+
+            def dec_os():
+                ctx.sao_decide_device(dst[0].ptr, cols, cols, rows, bd, lam, log2_offset_scale=0, **common)
+
+            def three():
+                for _ in range(3):
+                    dec_os()
+
+            def choose():
+                ctx.sao_slice_flags_device(dst[0].ptr, cols, cols, rows, bd, lam, n_slices=n_slices, slice_flags_ptr=dfl.ptr,
+                                           slice_flags_frame_stride=n_slices, slice_record_ptr=dsr.ptr, slice_record_frame_stride=n_slices,
+                                           workspace_ptr=dws.ptr, workspace_bytes=need, **common)
+            forms = {"decide_os": dec_os, "three_decide_os": three, "slice_flags": choose}
+            timed(ctx, dec_os, 30, 0)   # settle the clocks
+            ms = {k: [] for k in forms}
+            for _ in range(a.rounds):
+                for k, fn in forms.items():
+                    ms[k].append(timed(ctx, fn, a.steps, 5))
+            med = {k: float(np.median(v)) for k, v in ms.items()}
+            spread = {k: float(max(v) - min(v)) for k, v in ms.items()}
+            choose()
+            ctx.synchronize()
+            chosen = np.bincount(dfl.download(n * n_slices), minlength=4)
+            line = {"stage": "sao_slice_flags", "workload": "%dx%d %d-bit x %d, %d-sample CTBs, Y + Cb + Cr on one grid, %d slices per frame"
+                    % (w, h, bd, n, 1 << L, n_slices), "ctbs": g * n, "lambda_q8": lam, "workspace_bytes": need, "ms_per_call": med, "rounds_ms": ms,
+                    "spread_ms": spread, "slice_flags_over_decide_os": med["slice_flags"] / med["decide_os"],
+                    "slice_flags_over_three_decide_os": med["slice_flags"] / med["three_decide_os"],
+                    "slice_flags_slower_than_three_decide_os": bool(med["slice_flags"] > med["three_decide_os"]),
+                    "slices_per_pair_0_1_2_3": [int(x) for x in chosen]}
+            lines.append(line)
+            print(json.dumps(line), flush=True)
+            for d in (dsl, dfl, dsr):
+                d.free()
+        for d in dst + dprm + [ddec, dws]:
+            d.free()
+    if a.out:
+        with open(a.out, "a") as fh:
+            for line in lines:
+                fh.write(json.dumps(line) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--slice-flags", action="store_true", help="the slice-level flags chosen on the device against one and three _os decisions")
+    ap.add_argument("--slices", default="8,135", help="--slice-flags: slices per frame (whole CTB rows)")
     ap.add_argument("--decide", action="store_true", help="the decision per CTB against the luma statistics pass and the two pick launches")
     ap.add_argument("--ctbs", default="6,4", help="--decide: log2 of the CTB sizes")
     ap.add_argument("--semi-planar", action="store_true", help="the pair-plane entry against two planar launches, with and without the split copies")
@@ -229,6 +307,8 @@ def main():
     a = ap.parse_args()
     if a.decide:
         return decide(a)
+    if a.slice_flags:
+        return slice_flags(a)
     if a.semi_planar:
         if a.contents == "flat,blocky,noise":
             a.contents = "noise,flat"
