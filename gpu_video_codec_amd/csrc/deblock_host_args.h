@@ -162,24 +162,39 @@ inline int tmp_planes(hevcdbk_context *ctx, const hevcdbk_device_planes *p, hipS
     second.src = ctx->dev_tmp.p;
     return HEVCDBK_OK;
 }
-inline int tmp_done(hevcdbk_context *ctx, hipStream_t s)
+/* the fence of one of the context's scratch buffers (dev_tmp / tmp_ev / tmp_used here, dev_sao in deblock_host_h265.cpp): an event
+ * behind the last launch on s that touches the buffer.  Where the record itself fails there is nothing the next user could wait
+ * for, so the stream is drained instead: the buffer is never left with work queued that its next user is not ordered behind.
+ * failing: the call is returning an error already, and hevcdbk_last_error keeps speaking of that first failure */
+inline int fence_scratch(hevcdbk_context *ctx, hipEvent_t ev, bool &used, hipStream_t s, bool failing = false)
 {
-    HIP_TRY(ctx, hipEventRecord(ctx->tmp_ev, s));
-    ctx->tmp_used = true;
+    const hipError_t e = hipEventRecord(ev, s);
+    if (e != hipSuccess) {
+        if (!failing) (void)hip_ok(ctx, e, "hipEventRecord(scratch fence)");
+        (void)hipStreamSynchronize(s);
+        (void)hipGetLastError();
+        return HEVCDBK_ERR_HIP;
+    }
+    used = true;
     return HEVCDBK_OK;
 }
+inline int tmp_done(hevcdbk_context *ctx, hipStream_t s, bool failing = false) { return fence_scratch(ctx, ctx->tmp_ev, ctx->tmp_used, s, failing); }
 
 /* the two-launch form itself: deblock(first) filters the plane into the scratch plane, sao() -- its source now the scratch plane --
- * reads it from there; fenced for the next user */
+ * reads it from there; fenced for the next user whatever the launches returned: a deblocking launch that was enqueued writes the
+ * scratch plane even when the SAO launch behind it failed, and the next call may come on another stream */
 template <class Deblock, class Sao>
 int through_scratch(hevcdbk_context *ctx, const hevcdbk_device_planes *p, hipStream_t s, DbkSaoArgs &sa, Deblock deblock, Sao sao)
 {
     hevcdbk_device_planes first, second;
     if (int rc = tmp_planes(ctx, p, s, first, second)) return rc;
-    if (int rc = deblock(first)) return rc;
-    sa.src = (const uint8_t *)second.src;
-    if (int rc = sao()) return rc;
-    return tmp_done(ctx, s);
+    int rc = deblock(first);
+    if (rc == HEVCDBK_OK) {
+        sa.src = (const uint8_t *)second.src;
+        rc = sao();
+    }
+    const int rc2 = tmp_done(ctx, s, rc != HEVCDBK_OK);
+    return rc ? rc : rc2;
 }
 
 /* the fused kernel takes plane p (every chroma format, one QP or a QP map: the conditions of deblock_sao_plane_h265) */

@@ -336,7 +336,8 @@ int deblock_sao_plane(hevcdbk_context *ctx, const hevcdbk_device_planes *p, unsi
 
 /* 4:2:2 chroma planes (ctb_log2_h[i] = sa[i].ctb_log2 + 1): their SAO parameters rewritten as those of square CTBs into the
  * context's scratch (dbk_launch_sao_rows_x2), so that every kernel after this sees square CTBs.  Like dev_tmp, the scratch is
- * fenced by an event: the next user waits for the last launch that read it (sao_done) */
+ * fenced by an event: the next user waits for the last launch that touched it (sao_done), whatever that launch and the ones
+ * behind it returned */
 /* the bytes of a 4:2:2 chroma plane's rows of CTBs, doubled like the parameters (dbk_launch_sao_nox_rows_x2) */
 size_t nox_x2_bytes(const DbkSaoArgs &a, const DbkSaoNox &nx)
 {
@@ -344,7 +345,10 @@ size_t nox_x2_bytes(const DbkSaoArgs &a, const DbkSaoNox &nx)
     return cols * rows * (nx.frame_stride ? (size_t)a.n_frames : 1);
 }
 
-/* nx (may be NULL): the planes' slice / tile boundary bytes, rewritten with the parameters into the same scratch */
+int sao_done(hevcdbk_context *ctx, hipStream_t s, bool failing = false);
+
+/* nx (may be NULL): the planes' slice / tile boundary bytes, rewritten with the parameters into the same scratch.  A launch that
+ * fails after another was enqueued leaves the scratch fenced: the enqueued one writes it */
 int sao_square_params(hevcdbk_context *ctx, DbkSaoArgs *sa, const unsigned *ctb_log2_h, unsigned n, hipStream_t s, DbkSaoNox *nx = nullptr)
 {
     size_t entries = 0, nox_bytes = 0;
@@ -367,21 +371,25 @@ int sao_square_params(hevcdbk_context *ctx, DbkSaoArgs *sa, const unsigned *ctb_
         if (ctb_log2_h[i] != (unsigned)sa[i].ctb_log2) {
             if (nx) {
                 const size_t nb = nox_x2_bytes(sa[i], nx[i]);
-                if (!hip_ok(ctx, dbk_launch_sao_nox_rows_x2(sa[i], nx[i], nox_dst, s), "SAO border launch")) return HEVCDBK_ERR_HIP;
+                if (!hip_ok(ctx, dbk_launch_sao_nox_rows_x2(sa[i], nx[i], nox_dst, s), "SAO border launch")) {
+                    (void)sao_done(ctx, s, true);
+                    return HEVCDBK_ERR_HIP;
+                }
                 nox_dst += nb;
             }
             const size_t k = dbk_sao_rows_x2_entries(sa[i]);
-            if (!hip_ok(ctx, dbk_launch_sao_rows_x2(sa[i], dst, s), "SAO parameter launch")) return HEVCDBK_ERR_HIP;
+            if (!hip_ok(ctx, dbk_launch_sao_rows_x2(sa[i], dst, s), "SAO parameter launch")) {
+                (void)sao_done(ctx, s, true);
+                return HEVCDBK_ERR_HIP;
+            }
             dst += k;
         }
     return HEVCDBK_OK;
 }
-int sao_done(hevcdbk_context *ctx, hipStream_t s)
+int sao_done(hevcdbk_context *ctx, hipStream_t s, bool failing)
 {
     if (!ctx->sao_ev) return HEVCDBK_OK; /* no 4:2:2 plane ever used the scratch */
-    HIP_TRY(ctx, hipEventRecord(ctx->sao_ev, s));
-    ctx->sao_used = true;
-    return HEVCDBK_OK;
+    return fence_scratch(ctx, ctx->sao_ev, ctx->sao_used, s, failing);
 }
 
 /* what a deblocking + SAO call says about its picture, whichever generation of the C ABI it came through */
@@ -471,9 +479,10 @@ int sao_pass(hevcdbk_context *ctx, const hevcdbk_device_planes *p, const hevcdbk
     if (int rc = bind(ctx)) return rc;
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->compute;
     if (int rc = sao_square_params(ctx, &a, &sao.ctb_log2_h, 1, s, nxp)) return rc;
-    /* (a failed launch leaves the parameter launch unfenced: as the _cf generation wrote it, before the deblocking + SAO entries fenced "whatever followed") */
-    if (!hip_ok(ctx, g4 ? dbk_launch_sao_g4(a, (int)p->sample_bytes, s, nxp) : dbk_launch_sao(a, (int)p->sample_bytes, s, nxp), "SAO launch")) return HEVCDBK_ERR_HIP;
-    return sao.ctb_log2_h != sao.ctb_log2_w ? sao_done(ctx, s) : HEVCDBK_OK;
+    const int rc = hip_ok(ctx, g4 ? dbk_launch_sao_g4(a, (int)p->sample_bytes, s, nxp) : dbk_launch_sao(a, (int)p->sample_bytes, s, nxp), "SAO launch") ? HEVCDBK_OK : HEVCDBK_ERR_HIP;
+    if (sao.ctb_log2_h != sao.ctb_log2_w)
+        if (int rc2 = sao_done(ctx, s, rc != HEVCDBK_OK)) return rc ? rc : rc2; /* the parameter launch is fenced whatever followed it */
+    return rc;
 }
 
 /* the one-plane deblocking + SAO entries (pic.g4: the entry takes a g4 plane) */
@@ -491,7 +500,7 @@ int deblock_sao_one(hevcdbk_context *ctx, Picture pic, const hevcdbk_device_plan
     if (int rc = sao_square_params(ctx, &sa, &sao.ctb_log2_h, 1, s, nxp)) return rc;
     const int rc = deblock_sao_plane_h265(ctx, pic, p, c_idx, h, sa, sl, nxp, s);
     if (sao.ctb_log2_h != sao.ctb_log2_w)
-        if (int rc2 = sao_done(ctx, s)) return rc ? rc : rc2; /* the parameter launch is fenced whatever followed it */
+        if (int rc2 = sao_done(ctx, s, rc != HEVCDBK_OK)) return rc ? rc : rc2; /* the parameter launch is fenced whatever followed it */
     return rc;
 }
 
@@ -552,7 +561,7 @@ int deblock_sao_planes(hevcdbk_context *ctx, Picture pic, const hevcdbk_device_p
     for (unsigned i = 0; !one && i < n_planes && rc == HEVCDBK_OK; i++) /* each plane the kernels of its own generation */
         rc = deblock_sao_plane_h265(ctx, pic, &planes[i], (int)i, h[i], sa[i], sl[i], nxp ? &nxp[i] : nullptr, s);
     if (rect)
-        if (int rc2 = sao_done(ctx, s)) return rc ? rc : rc2; /* the parameter launch is fenced whatever followed it */
+        if (int rc2 = sao_done(ctx, s, rc != HEVCDBK_OK)) return rc ? rc : rc2; /* the parameter launch is fenced whatever followed it */
     return rc;
 }
 

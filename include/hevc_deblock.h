@@ -472,7 +472,11 @@ HEVCDBK_API int hevc_sao_filter_device(hevcdbk_context *ctx, const hevcdbk_devic
  * by the context.  `fused`: HEVCDBK_FUSED_AUTO picks, _OFF forces the two launches (same bytes; for A/B runs), _ON returns
  * HEVCDBK_ERR_UNSUPPORTED where the fused kernel does not apply.  The scratch plane of the two-launch form belongs to the
  * context and is reused by the next such call; its reuse is fenced by an event, so calls that hand in different streams are
- * ordered on it (like every entry point, a context serves one host thread at a time).  Parity: the deblocking stage as for
+ * ordered on it (like every entry point, a context serves one host thread at a time).  The fence holds after a call that
+ * returned HEVCDBK_ERR_HIP as well: whatever that call had enqueued on its stream, the next call on any stream is ordered
+ * behind it (where the event itself could not be recorded, the failing call waits for its stream instead).  A call blocks
+ * the host only when the scratch has to grow: it then waits for the previous user before the buffer is freed.  The same
+ * holds for the context's second scratch, the 4:2:2 SAO parameters of the _cf and later entries.  Parity: the deblocking stage as for
  * its own entry points; SAO against oracle/h265_oracle.c only ("parity unpinned").
  */
 #define HEVCDBK_FUSED_AUTO 0

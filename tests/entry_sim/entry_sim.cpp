@@ -351,16 +351,13 @@ Result run(const Entry &e, const Ops &o, long id, bool borders, bool offsets, bo
             if (refusal(rc))
                 for (size_t at = 0; at < t.size(); at = t.find('\n', at) + 1)
                     if (t.compare(at, 13, "hipSetDevice\n") != 0) { violation("work after a refusal", e.name, id, t); break; }
-            const size_t x2 = t.rfind("sao_rows_x2:");
-            /* the SAO pass entries return at once when their own launch fails, as they did before the deblocking + SAO entries
-             * learnt to fence "whatever followed": asked of them only when the call succeeded */
-            if (x2 != std::string::npos && (rc == HEVCDBK_OK || !std::strstr(e.name, "sao_filter"))) {
-                bool failed = false;
-                for (size_t at = t.find("rows_x2:"); at != std::string::npos; at = t.find("rows_x2:", at + 1))
-                    failed = failed || t.compare(t.find('\n', at) - 8, 8, " -> FAIL") == 0;
-                if (!failed && t.find("hipEventRecord " + sao_ev + " ", x2) == std::string::npos)
-                    violation("no fence after the parameter launch", e.name, id, t);
-            }
+            /* the last launch into the scratch that was enqueued (parameters or border bytes) is followed by the record, whether the
+             * launches after it -- another one into the scratch, deblocking, SAO -- succeeded or not, in every entry */
+            size_t x2 = std::string::npos;
+            for (size_t at = t.find("rows_x2:"); at != std::string::npos; at = t.find("rows_x2:", at + 1))
+                if (t.compare(t.find('\n', at) - 8, 8, " -> FAIL") != 0) x2 = at;
+            if (x2 != std::string::npos && t.find("hipEventRecord " + sao_ev + " ", x2) == std::string::npos)
+                violation("no fence after the parameter launch", e.name, id, t);
         }
         res.launched = res.launched || t.find(": src=") != std::string::npos || t.find(": s.src=") != std::string::npos || t.find("h265_bs:") != std::string::npos;
         for (char &ch : t)

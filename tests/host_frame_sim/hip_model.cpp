@@ -1,7 +1,8 @@
 /*
- * hip_model.cpp -- the model of hip_model.h: the 31 HIP symbols the two host sources use, and the kernel launchers and predicates
+ * hip_model.cpp -- the model of hip_model.h: the 31 HIP symbols the host sources use, and the kernel launchers and predicates
  * of deblock_kernels.h.  Only the thread inside a host entry makes HIP calls (the staging crew never does), so the model needs no
- * lock of its own.  A launcher enqueues a marker operation; see run_marker() for what it does when it executes.
+ * lock of its own.  A launcher enqueues a marker operation; see run_marker(), run_sao(), run_fused() and run_derive() for what
+ * they do when they execute.
  */
 #include <hip/hip_runtime_api.h>
 
@@ -34,8 +35,17 @@ struct Alloc {
 struct Region { char *primary, *alias; size_t n; int fd; };
 
 struct Event {
-    uint64_t recorded = 0, completed = 0; /* generation of the last record enqueued / executed */
+    uint64_t recorded = 0, completed = 0; /* generation of the last record enqueued / the latest one executed */
     int not_ready_left = 0;
+    /* per record: a wait is for ONE record, and the records of an event that several streams record need not execute in order */
+    std::vector<bool> done{true};
+    bool is_done(uint64_t gen) const { return gen < done.size() && done[gen]; }
+    void mark(uint64_t gen)
+    {
+        if (done.size() <= gen) done.resize(gen + 1, false);
+        done[gen] = true;
+        if (completed < gen) completed = gen;
+    }
 };
 struct Op {
     enum { WORK, RECORD, WAIT } kind;
@@ -57,6 +67,7 @@ struct Model {
     std::vector<std::string> violations;
     std::vector<ModelWrite> writes;
     int sync_pageable = 0;
+    int blocking = 0, frees = 0;
     int depth = 0;
 } M;
 
@@ -105,13 +116,13 @@ bool host_locked(const void *p, size_t n)
     return false;
 }
 
-bool runnable(const Stream &s) { return !s.q.empty() && !(s.q.front().kind == Op::WAIT && s.q.front().ev->completed < s.q.front().gen); }
+bool runnable(const Stream &s) { return !s.q.empty() && !(s.q.front().kind == Op::WAIT && !s.q.front().ev->is_done(s.q.front().gen)); }
 void run_head(Stream &s)
 {
     Op op = std::move(s.q.front());
     s.q.pop_front();
     if (op.kind == Op::WORK) op.fn();
-    else if (op.kind == Op::RECORD && op.ev->completed < op.gen) op.ev->completed = op.gen;
+    else if (op.kind == Op::RECORD) op.ev->mark(op.gen);
 }
 void force_event(Event *e, uint64_t gen);
 /* run the stream's operations up to and including its n-th */
@@ -131,15 +142,17 @@ void force_ops(Stream &s, size_t n)
 }
 void force_event(Event *e, uint64_t gen)
 {
-    if (e->completed >= gen) return;
+    if (e->is_done(gen)) return;
     for (Stream *s : M.streams)
         for (size_t i = 0; i < s->q.size(); i++)
-            if (s->q[i].kind == Op::RECORD && s->q[i].ev == e && s->q[i].gen >= gen) {
+            /* the record the wait was made for, not a later one: an event the caller records on several streams may have a later
+             * record queued on the very stream that waits */
+            if (s->q[i].kind == Op::RECORD && s->q[i].ev == e && s->q[i].gen == gen) {
                 force_ops(*s, i + 1);
                 return;
             }
     violation("an event wait whose record is on no stream");
-    e->completed = gen;
+    e->mark(gen);
 }
 void run_all_runnable()
 {
@@ -237,24 +250,41 @@ struct Marker {
     uint64_t h0; /* the scalar operands, folded when the launch was made */
     size_t map_rows;
     std::string name;
+    DbkSlOffs sl = {nullptr, 0, 0, 4, 0u}; /* the per-slice operand of the later generations: n_bytes 0 = none */
+    int row_mul = 1;                       /* 2: a plane of Cb / Cr pairs, whose rows hold 2 * plane_w samples */
 };
-void run_marker(const Marker &m)
+/* every operand array in full, as it is NOW */
+bool marker_hash(const Marker &m, uint64_t &h)
 {
     const DbkArgs &a = m.a;
-    /* every operand array in full, as it is NOW */
-    uint64_t h = m.h0;
-    if (!dev_ok(a.vert_bs, (size_t)a.n_vert, m.name + " vert bS") || !dev_ok(a.hor_bs, (size_t)a.n_hor, m.name + " hor bS")) return;
+    h = m.h0;
+    if (!dev_ok(a.vert_bs, (size_t)a.n_vert, m.name + " vert bS") || !dev_ok(a.hor_bs, (size_t)a.n_hor, m.name + " hor bS")) return false;
     h = model_fold(h, a.vert_bs, (size_t)a.n_vert);
     h = model_fold(h, a.hor_bs, (size_t)a.n_hor);
     if (a.qp_map) {
         const size_t n = m.map_rows * (size_t)a.map_stride;
-        if (!dev_ok(a.qp_map, n, m.name + " QP map")) return;
+        if (!dev_ok(a.qp_map, n, m.name + " QP map")) return false;
         h = model_fold(h, a.qp_map, n);
     }
+    if (m.sl.n_bytes) {
+        const int n = m.sl.frame_stride ? (a.n_frames > 0 ? a.n_frames : 1) : 1;
+        for (int f = 0; f < n; f++) {
+            const int8_t *p = m.sl.offs + (size_t)f * (size_t)m.sl.frame_stride;
+            if (!dev_ok(p, m.sl.n_bytes, m.name + " per-slice offsets")) return false;
+            h = model_fold(h, p, m.sl.n_bytes);
+        }
+    }
+    return true;
+}
+void run_marker(const Marker &m)
+{
+    const DbkArgs &a = m.a;
+    uint64_t h;
+    if (!marker_hash(m, h)) return;
     const int b0 = a.by_begin, b1 = a.by_count ? a.by_begin + a.by_count : a.nby;
     const long long y0 = b0 <= 0 ? 0 : 8ll * b0 - 4, y1 = 8ll * b1 - 4 > a.plane_h ? a.plane_h : 8ll * b1 - 4;
     if (y1 <= y0) return;
-    const size_t rb = (size_t)a.plane_w * (size_t)m.sb;
+    const size_t rb = (size_t)a.plane_w * (size_t)m.sb * (size_t)m.row_mul;
     const int frames = a.n_frames > 0 ? a.n_frames : 1;
     /* the kernels move words of four samples: bases, pitch and frame stride are multiples of that, whatever the transport */
     const size_t word = 4 * (size_t)m.sb;
@@ -336,13 +366,108 @@ Marker h265_marker(const DbkH265Args &p, int sb, bool chroma, int cf, const char
 {
     return {p.base, sb, chroma ? 1 : 0, fold_h265(p), map_rows_of(p.base, chroma && cf == 1 ? 2 : 1), name};
 }
-hipError_t not_modelled() { violation("a launcher the host-frame operators do not use was called"); return hipErrorNotSupported; }
+Marker later_marker(const DbkH265Args &p, const DbkSlOffs &sl, int sb, bool chroma, int cf, const char *name)
+{
+    DbkH265Args q = p;
+    if (sl.n_bytes) q.tc_off = q.beta_off = 0; /* with the operand the call's own pair is not read (_sl) or is zero (_g4, _sp) */
+    Marker m = h265_marker(q, sb, chroma, cf, name);
+    m.sl = sl;
+    return m;
+}
+/* the plane of pairs: the odd samples' QP offset is a scalar operand of its own */
+Marker sp_marker(const DbkH265Args &p, const DbkSlOffs &sl, int cr_qp_offset, int sb, const char *name)
+{
+    Marker m = later_marker(p, sl, sb, true, 1, name);
+    m.h0 = model_fold_int(m.h0, cr_qp_offset);
+    m.row_mul = 2;
+    return m;
+}
+
+/* ---- the SAO operation: dst = src ^ model_m(hash of the scalar operands and of every operand array as it is when the operation runs) ---- */
+
+struct SaoOp {
+    DbkSaoArgs a;
+    const DbkSaoCtb *cr; /* the odd samples' grid of a plane of pairs, else NULL */
+    bool has_nx;
+    DbkSaoNox nx;
+    int sb, row_mul;
+    std::string name;
+};
+SaoOp sao_op(const DbkSaoArgs &a, const DbkSaoCtb *cr, const DbkSaoNox *nx, int sb, int row_mul, const char *name)
+{
+    return {a, cr, nx != nullptr && nx->nox != nullptr, nx ? *nx : DbkSaoNox{nullptr, 0, 0}, sb, row_mul, name};
+}
+bool sao_hash(const SaoOp &o, uint64_t &h)
+{
+    const DbkSaoArgs &a = o.a;
+    h = model_sao_hash0(a.max_v, a.band_shift, a.ctb_log2);
+    const size_t frames = a.n_frames > 0 ? (size_t)a.n_frames : 1;
+    const size_t cols = (size_t)((a.plane_w + (1 << a.ctb_log2) - 1) >> a.ctb_log2), rows = (size_t)((a.plane_h + (1 << a.ctb_log2) - 1) >> a.ctb_log2);
+    /* a grid of every frame (one, where the frames share it), bounds per frame from the strides */
+    auto grid = [&](const void *base, size_t stride, size_t frame_stride, size_t row, size_t n_rows, const char *what) {
+        for (size_t f = 0; f < (frame_stride ? frames : 1); f++) {
+            const uint8_t *p = (const uint8_t *)base + f * frame_stride;
+            if (!dev_ok(p, span(stride, row, n_rows), o.name + " " + what)) return false;
+            h = model_fold_rows(h, p, stride, row, n_rows);
+        }
+        return true;
+    };
+    const size_t e = sizeof(DbkSaoCtb);
+    if (!grid(a.params, (size_t)a.params_stride * e, (size_t)a.params_frame_stride * e, cols * e, rows, "parameters")) return false;
+    if (o.cr && !grid(o.cr, (size_t)a.params_stride * e, (size_t)a.params_frame_stride * e, cols * e, rows, "parameters (Cr)")) return false;
+    if (a.keep && !grid(a.keep, (size_t)a.keep_stride, (size_t)a.keep_frame_stride, (size_t)(a.plane_w + 7) / 8, (size_t)(a.plane_h + 7) / 8, "keep map")) return false;
+    if (o.has_nx && !grid(o.nx.nox, (size_t)o.nx.stride, (size_t)o.nx.frame_stride, cols, rows, "border bytes")) return false;
+    return true;
+}
+/* every row of every frame, src -> dst: the bytes f(y, x) xor-ed in */
+template <class F>
+void write_planes(const std::string &name, const uint8_t *src, uint8_t *dst, long long pitch, long long frame_stride, int n_frames, int plane_h, size_t rb,
+                  int sb, F f)
+{
+    const size_t word = 4 * (size_t)sb;
+    if ((uintptr_t)src % word || (uintptr_t)dst % word || (size_t)pitch % word || (size_t)frame_stride % word) {
+        violation(name + " src " + hex(src) + " dst " + hex(dst) + " pitch " + std::to_string(pitch) + ": not aligned to " + std::to_string(word) + " bytes (four samples)");
+        return;
+    }
+    const int frames = n_frames > 0 ? n_frames : 1;
+    const size_t bytes = span((size_t)pitch, rb, (size_t)plane_h);
+    for (int fr = 0; fr < frames; fr++) {
+        const uint8_t *s = src + (size_t)fr * (size_t)frame_stride;
+        uint8_t *d = dst + (size_t)fr * (size_t)frame_stride;
+        if (!dev_ok(s, bytes, name + " src " + hex(s)) || !dev_ok(d, bytes, name + " dst " + hex(d))) return;
+        for (int y = 0; y < plane_h; y++)
+            for (size_t x = 0; x < rb; x++) d[(size_t)y * (size_t)pitch + x] = (uint8_t)(s[(size_t)y * (size_t)pitch + x] ^ f((unsigned)y, (unsigned)x));
+    }
+}
+void run_sao(const SaoOp &o)
+{
+    uint64_t h;
+    if (!sao_hash(o, h)) return;
+    const DbkSaoArgs &a = o.a;
+    write_planes(o.name, a.src, a.dst, a.pitch, a.frame_stride, a.n_frames, a.plane_h, (size_t)a.plane_w * (size_t)o.sb * (size_t)o.row_mul, o.sb,
+                 [h](unsigned y, unsigned x) { return model_m(h, kModelSaoPlane, y, x); });
+}
+/* deblocking + SAO in one kernel: ONE operation, both hashes, the deblocking operands' src to the SAO operands' dst */
+struct Fused { Marker m; SaoOp s; };
+void run_fused(const Fused &f)
+{
+    uint64_t hd, hs;
+    if (!marker_hash(f.m, hd) || !sao_hash(f.s, hs)) return;
+    const DbkSaoArgs &a = f.s.a;
+    const int chroma = f.m.chroma;
+    write_planes(f.s.name, f.m.a.src, a.dst, a.pitch, a.frame_stride, a.n_frames, a.plane_h, (size_t)a.plane_w * (size_t)f.s.sb * (size_t)f.s.row_mul, f.s.sb,
+                 [hd, hs, chroma](unsigned y, unsigned x) { return (uint8_t)(model_m(hd, chroma, y, x) ^ model_m(hs, kModelSaoPlane, y, x)); });
+}
+hipError_t launch_fused(hipStream_t s, const char *name, std::vector<Fused> fs)
+{
+    return launch(s, name, [fs] { for (const Fused &f : fs) run_fused(f); });
+}
 
 /* launchers that produce operands: a hash of their inputs over their whole output */
 struct Derive { std::vector<std::pair<const void *, size_t>> in; std::vector<std::pair<uint8_t *, size_t>> out; std::string name; };
 void run_derive(const Derive &d)
 {
-    uint64_t h = kModelHash0 ^ 0xb5;
+    uint64_t h = kModelDeriveHash0;
     for (auto &i : d.in) {
         if (!dev_ok(i.first, i.second, d.name + " input")) return;
         h = model_fold(h, i.first, i.second);
@@ -374,8 +499,12 @@ void model_begin(const ModelCase &c)
     M.violations.clear();
     M.writes.clear();
     M.sync_pageable = 0;
+    M.blocking = M.frees = 0;
     M.depth = 0;
 }
+int model_blocking_calls() { return M.blocking; }
+int model_device_frees() { return M.frees; }
+void model_set_supports(bool supports) { M.c.supports = supports; }
 int model_calls(int kind) { return M.calls[kind]; }
 const std::vector<std::string> &model_violations() { return M.violations; }
 int model_sync_pageable_copies() { return M.sync_pageable; }
@@ -432,7 +561,7 @@ hipError_t hipDeviceGetAttribute(int *v, hipDeviceAttribute_t at, int)
     *v = at == hipDeviceAttributeIsLargeBar ? (M.c.large_bar ? 1 : 0) : 256;
     return hipSuccess;
 }
-hipError_t hipDeviceSynchronize(void) { model_drain(); return hipSuccess; }
+hipError_t hipDeviceSynchronize(void) { M.blocking++; model_drain(); return hipSuccess; }
 hipError_t hipDeviceGetPCIBusId(char *buf, int len, int) { if (len > 0) buf[0] = 0; return hipErrorInvalidDevice; }
 hipError_t hipGetDeviceProperties(hipDeviceProp_t *p, int) { std::memset(p, 0, sizeof(*p)); return hipSuccess; }
 
@@ -490,7 +619,7 @@ static hipError_t release(void *p, bool host)
     }
     return hipErrorInvalidValue;
 }
-hipError_t hipFree(void *p) { return release(p, false); }
+hipError_t hipFree(void *p) { if (p) M.frees++; return release(p, false); }
 hipError_t hipHostFree(void *p) { return release(p, true); }
 hipError_t hipHostRegister(void *p, size_t bytes, unsigned)
 {
@@ -567,6 +696,7 @@ hipError_t hipStreamDestroy(hipStream_t hs)
 }
 hipError_t hipStreamSynchronize(hipStream_t hs)
 {
+    M.blocking++;
     tick();
     Stream *s = stream_of(hs);
     if (!s) return hipErrorInvalidHandle;
@@ -623,6 +753,7 @@ hipError_t hipEventRecord(hipEvent_t he, hipStream_t hs)
 }
 hipError_t hipEventSynchronize(hipEvent_t he)
 {
+    M.blocking++;
     tick();
     Event *e = event_of(he);
     if (!e) return hipErrorInvalidHandle;
@@ -659,7 +790,13 @@ bool dbk_multi_supports(const DbkArgs *, int, const int *) { return M.c.supports
 bool dbk_packed_h265_supports(const DbkH265Args &, int, bool) { return M.c.supports; }
 bool dbk_deblock_sao_supports(const DbkArgs &, const DbkSaoArgs &, int, bool) { return M.c.supports; }
 bool dbk_packed_h265_sp_supports(const DbkH265Args &, int) { return M.c.supports; }
-size_t dbk_sao_rows_x2_entries(const DbkSaoArgs &) { return 0; }
+bool dbk_deblock_sao_sp_supports(const DbkH265Args &, const DbkSaoArgs &, int) { return M.c.supports; }
+/* the count of the real launcher (sao.hip) */
+size_t dbk_sao_rows_x2_entries(const DbkSaoArgs &a)
+{
+    const long long cols = (a.plane_w + (1 << a.ctb_log2) - 1) >> a.ctb_log2, rows = (a.plane_h + (1 << a.ctb_log2) - 1) >> a.ctb_log2;
+    return (size_t)(cols * rows * (a.params_frame_stride ? a.n_frames : 1));
+}
 
 /* ---- launchers ------------------------------------------------------------------------------------------------------------------------------ */
 
@@ -723,38 +860,162 @@ hipError_t dbk_launch_h265_chroma_bs(const uint8_t *vert, const uint8_t *hor, in
     return dbk_launch_h265_chroma_bs_cf(vert, hor, w, h, 1, cvert, chor, s);
 }
 
-/* what the host-frame operators never launch: the device entries of the same sources are tests/entry_sim's */
-hipError_t dbk_launch_h265_sl(const DbkH265Args &, const DbkSlOffs &, int, int, hipStream_t) { return not_modelled(); }
-hipError_t dbk_launch_packed_h265_sl(const DbkH265Args &, const DbkSlOffs &, int, bool, int, hipStream_t) { return not_modelled(); }
-hipError_t dbk_launch_h265_g4(const DbkH265Args &, const DbkSlOffs &, int, int, hipStream_t) { return not_modelled(); }
-hipError_t dbk_launch_packed_h265_g4(const DbkH265Args &, const DbkSlOffs &, int, int, hipStream_t) { return not_modelled(); }
-hipError_t dbk_launch_h265_sp(const DbkH265Args &, const DbkSlOffs &, int, int, hipStream_t) { return not_modelled(); }
-hipError_t dbk_launch_packed_h265_sp(const DbkH265Args &, const DbkSlOffs &, int, int, hipStream_t) { return not_modelled(); }
-hipError_t dbk_launch_h265_slice_offsets(const uint16_t *, int, const int8_t *, unsigned, int, int, int8_t *, int, hipStream_t) { return not_modelled(); }
-hipError_t dbk_launch_sao(const DbkSaoArgs &, int, hipStream_t, const DbkSaoNox *) { return not_modelled(); }
-hipError_t dbk_launch_sao_g4(const DbkSaoArgs &, int, hipStream_t, const DbkSaoNox *) { return not_modelled(); }
-hipError_t dbk_launch_sao_sp(const DbkSaoArgs &, const DbkSaoCtb *, int, hipStream_t, const DbkSaoNox *) { return not_modelled(); }
-hipError_t dbk_launch_sao_borders(const uint16_t *, const uint8_t *, const uint16_t *, int, int, int, int, uint8_t *, int, hipStream_t) { return not_modelled(); }
-hipError_t dbk_launch_sao_rows_x2(DbkSaoArgs &, DbkSaoCtb *, hipStream_t) { return not_modelled(); }
-hipError_t dbk_launch_sao_nox_rows_x2(const DbkSaoArgs &, DbkSaoNox &, uint8_t *, hipStream_t) { return not_modelled(); }
-hipError_t dbk_launch_deblock_sao(const DbkArgs &, const DbkSaoArgs &, int, bool, hipStream_t) { return not_modelled(); }
-hipError_t dbk_launch_deblock_sao_multi(const DbkArgs *, const DbkSaoArgs *, int, int, hipStream_t) { return not_modelled(); }
-hipError_t dbk_launch_deblock_sao_multi_h265(const DbkH265Args *, const DbkSaoArgs *, int, int, hipStream_t) { return not_modelled(); }
-hipError_t dbk_launch_deblock_sao_h265_cf(const DbkH265Args &, const DbkSaoArgs &, int, bool, int, hipStream_t, const DbkSaoNox *) { return not_modelled(); }
-hipError_t dbk_launch_deblock_sao_h265_sl(const DbkH265Args &, const DbkSaoArgs &, const DbkSlOffs &, int, bool, int, hipStream_t, const DbkSaoNox *)
+/* ---- the later generations of deblocking: as h265_marker, plus the per-slice operand as it is when the operation runs ---- */
+
+hipError_t dbk_launch_h265_sl(const DbkH265Args &h, const DbkSlOffs &sl, int sb, int cf, hipStream_t s)
 {
-    return not_modelled();
+    const Marker m = later_marker(h, sl, sb, cf != 0, cf ? cf : 1, "h265_sl");
+    return launch(s, m.name, [m] { run_marker(m); });
 }
-hipError_t dbk_launch_deblock_sao_h265_g4(const DbkH265Args &, const DbkSaoArgs &, const DbkSlOffs &, int, int, hipStream_t, const DbkSaoNox *)
+hipError_t dbk_launch_packed_h265_sl(const DbkH265Args &h, const DbkSlOffs &sl, int sb, bool chroma, int cf, hipStream_t s)
 {
-    return not_modelled();
+    const Marker m = later_marker(h, sl, sb, chroma, cf, "packed_h265_sl");
+    return launch(s, m.name, [m] { run_marker(m); });
 }
-hipError_t dbk_launch_deblock_sao_multi_h265_cf(const DbkH265Args *, const DbkSaoArgs *, int, int, int, hipStream_t, const DbkSaoNox *) { return not_modelled(); }
-hipError_t dbk_launch_deblock_sao_multi_h265_sl(const DbkH265Args *, const DbkSaoArgs *, const DbkSlOffs &, int, int, int, hipStream_t, const DbkSaoNox *)
+hipError_t dbk_launch_h265_g4(const DbkH265Args &h, const DbkSlOffs &sl, int sb, int cf, hipStream_t s)
 {
-    return not_modelled();
+    const Marker m = later_marker(h, sl, sb, true, cf, "h265_g4");
+    return launch(s, m.name, [m] { run_marker(m); });
 }
-hipError_t dbk_launch_deblock_sao_multi_h265_g4(const DbkH265Args *, const DbkSaoArgs *, const DbkSlOffs &, int, int, int, hipStream_t, const DbkSaoNox *)
+hipError_t dbk_launch_packed_h265_g4(const DbkH265Args &h, const DbkSlOffs &sl, int sb, int cf, hipStream_t s)
 {
-    return not_modelled();
+    const Marker m = later_marker(h, sl, sb, true, cf, "packed_h265_g4");
+    return launch(s, m.name, [m] { run_marker(m); });
+}
+hipError_t dbk_launch_h265_sp(const DbkH265Args &h, const DbkSlOffs &sl, int cr_qp_offset, int sb, hipStream_t s)
+{
+    const Marker m = sp_marker(h, sl, cr_qp_offset, sb, "h265_sp");
+    return launch(s, m.name, [m] { run_marker(m); });
+}
+hipError_t dbk_launch_packed_h265_sp(const DbkH265Args &h, const DbkSlOffs &sl, int cr_qp_offset, int sb, hipStream_t s)
+{
+    const Marker m = sp_marker(h, sl, cr_qp_offset, sb, "packed_h265_sp");
+    return launch(s, m.name, [m] { run_marker(m); });
+}
+
+/* ---- producers of per-CTB operands ---- */
+
+hipError_t dbk_launch_h265_slice_offsets(const uint16_t *slice_idx, int in_stride, const int8_t *table, unsigned n_slices, int ctbs_x, int ctbs_y, int8_t *offs,
+                                         int offs_stride, hipStream_t s)
+{
+    Derive d{{{slice_idx, 2 * span((size_t)in_stride, (size_t)ctbs_x, (size_t)ctbs_y)}}, {{(uint8_t *)offs, 2 * span((size_t)offs_stride, (size_t)ctbs_x, (size_t)ctbs_y)}},
+             "h265_slice_offsets"};
+    if (n_slices) d.in.push_back({table, 2 * (size_t)n_slices});
+    return launch(s, d.name, [d] { run_derive(d); });
+}
+hipError_t dbk_launch_sao_borders(const uint16_t *slice_idx, const uint8_t *slice_across, const uint16_t *tile_idx, int, int ctbs_x, int ctbs_y, int in_stride,
+                                  uint8_t *nox, int nox_stride, hipStream_t s)
+{
+    const size_t n = span((size_t)in_stride, (size_t)ctbs_x, (size_t)ctbs_y);
+    Derive d{{{slice_idx, 2 * n}, {slice_across, n}}, {{nox, span((size_t)nox_stride, (size_t)ctbs_x, (size_t)ctbs_y)}}, "sao_borders"};
+    if (tile_idx) d.in.push_back({tile_idx, 2 * n});
+    return launch(s, d.name, [d] { run_derive(d); });
+}
+/* 4:2:2 chroma: the caller's grid of every frame into the context's scratch; the operands are re-pointed as the real launchers do */
+hipError_t dbk_launch_sao_rows_x2(DbkSaoArgs &a, DbkSaoCtb *dst, hipStream_t s)
+{
+    const size_t cols = (size_t)((a.plane_w + (1 << a.ctb_log2) - 1) >> a.ctb_log2), rows = (size_t)((a.plane_h + (1 << a.ctb_log2) - 1) >> a.ctb_log2);
+    const size_t e = sizeof(DbkSaoCtb);
+    Derive d{{}, {{(uint8_t *)dst, dbk_sao_rows_x2_entries(a) * e}}, "sao_rows_x2"};
+    for (size_t f = 0; f < (a.params_frame_stride ? (size_t)a.n_frames : 1); f++)
+        d.in.push_back({a.params + f * (size_t)a.params_frame_stride, span((size_t)a.params_stride * e, cols * e, (rows + 1) / 2)});
+    a.params = dst;
+    a.params_stride = (int)cols;
+    a.params_frame_stride = a.params_frame_stride ? (long long)(rows * cols) : 0;
+    return launch(s, d.name, [d] { run_derive(d); });
+}
+hipError_t dbk_launch_sao_nox_rows_x2(const DbkSaoArgs &a, DbkSaoNox &nx, uint8_t *dst, hipStream_t s)
+{
+    const size_t cols = (size_t)((a.plane_w + (1 << a.ctb_log2) - 1) >> a.ctb_log2), rows = (size_t)((a.plane_h + (1 << a.ctb_log2) - 1) >> a.ctb_log2);
+    const bool per_frame = nx.frame_stride != 0;
+    Derive d{{}, {{dst, cols * rows * (per_frame ? (size_t)a.n_frames : 1)}}, "sao_nox_rows_x2"};
+    for (size_t f = 0; f < (per_frame ? (size_t)a.n_frames : 1); f++)
+        d.in.push_back({nx.nox + f * (size_t)nx.frame_stride, span((size_t)nx.stride, cols, (rows + 1) / 2)});
+    nx.nox = dst;
+    nx.stride = (int)cols;
+    nx.frame_stride = per_frame ? (long long)(rows * cols) : 0;
+    return launch(s, d.name, [d] { run_derive(d); });
+}
+
+/* ---- the SAO pass ---- */
+
+hipError_t dbk_launch_sao(const DbkSaoArgs &a, int sb, hipStream_t s, const DbkSaoNox *nx)
+{
+    const SaoOp o = sao_op(a, nullptr, nx, sb, 1, "sao");
+    return launch(s, o.name, [o] { run_sao(o); });
+}
+hipError_t dbk_launch_sao_g4(const DbkSaoArgs &a, int sb, hipStream_t s, const DbkSaoNox *nx)
+{
+    const SaoOp o = sao_op(a, nullptr, nx, sb, 1, "sao_g4");
+    return launch(s, o.name, [o] { run_sao(o); });
+}
+hipError_t dbk_launch_sao_sp(const DbkSaoArgs &a, const DbkSaoCtb *params_cr, int sb, hipStream_t s, const DbkSaoNox *nx)
+{
+    const SaoOp o = sao_op(a, params_cr, nx, sb, 2, "sao_sp");
+    return launch(s, o.name, [o] { run_sao(o); });
+}
+
+/* ---- deblocking + SAO in one kernel, single-plane and multi-plane (plane 0 luma, the others chroma), every generation ---- */
+
+hipError_t dbk_launch_deblock_sao(const DbkArgs &d, const DbkSaoArgs &a, int sb, bool chroma, hipStream_t s)
+{
+    return launch_fused(s, "deblock_sao", {{ref_marker(d, sb, chroma, "deblock_sao"), sao_op(a, nullptr, nullptr, sb, 1, "deblock_sao")}});
+}
+hipError_t dbk_launch_deblock_sao_multi(const DbkArgs *d, const DbkSaoArgs *a, int n, int sb, hipStream_t s)
+{
+    std::vector<Fused> fs;
+    for (int i = 0; i < n; i++) fs.push_back({ref_marker(d[i], sb, i != 0, "deblock_sao_multi"), sao_op(a[i], nullptr, nullptr, sb, 1, "deblock_sao_multi")});
+    return launch_fused(s, "deblock_sao_multi", fs);
+}
+namespace {
+hipError_t fused_multi(const DbkH265Args *h, const DbkSaoArgs *a, const DbkSlOffs &sl, int n, int sb, int cf, hipStream_t s, const DbkSaoNox *nx, const char *name)
+{
+    std::vector<Fused> fs;
+    for (int i = 0; i < n; i++) fs.push_back({later_marker(h[i], sl, sb, i != 0, cf, name), sao_op(a[i], nullptr, nx ? &nx[i] : nullptr, sb, 1, name)});
+    return launch_fused(s, name, fs);
+}
+const DbkSlOffs kNoOffsets = {nullptr, 0, 0, 4, 0u};
+} /* namespace */
+hipError_t dbk_launch_deblock_sao_multi_h265(const DbkH265Args *h, const DbkSaoArgs *a, int n, int sb, hipStream_t s)
+{
+    return fused_multi(h, a, kNoOffsets, n, sb, 1, s, nullptr, "deblock_sao_multi_h265");
+}
+hipError_t dbk_launch_deblock_sao_h265_cf(const DbkH265Args &h, const DbkSaoArgs &a, int sb, bool chroma, int cf, hipStream_t s, const DbkSaoNox *nx)
+{
+    return launch_fused(s, "deblock_sao_h265_cf", {{later_marker(h, kNoOffsets, sb, chroma, cf, "deblock_sao_h265_cf"), sao_op(a, nullptr, nx, sb, 1, "deblock_sao_h265_cf")}});
+}
+hipError_t dbk_launch_deblock_sao_h265_sl(const DbkH265Args &h, const DbkSaoArgs &a, const DbkSlOffs &sl, int sb, bool chroma, int cf, hipStream_t s,
+                                          const DbkSaoNox *nx)
+{
+    return launch_fused(s, "deblock_sao_h265_sl", {{later_marker(h, sl, sb, chroma, cf, "deblock_sao_h265_sl"), sao_op(a, nullptr, nx, sb, 1, "deblock_sao_h265_sl")}});
+}
+hipError_t dbk_launch_deblock_sao_h265_g4(const DbkH265Args &h, const DbkSaoArgs &a, const DbkSlOffs &sl, int sb, int cf, hipStream_t s, const DbkSaoNox *nx)
+{
+    return launch_fused(s, "deblock_sao_h265_g4", {{later_marker(h, sl, sb, true, cf, "deblock_sao_h265_g4"), sao_op(a, nullptr, nx, sb, 1, "deblock_sao_h265_g4")}});
+}
+hipError_t dbk_launch_deblock_sao_multi_h265_cf(const DbkH265Args *h, const DbkSaoArgs *a, int n, int sb, int cf, hipStream_t s, const DbkSaoNox *nx)
+{
+    return fused_multi(h, a, kNoOffsets, n, sb, cf, s, nx, "deblock_sao_multi_h265_cf");
+}
+hipError_t dbk_launch_deblock_sao_multi_h265_sl(const DbkH265Args *h, const DbkSaoArgs *a, const DbkSlOffs &sl, int n, int sb, int cf, hipStream_t s,
+                                                const DbkSaoNox *nx)
+{
+    return fused_multi(h, a, sl, n, sb, cf, s, nx, "deblock_sao_multi_h265_sl");
+}
+hipError_t dbk_launch_deblock_sao_multi_h265_g4(const DbkH265Args *h, const DbkSaoArgs *a, const DbkSlOffs &sl, int n, int sb, int cf, hipStream_t s,
+                                                const DbkSaoNox *nx)
+{
+    return fused_multi(h, a, sl, n, sb, cf, s, nx, "deblock_sao_multi_h265_g4");
+}
+hipError_t dbk_launch_deblock_sao_h265_sp(const DbkH265Args &h, const DbkSaoArgs &a, const DbkSaoCtb *params_cr, const DbkSlOffs &sl, int cr_qp_offset, int sb,
+                                          hipStream_t s, const DbkSaoNox *nx)
+{
+    return launch_fused(s, "deblock_sao_h265_sp", {{sp_marker(h, sl, cr_qp_offset, sb, "deblock_sao_h265_sp"), sao_op(a, params_cr, nx, sb, 2, "deblock_sao_h265_sp")}});
+}
+hipError_t dbk_launch_deblock_sao_h265_nv12(const DbkH265Args *h, const DbkSaoArgs *a, const DbkSaoCtb *params_cr, const DbkSlOffs &sl, int cr_qp_offset, int sb,
+                                            hipStream_t s, const DbkSaoNox *nx)
+{
+    return launch_fused(s, "deblock_sao_h265_nv12",
+                        {{later_marker(h[0], sl, sb, false, 1, "deblock_sao_h265_nv12"), sao_op(a[0], nullptr, nx ? &nx[0] : nullptr, sb, 1, "deblock_sao_h265_nv12")},
+                         {sp_marker(h[1], sl, cr_qp_offset, sb, "deblock_sao_h265_nv12"), sao_op(a[1], params_cr, nx ? &nx[1] : nullptr, sb, 2, "deblock_sao_h265_nv12")}});
 }

@@ -1,12 +1,17 @@
 /*
- * hip_model.h -- a model of the HIP runtime for CPU tests of the host-frame operators (csrc/deblock_host.cpp,
- * csrc/deblock_host_h265.cpp), and of the kernel launchers above it.  Unlike the stubs of tests/entry_sim, which complete
+ * hip_model.h -- a model of the HIP runtime for CPU tests of the host sources (csrc/deblock_host.cpp, csrc/deblock_host_h265.cpp,
+ * csrc/deblock_host_sp.cpp), and of the kernel launchers above it: the host-frame operators (tests/host_frame_sim) and the device
+ * entries that take the caller's stream (tests/device_stream_sim).  Unlike the stubs of tests/entry_sim, which complete
  * everything at once, the model DEFERS: a stream is a FIFO of operations, nothing runs when it is enqueued, and a scheduler
  * fixed per case decides inside which later HIP call an operation runs.  Streams are ordered against each other by
  * hipStreamWaitEvent on a recorded event and by nothing else.  Every behaviour here is one the real runtime may show.
+ * What a kernel operation writes is decided when it RUNS, from what its operand arrays hold then: an operation that runs
+ * before its operands were produced, or after they were overwritten, leaves other bytes than the test expects.
  *
  * Not modelled: time (hipEventElapsedTime answers 0 ms), the order of the DMA engines beyond stream order, and several
- * contexts or host threads sharing the runtime (hevcdbk_filter_yuv_file_multi).
+ * contexts or host threads sharing the runtime (hevcdbk_filter_yuv_file_multi).  hipFree waits for the device, as the
+ * runtime's does: a buffer the code under test frees while work that uses it is queued is therefore never seen freed by that
+ * work.  Growth of a context's scratch is checked for its results and for deadlock, not for use after free.
  */
 #pragma once
 #include <cstddef>
@@ -40,6 +45,11 @@ int model_calls(int kind);
 /* violations recorded since model_begin: access checks, deadlocks, one line each */
 const std::vector<std::string> &model_violations();
 int model_sync_pageable_copies();
+/* blocking calls since model_begin: hipStreamSynchronize, hipDeviceSynchronize, hipEventSynchronize; and hipFree of device memory */
+int model_blocking_calls();
+int model_device_frees();
+/* what the *_supports predicates answer from now on (a session mixes calls the fused kernels take with calls they do not) */
+void model_set_supports(bool supports);
 /* operations still queued on any stream */
 size_t model_pending_ops();
 /* run everything that is queued (the test's own clean-up; not a HIP call of the code under test) */
@@ -87,3 +97,22 @@ inline void model_derived(uint64_t h, uint8_t *out, size_t n)
     for (size_t i = 0; i < n; i++) out[i] = (uint8_t)model_mix64(h + i);
 }
 constexpr uint64_t kModelHash0 = 0xcbf29ce484222325ull;
+
+/* ---- the SAO operations: a hash of the scalar operands and of every operand array, row by row of its grid (the bytes between
+ * the rows of a strided array belong to nobody) ---- */
+inline uint64_t model_fold_rows(uint64_t h, const void *base, size_t stride_bytes, size_t row_bytes, size_t rows)
+{
+    for (size_t r = 0; r < rows; r++) h = model_fold(h, (const uint8_t *)base + r * stride_bytes, row_bytes);
+    return h;
+}
+inline uint64_t model_sao_hash0(int max_v, int band_shift, int ctb_log2)
+{
+    uint64_t h = kModelHash0 ^ 0x5a0;
+    h = model_fold_int(h, max_v);
+    h = model_fold_int(h, band_shift);
+    return model_fold_int(h, ctb_log2);
+}
+/* the plane model_m takes for the SAO stage: deblocking uses 0 (luma) and 1 (chroma) */
+constexpr int kModelSaoPlane = 2;
+/* the launchers that produce operands (model_derived over their output) start their hash of the inputs here */
+constexpr uint64_t kModelDeriveHash0 = kModelHash0 ^ 0xb5;

@@ -8,9 +8,10 @@ generations of an entry where include/hevc_deblock.h promises that they are the 
   * a _nox entry without borders and the _cf entry;
   * a _cf entry with 4:2:0 and square CTBs and the original entry, where neither was refused before the launch.
 
-Of every call it asks that nothing is enqueued after a refusal, and that a launch of 4:2:2 SAO parameters into the context's scratch
-is followed by the record of the event that fences it, whatever the launches after it returned (the SAO pass entries: when they
-succeeded).  Both builds of the host source, product and diagnostic."""
+Of every call it asks that nothing is enqueued after a refusal, and that the last launch into the context's scratch for 4:2:2 SAO
+parameters that was enqueued (parameters or border bytes) is followed by the record of the event that fences it, whatever the
+launches after it returned, in the SAO pass entries as in the deblocking + SAO entries.  Both builds of the host source, product
+and diagnostic."""
 import os
 import re
 import subprocess

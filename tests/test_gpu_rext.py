@@ -449,3 +449,93 @@ def test_fused_on_is_one_launch(ctx, h265, fmt, use_map):
     _check(planes, want, 2, (fmt, use_map))
     for x in keep:
         x.free()
+
+
+def _scratch_422_on_two_streams():
+    """the body of test_422_parameter_scratch_on_two_caller_streams, run in a process of its own"""
+    import ctypes as C
+    from gpu_video_codec_amd import _lib, deblock
+    L = _lib.lib()
+    hip = C.CDLL("libamdhip64.so")
+    hip.hipStreamCreateWithFlags.argtypes = [C.POINTER(C.c_void_p), C.c_uint]
+    hip.hipStreamSynchronize.argtypes = [C.c_void_p]
+    hip.hipStreamDestroy.argtypes = [C.c_void_p]
+    # a context of its own: grow_device never shrinks, so on a context that an earlier 4:2:2 call has used the scratch may
+    # already hold the large plane's grid.  Here the first small call allocates exactly what it needs (4 x 8 x 2 entries), the
+    # other small one less, and the large plane (16 x 32 x 2 entries) finds it too small
+    ctx = deblock.Context(0)
+    streams, cases = [], []
+    try:
+        for _ in range(2):
+            s = C.c_void_p()
+            assert hip.hipStreamCreateWithFlags(C.byref(s), 1) == 0   # hipStreamNonBlocking
+            streams.append(s)
+        rng = np.random.default_rng(422)
+        cf, lw, lh, bd, n, qp = 2, 4, 5, 8, 2, 35
+        hp = _lib.H265Params(1, -1, 3, -2)
+        # (plane, parameters on the device, parameters, expected frames, deblocked first)
+        for (w, h, dbk) in ((64, 128, False), (32, 64, True), (256, 512, False)):   # the third is the large one
+            frames = np.stack([blocky(rng, w, h, bd) for _ in range(n)])
+            prm = np.stack([rx.random_sao_params(w, h, lw, lh, rng, bd) for _ in range(n)])
+            vb, hb = rand_bs(rng, w, h)
+            pl = Plane(ctx, frames, bd, True, vb, hb)
+            dp = upload_params(ctx, prm)
+            want = []
+            for f in range(n):
+                d = rx.filter_chroma_plane(frames[f], vb, hb, cf, qp=qp, bit_depth=bd, tc_offset_div2=1, c_qp_offset=3) if dbk else frames[f]
+                want.append(rx.sao_plane(d, prm[f], lw, lh, bit_depth=bd))
+            cases.append((pl, dp, prm, want, dbk))
+        entries = [2 * (-(-pl.b.w >> lw)) * (-(-pl.b.h >> lw)) for pl, _d, _p, _w, _k in cases]   # of the doubled grid, both frames
+        assert entries[1] < entries[0] < entries[2], entries
+        ctx.synchronize()   # the uploads are done; from here on nothing synchronises with the host until the end
+
+        def call(k, stream):
+            pl, dp, prm, _want, dbk = cases[k]
+            planes = pl.planes()
+            stride, frame_stride = prm.shape[2], prm.shape[1] * prm.shape[2]
+            if dbk:
+                rc = L.hevcdbk_h265_deblock_sao_device_cf(ctx.handle, C.byref(planes), 1, cf, qp, C.byref(hp), dp.ptr, stride, frame_stride, lw, lh,
+                                                          None, 0, 0, _lib.FUSED_AUTO, stream)
+            else:
+                rc = L.hevcdbk_sao_filter_device_cf(ctx.handle, C.byref(planes), dp.ptr, stride, frame_stride, lw, lh, None, 0, 0, stream)
+            assert rc == 0, (k, rc, L.hevcdbk_last_error(ctx.handle))
+        for rnd in range(6):
+            call(0, streams[0])      # the first of them is the scratch's first use
+            call(1, streams[1])
+        call(2, streams[0])          # the scratch grows: the library waits for the event of the last small call first
+        for rnd in range(2):
+            call(1, streams[1])
+            call(0, streams[0])
+            call(2, streams[1])      # ... and the large one on the other stream, fenced against its own previous use
+        for s in streams:
+            assert hip.hipStreamSynchronize(s) == 0
+        for k, (pl, dp, prm, want, dbk) in enumerate(cases):
+            for f in range(n):
+                assert np.array_equal(pl.out(f), want[f]), (k, f)
+    finally:
+        for s in streams:
+            hip.hipStreamSynchronize(s)
+            hip.hipStreamDestroy(s)
+        for pl, dp, _p, _w, _d in cases:
+            pl.free()
+            dp.free()
+        ctx.close()
+
+
+def test_422_parameter_scratch_on_two_caller_streams():
+    """the SAO parameters of a 4:2:2 chroma plane are rewritten for square CTBs into ONE scratch buffer per context (dev_sao) while
+    the caller may hand in any stream; its reuse is fenced by an event (sao_ev) and it is only re-allocated after that event has
+    completed.  On a context of its own -- so that the scratch is as small as the first call made it -- two non-blocking streams,
+    hevcdbk_sao_filter_device_cf on one plane and hevcdbk_h265_deblock_sao_device_cf on another (CTBs of 16 x 32 samples, a parameter
+    grid of its own each) alternately with NO host synchronisation between them, then a plane large enough for the scratch to grow,
+    on the other stream, and the small ones again; every output against tests/rext_oracle.py.  The stream phase runs in a child
+    process under a time limit of its own: calls queued without a host synchronisation are what would hang if a fence were wrong.
+    A card is too fast for this to prove the fence (tests/device_stream_sim does that on the CPU); it ties the sessions there to
+    operands the card accepts."""
+    import os
+    import subprocess
+    import sys
+    tests = os.path.dirname(os.path.abspath(__file__))
+    code = "import sys; sys.path[:0] = [%r, %r]; import test_gpu_rext as t; t._scratch_422_on_two_streams(); print('SCRATCH-OK')" % (os.path.dirname(tests), tests)
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "SCRATCH-OK" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
