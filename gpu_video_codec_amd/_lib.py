@@ -54,6 +54,7 @@ EXPORTS = [
     "hevcdbk_sao_stats_device", "hevcdbk_sao_pick_device", "hevcdbk_sao_stats_device_sp",
     "hevcdbk_sao_decide_device", "hevcdbk_sao_pick_device_os", "hevcdbk_sao_decide_device_os",
     "hevcdbk_sao_decide_device_sf", "hevcdbk_sao_slice_flags_device", "hevcdbk_sao_slice_flags_workspace",
+    "hevcdbk_sse_device", "hevcdbk_sse_device_sp", "hevcdbk_sse_totals_device",
 ]
 
 # chroma_format_idc of the spec-exact mode and SAO (HEVCDBK_CHROMA_*): 4:0:0, 4:2:0, 4:2:2, 4:4:4
@@ -376,6 +377,13 @@ def lib():
                                                                     C.c_void_p]
         L.hevcdbk_sao_slice_flags_workspace.argtypes = [C.c_uint, C.c_uint, C.c_uint, C.c_uint]
         L.hevcdbk_sao_slice_flags_workspace.restype = C.c_size_t
+        # measured distortion: uint64 per CTB of a plane (two CTB shapes) or of a pair plane (one shape, two arrays), and their totals
+        L.hevcdbk_sse_device.argtypes = [C.c_void_p, C.POINTER(DevicePlanes), C.c_void_p, C.c_size_t, C.c_size_t, C.c_uint, C.c_uint,
+                                         C.c_void_p, C.c_uint, C.c_size_t, C.c_void_p]
+        L.hevcdbk_sse_device_sp.argtypes = [C.c_void_p, C.POINTER(DevicePlanes), C.c_void_p, C.c_size_t, C.c_size_t, C.c_uint, C.c_void_p,
+                                            C.c_void_p, C.c_uint, C.c_size_t, C.c_void_p]
+        L.hevcdbk_sse_totals_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint, C.c_size_t, C.c_uint, C.c_uint, C.c_uint, C.c_void_p,
+                                                C.c_uint, C.c_size_t, C.c_uint, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
         L.hevc_deblock_sao_h265_device_planes.argtypes = [C.c_void_p, C.POINTER(DevicePlanes), C.c_uint, C.c_uint, C.POINTER(H265Params),
                                                           C.POINTER(SaoPlane), C.c_int, C.c_void_p]
         L.hevcdbk_set_host_threads.argtypes = [C.c_void_p, C.c_uint]

@@ -588,6 +588,43 @@ class Context:
                                                        slice_flags_frame_stride, slice_record_ptr, slice_record_frame_stride, workspace_ptr,
                                                        workspace_bytes, stream), self.handle)
 
+    def sse_device(self, planes, org_ptr, ctb_log2, *, org_pitch=None, org_frame_stride=None, ctb_log2_h=None, chroma_format="420",
+                   out_ptr, out_stride, out_frame_stride=0, stream=None, semi_planar=False, out_cr_ptr=None):
+        """hevcdbk_sse_device: the sum of squared errors of the plane planes.src against the original at org_ptr (device memory, the
+        same geometry and container; pitch and frame stride default to the plane's), exact, one uint64 per CTB at out_ptr (device
+        memory, 8-byte aligned), out_stride entries per CTB row, out_frame_stride entries between frames.  Every sample counts: no keep
+        map, no borders.  ctb_log2 / ctb_log2_h / chroma_format as for sao_stats_device.  semi_planar=True: hevcdbk_sse_device_sp --
+        planes of interleaved Cb / Cr pairs (plane_w x plane_h per component); out_ptr takes Cb's sums (the even samples), out_cr_ptr
+        (needed) Cr's; square CTBs of ctb_log2 3..5."""
+        cf = _lib.chroma_format_idc(chroma_format)
+        pitch = planes.pitch if org_pitch is None else org_pitch
+        fstride = planes.frame_stride if org_frame_stride is None else org_frame_stride
+        if semi_planar:
+            if cf != _lib.CHROMA_420:
+                raise ValueError("semi_planar is 4:2:0 only")
+            if out_cr_ptr is None:
+                raise ValueError("semi_planar needs out_cr_ptr: the sums of the odd samples")
+            if ctb_log2_h is not None and ctb_log2_h != ctb_log2:
+                raise ValueError("semi_planar takes square CTBs")
+            _chk(_lib.lib().hevcdbk_sse_device_sp(self.handle, C.byref(planes), org_ptr, pitch, fstride, ctb_log2, out_ptr, out_cr_ptr, out_stride,
+                                                  out_frame_stride, stream), self.handle)
+            return
+        if out_cr_ptr is not None:
+            raise ValueError("out_cr_ptr belongs to semi_planar=True")
+        lh = _ctb_log2_h(ctb_log2, ctb_log2_h, cf, planes.is_chroma)
+        _chk(_lib.lib().hevcdbk_sse_device(self.handle, C.byref(planes), org_ptr, pitch, fstride, ctb_log2, lh, out_ptr, out_stride,
+                                           out_frame_stride, stream), self.handle)
+
+    def sse_totals_device(self, sse_ptr, sse_stride, ctbs_x, ctbs_y, *, n_frames=1, sse_frame_stride=0, slice_idx_ptr=None, idx_stride=0,
+                          idx_frame_stride=0, n_slices=1, slice_total_ptr=None, slice_total_frame_stride=0, frame_total_ptr=None, stream=None):
+        """hevcdbk_sse_totals_device: the sums of sse_device's array (or of any uint64 per CTB) per slice and per frame, modulo 2^64.
+        slice_idx_ptr: uint16 per CTB as sao_decide_device takes it, None = every CTB in slice 0.  slice_total_ptr: n_slices uint64 per
+        frame, slice_total_frame_stride entries apart; frame_total_ptr: one uint64 per frame, CTBs with an index >= n_slices included.
+        Either may be None, not both.  At most 600 slices."""
+        _chk(_lib.lib().hevcdbk_sse_totals_device(self.handle, sse_ptr, sse_stride, sse_frame_stride, ctbs_x, ctbs_y, n_frames, slice_idx_ptr,
+                                                  idx_stride, idx_frame_stride, n_slices, slice_total_ptr, slice_total_frame_stride,
+                                                  frame_total_ptr, stream), self.handle)
+
     def deblock_sao_device(self, planes, qp, params_ptr, params_stride, ctb_log2, *, params_frame_stride=0, keep_ptr=None,
                            keep_stride=0, keep_frame_stride=0, tc_table=None, beta_table=None, fused=_lib.FUSED_AUTO, stream=None):
         """hevc_deblock_sao_device: reference-exact deblocking followed by SAO, src -> dst, one kernel where it applies.

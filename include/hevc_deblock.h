@@ -1159,6 +1159,67 @@ HEVCDBK_API int hevcdbk_sao_slice_flags_device(hevcdbk_context *ctx, const hevcd
                                                size_t slice_flags_frame_stride, hevcdbk_sao_slice_record *slice_record,
                                                size_t slice_record_frame_stride, void *workspace, size_t workspace_bytes, void *hip_stream);
 
+/*
+ * Measured distortion: the sum of squared errors of a plane in HBM against the original, per CTB -- what the delta_d of the decision
+ * and the totals of the slice records PREDICT, measured: the prediction equals the real change of the SSE only where the final clip
+ * of SAO never acts, and deblocking has no prediction at all.  Nothing is read back: filter -> this call on the deblocked plane ->
+ * SAO -> this call on SAO's output gives the distortion of every CTB before and after each stage, hevcdbk_sse_totals_device that of
+ * every slice and frame (rate control, PSNR = one log10 on the host), all on the device.
+ *   - rec and org mean what they mean to hevcdbk_sao_stats_device: of rec the members src, pitch, frame_stride, n_frames, plane_w,
+ *     plane_h, bit_depth (8..16) and sample_bytes are used -- to measure an SAO output pass a descriptor whose src is that output;
+ *     org has the same geometry with its own pitch and frame stride, a frame stride of 0 = one original for every frame.  plane_w
+ *     and plane_h are multiples of 4 and at least 8; the CTB grid is taken by ceiling; ctb_log2_w 3..6, ctb_log2_h = ctb_log2_w or
+ *     ctb_log2_w + 1 and at most 6.
+ *   - sse[f * sse_frame_stride + cy * sse_stride + cx] = the sum of (org - rec)^2 over the samples of that CTB that lie inside the
+ *     plane, exact (a 64 x 64 CTB at 16 bit reaches 4096 * 65535^2, about 2^44).  EVERY sample counts: there is no keep map and no
+ *     borders operand -- a kept sample contributes equally before and after SAO.  Entries beyond the CTB columns are not touched;
+ *     every entry of the grid is written once, with a plain store; no atomics; the same bits every run.
+ *   - Rows that start at a multiple of 16 bytes in both planes (addresses, pitches and frame strides) are fetched 16 bytes per lane
+ *     and load, rows at a multiple of four samples four samples per load, anything else sample by sample; the three give the same
+ *     result.  No byte outside the plane_w x plane_h samples of a frame is read: the last row of the last frame may end the
+ *     allocation.
+ * Refusals, before the context is bound, in this order: NULL ctx / rec / rec->src / org / sse, a bad depth or sample_bytes --
+ * HEVCDBK_ERR_ARG; the plane size -- HEVCDBK_ERR_DIMENSIONS; the CTB shape; a pitch below a row, more than 65535 frames or rows;
+ * sse_stride below the CTB columns or above 0x7fffffff, sse at an address that is no multiple of 8; sse_frame_stride below one grid
+ * with n_frames > 1 -- HEVCDBK_ERR_ARG; LAST a pitch, frame stride or address that is no multiple of the sample size --
+ * HEVCDBK_ERR_UNSUPPORTED.  One launch, asynchronous on hip_stream (NULL = the context's compute stream).
+ */
+HEVCDBK_API int hevcdbk_sse_device(hevcdbk_context *ctx, const hevcdbk_device_planes *rec, const void *org, size_t org_pitch,
+                                   size_t org_frame_stride, unsigned ctb_log2_w, unsigned ctb_log2_h, uint64_t *sse, unsigned sse_stride,
+                                   size_t sse_frame_stride, void *hip_stream);
+
+/*
+ * The same of a plane of interleaved Cb / Cr pairs, described as for hevcdbk_sao_stats_device_sp: is_chroma = 1, plane_w x plane_h per
+ * component, a pitch of at least two samples per pair, square CTBs of ctb_log2 3..5.  One launch fills both arrays: sse_cb is, byte
+ * for byte, what hevcdbk_sse_device gives for the plane of the even samples, sse_cr the same for the odd samples (NV21: swap them),
+ * with one stride and one frame stride.  Refusals: those of hevcdbk_sse_device in its order with what a pair plane replaces --
+ * is_chroma beside the depth, the doubled pitch -- and, after the frame stride, two outputs whose extents meet: HEVCDBK_ERR_ARG.
+ */
+HEVCDBK_API int hevcdbk_sse_device_sp(hevcdbk_context *ctx, const hevcdbk_device_planes *rec, const void *org, size_t org_pitch,
+                                      size_t org_frame_stride, unsigned ctb_log2, uint64_t *sse_cb, uint64_t *sse_cr,
+                                      unsigned sse_stride, size_t sse_frame_stride, void *hip_stream);
+
+/*
+ * Per slice and per frame: sums of an array of the two entries above (or of any uint64_t per CTB).  slice_idx is what
+ * hevcdbk_h265_sao_borders_device and the decision entries take (uint16_t per CTB, idx_stride entries per row, a frame stride of 0 =
+ * shared); NULL = every CTB is in slice 0.  The chroma grids of every chroma format have the luma grid's counts, so the one luma
+ * slice_idx serves each component's array: one call per component.
+ *   - slice_total[f * slice_total_frame_stride + s], s < n_slices = the sum of the frame's entries whose slice index is s; a slice
+ *     with no CTB gets 0.  frame_total[f] = the sum of ALL entries of the frame, CTBs whose index is >= n_slices included.  Either
+ *     output may be NULL, not both.
+ *   - Sums are modulo 2^64; on inputs from the entries above they never wrap (a frame has fewer than 2^32 samples).  One workgroup
+ *     per frame, 64-bit integer adds in LDS -- they commute: the same bits every run; one plain store per output, no global atomics.
+ * Refusals, in this order: NULL ctx / sse or both outputs NULL -- HEVCDBK_ERR_ARG; ctbs_x or ctbs_y of 0 or above 65535 --
+ * HEVCDBK_ERR_DIMENSIONS; sse_stride (idx_stride with slice_idx) below ctbs_x or above 0x7fffffff; n_slices of 0 or above 65536; more
+ * than 65535 frames; slice_total_frame_stride below n_slices with n_frames > 1; sse, slice_total or frame_total at an address that
+ * is no multiple of 8, slice_idx of 2; outputs meeting each other or the input -- HEVCDBK_ERR_ARG; LAST n_slices > 600 --
+ * HEVCDBK_ERR_UNSUPPORTED, the cap of hevcdbk_sao_slice_flags_device for the same reason.
+ */
+HEVCDBK_API int hevcdbk_sse_totals_device(hevcdbk_context *ctx, const uint64_t *sse, unsigned sse_stride, size_t sse_frame_stride,
+                                          unsigned ctbs_x, unsigned ctbs_y, unsigned n_frames, const uint16_t *slice_idx,
+                                          unsigned idx_stride, size_t idx_frame_stride, unsigned n_slices, uint64_t *slice_total,
+                                          size_t slice_total_frame_stride, uint64_t *frame_total, void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif
