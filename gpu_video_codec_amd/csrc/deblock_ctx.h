@@ -2,6 +2,8 @@
  * deblock_ctx.h -- PRIVATE to the library: the context behind `hevcdbk_context *` and the host-side helpers the C-ABI
  * translation units share (deblock_host.cpp: context, plumbing, reference-exact operators, file operators;
  * deblock_host_h265.cpp: spec-exact mode and SAO).  Nothing here is exported (the library is built with hidden visibility).
+ * Of the steps the host-frame operators are made of, those the spec-exact frame entry takes too are declared here (FrameLayout,
+ * crew_copy_frame, set_timing, GpuDrain); the others and the transports themselves are internal to deblock_host.cpp.
  */
 #pragma once
 #include <hip/hip_runtime_api.h>
@@ -76,8 +78,9 @@ inline size_t plane_span(size_t pitch, size_t row_bytes, unsigned h) { return h 
 
 /* Every path out of a host-frame operator that is not HEVCDBK_OK waits for the GPU: kernels and DMAs of earlier strips or frames may
  * still be storing into the ring, the push buffer or the caller's own page-locked planes, and the header promises that transfers
- * have completed when the operators return.  Declared before the crew's scope guard (CrewScope / Scope), so it runs after the
- * crew has been waited for, and before the caller gets its planes back.  Errors are ignored here: the call is failing already. */
+ * have completed when the operators return.  It lives in the entry and the crew's guard (CrewJobs) in the transport function the entry
+ * calls, so it runs after the crew has been waited for, and before the caller gets its planes back.  Errors are ignored here: the call
+ * is failing already. */
 struct GpuDrain {
     hevcdbk_context *ctx;
     bool ok = false; /* set on the way out of a call that succeeded: it has waited for its own work */
@@ -98,10 +101,23 @@ int launch(hevcdbk_context *ctx, const DbkArgs &a0, int sample_bytes, bool chrom
 int ensure_crew(hevcdbk_context *ctx);
 /* fine-grained device memory of at least `bytes` that the host's cores can write (large-BAR devices), or NULL: no such memory here */
 uint8_t *push_buffer(hevcdbk_context *ctx, size_t bytes);
-/* every plane of `frame` (tight rows of pw[i] * sb bytes at base + plane_off[i]) copied by the crew and the calling thread, which
- * returns when all of it is done.  to_frame: base -> the caller's planes, else the caller's planes -> base; base_is_device: base is
- * HBM seen through the BAR (streaming stores, flushed by a read) */
-int crew_copy_frame(hevcdbk_context *ctx, const hevcdbk_frame *frame, int npl, const unsigned *pw, const unsigned *ph, unsigned sb,
-                    uint8_t *base, const size_t *plane_off, bool to_frame, bool base_is_device);
+/* a frame in staging (the reference allocates per call, gpu.cu:1103-1169 + 1236-1244; here it persists): tight rows, the planes one
+ * after the other, each at a multiple of `align` bytes (256: ONE pinned and ONE device buffer, so a small frame moves in one DMA) */
+struct FrameLayout {
+    int npl; unsigned pw[3], ph[3], sb;
+    size_t row_bytes[3], plane_bytes[3], plane_off[3], frame_bytes; /* 0 for the planes a frame does not have */
+};
+FrameLayout frame_layout(int npl, const unsigned *pw, const unsigned *ph, unsigned sb, size_t align = 256);
+/* every plane of `frame` (tight rows at base + L.plane_off[i]) copied by the crew and the calling thread, which returns when all of
+ * it is done.  to_frame: base -> the caller's planes, else the caller's planes -> base; base_is_device: base is HBM seen through the
+ * BAR (streaming stores, flushed by a read) */
+int crew_copy_frame(hevcdbk_context *ctx, const hevcdbk_frame *frame, const FrameLayout &L, uint8_t *base, bool to_frame, bool base_is_device);
+/* the reference's figures of one frame (sums of its serial phases, gpu.cu:1292-1303) and the wall clock of the call; t may be NULL */
+inline void set_timing(hevcdbk_timing *t, double exec_s, double copy_s, double wall_s)
+{
+    if (!t) return;
+    t->exec_s = exec_s; t->copy_s = copy_s; t->total_s = exec_s + copy_s; /* gpu.cu:1302 */
+    t->pipelined_s = wall_s;
+}
 
 } /* namespace dbkh */

@@ -343,16 +343,80 @@ int frame_plane_args(hevcdbk_context *ctx, void *const dplane[3], int k, unsigne
     return planes_to_args(&p, qp->qp, tables, a);
 }
 
-/* true (and the launch is done) when the whole frame went out as ONE fused launch */
-int launch_frame_fused(hevcdbk_context *ctx, const DbkArgs *args, int npl, unsigned sb, hipStream_t s, bool *done)
+/* ---- the steps the host-frame operators are made of, each written once ---- */
+FrameLayout frame_layout(int npl, const unsigned *pw, const unsigned *ph, unsigned sb, size_t align)
+{
+    FrameLayout L{};
+    L.npl = npl; L.sb = sb;
+    for (int i = 0; i < npl; i++) {
+        L.pw[i] = pw[i]; L.ph[i] = ph[i];
+        L.row_bytes[i] = (size_t)pw[i] * sb;
+        L.plane_bytes[i] = L.row_bytes[i] * ph[i];
+        L.plane_off[i] = L.frame_bytes;
+        L.frame_bytes = (L.frame_bytes + L.plane_bytes[i] + align - 1) / align * align;
+    }
+    return L;
+}
+
+/* pack / unpack by the calling thread: plane i between the caller's pitched rows and tight rows at `tight` (tight on both sides: one
+ * copy); copy_frame: every plane, the tight ones at base + L.plane_off[i] */
+static void copy_plane(const hevcdbk_frame &fr, const FrameLayout &L, int i, uint8_t *tight, bool to_frame)
+{
+    const size_t rb = L.row_bytes[i];
+    if (to_frame) copy_rows({(uint8_t *)fr.plane[i], tight, fr.pitch[i], rb, rb, L.ph[i], nullptr}, false);
+    else copy_rows({tight, (const uint8_t *)fr.plane[i], rb, fr.pitch[i], rb, L.ph[i], nullptr}, false);
+}
+static void copy_frame(const hevcdbk_frame &fr, const FrameLayout &L, uint8_t *base, bool to_frame)
+{
+    for (int i = 0; i < L.npl; i++) copy_plane(fr, L, i, base + L.plane_off[i], to_frame);
+}
+
+/* The planes of a frame (or of a batch of frames) on stream s: ONE fused launch where the fused kernel takes them, else one per plane.
+ * ev_begin / ev_end (may be NULL): the first launch stamps its own begin, the last its own end (one stream: the last launch ends
+ * last) -- no marker packets.  The pair is cleared again on every path out. */
+static int launch_frame(hevcdbk_context *ctx, const DbkArgs *args, int npl, unsigned sb, hipStream_t s, hipEvent_t ev_begin = nullptr, hipEvent_t ev_end = nullptr)
 {
     const int sbs[3] = {(int)sb, (int)sb, (int)sb};
-    *done = false;
-    if (!dbk_multi_supports(args, npl, sbs)) return HEVCDBK_OK;
-    if (!hip_ok(ctx, dbk_launch_packed_multi(args, npl, (int)sb, s), "kernel launch")) return HEVCDBK_ERR_HIP;
-    *done = true;
+    if (npl > 1 && dbk_multi_supports(args, npl, sbs)) {
+        dbk_set_next_launch_events(ev_begin, ev_end);
+        const hipError_t e = dbk_launch_packed_multi(args, npl, (int)sb, s);
+        dbk_set_next_launch_events(nullptr, nullptr);
+        return hip_ok(ctx, e, "kernel launch") ? HEVCDBK_OK : HEVCDBK_ERR_HIP;
+    }
+    for (int k = 0; k < npl; k++) {
+        dbk_set_next_launch_events(k == 0 ? ev_begin : nullptr, k == npl - 1 ? ev_end : nullptr);
+        const int rc = launch(ctx, args[k], (int)sb, k != 0, HEVCDBK_KERNEL_AUTO, s);
+        dbk_set_next_launch_events(nullptr, nullptr);
+        if (rc) return rc;
+    }
     return HEVCDBK_OK;
 }
+
+/* has the GPU reached `e`?  Never blocks.  "Not ready" is not an error (and is cleared); any other answer than success is returned. */
+static inline int poll_event(hevcdbk_context *ctx, hipEvent_t e, bool *ready)
+{
+    const hipError_t q = hipEventQuery(e);
+    *ready = q == hipSuccess;
+    if (q == hipErrorNotReady) { (void)hipGetLastError(); return HEVCDBK_OK; }
+    return hip_ok(ctx, q, "hipEventQuery") ? HEVCDBK_OK : HEVCDBK_ERR_HIP;
+}
+
+/* The operand fence: ev[12] behind the bS / QP map upload on h2d, waited for by every stream a kernel of the call may run on.  Nothing
+ * uploaded (the default bS resident, no QP map): nothing is in flight on h2d that a kernel has to wait for, and neither call is made. */
+static inline int fence_operands(hevcdbk_context *ctx, bool uploaded)
+{
+    return !uploaded || hip_ok(ctx, hipEventRecord(ctx->ev[12], ctx->h2d), "hipEventRecord") ? HEVCDBK_OK : HEVCDBK_ERR_HIP;
+}
+static inline int wait_operands(hevcdbk_context *ctx, bool uploaded, hipStream_t s)
+{
+    return !uploaded || hip_ok(ctx, hipStreamWaitEvent(s, ctx->ev[12], 0), "hipStreamWaitEvent") ? HEVCDBK_OK : HEVCDBK_ERR_HIP;
+}
+
+using WallClock = std::chrono::steady_clock::time_point;
+static inline double seconds_since(WallClock t0) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); }
+
+/* the sequence and file forms: the wall clock of the whole run, the per-frame figures zero */
+static void set_timing_pipelined(hevcdbk_timing *t, double wall_s) { set_timing(t, 0.0, 0.0, wall_s); }
 
 /* threads that copy during a large pageable frame, the caller included: what the context was told (hevcdbk_set_host_threads), else 4
  * (tools/ubench/host_stage.hip: the box's staging rate stops growing between 4 and 8 threads).  The product reads no environment;
@@ -492,11 +556,42 @@ uint8_t *push_buffer(hevcdbk_context *ctx, size_t bytes)
     return (uint8_t *)ctx->dev_push.p;
 }
 
-int crew_copy_frame(hevcdbk_context *ctx, const hevcdbk_frame *frame, int npl, const unsigned *pw, const unsigned *ph, unsigned sb,
-                    uint8_t *base, const size_t *plane_off, bool to_frame, bool base_is_device)
+/* The copy groups of a transport, one per strip (or frame) and direction.  Every path out of the transport waits for the jobs it handed out
+ * (they point into gin / gout) and puts the crew to sleep.  It lives in the transport function: the entry's GpuDrain runs after it. */
+struct CrewJobs {
+    StageCrew *crew; /* NULL: nothing is handed out */
+    size_t n;
+    std::unique_ptr<CopyGroup[]> gin, gout;
+    CrewJobs(StageCrew *c, size_t n_) : crew(c), n(n_), gin(new CopyGroup[n_]), gout(new CopyGroup[n_]) {}
+    ~CrewJobs() { if (!crew) return; for (size_t k = 0; k < n; k++) { crew->wait(gin[k]); crew->wait(gout[k]); } crew->end(); }
+};
+
+/* into how many pieces a row range of `bytes` is cut for the crew: pieces of at least min_piece bytes, `most` of them at the most */
+static inline unsigned piece_count(size_t bytes, size_t min_piece, unsigned most)
+{
+    const unsigned pieces = (unsigned)(bytes / min_piece);
+    return pieces < 1 ? 1 : pieces > most ? most : pieces;
+}
+
+/* Rows [r0, r1) of plane i as `pieces` jobs of group g (its pending count set by the caller) between the caller's plane and tight rows, row 0
+ * at `tight` (to_device: HBM seen through the BAR): to_frame = out, on the crew's second lane.  No crew: this thread copies here and now. */
+static void submit_rows(StageCrew *crew, CopyGroup &g, const hevcdbk_frame &fr, const FrameLayout &L, int i, uint8_t *tight, bool to_frame,
+                 bool to_device, unsigned r0, unsigned r1, unsigned pieces)
+{
+    const size_t rb = L.row_bytes[i], pitch = fr.pitch[i];
+    for (unsigned p = 0; p < pieces; p++) {
+        const unsigned a = r0 + (unsigned)((uint64_t)(r1 - r0) * p / pieces), b = r0 + (unsigned)((uint64_t)(r1 - r0) * (p + 1) / pieces);
+        uint8_t *inner = tight + (size_t)a * rb, *user = (uint8_t *)fr.plane[i] + (size_t)a * pitch;
+        const CopyJob j = to_frame ? CopyJob{user, inner, pitch, rb, rb, b - a, &g, false} : CopyJob{inner, user, rb, pitch, rb, b - a, &g, to_device};
+        if (crew) crew->submit(j, to_frame ? StageCrew::LANE_OUT : StageCrew::LANE_IN);
+        else copy_rows(j, true);
+    }
+}
+
+int crew_copy_frame(hevcdbk_context *ctx, const hevcdbk_frame *frame, const FrameLayout &L, uint8_t *base, bool to_frame, bool base_is_device)
 {
     size_t total = 0;
-    for (int i = 0; i < npl; i++) total += (size_t)pw[i] * ph[i] * sb;
+    for (int i = 0; i < L.npl; i++) total += L.plane_bytes[i];
     /* below 1 MiB waking the crew costs more than it saves: the calling thread copies alone */
     const bool threads = total >= ((size_t)1 << 20);
     if (threads)
@@ -504,28 +599,11 @@ int crew_copy_frame(hevcdbk_context *ctx, const hevcdbk_frame *frame, int npl, c
     StageCrew *crew = threads ? ctx->crew : nullptr;
     const unsigned crew_n = crew && crew->workers() ? crew->workers() + 1 : 1;
     CopyGroup g;
-    std::vector<CopyJob> jobs;
-    for (int i = 0; i < npl; i++) {
-        const size_t rb = (size_t)pw[i] * sb;
-        unsigned pieces = (unsigned)((rb * ph[i]) / ((size_t)256 << 10));
-        pieces = pieces < 1 ? 1 : pieces > 4 * crew_n ? 4 * crew_n : pieces;
-        for (unsigned p = 0; p < pieces; p++) {
-            const unsigned a = (unsigned)((uint64_t)ph[i] * p / pieces), b = (unsigned)((uint64_t)ph[i] * (p + 1) / pieces);
-            if (a == b) continue;
-            uint8_t *inner = base + plane_off[i] + (size_t)a * rb, *user = (uint8_t *)frame->plane[i] + (size_t)a * frame->pitch[i];
-            if (to_frame) jobs.push_back({user, inner, frame->pitch[i], rb, rb, b - a, &g, false});
-            else jobs.push_back({inner, user, rb, frame->pitch[i], rb, b - a, &g, base_is_device});
-        }
-    }
-    if (!crew) {
-        for (const CopyJob &j : jobs) copy_rows(j, true);
-        return HEVCDBK_OK;
-    }
-    g.pending.store((int)jobs.size(), std::memory_order_release);
-    crew->begin();
-    for (const CopyJob &j : jobs) crew->submit(j, to_frame ? StageCrew::LANE_OUT : StageCrew::LANE_IN);
-    crew->wait(g); /* this thread copies too */
-    crew->end();
+    unsigned pieces[3] = {0, 0, 0}, n = 0;
+    for (int i = 0; i < L.npl; i++) n += pieces[i] = piece_count(L.plane_bytes[i], (size_t)256 << 10, 4 * crew_n);
+    if (crew) { g.pending.store((int)n, std::memory_order_release); crew->begin(); }
+    for (int i = 0; i < L.npl; i++) submit_rows(crew, g, *frame, L, i, base + L.plane_off[i], to_frame, base_is_device, 0, L.ph[i], pieces[i]);
+    if (crew) { crew->wait(g); crew->end(); } /* this thread copies too */
     return HEVCDBK_OK;
 }
 
@@ -1052,7 +1130,357 @@ int hevcdbk_device_pci_bus_id(const hevcdbk_context *ctx, char *buf, size_t len)
     return HEVCDBK_OK;
 }
 
-/* ---- host-frame operator ---- */
+/* ---- host-frame operator: the entry prepares a call and chooses one of three transports ---- */
+
+} /* extern "C": the transports are C++ */
+
+namespace {
+
+/* what hevc_deblocking_filter has prepared when it chooses the transport: staging for a frame of layout L, the operands on their way on h2d */
+struct FrameCall {
+    hevcdbk_context *ctx;
+    hevcdbk_frame *frame;
+    const hevcdbk_qp *qp; const hevcdbk_tables *tables;
+    hevcdbk_timing *timing; /* may be NULL */
+    const FrameLayout &L; /* the entry's own: no copy */
+    explicit FrameCall(const FrameLayout &l) : L(l) {}
+    DbkArgs args[3];        /* the planes where they lie in ctx->dev[0] */
+    const uint8_t *dmap;    /* the QP map on the device, or NULL */
+    bool operands_uploaded; /* else nothing is in flight on h2d that a kernel has to wait for */
+    WallClock wall0;
+};
+
+/*
+ * Small frame: no DMA at all.  The staging buffer is page-locked, fine-grained host memory the GPU can address, so
+ * the fused kernel reads and writes it across PCIe itself -- both directions at once, no copy set-up latency
+ * (352x288: 50 us per call against 82 us with a DMA each way; 1280x720: 182 against 230 us).  The reference's
+ * "copy" figure is therefore 0 for such frames and its "exec" figure contains the PCIe traffic.
+ */
+int small_direct(FrameCall &c)
+{
+    hevcdbk_context *ctx = c.ctx;
+    const hevcdbk_frame *frame = c.frame;
+    const FrameLayout &L = c.L;
+    const unsigned sb = L.sb;
+    hipEvent_t *ev = ctx->ev; /* 4..5 kernel */
+    uint8_t *const ring = (uint8_t *)ctx->pin[0].p;
+    /* planes that are page-locked caller memory themselves (and word aligned) need no staging either */
+    bool direct = true;
+    void *kplane[3] = {nullptr, nullptr, nullptr}; /* the planes as a kernel addresses them */
+    for (int i = 0; i < L.npl && direct; i++)
+        direct = frame->pitch[i] % (4 * sb) == 0 && (uintptr_t)frame->plane[i] % (4 * sb) == 0 &&
+                 is_pinned_host(ctx, frame->plane[i], plane_span(frame->pitch[i], L.row_bytes[i], L.ph[i]), &kplane[i]) && kplane[i] != nullptr;
+    if (!direct) copy_frame(*frame, L, ring, false);
+    void *hp[3];
+    for (int i = 0; i < 3; i++) hp[i] = direct ? kplane[i] : (void *)(ring + L.plane_off[i]);
+    DbkArgs ha[3];
+    for (int i = 0; i < L.npl; i++)
+        if (int rc = frame_plane_args(ctx, hp, i, frame->width, frame->height, frame->bit_depth, sb, true, c.qp, c.dmap, c.tables, ha[i],
+                                      direct ? frame->pitch : nullptr))
+            return rc;
+    /* The reference's own case (352x288, README.md:19-24) is all fixed costs, so they are counted: no cross-stream wait when the
+     * default bS is resident and there is no QP map (nothing was uploaded); the launch stamps its own begin and end into
+     * ev[4] / ev[5] (no marker packets, two HIP calls fewer); and this thread polls the end event instead of sleeping in a
+     * stream synchronisation (round 4: 52 -> about 40 us per call).  Operands the fused launch does not take after all (alignment of
+     * the caller's planes) go plane by plane. */
+    if (int rc = wait_operands(ctx, c.operands_uploaded, ctx->compute)) return rc;
+    if (int rc = launch_frame(ctx, ha, L.npl, sb, ctx->compute, ev[4], ev[5])) return rc;
+    for (bool ready = false; !ready;) {
+        if (int rc = poll_event(ctx, ev[5], &ready)) return rc;
+        if (!ready) _mm_pause();
+    }
+    if (!direct) copy_frame(*frame, L, ring, true);
+    if (c.timing) {
+        float ms = 0.f;
+        HIP_TRY(ctx, hipEventElapsedTime(&ms, ev[4], ev[5]));
+        set_timing(c.timing, ms * 1e-3, 0.0, seconds_since(c.wall0));
+    }
+    return HEVCDBK_OK;
+}
+
+/* Small frame through DMA copies around the kernel (the diagnostic build's "dmacopy", for A/B runs): one H2D, one fused launch, one
+ * D2H, all on the compute stream (no cross-stream events to pay for) */
+int small_dma(FrameCall &c)
+{
+    hevcdbk_context *ctx = c.ctx;
+    const FrameLayout &L = c.L;
+    hipEvent_t *ev = ctx->ev; /* 1..4 h2d ; 4..5 kernel ; 5..9 d2h */
+    /* pack the caller's pitched planes into the pinned staging buffer */
+    copy_frame(*c.frame, L, (uint8_t *)ctx->pin[0].p, false);
+    if (int rc = wait_operands(ctx, c.operands_uploaded, ctx->compute)) return rc; /* the bS upload, if there was one */
+    HIP_TRY(ctx, hipEventRecord(ev[1], ctx->compute));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->dev[0].p, ctx->pin[0].p, L.frame_bytes, hipMemcpyHostToDevice, ctx->compute));
+    HIP_TRY(ctx, hipEventRecord(ev[4], ctx->compute));
+    if (int rc = launch_frame(ctx, c.args, L.npl, L.sb, ctx->compute)) return rc;
+    HIP_TRY(ctx, hipEventRecord(ev[5], ctx->compute));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->pin[0].p, ctx->dev[0].p, L.frame_bytes, hipMemcpyDeviceToHost, ctx->compute));
+    HIP_TRY(ctx, hipEventRecord(ev[9], ctx->compute));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->compute));
+    /* un-stage, and the reference's three figures from the events around its three steps */
+    copy_frame(*c.frame, L, (uint8_t *)ctx->pin[0].p, true);
+    const double wall = seconds_since(c.wall0);
+    if (c.timing) {
+        float h2d = 0.f, d2h = 0.f, ms = 0.f;
+        HIP_TRY(ctx, hipEventElapsedTime(&h2d, ev[1], ev[4]));
+        HIP_TRY(ctx, hipEventElapsedTime(&d2h, ev[5], ev[9]));
+        HIP_TRY(ctx, hipEventElapsedTime(&ms, ev[4], ev[5]));
+        set_timing(c.timing, ms * 1e-3, ((double)h2d + d2h) * 1e-3, wall);
+    }
+    return HEVCDBK_OK;
+}
+
+struct Strip { int plane, b0, b1; unsigned r0, r1; };
+
+/* strips: `first` bytes (256 KiB), then doubling up to `mid` (1.5 MiB when a copy-out rides along -- the crew, the link and the
+ * un-staging then work on three different strips at any time -- 2 MiB when the link works alone: zc[i], a plane DMA'd where it lies),
+ * the last `mid` of a frame cut in two so that little is left to do when the last transfer ends */
+std::vector<Strip> strip_table(const FrameLayout &L, const bool *zc, size_t first, size_t mid_staged, size_t mid_locked)
+{
+    std::vector<Strip> strips;
+    size_t target = first;
+    for (int i = 0; i < L.npl; i++) {
+        const size_t rb = L.row_bytes[i], mid = zc[i] ? mid_locked : mid_staged;
+        const int nby = (int)(L.ph[i] / 8 + 1);
+        bool cut_tail = i == L.npl - 1; /* once, at the end of the frame */
+        for (int b0 = 0; b0 < nby;) {
+            int per = (int)(((target < mid ? target : mid) / rb) / 8);
+            per = per < 1 ? 1 : per;
+            const int left = nby - b0;
+            int take = per;
+            if (left <= per + per / 2) { /* no sliver at the end of a plane */
+                take = left;
+                if (cut_tail && left > 2 && target >= mid) take = (2 * left + 2) / 3;
+                cut_tail = false;
+            }
+            const int b1 = b0 + take;
+            const unsigned r0 = b0 == 0 ? 0u : (unsigned)(8 * b0 - 4), r1 = b1 == nby ? L.ph[i] : (unsigned)(8 * b1 - 4);
+            strips.push_back({i, b0, b1, r0, r1});
+            b0 = b1;
+            if (target < mid) target *= 2;
+        }
+    }
+    return strips;
+}
+
+/* the strips transport while it runs: what enqueueing a strip has to know */
+struct StripRun {
+    explicit StripRun(FrameCall &call) : c(call) {}
+    FrameCall &c;
+    std::vector<Strip> strips;
+    bool zc[3] = {false, false, false};             /* plane i is page-locked caller memory: DMA'd where it lies */
+    uint8_t *kout[3] = {nullptr, nullptr, nullptr}; /* where the kernel of plane i writes (device-side address), NULL = HBM + DMA */
+    uint8_t *dpush = nullptr;                       /* the crew writes the frame into HBM through the BAR, NULL = ring + DMA */
+    /* experiments of the diagnostic build (profiles/r04/experiments.md): all off in the product */
+    bool x_direct_in = false; int x_h2d_streams = 1, x_k_streams = 1;
+    hipEvent_t *te = nullptr; /* per strip: h2d start/end, kernel start/end, d2h start/end */
+    int64_t ns0 = 0;
+    double since(int64_t t) const { return t ? (double)(t - ns0) * 1e-9 : 0.0; }
+    int dma(const Strip &st, bool to_host, hipStream_t s);
+    int enqueue(CrewJobs &jobs, size_t k);
+};
+
+/* the strip's DMA between the host -- the caller's page-locked plane where it lies (pitched rows: a 2-D copy), else the ring -- and HBM */
+int StripRun::dma(const Strip &st, bool to_host, hipStream_t s)
+{
+    hevcdbk_context *ctx = c.ctx;
+    const int i = st.plane;
+    const size_t rb = c.L.row_bytes[i], off = c.L.plane_off[i] + (size_t)st.r0 * rb, hpitch = zc[i] ? c.frame->pitch[i] : rb;
+    uint8_t *dev = (uint8_t *)ctx->dev[0].p + off;
+    uint8_t *host = zc[i] ? (uint8_t *)c.frame->plane[i] + (size_t)st.r0 * hpitch : (uint8_t *)ctx->pin[0].p + off;
+    const hipMemcpyKind kind = to_host ? hipMemcpyDeviceToHost : hipMemcpyHostToDevice;
+    if (hpitch != rb)
+        HIP_TRY(ctx, hipMemcpy2DAsync(to_host ? host : dev, to_host ? hpitch : rb, to_host ? dev : host, to_host ? rb : hpitch, rb, st.r1 - st.r0, kind, s));
+    else
+        HIP_TRY(ctx, hipMemcpyAsync(to_host ? host : dev, to_host ? dev : host, (size_t)(st.r1 - st.r0) * rb, kind, s));
+    return HEVCDBK_OK;
+}
+
+int StripRun::enqueue(CrewJobs &jobs, size_t k)
+{
+    hevcdbk_context *ctx = c.ctx;
+    const Strip &st = strips[k];
+    const int i = st.plane;
+    const bool timing = c.timing != nullptr;
+    hevcdbk_strip_trace &tr = ctx->trace[k];
+    tr.plane = i; tr.row_begin = st.r0; tr.row_end = st.r1; tr.bytes = (size_t)(st.r1 - st.r0) * c.L.row_bytes[i];
+    if (dpush || !zc[i]) {
+        tr.stage_begin_s = since(jobs.gin[k].first_ns.load());
+        tr.stage_end_s = since(jobs.gin[k].done_ns.load());
+    }
+    tr.enqueue_begin_s = since(crew_now_ns());
+    const bool pushed = dpush != nullptr; /* the strip is in HBM already: the crew wrote it there */
+    const bool din = pushed || (x_direct_in && kout[i]); /* (experiment: the kernel reads the page-locked strip itself) */
+    hipStream_t hs = x_h2d_streams == 2 && (k & 1) ? ctx->d2h : ctx->h2d;
+    hipStream_t ks = x_k_streams == 2 && (k & 1) ? ctx->d2h : ctx->compute;
+    if (!din) {
+        if (timing) HIP_TRY(ctx, hipEventRecord(te[6 * k + 0], hs));
+        if (int rc = dma(st, false, hs)) return rc;
+        HIP_TRY(ctx, hipEventRecord(te[6 * k + 1], hs));
+        HIP_TRY(ctx, hipStreamWaitEvent(ks, te[6 * k + 1], 0));
+    }
+    DbkArgs sa = c.args[i];
+    sa.by_begin = st.b0; sa.by_count = st.b1 - st.b0;
+    if (kout[i]) sa.dst = kout[i]; /* src: the strip in HBM; dst: page-locked host memory, same pitch */
+    if (pushed) sa.src = dpush + c.L.plane_off[i];
+    else if (din) sa.src = kout[i];
+    /* the launch stamps its own begin and end into the strip's events (one kernel per launch() in this library): no marker
+     * packets around the kernels, whose chain is what the frame waits for */
+    dbk_set_next_launch_events(timing ? te[6 * k + 2] : nullptr, te[6 * k + 3]);
+    const int lrc = launch(ctx, sa, (int)c.L.sb, i != 0, HEVCDBK_KERNEL_AUTO, ks);
+    dbk_set_next_launch_events(nullptr, nullptr);
+    if (lrc) return lrc;
+    if (!kout[i]) {
+        HIP_TRY(ctx, hipStreamWaitEvent(ctx->d2h, te[6 * k + 3], 0));
+        if (timing) HIP_TRY(ctx, hipEventRecord(te[6 * k + 4], ctx->d2h));
+        if (int rc = dma(st, true, ctx->d2h)) return rc;
+        HIP_TRY(ctx, hipEventRecord(te[6 * k + 5], ctx->d2h));
+    }
+    tr.enqueue_end_s = since(crew_now_ns());
+    return HEVCDBK_OK;
+}
+
+/*
+ * Large frame: strip pipeline.  Image rows 8b-4 .. 8b+3 belong to block row b and to no other, so a plane splits
+ * into strips of whole block rows with no halo; strip s is uploaded, filtered (a launch over its block rows only)
+ * and downloaded while strip s+1 is being packed / uploaded and strip s-1 downloaded: the two DMA directions, the
+ * kernels and the host-side staging copies all overlap inside ONE frame.  The first strips are short (the link is
+ * idle until the first one has been staged), later ones long enough for the DMA engines to reach their rate
+ * (tools/ubench/host_stage.hip: one 512 KiB DMA 19 us, 2 MiB 46 us, 8.3 MB 155 us).  Pageable planes are staged
+ * by the context's crew of host threads (host_crew.h) while this thread feeds the three streams.
+ */
+int strips(FrameCall &c)
+{
+    hevcdbk_context *ctx = c.ctx;
+    const hevcdbk_frame *frame = c.frame;
+    const FrameLayout &L = c.L;
+    StripRun r(c);
+    /* planes in page-locked caller memory (hevcdbk_host_malloc_pinned) are DMA'd where they lie -- not for small frames,
+     * where one DMA of the packed staging buffer beats three DMAs of the caller's planes (they never get here) */
+    for (int i = 0; i < L.npl; i++) r.zc[i] = is_pinned_host(ctx, frame->plane[i], plane_span(frame->pitch[i], L.row_bytes[i], L.ph[i]));
+    /* The kernel writes its results straight into page-locked host memory -- the ring, or the caller's own page-locked plane when its
+     * rows are tight -- instead of into HBM with a D2H DMA behind it: posted writes across the link run at the DMA engines' rate
+     * (tools/ubench/host_stage.hip: 8.3 MB in 0.159 ms against 0.156 ms), and a DMA's set-up, two events and a cross-stream wait
+     * per strip disappear from the chain.  Pitched page-locked planes keep the 2-D DMA. */
+    const bool direct_out = crew_knob("HEVCDBK_HOST_DIRECT_OUT", true);
+    r.x_direct_in = crew_knob("HEVCDBK_HOST_DIRECT_IN", false);
+    r.x_h2d_streams = crew_knob("HEVCDBK_HOST_H2D_STREAMS2", false) ? 2 : 1;
+    r.x_k_streams = crew_knob("HEVCDBK_HOST_K_STREAMS2", false) ? 2 : 1;
+    const bool x_on_d2h = r.x_direct_in || r.x_h2d_streams == 2 || r.x_k_streams == 2; /* the experiments that put ev[12]'s wait or work of their own on d2h */
+    /* The bS / QP map upload (issued on h2d by the entry, ev[12] behind it) comes first on every stream a strip's kernel may run on.
+     * With H2D DMAs the strips' own events on h2d implied it; a strip the crew writes through the BAR has no such event, and
+     * its kernel would otherwise be free to start before a caller's bS array or QP map has arrived. */
+    if (int rc = wait_operands(ctx, c.operands_uploaded, ctx->compute)) return rc;
+    if (x_on_d2h)
+        if (int rc = wait_operands(ctx, c.operands_uploaded, ctx->d2h)) return rc;
+    /* Pageable planes on a large-BAR device: the crew writes the caller's rows straight into HBM through the BAR (posted writes,
+     * tools/ubench/bar_write.hip: 37-43 GB/s from one or two cores, as fast as filling the ring) -- no ring on the way in and no
+     * H2D DMA with its set-up, event and cross-stream wait per strip.  The buffer is fine-grained device memory, so no cache of the
+     * GPU holds a line of it across launches. */
+    const bool push_in = direct_out && crew_knob("HEVCDBK_HOST_PUSH", true);
+    bool any_staged = false;
+    for (int i = 0; i < L.npl; i++) {
+        any_staged |= !r.zc[i];
+        if (!direct_out) continue;
+        const size_t rb = L.row_bytes[i];
+        void *dp = nullptr;
+        if (!r.zc[i]) r.kout[i] = (uint8_t *)ctx->pin[0].p + L.plane_off[i]; /* hipHostMalloc memory: one address for host and device */
+        else if (frame->pitch[i] == rb && (uintptr_t)frame->plane[i] % (4 * L.sb) == 0 && is_pinned_host(ctx, frame->plane[i], rb * L.ph[i], &dp) && dp)
+            r.kout[i] = (uint8_t *)dp;
+    }
+    r.strips = strip_table(L, r.zc, crew_first_strip_bytes((size_t)256 << 10), crew_strip_bytes((size_t)3 << 19), crew_strip_bytes((size_t)2 << 20));
+    const size_t ns = r.strips.size();
+    if (int rc = ensure_timed_events(ctx, 6 * ns)) return rc;
+    r.te = ctx->timed_events.data();
+    StageCrew *crew = nullptr;
+    if (any_staged || push_in) { /* page-locked caller planes are pushed too: faster than a chain of DMAs for ONE frame */
+        if (int rc = ensure_crew(ctx)) return rc;
+        crew = ctx->crew;
+        if (push_in) r.dpush = push_buffer(ctx, L.frame_bytes); /* NULL: no such memory here -> ring + DMA */
+    }
+    CrewJobs jobs(crew, ns);
+    r.ns0 = std::chrono::duration_cast<std::chrono::nanoseconds>(c.wall0.time_since_epoch()).count();
+    ctx->trace.assign(ns, hevcdbk_strip_trace{});
+    /* a strip as row-range jobs for the crew: in = caller plane -> HBM (BAR) or ring, out = ring -> caller plane */
+    auto hand_out = [&](size_t k, bool in) {
+        const Strip &st = r.strips[k];
+        /* pieces of at least 128 KiB: as many as there are crew threads -- two for writes through the BAR, which two cores saturate */
+        const unsigned crew_n = crew->workers() ? crew->workers() : 1, most = in && r.dpush && crew_n > 2 ? 2 : crew_n;
+        const unsigned pieces = piece_count((size_t)(st.r1 - st.r0) * L.row_bytes[st.plane], (size_t)128 << 10, most);
+        CopyGroup &g = in ? jobs.gin[k] : jobs.gout[k];
+        g.pending.store((int)pieces, std::memory_order_release);
+        uint8_t *tight = (in && r.dpush ? r.dpush : (uint8_t *)ctx->pin[0].p) + L.plane_off[st.plane];
+        submit_rows(crew, g, *frame, L, st.plane, tight, !in, in && r.dpush, st.r0, st.r1, pieces);
+    };
+    /*
+     * One loop feeds everything, in strip order.  The copies-in of the whole frame go to the crew's first lane at once, so they run
+     * without a pause from the first microsecond; a strip whose copy-in is complete is handed to the runtime; a strip whose results
+     * have landed (event query, no blocking) goes to the crew's second lane for its copy-out.  This thread copies too until it has
+     * something to launch (the crew is still waking up then) and whenever there are no crew threads (hevcdbk_set_host_threads 1).
+     */
+    if (crew) crew->begin();
+    const bool alone = !crew || crew->workers() == 0;
+    size_t n_launched = 0, n_out = 0;
+    bool helped_once = false;
+    if (crew)
+        for (size_t k = 0; k < ns; k++)
+            if (r.dpush || !r.zc[r.strips[k].plane]) hand_out(k, true);
+    while (n_out < ns) {
+        bool progress = false;
+        if (n_launched < ns && ((!r.dpush && r.zc[r.strips[n_launched].plane]) || jobs.gin[n_launched].pending.load(std::memory_order_acquire) == 0)) {
+            if (int rc = r.enqueue(jobs, n_launched)) return rc;
+            n_launched++;
+            progress = true;
+        }
+        if (n_out < n_launched) {
+            bool landed = false;
+            if (int rc = poll_event(ctx, r.te[6 * n_out + (r.kout[r.strips[n_out].plane] ? 3 : 5)], &landed)) return rc;
+            if (landed) {
+                ctx->trace[n_out].d2h_seen_s = r.since(crew_now_ns());
+                if (!r.zc[r.strips[n_out].plane]) hand_out(n_out, false);
+                n_out++;
+                progress = true;
+            }
+        }
+        if (progress) continue;
+        if (crew && (alone || !helped_once)) { /* the one job: the first piece of the first strip, while the crew wakes up */
+            helped_once = true;
+            if (crew->help()) continue;
+        }
+        _mm_pause();
+    }
+    for (size_t k = 0; k < ns; k++)
+        if (!r.zc[r.strips[k].plane]) {
+            crew->wait(jobs.gout[k]);
+            ctx->trace[k].unstage_begin_s = r.since(jobs.gout[k].first_ns.load());
+            ctx->trace[k].unstage_end_s = r.since(jobs.gout[k].done_ns.load());
+        }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->compute));
+    if (x_on_d2h) HIP_TRY(ctx, hipStreamSynchronize(ctx->d2h));
+    const double wall = seconds_since(c.wall0);
+    if (!c.timing) return HEVCDBK_OK;
+    double copy = 0.0, exec = 0.0, push_covered = 0.0;
+    for (size_t k = 0; k < ns; k++) {
+        const int i = r.strips[k].plane;
+        float ms = 0.f;
+        if (r.dpush) { /* the upload was the crew's stores through the BAR: host clock, the time during
+                                                which at least one strip was being written (strips overlap) */
+            const double b = ctx->trace[k].stage_begin_s, e = ctx->trace[k].stage_end_s;
+            if (e > push_covered) copy += (e - (b > push_covered ? b : push_covered)) * 1e3;
+            if (e > push_covered) push_covered = e;
+        } else if (!(r.x_direct_in && r.kout[i])) {
+            HIP_TRY(ctx, hipEventElapsedTime(&ms, r.te[6 * k + 0], r.te[6 * k + 1])); copy += ms; ctx->trace[k].h2d_ms = ms;
+        }
+        HIP_TRY(ctx, hipEventElapsedTime(&ms, r.te[6 * k + 2], r.te[6 * k + 3])); exec += ms; ctx->trace[k].kernel_ms = ms;
+        if (r.kout[i]) continue; /* the download is the kernel's own stores: part of exec_s */
+        HIP_TRY(ctx, hipEventElapsedTime(&ms, r.te[6 * k + 4], r.te[6 * k + 5])); copy += ms; ctx->trace[k].d2h_ms = ms;
+    }
+    set_timing(c.timing, exec * 1e-3, copy * 1e-3, wall); /* the reference's figures are sums of its serial phases (gpu.cu:1292-1303) */
+    return HEVCDBK_OK;
+}
+
+} /* namespace */
+
+extern "C" {
 
 int hevc_deblocking_filter(hevcdbk_context *ctx, hevcdbk_frame *frame, const hevcdbk_bs *bs,
                            const hevcdbk_qp *qp, const hevcdbk_tables *tables, hevcdbk_timing *timing)
@@ -1061,726 +1489,57 @@ int hevc_deblocking_filter(hevcdbk_context *ctx, hevcdbk_frame *frame, const hev
     bool chroma = false;
     if (int rc = check_frame(*frame, chroma)) return rc;
     const unsigned W = frame->width, H = frame->height, sb = frame->sample_bytes;
-    const int npl = chroma ? 3 : 1;
     const unsigned pw[3] = {W, W / 2, W / 2}, ph[3] = {H, H / 2, H / 2};
     if (int rc = check_bs(bs, W, H, chroma)) return rc;
     if (int rc = bind(ctx)) return rc;
     GpuDrain drain{ctx}; /* every return below that is not HEVCDBK_OK waits for the GPU */
-
-    /* staging (the reference allocates per call, gpu.cu:1103-1169 + 1236-1244; here it persists): the planes sit
-     * one after the other, 256-byte aligned, in ONE pinned and ONE device buffer, so a small frame moves in one DMA */
-    size_t plane_bytes[3] = {0, 0, 0}, plane_off[3] = {0, 0, 0}, frame_bytes = 0;
-    for (int i = 0; i < npl; i++) {
-        plane_bytes[i] = (size_t)pw[i] * ph[i] * sb;
-        plane_off[i] = frame_bytes;
-        frame_bytes = (frame_bytes + plane_bytes[i] + 255) & ~(size_t)255;
-    }
+    const FrameLayout L = frame_layout(chroma ? 3 : 1, pw, ph, sb);
+    FrameCall c(L);
+    c.ctx = ctx; c.frame = frame; c.qp = qp; c.tables = tables; c.timing = timing;
     ctx->trace.clear();
-    if (int rc = grow_pinned(ctx, ctx->pin[0], frame_bytes)) return rc;
-    if (int rc = grow_device(ctx, ctx->dev[0], frame_bytes)) return rc;
-    uint8_t *hplane[3], *dplane_b[3];
-    for (int i = 0; i < 3; i++) {
-        hplane[i] = (uint8_t *)ctx->pin[0].p + plane_off[i];
-        dplane_b[i] = (uint8_t *)ctx->dev[0].p + plane_off[i];
-    }
-    const uint8_t *dmap = nullptr;
+    if (int rc = grow_pinned(ctx, ctx->pin[0], L.frame_bytes)) return rc;
+    if (int rc = grow_device(ctx, ctx->dev[0], L.frame_bytes)) return rc;
+    c.dmap = nullptr;
     size_t map_rows = 0;
     if (qp->map) {
         if (qp->ctu_log2 < 3 || qp->ctu_log2 > 8 || qp->map_stride < ((W + (1u << qp->ctu_log2) - 1) >> qp->ctu_log2))
             return HEVCDBK_ERR_ARG;
         map_rows = (H + (1u << qp->ctu_log2) - 1) >> qp->ctu_log2;
         if (int rc = grow_device(ctx, ctx->dev_map, map_rows * qp->map_stride)) return rc;
-        dmap = (const uint8_t *)ctx->dev_map.p;
+        c.dmap = (const uint8_t *)ctx->dev_map.p;
     }
-
-    const auto wall0 = std::chrono::steady_clock::now();
-    DbkArgs args[3];
-    void *dplane[3] = {dplane_b[0], dplane_b[1], dplane_b[2]};
-
-    /* events of the small-frame path: 12 bS / QP map uploaded ; 1..4 h2d ; 4..5 kernel ; 5..9 d2h */
-    hipEvent_t *ev = ctx->ev;
+    c.wall0 = std::chrono::steady_clock::now();
     bool bs_uploaded = false;
     if (int rc = stage_bs(ctx, W, H, chroma, bs, ctx->h2d, &bs_uploaded)) return rc;
-    if (dmap) HIP_TRY(ctx, hipMemcpyAsync((void *)dmap, qp->map, map_rows * qp->map_stride, hipMemcpyHostToDevice, ctx->h2d));
-    const bool operands_uploaded = bs_uploaded || dmap != nullptr; /* else nothing is in flight on h2d that a kernel has to wait for */
-    if (operands_uploaded) HIP_TRY(ctx, hipEventRecord(ev[12], ctx->h2d)); /* every kernel of this call waits for it */
-    for (int i = 0; i < npl; i++)
-        if (int rc = frame_plane_args(ctx, dplane, i, W, H, frame->bit_depth, sb, chroma, qp, dmap, tables, args[i])) return rc;
-
-    /* Small 4:2:0 frames (8-bit or 16-bit containers), where a DMA or a launch costs more than the work it carries: one H2D, one fused
-     * launch, one D2H, all on the compute stream (no cross-stream events to pay for). */
+    if (c.dmap) HIP_TRY(ctx, hipMemcpyAsync((void *)c.dmap, qp->map, map_rows * qp->map_stride, hipMemcpyHostToDevice, ctx->h2d));
+    c.operands_uploaded = bs_uploaded || c.dmap != nullptr;
+    if (int rc = fence_operands(ctx, c.operands_uploaded)) return rc; /* every kernel of this call waits for it */
+    void *dplane[3];
+    for (int i = 0; i < 3; i++) dplane[i] = (uint8_t *)ctx->dev[0].p + L.plane_off[i];
+    for (int i = 0; i < L.npl; i++)
+        if (int rc = frame_plane_args(ctx, dplane, i, W, H, frame->bit_depth, sb, chroma, qp, c.dmap, tables, c.args[i])) return rc;
+    /* Small 4:2:0 frames (8-bit or 16-bit containers), where a DMA or a launch costs more than the work it carries, take one fused
+     * launch with no DMA around it (small_direct); everything else is cut into strips. */
     const int sbs[3] = {(int)sb, (int)sb, (int)sb};
-    const bool small = chroma && frame_bytes <= ((size_t)2 << 20) && dbk_multi_supports(args, npl, sbs);
-    /* planes in page-locked caller memory (hevcdbk_host_malloc_pinned) are DMA'd where they lie -- not for small frames,
-     * where one DMA of the packed staging buffer beats three DMAs of the caller's planes */
-    bool zc[3] = {false, false, false};
-    if (!small)
-        for (int i = 0; i < npl; i++) zc[i] = is_pinned_host(ctx, frame->plane[i], plane_span(frame->pitch[i], (size_t)pw[i] * sb, ph[i]));
+    const bool small = chroma && L.frame_bytes <= ((size_t)2 << 20) && dbk_multi_supports(c.args, L.npl, sbs);
 #ifdef HEVCDBK_DIAG /* "dmacopy": small frames through DMA copies around the kernel instead (for A/B runs) */
     const bool host_direct = !g_dbk_diag.dmacopy;
 #else
     constexpr bool host_direct = true;
 #endif
-    if (small && host_direct) {
-        /*
-         * Small frame: no DMA at all.  The staging buffer is page-locked, fine-grained host memory the GPU can address, so
-         * the fused kernel reads and writes it across PCIe itself -- both directions at once, no copy set-up latency
-         * (352x288: 50 us per call against 82 us with a DMA each way; 1280x720: 182 against 230 us).  The reference's
-         * "copy" figure is therefore 0 for such frames and its "exec" figure contains the PCIe traffic.
-         */
-        /* planes that are page-locked caller memory themselves (and word aligned) need no staging either */
-        bool direct = true;
-        void *kplane[3] = {nullptr, nullptr, nullptr}; /* the planes as a kernel addresses them */
-        for (int i = 0; i < npl && direct; i++)
-            direct = frame->pitch[i] % (4 * sb) == 0 && (uintptr_t)frame->plane[i] % (4 * sb) == 0 &&
-                     is_pinned_host(ctx, frame->plane[i], plane_span(frame->pitch[i], (size_t)pw[i] * sb, ph[i]), &kplane[i]) && kplane[i] != nullptr;
-        if (!direct)
-            for (int i = 0; i < npl; i++) {
-                const size_t rb = (size_t)pw[i] * sb;
-                for (unsigned r = 0; r < ph[i]; r++)
-                    std::memcpy(hplane[i] + r * rb, (const uint8_t *)frame->plane[i] + r * frame->pitch[i], rb);
-            }
-        void *hp[3] = {direct ? kplane[0] : (void *)hplane[0], direct ? kplane[1] : (void *)hplane[1],
-                       direct ? kplane[2] : (void *)hplane[2]};
-        DbkArgs ha[3];
-        for (int i = 0; i < npl; i++)
-            if (int rc = frame_plane_args(ctx, hp, i, W, H, frame->bit_depth, sb, chroma, qp, dmap, tables, ha[i],
-                                          direct ? frame->pitch : nullptr))
-                return rc;
-        /* The reference's own case (352x288, README.md:19-24) is all fixed costs, so they are counted: no cross-stream wait when the
-         * default bS is resident and there is no QP map (nothing was uploaded); the fused launch stamps its own begin and end into
-         * ev[4] / ev[5] (no marker packets, two HIP calls fewer); and this thread polls the end event instead of sleeping in a
-         * stream synchronisation (round 4: 52 -> about 40 us per call). */
-        if (operands_uploaded) HIP_TRY(ctx, hipStreamWaitEvent(ctx->compute, ev[12], 0));
-        bool fused = false;
-        dbk_set_next_launch_events(ev[4], ev[5]);
-        const int frc = launch_frame_fused(ctx, ha, npl, sb, ctx->compute, &fused);
-        dbk_set_next_launch_events(nullptr, nullptr);
-        if (frc) return frc;
-        if (!fused) { /* operands the fused launch does not take after all (alignment of the caller's planes): plane by plane */
-            for (int k = 0; k < npl; k++) {
-                dbk_set_next_launch_events(k == 0 ? ev[4] : nullptr, k == npl - 1 ? ev[5] : nullptr);
-                const int rc = launch(ctx, ha[k], (int)sb, k != 0, HEVCDBK_KERNEL_AUTO, ctx->compute);
-                dbk_set_next_launch_events(nullptr, nullptr);
-                if (rc) return rc;
-            }
-        }
-        for (;;) {
-            const hipError_t q = hipEventQuery(ev[5]);
-            if (q == hipSuccess) break;
-            if (q != hipErrorNotReady) HIP_TRY(ctx, q);
-            (void)hipGetLastError();
-            _mm_pause();
-        }
-        if (!direct)
-            for (int i = 0; i < npl; i++) {
-                const size_t rb = (size_t)pw[i] * sb;
-                for (unsigned r = 0; r < ph[i]; r++)
-                    std::memcpy((uint8_t *)frame->plane[i] + r * frame->pitch[i], hplane[i] + r * rb, rb);
-            }
-        if (timing) {
-            float ms = 0.f;
-            HIP_TRY(ctx, hipEventElapsedTime(&ms, ev[4], ev[5]));
-            timing->exec_s = ms * 1e-3;
-            timing->copy_s = 0.0;
-            timing->total_s = timing->exec_s;
-            timing->pipelined_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - wall0).count();
-        }
-        drain.ok = true;
-        return HEVCDBK_OK;
-    }
-    if (small) {
-        /* pack the caller's pitched planes into the pinned staging buffer */
-        for (int i = 0; i < npl; i++) {
-            const size_t rb = (size_t)pw[i] * sb;
-            for (unsigned r = 0; r < ph[i]; r++)
-                std::memcpy(hplane[i] + r * rb, (const uint8_t *)frame->plane[i] + r * frame->pitch[i], rb);
-        }
-        if (operands_uploaded) HIP_TRY(ctx, hipStreamWaitEvent(ctx->compute, ev[12], 0)); /* the bS upload, if there was one */
-        HIP_TRY(ctx, hipEventRecord(ev[1], ctx->compute));
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->dev[0].p, ctx->pin[0].p, frame_bytes, hipMemcpyHostToDevice, ctx->compute));
-        HIP_TRY(ctx, hipEventRecord(ev[4], ctx->compute));
-        bool fused = false;
-        if (int rc = launch_frame_fused(ctx, args, npl, sb, ctx->compute, &fused)) return rc;
-        if (!fused)
-            for (int k = 0; k < npl; k++)
-                if (int rc = launch(ctx, args[k], (int)sb, k != 0, HEVCDBK_KERNEL_AUTO, ctx->compute)) return rc;
-        HIP_TRY(ctx, hipEventRecord(ev[5], ctx->compute));
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->pin[0].p, ctx->dev[0].p, frame_bytes, hipMemcpyDeviceToHost, ctx->compute));
-        HIP_TRY(ctx, hipEventRecord(ev[9], ctx->compute));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->compute));
-    } else {
-        /*
-         * Large frame: strip pipeline.  Image rows 8b-4 .. 8b+3 belong to block row b and to no other, so a plane splits
-         * into strips of whole block rows with no halo; strip s is uploaded, filtered (a launch over its block rows only)
-         * and downloaded while strip s+1 is being packed / uploaded and strip s-1 downloaded: the two DMA directions, the
-         * kernels and the host-side staging copies all overlap inside ONE frame.  The first strips are short (the link is
-         * idle until the first one has been staged), later ones long enough for the DMA engines to reach their rate
-         * (tools/ubench/host_stage.hip: one 512 KiB DMA 19 us, 2 MiB 46 us, 8.3 MB 155 us).  Pageable planes are staged
-         * by the context's crew of host threads (host_crew.h) while this thread feeds the three streams.
-         */
-        struct Strip { int plane, b0, b1; unsigned r0, r1; };
-        std::vector<Strip> strips;
-        bool any_staged = false;
-        /* The kernel writes its results straight into page-locked host memory -- the ring, or the caller's own page-locked plane when its
-         * rows are tight -- instead of into HBM with a D2H DMA behind it: posted writes across the link run at the DMA engines' rate
-         * (tools/ubench/host_stage.hip: 8.3 MB in 0.159 ms against 0.156 ms), and a DMA's set-up, two events and a cross-stream wait
-         * per strip disappear from the chain.  Pitched page-locked planes keep the 2-D DMA. */
-        const bool direct_out = crew_knob("HEVCDBK_HOST_DIRECT_OUT", true);
-        /* experiments of the diagnostic build (profiles/r04/experiments.md): all off in the product */
-        const bool x_direct_in = crew_knob("HEVCDBK_HOST_DIRECT_IN", false);
-        const int x_h2d_streams = crew_knob("HEVCDBK_HOST_H2D_STREAMS2", false) ? 2 : 1;
-        const int x_k_streams = crew_knob("HEVCDBK_HOST_K_STREAMS2", false) ? 2 : 1;
-        /* The bS / QP map upload (issued on h2d above, ev[12] behind it) comes first on every stream a strip's kernel may run on.
-         * With H2D DMAs the strips' own events on h2d implied it; a strip the crew writes through the BAR has no such event, and
-         * its kernel would otherwise be free to start before a caller's bS array or QP map has arrived. */
-        if (operands_uploaded) {
-            HIP_TRY(ctx, hipStreamWaitEvent(ctx->compute, ev[12], 0));
-            if (x_direct_in || x_h2d_streams == 2 || x_k_streams == 2) HIP_TRY(ctx, hipStreamWaitEvent(ctx->d2h, ev[12], 0));
-        }
-        /* Pageable planes on a large-BAR device: the crew writes the caller's rows straight into HBM through the BAR (posted writes,
-         * tools/ubench/bar_write.hip: 37-43 GB/s from one or two cores, as fast as filling the ring) -- no ring on the way in and no
-         * H2D DMA with its set-up, event and cross-stream wait per strip.  The buffer is fine-grained device memory, so no cache of the
-         * GPU holds a line of it across launches. */
-        bool push_in = direct_out && crew_knob("HEVCDBK_HOST_PUSH", true);
-        uint8_t *kout[3] = {nullptr, nullptr, nullptr}; /* where the kernel of plane i writes (device-side address), NULL = HBM + DMA */
-        for (int i = 0; i < npl; i++) {
-            any_staged |= !zc[i];
-            if (!direct_out) continue;
-            const size_t rb = (size_t)pw[i] * sb;
-            void *dp = nullptr;
-            if (!zc[i]) kout[i] = hplane[i]; /* hipHostMalloc memory: one address for host and device */
-            else if (frame->pitch[i] == rb && (uintptr_t)frame->plane[i] % (4 * sb) == 0 && is_pinned_host(ctx, frame->plane[i], rb * ph[i], &dp) && dp)
-                kout[i] = (uint8_t *)dp;
-        }
-        {
-            /* strips: 256 KiB, then doubling up to `mid` (1.5 MiB when a copy-out rides along -- the crew, the link and the
-             * un-staging then work on three different strips at any time -- 2 MiB when the link works alone), the last `mid` of a
-             * frame cut in two so that little is left to do when the last transfer ends */
-            const size_t mid_staged = crew_strip_bytes((size_t)3 << 19), mid_locked = crew_strip_bytes((size_t)2 << 20);
-            size_t target = crew_first_strip_bytes((size_t)256 << 10);
-            for (int i = 0; i < npl; i++) {
-                const size_t rb = (size_t)pw[i] * sb, mid = zc[i] ? mid_locked : mid_staged;
-                const int nby = (int)(ph[i] / 8 + 1);
-                bool cut_tail = i == npl - 1; /* once, at the end of the frame */
-                for (int b0 = 0; b0 < nby;) {
-                    int per = (int)(((target < mid ? target : mid) / rb) / 8);
-                    per = per < 1 ? 1 : per;
-                    const int left = nby - b0;
-                    int take = per;
-                    if (left <= per + per / 2) { /* no sliver at the end of a plane */
-                        take = left;
-                        if (cut_tail && left > 2 && target >= mid) take = (2 * left + 2) / 3;
-                        cut_tail = false;
-                    }
-                    const int b1 = b0 + take;
-                    const unsigned r0 = b0 == 0 ? 0u : (unsigned)(8 * b0 - 4), r1 = b1 == nby ? ph[i] : (unsigned)(8 * b1 - 4);
-                    strips.push_back({i, b0, b1, r0, r1});
-                    b0 = b1;
-                    if (target < mid) target *= 2;
-                }
-            }
-        }
-        const size_t ns = strips.size();
-        const size_t need = 6 * ns;
-        while (ctx->timed_events.size() < need) {
-            hipEvent_t e;
-            HIP_TRY(ctx, hipEventCreate(&e));
-            ctx->timed_events.push_back(e);
-        }
-        hipEvent_t *te = ctx->timed_events.data(); /* per strip: h2d start/end, kernel start/end, d2h start/end */
-        StageCrew *crew = nullptr;
-        uint8_t *dpush = nullptr;
-        if (any_staged || push_in) { /* page-locked caller planes are pushed too: faster than a chain of DMAs for ONE frame */
-            if (int rc = ensure_crew(ctx)) return rc;
-            crew = ctx->crew;
-            if (push_in) dpush = push_buffer(ctx, frame_bytes); /* NULL: no such memory here -> ring + DMA */
-        }
-                std::unique_ptr<CopyGroup[]> gin(new CopyGroup[ns]), gout(new CopyGroup[ns]);
-        /* every path out of this block waits for the jobs it handed out (they point into gin / gout) and puts the crew to sleep */
-        struct CrewScope {
-            StageCrew *c; CopyGroup *a, *b; size_t n;
-            ~CrewScope() { if (!c) return; for (size_t k = 0; k < n; k++) { c->wait(a[k]); c->wait(b[k]); } c->end(); }
-        } scope{crew, gin.get(), gout.get(), ns};
-        const int64_t ns0 = std::chrono::duration_cast<std::chrono::nanoseconds>(wall0.time_since_epoch()).count();
-        auto since = [ns0](int64_t t) { return t ? (double)(t - ns0) * 1e-9 : 0.0; };
-        ctx->trace.assign(ns, hevcdbk_strip_trace{});
-        /* a strip as row-range jobs for the crew: in = caller plane -> HBM (BAR) or ring, out = ring -> caller plane */
-        auto hand_out = [&](size_t k, bool in) {
-            const Strip &st = strips[k];
-            const int i = st.plane;
-            const size_t rb = (size_t)pw[i] * sb, bytes = (size_t)(st.r1 - st.r0) * rb;
-            /* pieces of at least 128 KiB: as many as there are crew threads -- two for writes through the BAR, which two cores saturate */
-            const unsigned crew_n = crew->workers() ? crew->workers() : 1, most = in && dpush && crew_n > 2 ? 2 : crew_n;
-            unsigned pieces = (unsigned)(bytes / ((size_t)128 << 10));
-            pieces = pieces < 1 ? 1 : pieces > most ? most : pieces;
-            CopyGroup &g = in ? gin[k] : gout[k];
-            g.pending.store((int)pieces, std::memory_order_release);
-            const unsigned rows = st.r1 - st.r0;
-            for (unsigned p = 0; p < pieces; p++) {
-                const unsigned a = st.r0 + (unsigned)((uint64_t)rows * p / pieces), b = st.r0 + (unsigned)((uint64_t)rows * (p + 1) / pieces);
-                uint8_t *ring = hplane[i] + (size_t)a * rb, *user = (uint8_t *)frame->plane[i] + (size_t)a * frame->pitch[i];
-                if (in && dpush) crew->submit({dpush + plane_off[i] + (size_t)a * rb, user, rb, frame->pitch[i], rb, b - a, &g, true}, StageCrew::LANE_IN);
-                else if (in) crew->submit({ring, user, rb, frame->pitch[i], rb, b - a, &g}, StageCrew::LANE_IN);
-                else crew->submit({user, ring, frame->pitch[i], rb, rb, b - a, &g}, StageCrew::LANE_OUT);
-            }
-        };
-        auto enqueue = [&](size_t k) -> int {
-            const Strip &st = strips[k];
-            const int i = st.plane;
-            const size_t rb = (size_t)pw[i] * sb, off = (size_t)st.r0 * rb, bytes = (size_t)(st.r1 - st.r0) * rb;
-            hevcdbk_strip_trace &tr = ctx->trace[k];
-            tr.plane = i; tr.row_begin = st.r0; tr.row_end = st.r1; tr.bytes = bytes;
-            if (dpush || !zc[i]) {
-                tr.stage_begin_s = since(gin[k].first_ns.load());
-                tr.stage_end_s = since(gin[k].done_ns.load());
-            }
-            tr.enqueue_begin_s = since(crew_now_ns());
-            const bool tight = frame->pitch[i] == rb;
-            const bool pushed = dpush != nullptr; /* the strip is in HBM already: the crew wrote it there */
-            const bool din = pushed || (x_direct_in && kout[i]); /* (experiment: the kernel reads the page-locked strip itself) */
-            hipStream_t hs = x_h2d_streams == 2 && (k & 1) ? ctx->d2h : ctx->h2d;
-            hipStream_t ks = x_k_streams == 2 && (k & 1) ? ctx->d2h : ctx->compute;
-            if (!din) {
-                if (timing) HIP_TRY(ctx, hipEventRecord(te[6 * k + 0], hs));
-                if (zc[i] && !tight)
-                    HIP_TRY(ctx, hipMemcpy2DAsync((uint8_t *)dplane[i] + off, rb, (const uint8_t *)frame->plane[i] + (size_t)st.r0 * frame->pitch[i],
-                                                  frame->pitch[i], rb, st.r1 - st.r0, hipMemcpyHostToDevice, hs));
-                else
-                    HIP_TRY(ctx, hipMemcpyAsync((uint8_t *)dplane[i] + off, (zc[i] ? (const uint8_t *)frame->plane[i] : hplane[i]) + off, bytes,
-                                                hipMemcpyHostToDevice, hs));
-                HIP_TRY(ctx, hipEventRecord(te[6 * k + 1], hs));
-                HIP_TRY(ctx, hipStreamWaitEvent(ks, te[6 * k + 1], 0));
-            }
-            DbkArgs sa = args[i];
-            sa.by_begin = st.b0;
-            sa.by_count = st.b1 - st.b0;
-            if (kout[i]) sa.dst = kout[i]; /* src: the strip in HBM; dst: page-locked host memory, same pitch */
-            if (pushed) sa.src = dpush + plane_off[i];
-            else if (din) sa.src = kout[i];
-            /* the launch stamps its own begin and end into the strip's events (one kernel per launch() in this library): no marker
-             * packets around the kernels, whose chain is what the frame waits for */
-            dbk_set_next_launch_events(timing ? te[6 * k + 2] : nullptr, te[6 * k + 3]);
-            const int lrc = launch(ctx, sa, (int)sb, i != 0, HEVCDBK_KERNEL_AUTO, ks);
-            dbk_set_next_launch_events(nullptr, nullptr);
-            if (lrc) return lrc;
-            if (!kout[i]) {
-                HIP_TRY(ctx, hipStreamWaitEvent(ctx->d2h, te[6 * k + 3], 0));
-                if (timing) HIP_TRY(ctx, hipEventRecord(te[6 * k + 4], ctx->d2h));
-                if (zc[i] && !tight)
-                    HIP_TRY(ctx, hipMemcpy2DAsync((uint8_t *)frame->plane[i] + (size_t)st.r0 * frame->pitch[i], frame->pitch[i],
-                                                  (uint8_t *)dplane[i] + off, rb, rb, st.r1 - st.r0, hipMemcpyDeviceToHost, ctx->d2h));
-                else
-                    HIP_TRY(ctx, hipMemcpyAsync((zc[i] ? (uint8_t *)frame->plane[i] : hplane[i]) + off, (uint8_t *)dplane[i] + off, bytes,
-                                                hipMemcpyDeviceToHost, ctx->d2h));
-                HIP_TRY(ctx, hipEventRecord(te[6 * k + 5], ctx->d2h));
-            }
-            tr.enqueue_end_s = since(crew_now_ns());
-            return HEVCDBK_OK;
-        };
-        /*
-         * One loop feeds everything, in strip order.  The copies-in of the whole frame go to the crew's first lane at once, so they run
-         * without a pause from the first microsecond; a strip whose copy-in is complete is handed to the runtime; a strip whose results
-         * have landed (event query, no blocking) goes to the crew's second lane for its copy-out.  This thread copies too until it has
-         * something to launch (the crew is still waking up then) and whenever there are no crew threads (hevcdbk_set_host_threads 1).
-         */
-        if (crew) crew->begin();
-        const bool alone = !crew || crew->workers() == 0;
-        size_t n_launched = 0, n_out = 0;
-        bool helped_once = false;
-        if (crew)
-            for (size_t k = 0; k < ns; k++)
-                if (dpush || !zc[strips[k].plane]) hand_out(k, true);
-        while (n_out < ns) {
-            bool progress = false;
-            if (n_launched < ns && ((!dpush && zc[strips[n_launched].plane]) || gin[n_launched].pending.load(std::memory_order_acquire) == 0)) {
-                if (int rc = enqueue(n_launched)) return rc;
-                n_launched++;
-                progress = true;
-            }
-            if (n_out < n_launched) {
-                const hipError_t q = hipEventQuery(te[6 * n_out + (kout[strips[n_out].plane] ? 3 : 5)]);
-                if (q == hipSuccess) {
-                    ctx->trace[n_out].d2h_seen_s = since(crew_now_ns());
-                    if (!zc[strips[n_out].plane]) hand_out(n_out, false);
-                    n_out++;
-                    progress = true;
-                } else if (q != hipErrorNotReady) {
-                    HIP_TRY(ctx, q);
-                } else {
-                    (void)hipGetLastError(); /* "not ready" is not an error */
-                }
-            }
-            if (progress) continue;
-            if (crew && (alone || !helped_once)) { /* the one job: the first piece of the first strip, while the crew wakes up */
-                helped_once = true;
-                if (crew->help()) continue;
-            }
-            _mm_pause();
-        }
-        for (size_t k = 0; k < ns; k++)
-            if (!zc[strips[k].plane]) {
-                crew->wait(gout[k]);
-                ctx->trace[k].unstage_begin_s = since(gout[k].first_ns.load());
-                ctx->trace[k].unstage_end_s = since(gout[k].done_ns.load());
-            }
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->compute));
-        if (x_direct_in || x_k_streams == 2 || x_h2d_streams == 2) HIP_TRY(ctx, hipStreamSynchronize(ctx->d2h)); /* the experiments that put ev[12]'s wait or work of their own on d2h */
-        const auto wall1s = std::chrono::steady_clock::now();
-        if (timing) {
-            double copy = 0.0, exec = 0.0, push_covered = 0.0;
-            for (size_t k = 0; k < ns; k++) {
-                float ms = 0.f;
-                if (dpush) { /* the upload was the crew's stores through the BAR: host clock, the time during
-                                                        which at least one strip was being written (strips overlap) */
-                    const double b = ctx->trace[k].stage_begin_s, e = ctx->trace[k].stage_end_s;
-                    if (e > push_covered) copy += (e - (b > push_covered ? b : push_covered)) * 1e3;
-                    if (e > push_covered) push_covered = e;
-                } else if (!(x_direct_in && kout[strips[k].plane])) {
-                    HIP_TRY(ctx, hipEventElapsedTime(&ms, te[6 * k + 0], te[6 * k + 1])); copy += ms; ctx->trace[k].h2d_ms = ms;
-                }
-                HIP_TRY(ctx, hipEventElapsedTime(&ms, te[6 * k + 2], te[6 * k + 3])); exec += ms; ctx->trace[k].kernel_ms = ms;
-                if (kout[strips[k].plane]) continue; /* the download is the kernel's own stores: part of exec_s */
-                HIP_TRY(ctx, hipEventElapsedTime(&ms, te[6 * k + 4], te[6 * k + 5])); copy += ms; ctx->trace[k].d2h_ms = ms;
-            }
-            timing->exec_s = exec * 1e-3;   /* the reference's figures are sums of its serial phases (gpu.cu:1292-1303) */
-            timing->copy_s = copy * 1e-3;
-            timing->total_s = timing->exec_s + timing->copy_s;
-            timing->pipelined_s = std::chrono::duration<double>(wall1s - wall0).count();
-        }
-        drain.ok = true;
-        return HEVCDBK_OK;
-    }
-
-    /* small frame: un-stage, and the reference's three figures from the events around its three steps */
-    for (int i = 0; i < npl; i++) {
-        const size_t rb = (size_t)pw[i] * sb;
-        for (unsigned r = 0; r < ph[i]; r++)
-            std::memcpy((uint8_t *)frame->plane[i] + r * frame->pitch[i], hplane[i] + r * rb, rb);
-    }
-    const auto wall1 = std::chrono::steady_clock::now();
-    if (timing) {
-        float ms = 0.f;
-        double copy = 0.0;
-        HIP_TRY(ctx, hipEventElapsedTime(&ms, ev[1], ev[4])); copy += ms;
-        HIP_TRY(ctx, hipEventElapsedTime(&ms, ev[5], ev[9])); copy += ms;
-        HIP_TRY(ctx, hipEventElapsedTime(&ms, ev[4], ev[5]));
-        timing->exec_s = ms * 1e-3;
-        timing->copy_s = copy * 1e-3;
-        timing->total_s = timing->exec_s + timing->copy_s; /* gpu.cu:1302 */
-        timing->pipelined_s = std::chrono::duration<double>(wall1 - wall0).count();
-    }
-    drain.ok = true;
-    return HEVCDBK_OK;
+    const int rc = !small ? strips(c) : host_direct ? small_direct(c) : small_dma(c);
+    drain.ok = rc == HEVCDBK_OK; /* a call that succeeded has waited for its own work */
+    return rc;
 }
 
 /* ---- streaming host operator: H2D(n+1) || kernels(n) || D2H(n-1) ------------------------------------ */
 
 namespace {
-int filter_chunk(hevcdbk_context *ctx, uint8_t *host, size_t k, unsigned W, unsigned H, unsigned qp, const hevcdbk_bs *bs,
-                 const hevcdbk_tables *tables, int slot = 0, hipEvent_t done = nullptr);
-}
-
-
-extern "C" int hevc_deblocking_filter_sequence(hevcdbk_context *ctx, hevcdbk_frame *frames, unsigned n_frames,
-                                               const hevcdbk_bs *bs, const hevcdbk_qp *qp, const hevcdbk_tables *tables,
-                                               hevcdbk_timing *timing)
-{
-    if (!ctx || !frames || !qp) return HEVCDBK_ERR_ARG;
-    if (n_frames == 0) return HEVCDBK_OK;
-    if (qp->map) return HEVCDBK_ERR_UNSUPPORTED; /* one QP map per frame is not part of the streaming form */
-    const hevcdbk_frame &f0 = frames[0];
-    bool chroma = false;
-    if (int rc = check_frame(f0, chroma)) return rc;
-    const unsigned W = f0.width, H = f0.height, sb = f0.sample_bytes;
-    const int npl = chroma ? 3 : 1;
-    const unsigned pw[3] = {W, W / 2, W / 2}, ph[3] = {H, H / 2, H / 2};
-    for (unsigned i = 1; i < n_frames; i++) {
-        const hevcdbk_frame &fr = frames[i];
-        bool c2 = false;
-        if (fr.width != W || fr.height != H || fr.bit_depth != f0.bit_depth || fr.sample_bytes != sb) return HEVCDBK_ERR_ARG;
-        if (int rc = check_frame(fr, c2)) return rc;
-        if (c2 != chroma) return HEVCDBK_ERR_ARG;
-    }
-    if (int rc = check_bs(bs, W, H, chroma)) return rc;
-    if (int rc = bind(ctx)) return rc;
-    GpuDrain drain{ctx}; /* every return below that is not HEVCDBK_OK waits for the GPU (after the crew: its Scope is declared later) */
-    /* Small 8-bit 4:2:0 frames: per-frame DMA and launch costs outweigh the data, so the frames travel in groups -- packed
-     * back to back into one pinned chunk, ONE DMA each way and ONE batched fused launch per group (the file operator's path) */
-    {
-        const size_t fb = (size_t)W * H * 3 / 2;
-        if (chroma && sb == 1 && f0.bit_depth == 8 && fb <= ((size_t)2 << 20) && n_frames >= 4) {
-            size_t G = ((size_t)64 << 20) / fb;
-            G = G > 64 ? 64 : G;
-            /* two pinned chunks, two device chunks: the GPU works on group g while the host un-stages group g-1 and stages g+1 */
-            uint8_t *chunk[2];
-            for (int c = 0; c < 2; c++) {
-                if (int rc = grow_pinned(ctx, ctx->seq_pin[0][c], G * fb)) return rc;
-                chunk[c] = (uint8_t *)ctx->seq_pin[0][c].p;
-                if (!ctx->seq_ev[0][c]) HIP_TRY(ctx, hipEventCreate(&ctx->seq_ev[0][c]));
-            }
-            const size_t poff[3] = {0, (size_t)W * H, (size_t)W * H + (size_t)(W / 2) * (H / 2)};
-            const auto wall0 = std::chrono::steady_clock::now();
-            auto stage = [&](unsigned g0, size_t k, uint8_t *c, bool in) {
-                for (size_t i = 0; i < k; i++)
-                    for (int p = 0; p < 3; p++) {
-                        uint8_t *cp = c + i * fb + poff[p];
-                        uint8_t *fp = (uint8_t *)frames[g0 + i].plane[p];
-                        const size_t pitch = frames[g0 + i].pitch[p];
-                        if (pitch == pw[p]) { /* tightly packed plane: one copy */
-                            if (in) std::memcpy(cp, fp, (size_t)pw[p] * ph[p]);
-                            else std::memcpy(fp, cp, (size_t)pw[p] * ph[p]);
-                            continue;
-                        }
-                        for (unsigned r = 0; r < ph[p]; r++) {
-                            if (in) std::memcpy(cp + (size_t)r * pw[p], fp + r * pitch, pw[p]);
-                            else std::memcpy(fp + r * pitch, cp + (size_t)r * pw[p], pw[p]);
-                        }
-                    }
-            };
-            unsigned prev_g0 = 0;
-            size_t prev_k = 0;
-            int n = 0;
-            for (unsigned g0 = 0; g0 < n_frames; g0 += (unsigned)G, n++) {
-                const size_t k = n_frames - g0 < G ? n_frames - g0 : G;
-                stage(g0, k, chunk[n & 1], true);
-                if (int rc = filter_chunk(ctx, chunk[n & 1], k, W, H, qp->qp, bs, tables, n & 1, ctx->seq_ev[0][n & 1])) return rc;
-                if (prev_k) {
-                    HIP_TRY(ctx, hipEventSynchronize(ctx->seq_ev[0][(n - 1) & 1]));
-                    stage(prev_g0, prev_k, chunk[(n - 1) & 1], false);
-                }
-                prev_g0 = g0;
-                prev_k = k;
-            }
-            HIP_TRY(ctx, hipEventSynchronize(ctx->seq_ev[0][(n - 1) & 1]));
-            stage(prev_g0, prev_k, chunk[(n - 1) & 1], false);
-            if (timing) {
-                std::memset(timing, 0, sizeof(*timing));
-                timing->pipelined_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - wall0).count();
-            }
-            drain.ok = true;
-            return HEVCDBK_OK;
-        }
-    }
-    constexpr int K = hevcdbk_context::kSeqSlots;
-    size_t row_bytes[3], plane_bytes[3];
-    for (int k = 0; k < npl; k++) {
-        row_bytes[k] = (size_t)pw[k] * sb;
-        plane_bytes[k] = row_bytes[k] * ph[k];
-    }
-    /*
-     * Large frames that ALL lie in ordinary pageable memory, on a large-BAR device (round 4): the single-frame operator's way in
-     * and out, with a frame where it has a strip.  The staging crew writes frame i straight into slot i % K of fine-grained HBM
-     * through the BAR, the kernels of frame i read that slot and store their results into slot i % K of a page-locked ring, the
-     * crew copies them out into the caller's planes -- three frames at different stages at any time, no DMA, no staging copy on
-     * the way in, and this thread only launches and polls.  A slot of HBM is written again once the kernels that read it have
-     * ended, a slot of the ring once its copy-out has ended.
-     */
-    {
-        size_t poff[3] = {0, 0, 0}, fbytes = 0;
-        for (int k = 0; k < npl; k++) {
-            poff[k] = fbytes;
-            fbytes = (fbytes + plane_bytes[k] + 255) & ~(size_t)255;
-        }
-        bool pageable = fbytes > ((size_t)2 << 20) && n_frames >= 2;
-        for (unsigned i = 0; i < n_frames && pageable; i++)
-            for (int k = 0; k < npl && pageable; k++) pageable = !is_pinned_host(ctx, frames[i].plane[k], plane_span(frames[i].pitch[k], row_bytes[k], ph[k]));
-        uint8_t *dpush = pageable ? push_buffer(ctx, (size_t)K * fbytes) : nullptr;
-        if (dpush) {
-            if (int rc = grow_pinned(ctx, ctx->pin[1], (size_t)K * fbytes)) return rc;
-            uint8_t *const ring = (uint8_t *)ctx->pin[1].p;
-            if (int rc = ensure_crew(ctx)) return rc;
-            StageCrew *crew = ctx->crew;
-            if (int rc = ensure_timed_events(ctx, (size_t)K)) return rc;
-            hipEvent_t *done = ctx->timed_events.data(); /* per slot: the end of the kernels that read / wrote it last */
-            const auto wall0 = std::chrono::steady_clock::now();
-            if (int rc = stage_bs(ctx, W, H, chroma, bs, ctx->h2d)) return rc;
-            HIP_TRY(ctx, hipEventRecord(ctx->ev[12], ctx->h2d));
-            HIP_TRY(ctx, hipStreamWaitEvent(ctx->compute, ctx->ev[12], 0));
-            std::unique_ptr<CopyGroup[]> gin(new CopyGroup[n_frames]), gout(new CopyGroup[n_frames]);
-            struct Scope { /* every path out waits for the jobs handed out and puts the crew to sleep */
-                StageCrew *c; CopyGroup *a, *b; unsigned n;
-                ~Scope() { for (unsigned i = 0; i < n; i++) { c->wait(a[i]); c->wait(b[i]); } c->end(); }
-            } scope{crew, gin.get(), gout.get(), n_frames};
-            const unsigned crew_n = crew->workers() ? crew->workers() : 1;
-            auto hand = [&](unsigned i, bool in) {
-                const hevcdbk_frame &fr = frames[i];
-                const size_t slot = (size_t)(i % K) * fbytes;
-                CopyGroup &g = in ? gin[i] : gout[i];
-                struct Piece { int k; unsigned a, b; };
-                Piece pc[3 * 16];
-                int np = 0;
-                for (int k = 0; k < npl; k++) {
-                    unsigned pieces = (unsigned)(plane_bytes[k] / ((size_t)512 << 10));
-                    const unsigned most = in ? (crew_n > 2 ? 4u : 2u) : 2 * crew_n; /* the BAR is saturated by two cores: few, long pieces */
-                    pieces = pieces < 1 ? 1 : pieces > most ? most : pieces;
-                    pieces = pieces > 16 ? 16 : pieces;
-                    for (unsigned q = 0; q < pieces; q++) pc[np++] = {k, (unsigned)((uint64_t)ph[k] * q / pieces), (unsigned)((uint64_t)ph[k] * (q + 1) / pieces)};
-                }
-                g.pending.store(np, std::memory_order_release);
-                for (int q = 0; q < np; q++) {
-                    const int k = pc[q].k;
-                    uint8_t *user = (uint8_t *)fr.plane[k] + (size_t)pc[q].a * fr.pitch[k];
-                    const size_t inner = slot + poff[k] + (size_t)pc[q].a * row_bytes[k];
-                    if (in) crew->submit({dpush + inner, user, row_bytes[k], fr.pitch[k], row_bytes[k], pc[q].b - pc[q].a, &g, true}, StageCrew::LANE_IN);
-                    else crew->submit({user, ring + inner, fr.pitch[k], row_bytes[k], row_bytes[k], pc[q].b - pc[q].a, &g, false}, StageCrew::LANE_OUT);
-                }
-            };
-            crew->begin();
-            const bool alone = crew->workers() == 0;
-            unsigned n_in = 0, n_launched = 0, n_out = 0, n_fin = 0;
-            while (n_fin < n_frames) {
-                bool progress = false;
-                /* copies in: slot i % K of HBM is free once the kernels of frame i - K have been seen to end */
-                if (n_in < n_frames && n_in < n_out + (unsigned)K) {
-                    hand(n_in++, true);
-                    progress = true;
-                }
-                /* launch: the frame is in HBM, and its ring slot has been copied out */
-                if (n_launched < n_in && gin[n_launched].pending.load(std::memory_order_acquire) == 0 && n_launched < n_fin + (unsigned)K) {
-                    const unsigned i = n_launched;
-                    const size_t slot = (size_t)(i % K) * fbytes;
-                    DbkArgs args[3];
-                    void *dplane[3] = {dpush + slot + poff[0], dpush + slot + poff[1], dpush + slot + poff[2]};
-                    for (int k = 0; k < npl; k++) {
-                        if (int rc = frame_plane_args(ctx, dplane, k, W, H, f0.bit_depth, sb, chroma, qp, nullptr, tables, args[k])) return rc;
-                        args[k].dst = ring + slot + poff[k]; /* the kernels store into page-locked host memory */
-                    }
-                    const int sbs[3] = {(int)sb, (int)sb, (int)sb};
-                    if (chroma && dbk_multi_supports(args, npl, sbs)) {
-                        dbk_set_next_launch_events(nullptr, done[i % K]);
-                        const hipError_t e = dbk_launch_packed_multi(args, npl, (int)sb, ctx->compute);
-                        dbk_set_next_launch_events(nullptr, nullptr);
-                        if (!hip_ok(ctx, e, "kernel launch")) return HEVCDBK_ERR_HIP;
-                    } else {
-                        for (int k = 0; k < npl; k++) {
-                            if (k == npl - 1) dbk_set_next_launch_events(nullptr, done[i % K]); /* one stream: the last launch ends last */
-                            const int rc = launch(ctx, args[k], (int)sb, k != 0, HEVCDBK_KERNEL_AUTO, ctx->compute);
-                            dbk_set_next_launch_events(nullptr, nullptr);
-                            if (rc) return rc;
-                        }
-                    }
-                    n_launched++;
-                    progress = true;
-                }
-                /* results landed: copies out */
-                if (n_out < n_launched) {
-                    const hipError_t q = hipEventQuery(done[n_out % K]);
-                    if (q == hipSuccess) {
-                        hand(n_out++, false);
-                        progress = true;
-                    } else if (q != hipErrorNotReady) {
-                        HIP_TRY(ctx, q);
-                    } else {
-                        (void)hipGetLastError();
-                    }
-                }
-                while (n_fin < n_out && gout[n_fin].pending.load(std::memory_order_acquire) == 0) {
-                    n_fin++;
-                    progress = true;
-                }
-                if (progress) continue;
-                if (alone && crew->help()) continue;
-                _mm_pause();
-            }
-            HIP_TRY(ctx, hipStreamSynchronize(ctx->compute));
-            if (timing) {
-                std::memset(timing, 0, sizeof(*timing));
-                timing->pipelined_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - wall0).count();
-            }
-            drain.ok = true;
-            return HEVCDBK_OK;
-        }
-    }
-    for (int s = 0; s < K; s++) {
-        for (int k = 0; k < npl; k++)
-            if (int rc = grow_device(ctx, ctx->seq_dev[s][k], plane_bytes[k])) return rc;
-        for (int e = 0; e < 3; e++)
-            if (!ctx->seq_ev[s][e]) HIP_TRY(ctx, hipEventCreate(&ctx->seq_ev[s][e]));
-    }
-    /* bS: shared by all frames of the sequence, uploaded once (the default pattern: once per geometry) */
-    const auto wall0 = std::chrono::steady_clock::now();
-    if (int rc = stage_bs(ctx, W, H, chroma, bs, ctx->h2d)) return rc;
-
-    std::vector<uint8_t> pinned((size_t)n_frames * 3, 0); /* plane k of frame i is page-locked caller memory */
-    /* un-stage frame `i` (its D2H has been issued into slot i % K) */
-    auto finish = [&](unsigned i) -> int {
-        const int s = (int)(i % K);
-        HIP_TRY(ctx, hipEventSynchronize(ctx->seq_ev[s][2]));
-        hevcdbk_frame &fr = frames[i];
-        for (int k = 0; k < npl; k++) {
-            if (pinned[(size_t)i * 3 + k]) continue; /* the DMA wrote the caller's plane directly */
-            for (unsigned r = 0; r < ph[k]; r++)
-                std::memcpy((uint8_t *)fr.plane[k] + r * fr.pitch[k], (const uint8_t *)ctx->seq_pin[s][k].p + r * row_bytes[k], row_bytes[k]);
-        }
-        return HEVCDBK_OK;
-    };
-
-    for (unsigned i = 0; i < n_frames; i++) {
-        const int s = (int)(i % K);
-        if (i >= (unsigned)K)
-            if (int rc = finish(i - K)) return rc; /* slot s is free again once frame i-K has left it */
-        hevcdbk_frame &fr = frames[i];
-        /* H2D: straight from pinned caller memory, or via the slot's pinned staging */
-        for (int k = 0; k < npl; k++) {
-            const void *hsrc = fr.plane[k];
-            size_t hpitch = fr.pitch[k];
-            pinned[(size_t)i * 3 + k] = is_pinned_host(ctx, fr.plane[k], plane_span(fr.pitch[k], row_bytes[k], ph[k])); /* asked once per plane: the query is not free */
-            if (!pinned[(size_t)i * 3 + k]) {
-                if (int rc = grow_pinned(ctx, ctx->seq_pin[s][k], plane_bytes[k])) return rc;
-                for (unsigned r = 0; r < ph[k]; r++)
-                    std::memcpy((uint8_t *)ctx->seq_pin[s][k].p + r * row_bytes[k], (const uint8_t *)fr.plane[k] + r * fr.pitch[k], row_bytes[k]);
-                hsrc = ctx->seq_pin[s][k].p;
-                hpitch = row_bytes[k];
-            }
-            HIP_TRY(ctx, hipMemcpy2DAsync(ctx->seq_dev[s][k].p, row_bytes[k], hsrc, hpitch, row_bytes[k], ph[k],
-                                          hipMemcpyHostToDevice, ctx->h2d));
-        }
-        HIP_TRY(ctx, hipEventRecord(ctx->seq_ev[s][0], ctx->h2d));
-        /* kernels */
-        HIP_TRY(ctx, hipStreamWaitEvent(ctx->compute, ctx->seq_ev[s][0], 0));
-        DbkArgs args[3];
-        void *dplane[3] = {ctx->seq_dev[s][0].p, ctx->seq_dev[s][1].p, ctx->seq_dev[s][2].p};
-        for (int k = 0; k < npl; k++)
-            if (int rc = frame_plane_args(ctx, dplane, k, W, H, f0.bit_depth, sb, chroma, qp, nullptr, tables, args[k])) return rc;
-        bool fused = false;
-        if (chroma)
-            if (int rc = launch_frame_fused(ctx, args, npl, sb, ctx->compute, &fused)) return rc;
-        if (!fused)
-            for (int k = 0; k < npl; k++)
-                if (int rc = launch(ctx, args[k], (int)sb, k != 0, HEVCDBK_KERNEL_AUTO, ctx->compute)) return rc;
-        HIP_TRY(ctx, hipEventRecord(ctx->seq_ev[s][1], ctx->compute));
-        /* D2H */
-        HIP_TRY(ctx, hipStreamWaitEvent(ctx->d2h, ctx->seq_ev[s][1], 0));
-        for (int k = 0; k < npl; k++) {
-            void *hdst = fr.plane[k];
-            size_t hpitch = fr.pitch[k];
-            if (!pinned[(size_t)i * 3 + k]) { hdst = ctx->seq_pin[s][k].p; hpitch = row_bytes[k]; }
-            HIP_TRY(ctx, hipMemcpy2DAsync(hdst, hpitch, ctx->seq_dev[s][k].p, row_bytes[k], row_bytes[k], ph[k],
-                                          hipMemcpyDeviceToHost, ctx->d2h));
-        }
-        HIP_TRY(ctx, hipEventRecord(ctx->seq_ev[s][2], ctx->d2h));
-        /* slot s is written again by the H2D of frame i+K, which is issued only after finish(i) has seen this
-         * frame's D2H (and so its kernels) complete */
-    }
-    for (unsigned i = n_frames > (unsigned)K ? n_frames - K : 0; i < n_frames; i++)
-        if (int rc = finish(i)) return rc;
-    const auto wall1 = std::chrono::steady_clock::now();
-    if (timing) {
-        std::memset(timing, 0, sizeof(*timing));
-        timing->pipelined_s = std::chrono::duration<double>(wall1 - wall0).count(); /* whole sequence */
-    }
-    drain.ok = true;
-    return HEVCDBK_OK;
-}
-
-namespace {
-
 /* k planar 8-bit 4:2:0 frames back to back in pinned host memory: upload, filter all planes as batches, download */
 /* slot: which of the two device chunk buffers to use; done == NULL: return when the chunk is back in `host`, else return at
  * once and record `done` behind the download */
 int filter_chunk(hevcdbk_context *ctx, uint8_t *host, size_t k, unsigned W, unsigned H, unsigned qp, const hevcdbk_bs *bs,
-                 const hevcdbk_tables *tables, int slot, hipEvent_t done)
+                 const hevcdbk_tables *tables, int slot = 0, hipEvent_t done = nullptr)
 {
     const size_t ysz = (size_t)W * H, csz = ysz / 4, fb = ysz + 2 * csz;
     const size_t nv = hevcdbk_num_vert_bs(W, H), nh = hevcdbk_num_hor_bs(W, H);
@@ -1806,11 +1565,7 @@ int filter_chunk(hevcdbk_context *ctx, uint8_t *host, size_t k, unsigned W, unsi
         p.hor_bs = i == 0 ? dbs + nv : dbs + nv + nh + ncv;
         if (int rc = planes_to_args(&p, qp, tables, args[i])) return rc;
     }
-    bool fused = false;
-    if (int rc = launch_frame_fused(ctx, args, 3, 1, s, &fused)) return rc;
-    if (!fused)
-        for (int i = 0; i < 3; i++)
-            if (int rc = launch(ctx, args[i], 1, i != 0, HEVCDBK_KERNEL_AUTO, s)) return rc;
+    if (int rc = launch_frame(ctx, args, 3, 1, s)) return rc;
     HIP_TRY(ctx, hipMemcpyAsync(host, d, k * fb, hipMemcpyDeviceToHost, s));
     if (done) HIP_TRY(ctx, hipEventRecord(done, s));
     else HIP_TRY(ctx, hipStreamSynchronize(s));
@@ -1818,7 +1573,246 @@ int filter_chunk(hevcdbk_context *ctx, uint8_t *host, size_t k, unsigned W, unsi
     return HEVCDBK_OK;
 }
 
+/* a validated call of hevc_deblocking_filter_sequence: n_frames frames of one geometry, L their layout */
+struct SequenceCall {
+    hevcdbk_context *ctx;
+    hevcdbk_frame *frames;
+    unsigned n_frames;
+    const hevcdbk_bs *bs; const hevcdbk_qp *qp; const hevcdbk_tables *tables;
+    hevcdbk_timing *timing; /* may be NULL */
+    bool chroma;
+    FrameLayout L;
+};
+constexpr int K = hevcdbk_context::kSeqSlots;
+
+/* Small 8-bit 4:2:0 frames: per-frame DMA and launch costs outweigh the data, so the frames travel in groups -- packed
+ * back to back into one pinned chunk, ONE DMA each way and ONE batched fused launch per group (the file operator's path) */
+int sequence_chunks(SequenceCall &c)
+{
+    hevcdbk_context *ctx = c.ctx;
+    const FrameLayout P = frame_layout(3, c.L.pw, c.L.ph, 1, 1); /* a frame of the chunk: Y, U, V back to back */
+    const size_t fb = P.frame_bytes;
+    size_t G = ((size_t)64 << 20) / fb;
+    G = G > 64 ? 64 : G;
+    /* two pinned chunks, two device chunks: the GPU works on group g while the host un-stages group g-1 and stages g+1 */
+    uint8_t *chunk[2];
+    for (int k = 0; k < 2; k++) {
+        if (int rc = grow_pinned(ctx, ctx->seq_pin[0][k], G * fb)) return rc;
+        chunk[k] = (uint8_t *)ctx->seq_pin[0][k].p;
+        if (!ctx->seq_ev[0][k]) HIP_TRY(ctx, hipEventCreate(&ctx->seq_ev[0][k]));
+    }
+    const WallClock wall0 = std::chrono::steady_clock::now();
+    auto stage = [&](unsigned g0, size_t k, uint8_t *at, bool to_frames) { for (size_t i = 0; i < k; i++) copy_frame(c.frames[g0 + i], P, at + i * fb, to_frames); };
+    unsigned prev_g0 = 0;
+    size_t prev_k = 0;
+    int n = 0;
+    for (unsigned g0 = 0; g0 < c.n_frames; g0 += (unsigned)G, n++) {
+        const size_t k = c.n_frames - g0 < G ? c.n_frames - g0 : G;
+        stage(g0, k, chunk[n & 1], false);
+        if (int rc = filter_chunk(ctx, chunk[n & 1], k, c.L.pw[0], c.L.ph[0], c.qp->qp, c.bs, c.tables, n & 1, ctx->seq_ev[0][n & 1])) return rc;
+        if (prev_k) {
+            HIP_TRY(ctx, hipEventSynchronize(ctx->seq_ev[0][(n - 1) & 1]));
+            stage(prev_g0, prev_k, chunk[(n - 1) & 1], true);
+        }
+        prev_g0 = g0;
+        prev_k = k;
+    }
+    HIP_TRY(ctx, hipEventSynchronize(ctx->seq_ev[0][(n - 1) & 1]));
+    stage(prev_g0, prev_k, chunk[(n - 1) & 1], true);
+    set_timing_pipelined(c.timing, seconds_since(wall0));
+    return HEVCDBK_OK;
+}
+
+/*
+ * Large frames that ALL lie in ordinary pageable memory, on a large-BAR device (round 4): the single-frame operator's way in
+ * and out, with a frame where it has a strip.  The staging crew writes frame i straight into slot i % K of fine-grained HBM
+ * (dpush) through the BAR, the kernels of frame i read that slot and store their results into slot i % K of a page-locked ring, the
+ * crew copies them out into the caller's planes -- three frames at different stages at any time, no DMA, no staging copy on
+ * the way in, and this thread only launches and polls.  A slot of HBM is written again once the kernels that read it have
+ * ended, a slot of the ring once its copy-out has ended.
+ */
+int sequence_push(SequenceCall &c, uint8_t *dpush)
+{
+    hevcdbk_context *ctx = c.ctx;
+    const FrameLayout &L = c.L;
+    const unsigned n_frames = c.n_frames;
+    if (int rc = grow_pinned(ctx, ctx->pin[1], (size_t)K * L.frame_bytes)) return rc;
+    uint8_t *const ring = (uint8_t *)ctx->pin[1].p;
+    if (int rc = ensure_crew(ctx)) return rc;
+    StageCrew *crew = ctx->crew;
+    if (int rc = ensure_timed_events(ctx, (size_t)K)) return rc;
+    hipEvent_t *done = ctx->timed_events.data(); /* per slot: the end of the kernels that read / wrote it last */
+    const WallClock wall0 = std::chrono::steady_clock::now();
+    if (int rc = stage_bs(ctx, L.pw[0], L.ph[0], c.chroma, c.bs, ctx->h2d)) return rc;
+    if (int rc = fence_operands(ctx, true)) return rc;
+    if (int rc = wait_operands(ctx, true, ctx->compute)) return rc;
+    CrewJobs jobs(crew, n_frames);
+    const unsigned crew_n = crew->workers() ? crew->workers() : 1;
+    /* frame i as row-range jobs: in = caller planes -> its slot of HBM, out = its slot of the ring -> caller planes; pieces of at least
+     * 512 KiB, 16 a plane at the most; the BAR is saturated by two cores: few, long pieces */
+    auto hand = [&](unsigned i, bool in) {
+        uint8_t *slot = (in ? dpush : ring) + (size_t)(i % K) * L.frame_bytes;
+        CopyGroup &g = in ? jobs.gin[i] : jobs.gout[i];
+        const unsigned most = in ? (crew_n > 2 ? 4u : 2u) : (2 * crew_n > 16 ? 16u : 2 * crew_n);
+        unsigned pieces[3] = {0, 0, 0}, np = 0;
+        for (int k = 0; k < L.npl; k++) np += pieces[k] = piece_count(L.plane_bytes[k], (size_t)512 << 10, most);
+        g.pending.store((int)np, std::memory_order_release);
+        for (int k = 0; k < L.npl; k++) submit_rows(crew, g, c.frames[i], L, k, slot + L.plane_off[k], !in, in, 0, L.ph[k], pieces[k]);
+    };
+    crew->begin();
+    const bool alone = crew->workers() == 0;
+    unsigned n_in = 0, n_launched = 0, n_out = 0, n_fin = 0;
+    while (n_fin < n_frames) {
+        bool progress = false;
+        /* copies in: slot i % K of HBM is free once the kernels of frame i - K have been seen to end */
+        if (n_in < n_frames && n_in < n_out + (unsigned)K) {
+            hand(n_in++, true);
+            progress = true;
+        }
+        /* launch: the frame is in HBM, and its ring slot has been copied out */
+        if (n_launched < n_in && jobs.gin[n_launched].pending.load(std::memory_order_acquire) == 0 && n_launched < n_fin + (unsigned)K) {
+            const unsigned i = n_launched;
+            const size_t slot = (size_t)(i % K) * L.frame_bytes;
+            DbkArgs args[3];
+            void *dplane[3] = {dpush + slot + L.plane_off[0], dpush + slot + L.plane_off[1], dpush + slot + L.plane_off[2]};
+            for (int k = 0; k < L.npl; k++) {
+                if (int rc = frame_plane_args(ctx, dplane, k, L.pw[0], L.ph[0], c.frames[0].bit_depth, L.sb, c.chroma, c.qp, nullptr, c.tables, args[k])) return rc;
+                args[k].dst = ring + slot + L.plane_off[k]; /* the kernels store into page-locked host memory */
+            }
+            if (int rc = launch_frame(ctx, args, L.npl, L.sb, ctx->compute, nullptr, done[i % K])) return rc;
+            n_launched++;
+            progress = true;
+        }
+        /* results landed: copies out */
+        if (n_out < n_launched) {
+            bool landed = false;
+            if (int rc = poll_event(ctx, done[n_out % K], &landed)) return rc;
+            if (landed) {
+                hand(n_out++, false);
+                progress = true;
+            }
+        }
+        while (n_fin < n_out && jobs.gout[n_fin].pending.load(std::memory_order_acquire) == 0) {
+            n_fin++;
+            progress = true;
+        }
+        if (progress) continue;
+        if (alone && crew->help()) continue;
+        _mm_pause();
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->compute));
+    set_timing_pipelined(c.timing, seconds_since(wall0));
+    return HEVCDBK_OK;
+}
+
+/* every other sequence: a ring of K slots, H2D(n+1) || kernels(n) || D2H(n-1) on the three streams; page-locked caller planes are
+ * DMA'd where they lie, the others through the slot's pinned staging */
+int sequence_dma(SequenceCall &c)
+{
+    hevcdbk_context *ctx = c.ctx;
+    const FrameLayout &L = c.L;
+    const unsigned n_frames = c.n_frames;
+    for (int s = 0; s < K; s++) {
+        for (int k = 0; k < L.npl; k++)
+            if (int rc = grow_device(ctx, ctx->seq_dev[s][k], L.plane_bytes[k])) return rc;
+        for (int e = 0; e < 3; e++)
+            if (!ctx->seq_ev[s][e]) HIP_TRY(ctx, hipEventCreate(&ctx->seq_ev[s][e]));
+    }
+    /* bS: shared by all frames of the sequence, uploaded once (the default pattern: once per geometry) */
+    const WallClock wall0 = std::chrono::steady_clock::now();
+    if (int rc = stage_bs(ctx, L.pw[0], L.ph[0], c.chroma, c.bs, ctx->h2d)) return rc;
+
+    std::vector<uint8_t> pinned((size_t)n_frames * 3, 0); /* plane k of frame i is page-locked caller memory */
+    /* un-stage frame `i` (its D2H has been issued into slot i % K) */
+    auto finish = [&](unsigned i) -> int {
+        const int s = (int)(i % K);
+        HIP_TRY(ctx, hipEventSynchronize(ctx->seq_ev[s][2]));
+        for (int k = 0; k < L.npl; k++)
+            if (!pinned[(size_t)i * 3 + k]) copy_plane(c.frames[i], L, k, (uint8_t *)ctx->seq_pin[s][k].p, true); /* else the DMA wrote the caller's plane directly */
+        return HEVCDBK_OK;
+    };
+
+    for (unsigned i = 0; i < n_frames; i++) {
+        const int s = (int)(i % K);
+        if (i >= (unsigned)K)
+            if (int rc = finish(i - K)) return rc; /* slot s is free again once frame i-K has left it */
+        hevcdbk_frame &fr = c.frames[i];
+        /* H2D: straight from pinned caller memory, or via the slot's pinned staging */
+        for (int k = 0; k < L.npl; k++) {
+            const bool lies = is_pinned_host(ctx, fr.plane[k], plane_span(fr.pitch[k], L.row_bytes[k], L.ph[k])); /* asked once per plane: the query is not free */
+            pinned[(size_t)i * 3 + k] = lies;
+            if (!lies) {
+                if (int rc = grow_pinned(ctx, ctx->seq_pin[s][k], L.plane_bytes[k])) return rc;
+                copy_plane(fr, L, k, (uint8_t *)ctx->seq_pin[s][k].p, false);
+            }
+            HIP_TRY(ctx, hipMemcpy2DAsync(ctx->seq_dev[s][k].p, L.row_bytes[k], lies ? fr.plane[k] : ctx->seq_pin[s][k].p, lies ? fr.pitch[k] : L.row_bytes[k],
+                                          L.row_bytes[k], L.ph[k], hipMemcpyHostToDevice, ctx->h2d));
+        }
+        HIP_TRY(ctx, hipEventRecord(ctx->seq_ev[s][0], ctx->h2d));
+        /* kernels */
+        HIP_TRY(ctx, hipStreamWaitEvent(ctx->compute, ctx->seq_ev[s][0], 0));
+        DbkArgs args[3];
+        void *dplane[3] = {ctx->seq_dev[s][0].p, ctx->seq_dev[s][1].p, ctx->seq_dev[s][2].p};
+        for (int k = 0; k < L.npl; k++)
+            if (int rc = frame_plane_args(ctx, dplane, k, L.pw[0], L.ph[0], fr.bit_depth, L.sb, c.chroma, c.qp, nullptr, c.tables, args[k])) return rc;
+        if (int rc = launch_frame(ctx, args, L.npl, L.sb, ctx->compute)) return rc;
+        HIP_TRY(ctx, hipEventRecord(ctx->seq_ev[s][1], ctx->compute));
+        /* D2H */
+        HIP_TRY(ctx, hipStreamWaitEvent(ctx->d2h, ctx->seq_ev[s][1], 0));
+        for (int k = 0; k < L.npl; k++) {
+            const bool lies = pinned[(size_t)i * 3 + k];
+            HIP_TRY(ctx, hipMemcpy2DAsync(lies ? fr.plane[k] : ctx->seq_pin[s][k].p, lies ? fr.pitch[k] : L.row_bytes[k], ctx->seq_dev[s][k].p,
+                                          L.row_bytes[k], L.row_bytes[k], L.ph[k], hipMemcpyDeviceToHost, ctx->d2h));
+        }
+        HIP_TRY(ctx, hipEventRecord(ctx->seq_ev[s][2], ctx->d2h));
+        /* slot s is written again by the H2D of frame i+K, which is issued only after finish(i) has seen this
+         * frame's D2H (and so its kernels) complete */
+    }
+    for (unsigned i = n_frames > (unsigned)K ? n_frames - K : 0; i < n_frames; i++)
+        if (int rc = finish(i)) return rc;
+    set_timing_pipelined(c.timing, seconds_since(wall0)); /* whole sequence */
+    return HEVCDBK_OK;
+}
+
 } /* namespace */
+
+extern "C" int hevc_deblocking_filter_sequence(hevcdbk_context *ctx, hevcdbk_frame *frames, unsigned n_frames,
+                                               const hevcdbk_bs *bs, const hevcdbk_qp *qp, const hevcdbk_tables *tables,
+                                               hevcdbk_timing *timing)
+{
+    if (!ctx || !frames || !qp) return HEVCDBK_ERR_ARG;
+    if (n_frames == 0) return HEVCDBK_OK;
+    if (qp->map) return HEVCDBK_ERR_UNSUPPORTED; /* one QP map per frame is not part of the streaming form */
+    const hevcdbk_frame &f0 = frames[0];
+    bool chroma = false;
+    if (int rc = check_frame(f0, chroma)) return rc;
+    const unsigned W = f0.width, H = f0.height, sb = f0.sample_bytes;
+    const unsigned pw[3] = {W, W / 2, W / 2}, ph[3] = {H, H / 2, H / 2};
+    for (unsigned i = 1; i < n_frames; i++) {
+        const hevcdbk_frame &fr = frames[i];
+        bool c2 = false;
+        if (fr.width != W || fr.height != H || fr.bit_depth != f0.bit_depth || fr.sample_bytes != sb) return HEVCDBK_ERR_ARG;
+        if (int rc = check_frame(fr, c2)) return rc;
+        if (c2 != chroma) return HEVCDBK_ERR_ARG;
+    }
+    if (int rc = check_bs(bs, W, H, chroma)) return rc;
+    if (int rc = bind(ctx)) return rc;
+    GpuDrain drain{ctx}; /* every return below that is not HEVCDBK_OK waits for the GPU (after the crew: its guard lives in the transport) */
+    SequenceCall c{ctx, frames, n_frames, bs, qp, tables, timing, chroma, frame_layout(chroma ? 3 : 1, pw, ph, sb)};
+    int rc;
+    if (chroma && sb == 1 && f0.bit_depth == 8 && (size_t)W * H * 3 / 2 <= ((size_t)2 << 20) && n_frames >= 4) {
+        rc = sequence_chunks(c);
+    } else {
+        bool pageable = c.L.frame_bytes > ((size_t)2 << 20) && n_frames >= 2;
+        for (unsigned i = 0; i < n_frames && pageable; i++)
+            for (int k = 0; k < c.L.npl && pageable; k++)
+                pageable = !is_pinned_host(ctx, frames[i].plane[k], plane_span(frames[i].pitch[k], c.L.row_bytes[k], c.L.ph[k]));
+        uint8_t *dpush = pageable ? push_buffer(ctx, (size_t)K * c.L.frame_bytes) : nullptr;
+        rc = dpush ? sequence_push(c, dpush) : sequence_dma(c);
+    }
+    drain.ok = rc == HEVCDBK_OK;
+    return rc;
+}
 
 /* ---- multi-frame .yuv file -> file: read || filter || write ---------------------------- */
 
@@ -1882,10 +1876,7 @@ int hevcdbk_filter_yuv_file(hevcdbk_context *ctx, const char *in_name, const cha
     if (rc != HEVCDBK_OK) return rc;
     if (!io_ok) return HEVCDBK_ERR_IO;
     if (n_frames_out) *n_frames_out = (unsigned)n;
-    if (timing) {
-        std::memset(timing, 0, sizeof(*timing));
-        timing->pipelined_s = std::chrono::duration<double>(wall1 - wall0).count();
-    }
+    set_timing_pipelined(timing, std::chrono::duration<double>(wall1 - wall0).count());
     return HEVCDBK_OK;
 }
 
@@ -1959,10 +1950,7 @@ int hevcdbk_filter_yuv_file_multi(const int *devices, unsigned n_devices, const 
         if (rc != HEVCDBK_OK) return rc;
     if (!closed) return HEVCDBK_ERR_IO;
     if (n_frames_out) *n_frames_out = (unsigned)n;
-    if (timing) {
-        std::memset(timing, 0, sizeof(*timing));
-        timing->pipelined_s = std::chrono::duration<double>(wall1 - wall0).count();
-    }
+    set_timing_pipelined(timing, std::chrono::duration<double>(wall1 - wall0).count());
     return HEVCDBK_OK;
 }
 

@@ -217,14 +217,9 @@ int hevcdbk_h265_filter_frame_cf(hevcdbk_context *ctx, hevcdbk_frame *frame, int
     if (int rc = bind(ctx)) return rc;
     GpuDrain drain{ctx}; /* every return below that is not HEVCDBK_OK waits for the GPU */
 
-    size_t plane_bytes[3] = {0, 0, 0}, plane_off[3] = {0, 0, 0}, frame_bytes = 0;
-    for (int i = 0; i < npl; i++) {
-        plane_bytes[i] = (size_t)pw[i] * ph[i] * sb;
-        plane_off[i] = frame_bytes;
-        frame_bytes = (frame_bytes + plane_bytes[i] + 255) & ~(size_t)255;
-    }
-    if (int rc = grow_pinned(ctx, ctx->pin[0], frame_bytes)) return rc;
-    if (int rc = grow_device(ctx, ctx->dev[0], frame_bytes)) return rc;
+    const FrameLayout L = frame_layout(npl, pw, ph, sb);
+    if (int rc = grow_pinned(ctx, ctx->pin[0], L.frame_bytes)) return rc;
+    if (int rc = grow_device(ctx, ctx->dev[0], L.frame_bytes)) return rc;
     if (int rc = grow_device(ctx, ctx->dev_bs, nv + nh + ncv + nch)) return rc;
     ctx->bs_default_at = nullptr; /* dev_bs no longer holds the reference's default pattern */
     if (qp->map)
@@ -243,13 +238,13 @@ int hevcdbk_h265_filter_frame_cf(hevcdbk_context *ctx, hevcdbk_frame *frame, int
      * the ring filled and emptied by the crew.  Not cut into strips: the bS derivation wants the whole picture's units first. */
     const auto wall0 = std::chrono::steady_clock::now();
     uint8_t *const ring = (uint8_t *)ctx->pin[0].p;
-    uint8_t *const dpush = push_buffer(ctx, frame_bytes);
+    uint8_t *const dpush = push_buffer(ctx, L.frame_bytes);
     uint8_t *const din = dpush ? dpush : (uint8_t *)ctx->dev[0].p;    /* what the kernels read */
     uint8_t *const dout = dpush ? ring : (uint8_t *)ctx->dev[0].p;    /* what they write */
-    if (int rc = crew_copy_frame(ctx, frame, npl, pw, ph, sb, dpush ? dpush : ring, plane_off, false, dpush != nullptr)) return rc;
+    if (int rc = crew_copy_frame(ctx, frame, L, dpush ? dpush : ring, false, dpush != nullptr)) return rc;
     const double push_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - wall0).count();
     HIP_TRY(ctx, hipEventRecord(ev[0], s));
-    if (!dpush) HIP_TRY(ctx, hipMemcpyAsync(ctx->dev[0].p, ring, frame_bytes, hipMemcpyHostToDevice, s));
+    if (!dpush) HIP_TRY(ctx, hipMemcpyAsync(ctx->dev[0].p, ring, L.frame_bytes, hipMemcpyHostToDevice, s));
     if (dmap) HIP_TRY(ctx, hipMemcpyAsync(dmap, qp->map, map_rows * qp->map_stride, hipMemcpyHostToDevice, s));
     if (units) {
         /* device layout: ref0 | ref1 | mv0 | mv1 | flags (descending alignment) */
@@ -278,9 +273,9 @@ int hevcdbk_h265_filter_frame_cf(hevcdbk_context *ctx, hevcdbk_frame *frame, int
     for (int i = 0; i < npl; i++) {
         hevcdbk_device_planes p;
         std::memset(&p, 0, sizeof(p));
-        p.src = din + plane_off[i];
-        p.dst = dout + plane_off[i];
-        p.pitch = (size_t)pw[i] * sb; p.frame_stride = plane_bytes[i]; p.n_frames = 1;
+        p.src = din + L.plane_off[i];
+        p.dst = dout + L.plane_off[i];
+        p.pitch = L.row_bytes[i]; p.frame_stride = L.plane_bytes[i]; p.n_frames = 1;
         p.plane_w = pw[i]; p.plane_h = ph[i]; p.bit_depth = frame->bit_depth; p.sample_bytes = sb;
         p.is_chroma = i != 0;
         p.vert_bs = i == 0 ? dbs : dcv;
@@ -291,20 +286,19 @@ int hevcdbk_h265_filter_frame_cf(hevcdbk_context *ctx, hevcdbk_frame *frame, int
         if (int rc = launch_h265(ctx, h, kNoSlOffs, Gen::CF, (int)sb, i, cf, HEVCDBK_KERNEL_AUTO, s)) return rc;
     }
     HIP_TRY(ctx, hipEventRecord(ev[2], s));
-    if (!dpush) HIP_TRY(ctx, hipMemcpyAsync(ring, ctx->dev[0].p, frame_bytes, hipMemcpyDeviceToHost, s));
+    if (!dpush) HIP_TRY(ctx, hipMemcpyAsync(ring, ctx->dev[0].p, L.frame_bytes, hipMemcpyDeviceToHost, s));
     HIP_TRY(ctx, hipEventRecord(ev[3], s));
     HIP_TRY(ctx, hipStreamSynchronize(s));
-    if (int rc = crew_copy_frame(ctx, frame, npl, pw, ph, sb, ring, plane_off, true, false)) return rc;
+    if (int rc = crew_copy_frame(ctx, frame, L, ring, true, false)) return rc;
     const auto wall1 = std::chrono::steady_clock::now();
     if (timing) {
         float a = 0.f, b = 0.f, c = 0.f;
         HIP_TRY(ctx, hipEventElapsedTime(&a, ev[0], ev[1]));
         HIP_TRY(ctx, hipEventElapsedTime(&b, ev[1], ev[2]));
         HIP_TRY(ctx, hipEventElapsedTime(&c, ev[2], ev[3]));
-        timing->exec_s = b * 1e-3;   /* with the BAR path the download is the kernels' own stores: inside exec_s */
-        timing->copy_s = (a + c) * 1e-3 + (dpush ? push_s : 0.0); /* uploads of bS / units / map (+ the frame: DMA, or the crew's writes) */
-        timing->total_s = timing->exec_s + timing->copy_s;
-        timing->pipelined_s = std::chrono::duration<double>(wall1 - wall0).count();
+        /* exec: with the BAR path the download is the kernels' own stores, inside it; copy: uploads of bS / units / map (+ the frame: DMA, or
+         * the crew's writes) */
+        set_timing(timing, b * 1e-3, (a + c) * 1e-3 + (dpush ? push_s : 0.0), std::chrono::duration<double>(wall1 - wall0).count());
     }
     drain.ok = true;
     return HEVCDBK_OK;

@@ -4,6 +4,9 @@
  * the two real sources linked against the model of the HIP runtime in hip_model.cpp.
  *
  *   host_frame_sim check SEED N        N cases made from SEED; one line per violation, then "K violations"
+ *   host_frame_sim calls SEED N        the fault-free call of each of the N cases, one line: the case, the return code, how often it made
+ *                                      each kind of HIP call (hipEventQuery left out: how often a call polls is up to the crew's threads),
+ *                                      its blocking calls and its kernel operations -- the same for two builds that behave the same
  *   host_frame_sim strips W H SB CHROMA [BAR [PITCHED]]   the strips of one pageable frame (PITCHED: rows 16 samples apart from tight), as hevcdbk_last_frame_trace reports them
  *   host_frame_sim crewfail            thread creation fails inside ensure_crew (plain builds only)
  *
@@ -49,6 +52,7 @@ struct Rng {
 };
 
 int g_violations = 0;
+bool g_list_calls = false; /* the `calls` command */
 std::string g_case;
 void violation(const char *prop, const std::string &what)
 {
@@ -643,7 +647,14 @@ void run_case(uint32_t seed)
         model_begin(model_case(c, FAULT_NONE, 0));
         const int rc = call_entry(c, ctx, o, f, (seed & 1) != 0);
         for (int k = 0; k < FAULT_KINDS; k++) calls[k] = model_calls(k);
-        if (rc == HEVCDBK_ERR_ARG || rc == HEVCDBK_ERR_UNSUPPORTED) {
+        if (g_list_calls) { /* the listing: what the fault-free call asked of the runtime, and nothing else of the case */
+            std::string line = "calls " + g_case + " rc=" + std::to_string(rc);
+            for (int k = 1; k < FAULT_KINDS; k++)
+                if (k != FAULT_EVENT_QUERY) line += std::string(" ") + model_fault_name(k) + "=" + std::to_string(calls[k]);
+            std::printf("%s blocking=%d writes=%zu\n", line.c_str(), model_blocking_calls(), model_writes().size());
+            model_drain();
+            for (int k = 0; k < FAULT_KINDS; k++) calls[k] = 0; /* no injected failures either */
+        } else if (rc == HEVCDBK_ERR_ARG || rc == HEVCDBK_ERR_UNSUPPORTED) {
             g_tally.refused[kEntry[c.entry]]++;
             check_model("refused");
             for (int k = 0; k < FAULT_KINDS; k++) calls[k] = 0;
@@ -711,6 +722,14 @@ int cmd_check(uint32_t seed, int n)
     for (auto &kv : g_tally.faults) std::printf("fault %s %d\n", kv.first.c_str(), kv.second);
     std::printf("%d violations\n", g_violations);
     return g_violations ? 1 : 0;
+}
+
+/* one line per case: a fingerprint of the fault-free call that two builds of the host sources can be compared by */
+int cmd_calls(uint32_t seed, int n)
+{
+    g_list_calls = true;
+    for (int i = 0; i < n; i++) run_case(seed * 100003u + (uint32_t)i);
+    return 0;
 }
 
 int cmd_strips(unsigned W, unsigned H, unsigned sb, bool chroma, bool bar, bool pitched)
@@ -792,12 +811,13 @@ int main(int argc, char **argv)
     std::setvbuf(stdout, nullptr, _IOLBF, 0);
     const std::string cmd = argc > 1 ? argv[1] : "";
     if (cmd == "check" && argc == 4) return cmd_check((uint32_t)std::strtoul(argv[2], nullptr, 10), std::atoi(argv[3]));
+    if (cmd == "calls" && argc == 4) return cmd_calls((uint32_t)std::strtoul(argv[2], nullptr, 10), std::atoi(argv[3]));
     if (cmd == "strips" && argc >= 6)
         return cmd_strips((unsigned)std::atoi(argv[2]), (unsigned)std::atoi(argv[3]), (unsigned)std::atoi(argv[4]), std::atoi(argv[5]) != 0,
                           argc > 6 ? std::atoi(argv[6]) != 0 : true, argc > 7 && std::atoi(argv[7]) != 0);
 #ifndef SIM_SANITIZED
     if (cmd == "crewfail") return cmd_crewfail();
 #endif
-    std::fprintf(stderr, "usage: host_frame_sim check SEED N | strips W H SB CHROMA [BAR [PITCHED]] | crewfail\n");
+    std::fprintf(stderr, "usage: host_frame_sim check SEED N | calls SEED N | strips W H SB CHROMA [BAR [PITCHED]] | crewfail\n");
     return 2;
 }

@@ -89,6 +89,21 @@ def test_thread_creation_failing_inside_a_call_is_an_error_code(built, program):
     assert r.returncode == 0 and "\n0 violations\n" in "\n" + r.stdout, r.stdout[-3000:] + r.stderr[-2000:]
 
 
+def test_calls_listing_is_a_stable_fingerprint(built):
+    """`calls SEED N`: one line per case -- the case, the return code of its fault-free call, how often it made each kind of HIP call
+    (all but hipEventQuery, whose count is the number of polls), its blocking calls and its kernel operations -- and the same lines from
+    two runs, the crew's threads real: what two builds of the host sources (a commit and its parent) can be compared by"""
+    runs = [subprocess.run([os.path.join(DIR, "host_frame_sim"), "calls", SEED, "200"], capture_output=True, text=True, timeout=300) for _ in range(2)]
+    assert all(r.returncode == 0 for r in runs), runs[0].stderr[-2000:] + runs[1].stderr[-2000:]
+    lines = runs[0].stdout.splitlines()
+    assert len(lines) == 200 and len({ln.split(" ")[1] for ln in lines}) == 200  # "calls seed=... ": every case once
+    kinds = FAULTS - {"hipEventQuery"}
+    for ln in lines:
+        assert re.match(r"calls seed=\d+ hevc", ln) and re.search(r" rc=-?\d+ ", ln) and "hipEventQuery" not in ln, ln
+        assert all(re.search(r" %s=\d+( |$)" % k, ln) for k in kinds | {"blocking", "writes"}), ln
+    assert runs[0].stdout == runs[1].stdout
+
+
 STRIP_SHAPES = [(1024, 1032, 1, 0), (256, 4104, 2, 0), (1920, 1088, 1, 1)]
 
 
